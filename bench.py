@@ -868,6 +868,66 @@ def emulate_config5(args):
     print(json.dumps(line))
 
 
+# ---- --dump-outputs: what the timed step handed its caller, for output-for-output comparison of two builds ------------
+DUMP_LIMIT_BYTES = 64 << 20
+DUMP_MAX_ROWS = 1 << 19  # rows per array; the widest rows (nodes 24 B, contacts 16 B, leaf volume 16 B, ...) keep the sum < 40 MB
+DUMP_SAMPLE_SEED = 1234
+
+
+def _dump_rows(a, float_dtype):
+    """a as float_dtype; more than DUMP_MAX_ROWS rows -> a fixed sample of them, kept in order.  The sample depends on the
+    row count alone, so two runs with the same count dump the same rows."""
+    import numpy as np
+    from numpy.lib import recfunctions
+    a = np.asarray(a)
+    if a.dtype.names:  # a record field (a leaf's BSphere / BBox): its floats side by side
+        a = recfunctions.structured_to_unstructured(a)
+    if a.shape[0] > DUMP_MAX_ROWS:
+        rows = np.sort(np.random.default_rng(DUMP_SAMPLE_SEED).choice(a.shape[0], DUMP_MAX_ROWS, replace=False))
+        a = a[rows]
+    return np.ascontiguousarray(a, dtype=float_dtype)
+
+
+def snapshot_outputs(bvh, trav):
+    """Device copies of what one step returned — the BVH fields (nodes, skips, extrema, sorted leaves) and the contact
+    list — taken without leaving the GPU idle: the steps after it reuse these buffers through cache=."""
+    return {"types": bvh.leaves.types, "num_leaves": len(bvh.leaves), "leaves": bvh.leaves.buf.clone(),
+            "nodes": bvh.nodes.clone(), "skips": bvh.skips.clone(),
+            "extrema": None if bvh.extrema is None else bvh.extrema.clone(), "contacts": trav.contacts.clone(),
+            "num_contacts": trav.num_contacts}
+
+
+def dump_outputs(directory, snap):
+    """Write a snapshot_outputs() as DIR/<name>.npy.  Floats keep their width (float32 or float64); indices, Morton codes
+    and counts become float64, exact for every value this benchmark produces (< 2**53)."""
+    import numpy as np
+    from implicitbvh_amd import abi
+
+    def fdt(a):
+        base = a.dtype.fields[a.dtype.names[0]][0].base if a.dtype.names else a.dtype
+        return np.float64 if base == np.float64 else np.float32
+
+    leaves = snap["leaves"].cpu().numpy().view(abi.leaf_dtype(snap["types"]))[: snap["num_leaves"]]
+    nodes = snap["nodes"].cpu().numpy()
+    out = {
+        "nodes": _dump_rows(nodes, fdt(nodes)),
+        "skips": _dump_rows(snap["skips"].cpu().numpy(), np.float64),
+        "leaf_volume": _dump_rows(leaves["volume"], fdt(leaves["volume"])),
+        "leaf_index": _dump_rows(leaves["index"], np.float64),
+        "leaf_morton": _dump_rows(leaves["morton"], np.float64),
+        "contacts": _dump_rows(snap["contacts"].cpu().numpy(), np.float64),
+        "num_contacts": np.array([snap["num_contacts"]], dtype=np.float64),
+    }
+    if snap["extrema"] is not None:
+        extrema = snap["extrema"].cpu().numpy()
+        out["extrema"] = _dump_rows(extrema, fdt(extrema))
+    total = sum(a.nbytes for a in out.values())
+    assert total <= DUMP_LIMIT_BYTES, f"--dump-outputs: {total} bytes exceed the {DUMP_LIMIT_BYTES}-byte limit"
+    os.makedirs(directory, exist_ok=True)
+    for name, a in out.items():
+        np.save(os.path.join(directory, f"{name}.npy"), a)
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--gpus", type=int, default=1)
@@ -889,7 +949,15 @@ def main():
     ap.add_argument("--virtual-ranks", type=int, default=0,
                     help="EMULATE BASELINE.json configs[4] on ONE GPU: this many virtual ranks (threads) x --n leaves (default 1.25e7) run the "
                          "distributed build + per-rank traversal; per-rank figures, no xGMI (nothing is measured about the links)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write what the last one returned (BVH nodes, skips, extrema, sorted leaves; the "
+                         "contact list and count) as DIR/<name>.npy, float32/float64, arrays over %d rows as a fixed sample; "
+                         "rank 0's slice when N > 1" % DUMP_MAX_ROWS)
     args = ap.parse_args()
+    if args.steps < 1 or args.warmup < 0:
+        ap.error("--steps must be >= 1 and --warmup >= 0")
+    if args.dump_outputs and args.virtual_ranks > 1:
+        ap.error("--dump-outputs is not supported with --virtual-ranks")
     if args.gpus > 1 and "WORLD_SIZE" not in os.environ:
         self_launch(args.gpus)  # (does not return)
     if args.virtual_ranks > 1:
@@ -1028,6 +1096,8 @@ def main():
         contacts_total, leaves_total = contacts, leaves_here
     ms_per_step = elapsed / args.steps * 1e3
     value = leaves_total * args.steps / elapsed / 1e6
+    # (the last timed step's results, copied on the device; written to disk once everything is timed)
+    snapshot = snapshot_outputs(*state) if args.dump_outputs and rank == 0 else None
 
     # The same K steps chained through cache= WITHOUT the read (a caller that sizes nothing from the count need not
     # wait for it; the count is read once, at the end)
@@ -1267,6 +1337,8 @@ def main():
         except OSError as e:
             print(f"bench.py: could not write {detail_path}: {e}", file=sys.stderr)
             detail_path = None
+        if snapshot is not None:
+            dump_outputs(args.dump_outputs, snapshot)
         short = compact_line(line, detail_path)
         text = json.dumps(short, separators=(",", ":"))
         if len(text) > 4096:  # (never: the compact line has a fixed shape; if it ever grows, drop the per-config block first)
