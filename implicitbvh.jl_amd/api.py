@@ -974,7 +974,7 @@ def _lvt_scratch(cache, types, n_items, slots=None, rays_bvh=None):
 
     def scratch_need():
         need = C.c_size_t()
-        if rays_bvh is not None:  # rays: room for the walker's shadow of the node levels as well (include/ibvh.h)
+        if rays_bvh is not None:  # rays: room for the binned path's tables where it serves the batch (include/ibvh.h)
             s = rays_bvh.struct()
             lib.call("ibvh_rays_scratch_bytes", C.byref(s), int(n_items), k, C.byref(need))
         else:

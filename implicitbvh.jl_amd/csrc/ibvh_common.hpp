@@ -506,7 +506,6 @@ struct Tuning {
     int ray_block = 0;      // rays per wave of lvt_rays_kernel (0 = chosen from the batch size; a power of two, 64 .. 1024)
     int lvt_wide = 0;       // 1 = 64-bit queue entries for every tree (otherwise only for 29 .. 31 levels)
     int msd_rescue = 1;     // 0 = ranges too large for one finish workgroup take the one-workgroup slow path of rounds 2 - 5 instead of the rescue workgroups (ibvh_msd_finish.hip)
-    int lvt_dual = 0;       // -DIBVH_VARIANTS builds only (variants/lvt_dual.inc): 1 = BBox-node leaf queries take the dual descent (7 - 25 % slower than lvt_queue_kernel, round 4)
     int lvt_blocks = 1;     // walker 2: 1 = the descent is shared per block of leaves (lvt_block_frontier_kernel), 0 = every wave descends on its own
     int lvt_block_shift = 0; // log2 of the leaves per block (0 = 11; 9 .. 12)
     int lvt_blocks_paired_below = -1; // block grids smaller than this take two levels per trip (-1 = 4096)
@@ -519,20 +518,16 @@ struct Tuning {
     int msd = 1;            // 0 = the build never takes the MSD partition path
     int msd_bits = 0, msd_cap = 0, msd_tile = 0, msd_ftpb = 0; // forced partition geometry (0 = chosen from n)
     int msd_avg = 1024;     // largest average cell before another first-level bit is taken
-    int msd_range = 1;      // 0 = first extra level on the next 8 bits, unmeasured
     int lvt_scan_fused = 1; // the scan behind walker 2's counting pass in one kernel (scan_fused_kernel / scan_fused_grouped_kernel); 0 = reduce + apply; N > 1 = at most N workgroups (development: the default is half of what the device holds at once)
     int msd_equalize = 0;   // equalised cells (ibvh_msd.hip): 0 = when the build asks (ibvh_build_desc.sort_equalize), 1 = always, -1 = never
     int msd_finish_pad_kb = 0; // LDS (KiB) a finish workgroup asks for at least: limits the workgroups per CU (0 = what it needs)
     int msd_resident_kb = 0; // LDS budget (KiB) of a finish workgroup that keeps its range's RECORDS in LDS: 0 = the plan decides
                              // (8,192-record geometry only), > 0 = every geometry with this budget, < 0 = never
     int bfs_wg_per_cu = 4;  // workgroups per CU of the BFS level kernels' fixed grid (ibvh_bfs.hip, level_grid)
-    int rays_shadow = 0;    // -DIBVH_VARIANTS builds only (variants/rays_shadow.inc): 1 = ray traversals walk the quantised 8-wide shadow of the node levels when the scratch has room
-                            // (ibvh_rays_scratch_bytes); measured slower than the binary walk on config 3 (4.6 vs 4.3 ms): off
     int rays_binned = 1;    // ray traversals (F32 trees) cut the walk at a level and finish it subtree by subtree out of LDS:
                             // 1 = where it pays (rays_bin_plan: >= 17 levels, or >= 13 under <= 8,192 rays; not a small tree under many
                             // rays), 2 = wherever the tree allows it, 0 = never
     int rays_subtree_depth = 0; // levels of such a subtree below its root (0 = 9: 512 leaves; at most 11)
-    int rays_fast_slab = 1;     // 0 = the binned path tests every box with isintersection_inv (A/B of the packed / v_min3 slab test)
     int rays_tail = 8;          // binned rays, subtree pass: walks a wave parks for the workgroup's unit rounds once its chunk is dry (0 = never: every walk is finished by its lane)
     int rays_items_per_ray = 0; // capacity of the (ray, subtree) item list per ray (0 = 16); a call that overflows it is served by the binary walker
 };

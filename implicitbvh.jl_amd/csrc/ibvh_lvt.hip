@@ -57,15 +57,12 @@ int run(const ibvh_bvh *drv, const ibvh_bvh *walk, const void *points, const voi
     dl = wl;
     if (drv && !layout_of(drv->types, lay, &dl)) return IBVH_ERR_UNSUPPORTED;
     if (!work && (!scratch || scratch_bytes < scan_scratch_bytes(n_items))) return IBVH_ERR_SCRATCH;
-    // RAYS: the quantised shadow of the node levels lives at the END of the scratch when the caller sized it with
-    // ibvh_rays_scratch_bytes (and the walk qualifies: rays_shadow_bytes); the contact cache gets what lies in between
-    size_t shadow_bytes = 0;
-    RayBinPlan bin_plan; // RAYS: the binned path's region, same place, when the tree and the batch qualify (it goes before the shadow)
+    // RAYS: the binned path's region lives at the END of the scratch when the caller sized it with ibvh_rays_scratch_bytes
+    // and the tree and the batch qualify; the contact cache gets what lies in between
+    RayBinPlan bin_plan;
     if (MODE == MODE_RAYS && !work) {
         bin_plan = rays_bin_plan(*walk, n_items);
         if (bin_plan.cut_level < start_level || scratch_bytes < scan_scratch_bytes(n_items) + bin_plan.bytes + 256) bin_plan = RayBinPlan{};
-        if (bin_plan.depth == 0) shadow_bytes = rays_shadow_bytes(*walk, n_items);
-        if (scratch_bytes < scan_scratch_bytes(n_items) + shadow_bytes + 256) shadow_bytes = 0;
     }
     // SELF / PAIR under BBox nodes: the rows of the shared descent (ibvh_lvt.hpp "BlockRows") live at the END of the scratch when
     // the caller sized it with ibvh_lvt_scratch_bytes; a smaller scratch simply has none (every wave descends on its own)
@@ -80,10 +77,9 @@ int run(const ibvh_bvh *drv, const ibvh_bvh *walk, const void *points, const voi
         if (!rows_bytes) qidx_bytes = 0;
         rows_bytes += qidx_bytes; // (one tail: [index array | rows])
     }
-    const size_t tail_bytes = bin_plan.depth ? bin_plan.bytes : (shadow_bytes ? shadow_bytes : rows_bytes);
+    const size_t tail_bytes = bin_plan.depth ? bin_plan.bytes : rows_bytes;
     const size_t cache_room = scratch_bytes - (tail_bytes ? tail_bytes + 256 : 0);
     char *tail_ptr = tail_bytes ? (char *)scratch + ((scratch_bytes - tail_bytes) & ~(size_t)255) : nullptr;
-    char *shadow_ptr = shadow_bytes ? tail_ptr : nullptr;
     const RayBins bins = bin_plan.depth ? rays_bins_at(bin_plan, tail_ptr) : RayBins{};
     const int K = work ? 0 : cache_slots_for(cache_room, n_items, lay.pair_bytes);
     return dispatch_leaf_node(walk->types, [&](auto lt, auto nt) -> int {
@@ -116,8 +112,6 @@ int run(const ibvh_bvh *drv, const ibvh_bvh *walk, const void *points, const voi
                 a.guard_total = nullptr;
                 a.guard_capacity = 0;
                 a.work = work;
-                a.shadow = shadow_ptr;
-                a.rays_filter = 0;
                 a.gate = nullptr;
                 a.blk_rows = rows_bytes ? (uint32_t *)(tail_ptr + qidx_bytes) : nullptr;
                 a.q_index_dense = qidx_bytes ? (I *)tail_ptr : nullptr;
@@ -170,8 +164,8 @@ ibvh_status ibvh_lvt_scratch_bytes(const ibvh_types *types, int64_t n_items, int
     return IBVH_OK;
 }
 
-// Scratch for the ray traversal entry points: ibvh_lvt_scratch_bytes for num_rays work items plus room for the shadow
-// of the node levels the ray walker builds for itself (see include/ibvh.h).
+// Scratch for the ray traversal entry points: ibvh_lvt_scratch_bytes for num_rays work items, or, when the binned path
+// serves the batch, that path's region behind a scratch without contact cache (see include/ibvh.h).
 ibvh_status ibvh_rays_scratch_bytes(const ibvh_bvh *bvh, int64_t num_rays, int32_t cache_slots, size_t *bytes_out) {
     if (!bvh || !bytes_out || num_rays < 0) return IBVH_ERR_INVALID_ARG;
     size_t base = 0;
@@ -182,8 +176,7 @@ ibvh_status ibvh_rays_scratch_bytes(const ibvh_bvh *bvh, int64_t num_rays, int32
         *bytes_out = (size_t)align_up((int64_t)base, 256) + bp.bytes + 512;
         return IBVH_OK;
     }
-    const size_t sh = rays_shadow_bytes(*bvh, num_rays);
-    *bytes_out = sh ? (size_t)align_up((int64_t)base, 256) + sh + 512 : base;
+    *bytes_out = base;
     return IBVH_OK;
 }
 

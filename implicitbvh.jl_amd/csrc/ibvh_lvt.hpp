@@ -47,11 +47,6 @@ template <class L, class N, class I> struct Args {
     // *guard_total <= guard_capacity (guard_total == nullptr: unguarded)
     const int64_t *guard_total;
     int64_t guard_capacity;
-    // RAYS: the quantised 8-wide shadow of the node levels (RayShadow below; nullptr: the binary walk) and which rays a
-    // launch serves: 0 all, 1 only IRREGULAR ones (a zero / non-finite direction component or a non-finite origin: the
-    // slab test is not monotone under box inclusion for them), 2 only regular ones
-    const char *shadow;
-    int32_t rays_filter;
     // RAYS: the binary walker as the stand-by of the binned path (RayBins below): it returns at once unless *gate != 0
     const int32_t *gate;
     // ibvh_lvt_work_counters only (COUNT instantiations): [0] node tests, [1] leaf tests, [2] node records fetched,
@@ -181,10 +176,7 @@ template <class I> struct PairCache {
     int32_t K;
 };
 
-#ifndef IBVH_BRUTE_DEPTH
-#define IBVH_BRUTE_DEPTH 7
-#endif
-constexpr int BRUTE_DEPTH = IBVH_BRUTE_DEPTH; // 2^7 = 128 leaves, 64 leaf-parents (one per lane) per brute-forced subtree
+constexpr int BRUTE_DEPTH = 7; // 2^7 = 128 leaves, 64 leaf-parents (one per lane) per brute-forced subtree
 constexpr int FRONTIER_CAP = 256; // frontier entries per wave and level (LDS); overflow -> exact walk
 
 // Per-lane query state + the emission rules shared by both kernels.
@@ -375,7 +367,7 @@ __global__ __launch_bounds__(256) void lvt_joint_kernel(Args<L, N, I> a, PairCac
 // ---- rays: constants and predicates shared by the per-lane walker and the binned path --------------------------------
 constexpr int RAY_BITS = 10, RAY_BLOCK_MAX = 1 << RAY_BITS;
 
-// a ray the shadow walk may serve: finite origin, finite non-zero direction with finite reciprocal
+// a ray the packed slab test may serve (ibvh_lvt_raybins.hip): finite origin, finite non-zero direction with finite reciprocal
 template <class T> IBVH_D bool ray_is_regular(const T *p, const T *d, const T *inv) {
     bool ok = true;
 #pragma unroll
@@ -946,7 +938,6 @@ int launch_rays(const Args<L, N, I> &a, const PairCache<I> &cache, bool write, h
 // walker 3 as the stand-by of the binned path: gated on a.gate, no contact cache (ibvh_lvt_rays.hip)
 template <class L, class N, class I>
 int launch_rays_standby(const Args<L, N, I> &standby, bool write, hipStream_t st, int ray_block, unsigned rblocks);
-size_t rays_shadow_bytes(const ibvh_bvh &bvh, int64_t num_rays); // (ibvh_lvt_rays.hip; 0 in the product library)
 // walker 4 (ibvh_lvt_raybins.hip)
 template <class L, class N, class I>
 int launch_rays_binned(const Args<L, N, I> &a, bool write, hipStream_t st, const RayBins &rb, int ray_block, unsigned rblocks);

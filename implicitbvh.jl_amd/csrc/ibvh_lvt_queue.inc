@@ -527,28 +527,13 @@ struct Sections {
 #endif
 enum { SEC_PROLOGUE = 0, SEC_DESCENT = 1, SEC_SUBTREE = 2, SEC_LOOPS = 3, SEC_LEAVES = 4, SEC_EPILOGUE = 5 };
 
-#ifndef IBVH_QUEUE_CAP
-#define IBVH_QUEUE_CAP 512
-#endif
-constexpr int QUEUE_CAP = IBVH_QUEUE_CAP; // candidate pairs per wave (LDS); drained whenever fewer than 64 slots are free
-#ifndef IBVH_QUEUE_WAVES
-#define IBVH_QUEUE_WAVES 1
-#endif
-constexpr int QUEUE_WAVES = IBVH_QUEUE_WAVES; // waves per workgroup (they share nothing: a workgroup is only a unit of dispatch)
+constexpr int QUEUE_CAP = 512; // candidate pairs per wave (LDS); drained whenever fewer than 64 slots are free
+constexpr int QUEUE_WAVES = 1; // waves per workgroup (they share nothing: a workgroup is only a unit of dispatch)
 // Waves per SIMD the register allocator has to leave room for.  Round 3, measured on MI355X with the DPP prologue and
 // the straight-line loads below (count pass, 1e6 / 1e7 leaves): 8 waves (64 VGPRs: 36 SGPR + 6 VGPR spills, 28 B of
 // scratch per lane) 0.188 / 1.75 ms; 7 waves (70 VGPRs, 15 SGPR spills to VGPR lanes, NO scratch) 0.156 / 1.37 ms; the
 // round-2 kernel at 8 waves (31 + 4 spills, 20 B of scratch) 0.165 / 1.42 ms.  (profiles/r03_lvt_variants.txt)
-#ifndef IBVH_QUEUE_MINWAVES
-#define IBVH_QUEUE_MINWAVES 7
-#endif
-#ifndef IBVH_LVT_QTABLE
-#define IBVH_LVT_QTABLE 0
-#endif
-#ifndef IBVH_LVT_STRAIGHT
-#define IBVH_LVT_STRAIGHT 7 // bit 0: descent loads, bit 1: leaf-parent loads, bit 2: leaf loads of the pair step — straight-line (clamped) instead of exec-masked
-#endif
-constexpr int QUEUE_MINWAVES = IBVH_QUEUE_MINWAVES; // waves per SIMD the register allocator has to leave room for (8: 64 VGPRs)
+constexpr int QUEUE_MINWAVES = 7;
 
 // Waves per SIMD a given instantiation can actually reach: Float64 volumes and 64-bit queue entries need more registers than
 // the bench types, and asking for 7 waves there only makes the allocator spill and warn (-Wpass-failed, 48 times in round 3).
@@ -572,25 +557,11 @@ __global__ __launch_bounds__(64 * QUEUE_WAVES, (queue_min_waves<L, N, I, WIDE, W
     __shared__ QE s_queue[QUEUE_WAVES][QUEUE_CAP];
     __shared__ Cnt s_cnt[QUEUE_WAVES][64];
     __shared__ I s_qside[QUEUE_WAVES][64]; // writing pass from the cache: the query's half of a pair, by query lane
-#if IBVH_LVT_QTABLE
-    // The wave's 64 query leaves (volume, index) in LDS: the leaf-test step fetches its candidate's query with one or two
-    // ds_read instead of five ds_bpermute out of registers, and the volume / index need not stay in VGPRs through the loops.
-    struct QRec {
-        L vol;
-        I idx;
-    };
-    __shared__ QRec s_query[QUEUE_WAVES][64];
-#endif
     Sections sec;
     sec.start();
     const bool dense_index = WRITE && a.q_index_dense != nullptr; // (the counting pass left every item's .index in a dense array)
     Q q(a, cache, dense_index);
     const int lane = threadIdx.x & 63, wv = __builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6)); // (uniform: LDS bases stay scalar)
-#if IBVH_LVT_QTABLE
-    // (the writing pass fills the table behind its cache path, which does not need it: the LDS store would make every wave wait for
-    // its leaf before the cache path's own loads are even requested)
-    if constexpr (!WRITE) s_query[wv][lane] = QRec{q.q_leaf, q.q_index};
-#endif
     if constexpr (!WRITE && !COUNT) {
         if (a.q_index_dense != nullptr && q.valid) a.q_index_dense[q.item] = q.q_index;
         // the tile aggregates of the scan that follows this pass (scan_fused_kernel): one word per wave, first waves only
@@ -660,9 +631,6 @@ __global__ __launch_bounds__(64 * QUEUE_WAVES, (queue_min_waves<L, N, I, WIDE, W
         }
         if (dense_index) q.load_leaf();
         q.lane_on = q.valid; // every item of the wave walks again
-#if IBVH_LVT_QTABLE
-        s_query[wv][lane] = QRec{q.q_leaf, q.q_index};
-#endif
     }
     // Pair walk: a wave none of whose queries touches the other tree's ROOT box finds nothing — leave before the
     // two-box split and the descent (two partially overlapping clouds: most waves of the larger one).  The root
@@ -840,7 +808,6 @@ __global__ __launch_bounds__(64 * QUEUE_WAVES, (queue_min_waves<L, N, I, WIDE, W
         const bool v = lane < avail;
         // (straight-line loads: lanes beyond the step re-read its first entry, a pair without a right leaf re-reads the left
         // one; both are masked by v / has_b afterwards)
-#if IBVH_LVT_STRAIGHT & 4
         const QE e = queue[off + (v ? lane : 0)];
         const int qi = (int)(e & 63u);
         const uint32_t pos = 2u * (uint32_t)(e >> 6); // 0-based position of the pair's left leaf
@@ -856,36 +823,8 @@ __global__ __launch_bounds__(64 * QUEUE_WAVES, (queue_min_waves<L, N, I, WIDE, W
                 mor_b = load_morton(rec_b, a.lay);
             }
         }
-#else
-        const QE e = v ? queue[off + lane] : (QE)0;
-        const int qi = (int)(e & 63u);
-        const uint32_t pos = 2u * (uint32_t)(e >> 6); // 0-based position of the pair's left leaf
-        const bool has_b = v & (pos + 1u < n_leaves);
-        L leaf_a = {}, leaf_b = {};
-        I idx_a = 0, idx_b = 0;
-        uint64_t mor_a = 0, mor_b = 0;
-        const char *rec = a.leaves + (int64_t)pos * a.lay.stride;
-        if (v) {
-            leaf_a = load_vol<L>(rec);
-            idx_a = load_index<I>(rec, a.lay);
-            if constexpr (NARROW)
-                if (a.narrow == IBVH_NARROW_MORTON_LT) mor_a = load_morton(rec, a.lay);
-        }
-        if (has_b) {
-            leaf_b = load_vol<L>(rec + a.lay.stride);
-            idx_b = load_index<I>(rec + a.lay.stride, a.lay);
-            if constexpr (NARROW)
-                if (a.narrow == IBVH_NARROW_MORTON_LT) mor_b = load_morton(rec + a.lay.stride, a.lay);
-        }
-#endif
-#if IBVH_LVT_QTABLE
-        const QRec qr = s_query[wv][qi];
-        const L ql = qr.vol;
-        const I qidx = qr.idx;
-#else
         const L ql = shuffle_from(q.q_leaf, qi);
         const I qidx = __shfl(q.q_index, qi, 64);
-#endif
         const uint32_t item_q = wave_item0 + (uint32_t)qi;
         bool hit_a = v & iscontact(ql, leaf_a), hit_b = has_b & iscontact(ql, leaf_b);
         work.add(1, (uint32_t)v + (uint32_t)has_b);
@@ -994,19 +933,8 @@ __global__ __launch_bounds__(64 * QUEUE_WAVES, (queue_min_waves<L, N, I, WIDE, W
         const int np = (int)(last - first32); // <= 64
         // lanes without a parent (a ragged last subtree) re-read the last one and stay out of box_mask: whatever they
         // compute below is masked (straight-line load: no exec-masked region, no "empty box" to materialise)
-#if IBVH_LVT_STRAIGHT & 2
         const N mybox = load_vol<N>(lp_nodes + (first32 + (uint32_t)(lane < np ? lane : np - 1)));
         const bool mine = lane < np;
-#else
-        N mybox; // lanes without a parent hold the empty box: it matches nothing
-#pragma unroll
-        for (int k = 0; k < 3; ++k) {
-            mybox.lo[k] = float_max<TN>();
-            mybox.up[k] = -float_max<TN>();
-        }
-        if (lane < np) mybox = load_vol<N>(lp_nodes + (first32 + (uint32_t)lane));
-        const bool mine = true;
-#endif
         work.add(2, lane < np);
         work.add(0, lane < np ? 2u : 0u); // against the wave's two boxes
         const uint32_t right_leaf = 2u * (first32 + (uint32_t)lane) + 1u; // of this lane's parent
@@ -1166,7 +1094,6 @@ __global__ __launch_bounds__(64 * QUEUE_WAVES, (queue_min_waves<L, N, I, WIDE, W
                 // region around the loads, and the ballot below is the compare mask itself)
                 work.add(2, have);
                 work.add(0, have ? 2u : 0u);
-#if IBVH_LVT_STRAIGHT & 1
                 const uint32_t idx = cur[have ? base + lane : base];
                 const N box = load_vol<N>(lvl_nodes + (idx - lvl_first));
                 bool hit;
@@ -1182,17 +1109,6 @@ __global__ __launch_bounds__(64 * QUEUE_WAVES, (queue_min_waves<L, N, I, WIDE, W
                     if constexpr (MODE == MODE_SELF) hit = hit & !((idx + 1u) <= (wave_next >> (levels - lvl)));
                     hit_mask = __builtin_amdgcn_ballot_w64(hit);
                 }
-#else
-                const uint32_t idx = have ? cur[base + lane] : 0u;
-                N box;
-                bool hit = false;
-                if (have) {
-                    box = load_vol<N>(lvl_nodes + (idx - lvl_first));
-                    hit = touches_wave(box);
-                    if constexpr (MODE == MODE_SELF) hit = hit & !((idx + 1u) <= (wave_next >> (levels - lvl)));
-                }
-                const uint64_t hit_mask = __builtin_amdgcn_ballot_w64(hit);
-#endif
                 const uint64_t hm = hit_mask;
                 if (lvl == cut_level) {
                     for (uint64_t todo = hm; todo != 0; todo &= todo - 1) {
@@ -1258,10 +1174,6 @@ __global__ __launch_bounds__(64 * QUEUE_WAVES, (queue_min_waves<L, N, I, WIDE, W
     sec.flush();
 }
 
-#ifdef IBVH_VARIANTS
-#include "../../variants/lvt_dual.inc"
-#endif
-
 template <class L, class N, class I, int MODE>
 int launch_queue(const Args<L, N, I> &a, const PairCache<I> &cache, bool write, hipStream_t st, bool *agg_zeroed) {
     static_assert(N::kind == IBVH_BBOX, "walker 2 needs nested node boxes");
@@ -1281,36 +1193,6 @@ int launch_queue(const Args<L, N, I> &a, const PairCache<I> &cache, bool write, 
     int64_t top = a.built_level > 7 ? a.built_level : 7; // level 7: 64 nodes, one 64-lane step
     if (top > a.tree.levels - 1) top = a.tree.levels - 1;
     aq.start_level = top; // also when the caller named a HIGHER level: levels 1..6 hold < 64 nodes each
-#ifdef IBVH_VARIANTS
-    if (g_tuning.lvt_dual) {
-        // the dual descent (lvt_dual_kernel): pairs pack (T index within its level << 7 | Q node): 32 bits up to 27 levels
-        const bool dwide = force_wide || a.tree.levels > 27;
-        const DualPlan dplan = make_dual_plan((int)aq.tree.levels, (uint32_t)aq.tree.virtual_leaves, (int)aq.start_level, sizeof(N));
-        if constexpr (kWorkTypes<L, N, I>) {
-            if (count_work) {
-                if (dwide || aq.narrow != IBVH_NARROW_NONE) return IBVH_ERR_UNSUPPORTED;
-                IBVH_LAUNCH((lvt_dual_kernel<L, N, I, MODE, false, false, false, true>), dim3(qblocks), dim3(64), 0, st, aq, cache, dplan);
-                IBVH_LAUNCH_CHECK();
-                return IBVH_OK;
-            }
-        }
-        const int dvariant = (write ? 1 : 0) | (aq.narrow != IBVH_NARROW_NONE ? 2 : 0) | (dwide ? 4 : 0);
-#define IBVH_DUAL_LAUNCH(W_, N_, D_) IBVH_LAUNCH((lvt_dual_kernel<L, N, I, MODE, W_, N_, D_>), dim3(qblocks), dim3(64), 0, st, aq, cache, dplan)
-        switch (dvariant) {
-        case 0: IBVH_DUAL_LAUNCH(false, false, false); break;
-        case 1: IBVH_DUAL_LAUNCH(true, false, false); break;
-        case 2: IBVH_DUAL_LAUNCH(false, true, false); break;
-        case 3: IBVH_DUAL_LAUNCH(true, true, false); break;
-        case 4: IBVH_DUAL_LAUNCH(false, false, true); break;
-        case 5: IBVH_DUAL_LAUNCH(true, false, true); break;
-        case 6: IBVH_DUAL_LAUNCH(false, true, true); break;
-        default: IBVH_DUAL_LAUNCH(true, true, true); break;
-        }
-#undef IBVH_DUAL_LAUNCH
-        IBVH_LAUNCH_CHECK();
-        return IBVH_OK;
-    }
-#endif
     const int64_t c = aq.tree.levels - BRUTE_DEPTH;
     const int cut = (int)(c > aq.start_level ? c : aq.start_level);
     if constexpr (kWorkTypes<L, N, I>) {

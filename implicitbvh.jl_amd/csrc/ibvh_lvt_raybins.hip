@@ -41,11 +41,6 @@ namespace lvt {
 // tell apart: the same boolean, for half the instructions (packed subtract / multiply on the six bounds as they lie in
 // memory, v_min3 / v_max3).  Rays and boxes that do not qualify take isintersection_inv.  Used by rays_top_kernel
 // (0.72 -> 0.65 ms on config 3).
-#ifdef IBVH_RAYS_NO_FAST_SLAB // (development builds: the walks without the second code path, tools/build_variant.sh)
-constexpr bool kRaysFastSlab = false;
-#else
-constexpr bool kRaysFastSlab = true;
-#endif
 typedef float ray_f2 __attribute__((ext_vector_type(2)));
 struct RayPk {
     ray_f2 p01, p20, p12, i01, i20, i12; // origin and reciprocals paired like a BBox{Float32}'s six floats: lo0 lo1 | lo2 up0 | up1 up2
@@ -96,7 +91,7 @@ __global__ __launch_bounds__(64) void rays_top_kernel(Args<L, N, I> a, RayBins r
     RayPk pk{};
     bool regular = true; // (idle lanes count as regular)
     constexpr bool kPacked = N::kind == IBVH_BBOX && std::is_same<T, float>::value; // (slab_fast is single precision)
-    const bool top_clean = kRaysFastSlab && kPacked && *rb.top_nan == 0; // (the knob rays_fast_slab = 0 stores -1 there)
+    const bool top_clean = kPacked && *rb.top_nan == 0;
     int ray = -1;
     uint32_t pi = 0, inode = 0, pend = 0, ord = 0;
     int level = 0;
@@ -375,10 +370,6 @@ template <class I> IBVH_D bool reserve_hits(const RayBins &rb, uint32_t &region,
     return false;
 }
 
-#ifdef IBVH_RAYSUB_HIST // (diagnostic build, tools/dbg_raysub_hist.py: wave-steps of the counting pass by number of busy lanes; [8], [9]: steps
-                        // after the wave's chunk ran dry with < 8 / >= 8 lanes busy)
-__device__ unsigned long long g_raysub_hist[16];
-#endif
 // ---- the tail of a rays_subtree_kernel workgroup (counting pass, round 6) -----------------------------------------------------
 // Walks still alive when their wave's chunk has run dry and <= tail_lanes lanes are busy are PARKED (<= RAYSUB_TAIL_MAX a wave) and
 // finished by the WHOLE workgroup as units (item, node whose two children are still to be tested): the walk's current node and
@@ -743,15 +734,6 @@ __global__ __launch_bounds__(RAYSUB_TPB) void rays_subtree_kernel(Args<L, N, I> 
                 }
             }
             const uint64_t idle_now = __builtin_amdgcn_ballot_w64(!busy);
-#ifdef IBVH_RAYSUB_HIST
-            if constexpr (!WRITE) {
-                if (lane == 0) {
-                    const int nb = 64 - __popcll(idle_now);
-                    atomicAdd(&g_raysub_hist[nb >= 64 ? 7 : nb / 8], 1ull);
-                    if (!more) atomicAdd(&g_raysub_hist[8 + (nb >= 8 ? 1 : 0)], 1ull);
-                }
-            }
-#endif
             if (idle_now == ~(uint64_t)0) break;
             if (more && __popcll(idle_now) >= 16) break;
             if (!more && 64 - __popcll(idle_now) <= tail_lanes) break;
@@ -797,7 +779,6 @@ int launch_rays_binned(const Args<L, N, I> &a, bool write, hipStream_t st, const
     const size_t lds = rays_subtree_lds(rb.depth, sizeof(N), sizeof(L), sizeof(I), sizeof(RayHit<I>), write);
     Args<L, N, I> standby = a;
     standby.gate = rb.flag;
-    standby.shadow = nullptr;
     const PairCache<I> none{nullptr, 0};
     if (!write) {
         // (header + the helper scans' header and tile aggregates right behind it: both scans take the one-kernel route, the second
@@ -805,7 +786,6 @@ int launch_rays_binned(const Args<L, N, I> &a, bool write, hipStream_t st, const
         const int64_t scan_words = 8 + ceil_div((int64_t)rb.cap > a.n_items ? (int64_t)rb.cap : a.n_items, (int64_t)SCAN_TILE) + 1;
         IBVH_HIP_CHECK(hipMemsetAsync(rb.cursor, 0, 2048 + (size_t)scan_words * 8, st));
         IBVH_HIP_CHECK(hipMemsetAsync(rb.bin_count, 0, (size_t)((char *)rb.items - (char *)rb.bin_count), st)); // counts, starts, cursors
-        if (!g_tuning.rays_fast_slab) IBVH_HIP_CHECK(hipMemsetAsync(rb.top_nan, 0xff, 4, st)); // (-1: no fast slab test anywhere)
         if constexpr (N::kind == IBVH_BBOX && std::is_same<typename N::elt, float>::value) {
             const int64_t top_first = level_start(a.tree.levels, a.tree.virtual_leaves, a.built_level) - 1; // (memory index of the first node that exists)
             const int64_t top_count = level_start(a.tree.levels, a.tree.virtual_leaves, rb.cut_level + 1) - 1 - top_first;
@@ -848,12 +828,3 @@ IBVH_FOR_SAME_FLOAT_COMBOS(IBVH_INSTANTIATE_RAYBINS, 0)
 } // namespace lvt
 } // namespace ibvh
 
-#ifdef IBVH_RAYSUB_HIST
-extern "C" int ibvh_debug_raysub_hist(unsigned long long *out /* 16 */, int reset) {
-    if (reset) {
-        unsigned long long z[16] = {};
-        return (int)hipMemcpyToSymbol(HIP_SYMBOL(ibvh::lvt::g_raysub_hist), z, sizeof(z));
-    }
-    return (int)hipMemcpyFromSymbol(out, HIP_SYMBOL(ibvh::lvt::g_raysub_hist), sizeof(unsigned long long) * 16);
-}
-#endif

@@ -84,9 +84,6 @@ __global__ __launch_bounds__(64) void lvt_rays_kernel(Args<L, N, I> a, PairCache
     uint32_t inode = 0, pend = 0;
     int level = 0;
     int64_t w = 0, cnt = 0;
-#ifdef IBVH_RAY_STEPS
-    int64_t steps = 0; // diagnostic build: the per-ray STEP count goes where the hit count belongs
-#endif
     bool meta_bad = false; // a position that does not fit the entry's meta field: the block walks again when writing
     int next = 0;          // wave-uniform: rays of the block handed out so far
 
@@ -115,7 +112,6 @@ __global__ __launch_bounds__(64) void lvt_rays_kernel(Args<L, N, I> a, PairCache
         if (idle != 0 && next < items_here) {
             const int rank = (int)__builtin_amdgcn_mbcnt_hi((uint32_t)(idle >> 32), __builtin_amdgcn_mbcnt_lo((uint32_t)idle, 0u));
             const int mine = next + rank;
-            bool took = false;
             if (ray < 0 && mine < items_here) {
                 const int64_t item = first_item + mine;
 #pragma unroll
@@ -124,11 +120,6 @@ __global__ __launch_bounds__(64) void lvt_rays_kernel(Args<L, N, I> a, PairCache
                     d[k] = a.dirs[3 * item + k];
                     inv[k] = T(1) / d[k];
                 }
-                // (behind the shadow walker this kernel serves the irregular rays only: Args::rays_filter)
-                took = !(a.rays_filter == 1 && ray_is_regular(p, d, inv));
-            }
-            if (took) {
-                const int64_t item = first_item + mine;
                 ray = mine;
                 pi = 0;
                 inode = pfirst;
@@ -140,17 +131,11 @@ __global__ __launch_bounds__(64) void lvt_rays_kernel(Args<L, N, I> a, PairCache
             const int taken = __popcll(idle);
             next = next + taken < items_here ? next + taken : items_here;
         }
-        if (__builtin_amdgcn_ballot_w64(ray >= 0) == 0) {
-            if (next >= items_here) break;
-            continue; // (a whole draw of rays that are not this launch's: draw again)
-        }
+        if (__builtin_amdgcn_ballot_w64(ray >= 0) == 0) break; // (an idle wave after the refill: the block is used up)
         // ---- walk: every busy lane advances its ray until a quarter of the wave has gone idle (or the block is used up
         // and everybody is done)
         for (;;) {
             if (ray >= 0) {
-#ifdef IBVH_RAY_STEPS
-                ++steps;
-#endif
                 const int cl = level + 1;
                 const uint32_t c0 = 2u * inode, c1 = c0 + 1u;
                 const uint32_t first = 1u << (cl - 1);
@@ -252,12 +237,7 @@ __global__ __launch_bounds__(64) void lvt_rays_kernel(Args<L, N, I> a, PairCache
                         inode = pfirst + pi;
                         level = plevel;
                     } else { // ray finished
-#ifdef IBVH_RAY_STEPS
-                        if constexpr (!WRITE) a.counts[first_item + ray] = (I)steps;
-                        steps = 0;
-#else
                         if constexpr (!WRITE) a.counts[first_item + ray] = (I)cnt;
-#endif
                         ray = -1;
                     }
                 }
@@ -273,27 +253,6 @@ __global__ __launch_bounds__(64) void lvt_rays_kernel(Args<L, N, I> a, PairCache
         const bool ok = __builtin_amdgcn_ballot_w64(meta_bad) == 0;
         if (region && lane == 0) *(int *)region = (s_fill <= entry_cap && ok) ? s_fill : -1;
     }
-}
-
-#ifdef IBVH_VARIANTS
-#include "../../variants/rays_shadow.inc"
-#endif
-
-// Bytes of the quantised shadow a ray traversal of `bvh` with `num_rays` rays uses, 0 when the binary walk serves it — always,
-// in the product library: the shadow walker is a development variant (variants/rays_shadow.inc, knob "rays_shadow").
-size_t rays_shadow_bytes(const ibvh_bvh &bvh, int64_t num_rays) {
-#ifdef IBVH_VARIANTS
-    // single-precision leaves under BBox{Float32} nodes, a fully built tree of 8 .. 26 levels, and enough rays for the one
-    // streaming pass over the nodes that builds the shadow to pay (at least one ray per 64 leaves)
-    if (bvh.types.node_kind != IBVH_BBOX || bvh.types.node_float != IBVH_F32 || bvh.types.leaf_float != IBVH_F32) return 0;
-    if (!g_tuning.rays_shadow) return 0;
-    if (bvh.built_level > 1 || num_rays * 64 < bvh.tree.real_leaves) return 0;
-    const RayShadow sh = make_ray_shadow(bvh.tree);
-    return sh.depths ? (size_t)sh.base[sh.depths] * SHADOW_ENTRY_BYTES : 0;
-#else
-    (void)bvh, (void)num_rays;
-    return 0;
-#endif
 }
 
 template <class L, class N, class I>
@@ -323,31 +282,6 @@ int launch_rays(const Args<L, N, I> &a, const PairCache<I> &cache, bool write, h
     if constexpr (kRayBinTypes<L, N>) {
         if (rb.cap > 0 && !count_work) return launch_rays_binned<L, N, I>(a, write, st, rb, ray_block, rblocks); // (3c), ibvh_lvt_raybins.hip
     }
-#ifdef IBVH_VARIANTS
-    if constexpr (std::is_same<typename L::elt, float>::value && std::is_same<N, BBox<float>>::value) {
-        if (a.shadow != nullptr && !count_work) {
-            // regular rays over the 8-wide shadow; the irregular ones (if any) by the binary walker behind it, without
-            // a cache of its own (the block headers belong to the shadow walker)
-            const ibvh_tree t{a.tree.levels, a.tree.real_leaves, 0, a.tree.virtual_leaves, 0};
-            const RayShadow sh = make_ray_shadow(t);
-            if (!write) // (the writing pass of a _count / _write pair finds the shadow where the count left it)
-                IBVH_LAUNCH((ray_shadow_build_kernel<N>), dim3((unsigned)ceil_div((int64_t)sh.base[sh.depths], 256)), dim3(256), 0, st, a.nodes,
-                            a.tree, sh, (ShadowEntry *)a.shadow);
-            Args<L, N, I> irr = a;
-            irr.rays_filter = 1;
-            const PairCache<I> none{nullptr, 0};
-            if (write) {
-                IBVH_LAUNCH((lvt_rays_wide_kernel<L, N, I, true>), dim3(rblocks), dim3(64), 0, st, a, cache, ray_block, sh);
-                IBVH_LAUNCH((lvt_rays_kernel<L, N, I, true>), dim3(rblocks), dim3(64), 0, st, irr, none, ray_block);
-            } else {
-                IBVH_LAUNCH((lvt_rays_wide_kernel<L, N, I, false>), dim3(rblocks), dim3(64), 0, st, a, cache, ray_block, sh);
-                IBVH_LAUNCH((lvt_rays_kernel<L, N, I, false>), dim3(rblocks), dim3(64), 0, st, irr, none, ray_block);
-            }
-            IBVH_LAUNCH_CHECK();
-            return IBVH_OK;
-        }
-    }
-#endif
     if constexpr (kWorkTypes<L, N, I>) {
         if (count_work) {
             IBVH_LAUNCH((lvt_rays_kernel<L, N, I, false, true>), dim3(rblocks), dim3(64), 0, st, a, cache, ray_block);

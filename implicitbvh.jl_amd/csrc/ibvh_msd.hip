@@ -1084,8 +1084,7 @@ static int launch_partitions(const Plan &p, const K *keys, int64_t n, const Reco
     const unsigned seg_grid = (unsigned)(p.max_seg < 1024 ? p.max_seg : 1024);
     for (int li = 0; li < levels; ++li) {
         const char *src = buf[li & 1];
-        const int measure = g_tuning.msd_range; // 0 = first extra level on the next 8 bits, unmeasured
-        const bool measured = li == 0 && measure != 0;
+        const bool measured = li == 0;
         if (measured) IBVH_LAUNCH((range_kernel<K>), dim3(stride_grid), dim3(256), 0, st, p.tb, li, (const K *)side[li & 1], tile);
         IBVH_LAUNCH((hist_level_kernel<K>), dim3(stride_grid), dim3(256), 0, st, p.tb, li, (const K *)side[li & 1], tile, measured ? 1 : 0);
         IBVH_LAUNCH((scan_level_kernel), dim3(seg_grid), dim3(1024), 0, st, p.tb, li, levels, cap, tile);

@@ -607,7 +607,7 @@ function lvt_two_pass(::Type{I}, like, n_items, types, slots, cache, count, writ
     need = Ref{Csize_t}(0)
     if isnothing(rays_of)
         check(c_lvt_scratch_bytes(types, n_items, slots, need), "ibvh_lvt_scratch_bytes")
-    else   # rays: room for the walker's quantised shadow of the node levels as well (include/ibvh.h)
+    else   # rays: room for the binned path's tables where it serves the batch (include/ibvh.h)
         check(c_rays_scratch_bytes(rays_of, n_items, slots, need), "ibvh_rays_scratch_bytes")
     end
     scratch = scratch!(:lvt, need[])

@@ -305,12 +305,9 @@ ibvh_status ibvh_traverse_pair_lvt_write(const ibvh_bvh *bvh1, const ibvh_bvh *b
  * and the walks are finished subtree by subtree out of LDS — the reference's walk cut in two, the same hit list in the same
  * order): 40 bytes x 16 items per ray (batches of up to 8 M rays).  A call that needs more raises a flag on the device and is served by the binary
  * walker in the same launch sequence; a caller that passes a smaller buffer (ibvh_lvt_scratch_bytes) gets the binary
- * walker from the start.  Otherwise it is ibvh_lvt_scratch_bytes(num_rays work items) — plus, ONLY while the development
- * knob "rays_shadow" is set (off by default: measured slower than the binary walk), room for a quantised
- * 8-wide shadow of the node levels that the counting call builds for itself and walks instead of the binary tree (one
- * 80-byte fetch per three levels; leaf parents' exact boxes and leaves still tested exactly: the hit list, order
- * included, is unchanged — csrc/ibvh_lvt.hip "(3b)").  Pass the SAME scratch buffer and size to a _count call and its
- * _write call. */
+ * walker from the start.  Otherwise it is ibvh_lvt_scratch_bytes(num_rays work items).  (A quantised 8-wide shadow
+ * walker, measured slower than the binary walk — DESIGN.md §8.3 — was removed from the sources; commit f9264f8 is the
+ * last that holds it.)  Pass the SAME scratch buffer and size to a _count call and its _write call. */
 ibvh_status ibvh_rays_scratch_bytes(const ibvh_bvh *bvh, int64_t num_rays, int32_t cache_slots, size_t *bytes_out);
 ibvh_status ibvh_traverse_rays_lvt_count(const ibvh_bvh *bvh, const void *points,
                                          const void *directions, int64_t num_rays,
@@ -620,11 +617,11 @@ ibvh_status ibvh_lvt_work_counters(const ibvh_bvh *bvh, const ibvh_bvh *bvh2, co
  * affect and not concurrently with them.  The library never reads the environment.  Names (exactly the table in
  * csrc/ibvh_core.hip; meanings: csrc/ibvh_common.hpp, struct Tuning): "ray_block", "lvt_wide", "lvt_xcd", "sort_tile",
  * "sort_lsd", "sort_msd_avg", "bucket_tpb", "msd", "msd_bits", "msd_cap", "msd_tile", "msd_ftpb", "msd_avg",
- * "msd_range", "msd_equalize", "msd_rescue", "lvt_scan_fused", "bfs_wg_per_cu", "lvt_blocks", "lvt_block_shift",
+ * "msd_equalize", "msd_rescue", "lvt_scan_fused", "bfs_wg_per_cu", "lvt_blocks", "lvt_block_shift",
  * "lvt_blocks_min_items", "lvt_blocks_paired_below", "rays_binned" (1 = the binned ray path where it pays, 2 =
- * wherever the tree allows it, 0 = never), "rays_fast_slab", "rays_subtree_depth", "rays_items_per_ray", "rays_tail",
- * "msd_resident_kb", "msd_finish_pad_kb".  Unknown name: IBVH_ERR_INVALID_ARG — that includes the names of
- * development variants whose kernels are not in libibvh.so (variants/ builds with -DIBVH_VARIANTS add their own). */
+ * wherever the tree allows it, 0 = never), "rays_subtree_depth", "rays_items_per_ray", "rays_tail",
+ * "msd_resident_kb", "msd_finish_pad_kb".  Unknown name: IBVH_ERR_INVALID_ARG — that includes the knobs of removed
+ * experiments (lvt_dual, rays_shadow, msd_range and rays_fast_slab; the last commit with them is f9264f8). */
 ibvh_status ibvh_set_tuning(const char *name, int32_t value);
 ibvh_status ibvh_get_tuning(const char *name, int32_t *value_out);
 
