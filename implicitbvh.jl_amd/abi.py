@@ -8,7 +8,7 @@ import ctypes as C
 
 import numpy as np
 
-ABI_VERSION = 5  # IBVH_ABI_VERSION of the include/ibvh.h this mirror was written against
+ABI_VERSION = 6  # IBVH_ABI_VERSION of the include/ibvh.h this mirror was written against
 
 # enums ---------------------------------------------------------------------------------------
 BSPHERE, BBOX = 0, 1
@@ -18,6 +18,7 @@ U16, U32, U64 = 0, 1, 2
 NARROW_NONE, NARROW_MORTON_LT, NARROW_INDEX_LT, NARROW_RAY_ORIGIN_OUTSIDE = 0, 1, 2, 3
 NARROW_MASK, OUTPUT_POSITIONS = 0xff, 0x100  # IBVH_NARROW_MASK, IBVH_OUTPUT_POSITIONS
 PAIR_SMALLER_DRIVES = 0x200  # IBVH_PAIR_SMALLER_DRIVES: pair LVT traversals, the BVH with fewer leaves supplies the work items (a set, not the reference's order)
+PAIR_MIXED_TYPES = 0x400  # IBVH_PAIR_MIXED_TYPES: pair LVT traversals of two BVHs of different leaf / node types (one index type)
 
 OK, ERR_INVALID_ARG, ERR_DOMAIN, ERR_UNSUPPORTED, ERR_CAPACITY, ERR_OVERFLOW, ERR_HIP, ERR_SCRATCH, ERR_PEER = range(9)
 
@@ -29,6 +30,10 @@ MORTON_BITS = {U16: 15, U32: 30, U64: 63}  # 3 x (5, 10, 21), morton/default.jl:
 
 class DomainError(ValueError):
     """Julia's DomainError (implicit_tree.jl:78-80)."""
+
+
+class MethodError(TypeError):
+    """Julia's MethodError: a conversion the reference has no method for (BSphere(::BBox), merge.jl)."""
 
 
 class CapacityError(RuntimeError):

@@ -969,7 +969,8 @@ def _cache_slots(cache, n_items, default):
     return max(default, min(64, want))
 
 
-def _lvt_scratch(cache, types, n_items, slots=None, rays_bvh=None):
+def _lvt_scratch(cache, types, n_items, slots=None, rays_bvh=None, types2=None):
+    """types2: the other BVH of a pair of two types (IBVH_PAIR_MIXED_TYPES): the larger of the two sizes (include/ibvh.h)."""
     k = _cache_slots(cache, n_items, LVT_CACHE_SLOTS if slots is None else slots)
 
     def scratch_need():
@@ -977,10 +978,13 @@ def _lvt_scratch(cache, types, n_items, slots=None, rays_bvh=None):
         if rays_bvh is not None:  # rays: room for the binned path's tables where it serves the batch (include/ibvh.h)
             s = rays_bvh.struct()
             lib.call("ibvh_rays_scratch_bytes", C.byref(s), int(n_items), k, C.byref(need))
-        else:
-            lib.call("ibvh_lvt_scratch_bytes", C.byref(types), int(n_items), k, C.byref(need))
-        return need.value
-    key = ("lvt_scratch", types.key(), int(n_items), k) if rays_bvh is None else \
+            return need.value
+        best = 0
+        for t in (types,) if types2 is None else (types, types2):
+            lib.call("ibvh_lvt_scratch_bytes", C.byref(t), int(n_items), k, C.byref(need))
+            best = max(best, need.value)
+        return best
+    key = ("lvt_scratch", types.key(), None if types2 is None else types2.key(), int(n_items), k) if rays_bvh is None else \
         ("rays_scratch", types.key(), int(n_items), k, len(rays_bvh.leaves), rays_bvh.built_level)
     need = _memo(key, scratch_need)
     s = cache._scratch if cache is not None else None
@@ -1034,8 +1038,17 @@ def _traverse_lvt_pair(bvh1, bvh2, sl1, sl2, narrow, cache):
         if not (b.built_level <= sl <= b.tree.levels <= 32):
             raise ValueError("bvh.built_level <= start_level <= bvh.tree.levels <= 32 must hold")
     n = max(len(bvh1.leaves), len(bvh2.leaves))
+    mixed = bvh1.types.key() != bvh2.types.key()
+    if mixed:  # two types (IBVH_PAIR_MIXED_TYPES): the walked tree's nodes are tested against NodeType(leaf) (traverse_pair.jl:196-197)
+        smaller = bool(narrow & abi.PAIR_SMALLER_DRIVES)
+        flip = len(bvh1.leaves) > len(bvh2.leaves) if smaller else not len(bvh1.leaves) >= len(bvh2.leaves)
+        drv, oth = (bvh2, bvh1) if flip else (bvh1, bvh2)
+        if drv.types.leaf_kind == abi.BBOX and oth.types.node_kind == abi.BSPHERE:
+            f = {abi.F32: "Float32", abi.F64: "Float64"}
+            raise abi.MethodError(f"no method matching BSphere{{{f[oth.types.node_float]}}}(::BBox{{{f[drv.types.leaf_float]}}})")
+        narrow |= abi.PAIR_MIXED_TYPES
     counts = _cache_tensor(cache.cache2 if cache else None, n, 0, idt, "cache2")
-    scratch = _lvt_scratch(cache, bvh1.types, n)
+    scratch = _lvt_scratch(cache, bvh1.types, n, types2=bvh2.types if mixed else None)
     sp, sn = _ptr(scratch), scratch.numel()
     s1, s2 = bvh1.struct(), bvh2.struct()
     spec = _speculative_buffer(cache, idt)

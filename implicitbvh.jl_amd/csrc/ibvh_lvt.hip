@@ -12,31 +12,6 @@
 namespace ibvh {
 namespace lvt {
 
-template <class L, class N, class I, int MODE>
-int launch(const Args<L, N, I> &a, const PairCache<I> &cache, bool write, hipStream_t st, const RayBins &rb = RayBins{}, bool *agg_zeroed = nullptr) {
-    if (a.n_items == 0) return IBVH_OK;
-    const bool count_work = a.work != nullptr; // (the counting pass of the COUNT instantiation; nothing else is launched)
-    if (count_work && (!kWorkTypes<L, N, I> || write)) return IBVH_ERR_UNSUPPORTED;
-    unsigned blocks = (unsigned)ceil_div(a.n_items, 256);
-    if constexpr (MODE == MODE_RAYS) {
-        return launch_rays<L, N, I>(a, cache, write, st, rb);
-    } else {
-        // BBox nodes with at least one node level below the start level: frontier descent + candidate queue (walker 2;
-        // trees deeper than 31 levels excepted: its wave-uniform arithmetic is 32-bit); everything else (BSphere nodes,
-        // start_level == levels): the exact joint walk
-        if constexpr (N::kind == IBVH_BBOX) {
-            if (a.start_level < a.tree.levels && a.tree.levels <= 31) return launch_queue<L, N, I, MODE>(a, cache, write, st, agg_zeroed);
-        }
-        if (count_work) return IBVH_ERR_UNSUPPORTED; // (BSphere nodes / start at the leaf level: the exact walk has no counters)
-        // (the exact walk keeps the run-time narrow switch: NARROW = true covers both)
-        if (write) IBVH_LAUNCH((lvt_joint_kernel<L, N, I, MODE, true, true>), dim3(blocks), dim3(256), 0, st, a, cache);
-        else IBVH_LAUNCH((lvt_joint_kernel<L, N, I, MODE, false, true>), dim3(blocks), dim3(256), 0, st, a, cache);
-    }
-    IBVH_LAUNCH_CHECK();
-    return IBVH_OK;
-}
-
-
 // shared driver of the six entry points
 template <int MODE>
 int run(const ibvh_bvh *drv, const ibvh_bvh *walk, const void *points, const void *dirs, int64_t n_items,
@@ -68,8 +43,12 @@ int run(const ibvh_bvh *drv, const ibvh_bvh *walk, const void *points, const voi
     // the caller sized it with ibvh_lvt_scratch_bytes; a smaller scratch simply has none (every wave descends on its own)
     // ... in front of them, every work item's .index (the counting pass writes it for the writing pass: Args::q_index_dense), when there
     // is room for both
+    // (the rows are covers of consecutive work items made of the DRIVING tree's nodes: only when those have the walked tree's node
+    // type — a mixed pair's driving nodes of another kind or float type are not rounded into covers, a BBox{Float64} rounded to
+    // Float32 may no longer contain its leaves)
+    const bool same_nodes = !drv || (drv->types.node_kind == walk->types.node_kind && drv->types.node_float == walk->types.node_float);
     size_t rows_bytes = 0, qidx_bytes = 0;
-    if (MODE != MODE_RAYS && !work && walk->types.node_kind == IBVH_BBOX) {
+    if (MODE != MODE_RAYS && !work && walk->types.node_kind == IBVH_BBOX && same_nodes) {
         rows_bytes = blk_rows_bytes(n_items, BLK_SHIFT_MIN);
         qidx_bytes = (size_t)align_up(n_items * (int64_t)(lay.pair_bytes / 2), 256);
         if (scratch_bytes < scan_scratch_bytes(n_items) + rows_bytes + qidx_bytes + 256) qidx_bytes = 0;
@@ -122,18 +101,31 @@ int run(const ibvh_bvh *drv, const ibvh_bvh *walk, const void *points, const voi
                 bool agg_zeroed = false;
                 a.blk_shift = 0;
                 const ibvh_bvh *qside = drv ? drv : walk;
-                a.q_nodes = (const N *)qside->nodes;
+                a.q_nodes = same_nodes ? (const N *)qside->nodes : nullptr;
                 a.q_tree = TreeDev{qside->tree.levels, qside->tree.real_leaves, qside->tree.virtual_leaves};
                 a.q_built_level = qside->built_level;
                 PairCache<I> cache{K ? (IndexPair<I> *)((char *)scratch + scan_scratch_bytes(n_items)) : nullptr, K};
-                if (int e = launch<L, N, I, MODE>(a, cache, write, st, bins, &agg_zeroed)) return e;
+                // one pass: the walked leaves' own type, or (a mixed pair, IBVH_PAIR_MIXED_TYPES) the driving leaves' type Q
+                auto pass = [&](bool wr, bool *agg) -> int {
+                    if constexpr (MODE != MODE_PAIR) {
+                        return launch<L, N, I, MODE>(a, cache, wr, st, bins, agg);
+                    } else {
+                        return dispatch_volume(drv->types.leaf_kind, drv->types.leaf_float, [&](auto qt) -> int {
+                            using Q = typename decltype(qt)::type;
+                            if constexpr (std::is_same<Q, L>::value) return launch<L, N, I, MODE>(a, cache, wr, st, bins, agg);
+                            else if constexpr (N::kind == IBVH_BSPHERE && Q::kind != IBVH_BSPHERE) return (int)IBVH_ERR_UNSUPPORTED; // (pair_common refuses it first)
+                            else return launch_pair_mixed<Q, L, N, I>(a, cache, wr, st, agg);
+                        });
+                    }
+                };
+                if (int e = pass(write, &agg_zeroed)) return e;
                 if (write || work) return (int)IBVH_OK;
                 if (int e = scan_counts<I>((I *)counts, n_items, enqueue ? nullptr : total_out, scratch, st, enqueue ? total_dev : nullptr,
                                            enqueue ? total_host : nullptr, nullptr, agg_zeroed)) return e;
                 if (enqueue && capacity > 0) {
                     a.guard_total = total_dev ? (const int64_t *)total_dev : (const int64_t *)scratch; // the total contacts
                     a.guard_capacity = sizeof(I) == 4 && capacity > (int64_t)INT32_MAX ? (int64_t)INT32_MAX : capacity;
-                    return launch<L, N, I, MODE>(a, cache, true, st, bins);
+                    return pass(true, nullptr);
                 }
                 return (int)IBVH_OK;
             });
@@ -265,7 +257,10 @@ static ibvh_status pair_common(const ibvh_bvh *bvh1, const ibvh_bvh *bvh2, int64
     if (!bvh1 || !bvh2) return IBVH_ERR_INVALID_ARG;
     if (int e = check_levels(*bvh1, sl1)) return (ibvh_status)e;
     if (int e = check_levels(*bvh2, sl2)) return (ibvh_status)e;
-    if (!same_types(bvh1->types, bvh2->types)) return IBVH_ERR_UNSUPPORTED;
+    // IBVH_PAIR_MIXED_TYPES: any two types with one index type (:50-52); without it, one type
+    const bool mixed = (narrow & IBVH_PAIR_MIXED_TYPES) != 0;
+    narrow &= ~IBVH_PAIR_MIXED_TYPES;
+    if (mixed ? bvh1->types.index_type != bvh2->types.index_type : !same_types(bvh1->types, bvh2->types)) return IBVH_ERR_UNSUPPORTED;
     if (!counts) return IBVH_ERR_INVALID_ARG;
     // the BVH with more leaves supplies the work items; flip restores (bvh1, bvh2) order (:15-36).  IBVH_PAIR_SMALLER_DRIVES: the
     // other way round (the contact SET is the same; the list's order is the smaller BVH's leaf order)
@@ -273,6 +268,8 @@ static ibvh_status pair_common(const ibvh_bvh *bvh1, const ibvh_bvh *bvh2, int64
     narrow &= ~IBVH_PAIR_SMALLER_DRIVES;
     const bool flip = smaller ? bvh1->tree.real_leaves > bvh2->tree.real_leaves : !(bvh1->tree.real_leaves >= bvh2->tree.real_leaves);
     const ibvh_bvh *drv = flip ? bvh2 : bvh1, *oth = flip ? bvh1 : bvh2;
+    // the walked tree's nodes are tested against NodeType(query) (:196-197): there is no BSphere(::BBox), the reference raises
+    if (drv->types.leaf_kind == IBVH_BBOX && oth->types.node_kind == IBVH_BSPHERE) return IBVH_ERR_UNSUPPORTED;
     return (ibvh_status)run<MODE_PAIR>(drv, oth, nullptr, nullptr, drv->tree.real_leaves, flip ? sl1 : sl2, narrow,
                                        flip ? 1 : 0, counts, total_out, contacts, scratch, scratch_bytes,
                                        (hipStream_t)stream, enqueue, capacity, (int64_t *)total_dev, (int64_t *)total_host);

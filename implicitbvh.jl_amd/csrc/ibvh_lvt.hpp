@@ -5,6 +5,8 @@
 //   ibvh_lvt.hip          entry points (extern "C"), type dispatch, the two-pass protocol (count -> scan -> write)
 //   ibvh_lvt_queue_*.hip  walker 2, lvt_queue_kernel (BBox nodes: frontier descent + candidate-pair queue), one unit
 //                         per mode (self / pair) — ibvh_lvt_queue.inc holds the kernel
+//   ibvh_lvt_mixed_*.hip  pair walks of two BVHs of different types (IBVH_PAIR_MIXED_TYPES): walkers 1 and 2 with the driving
+//                         leaves' type Q as the query type, split over four units (ibvh_lvt_mixed.inc, IBVH_FOR_MIXED_* below)
 //   ibvh_lvt_rays.hip     walker 3, lvt_rays_kernel (per-lane ray walk)
 //   ibvh_lvt_raybins.hip  walker 4, rays binned by subtree (rays_top / tilehist / binscan / scatter / subtree / place)
 //
@@ -179,14 +181,16 @@ template <class I> struct PairCache {
 constexpr int BRUTE_DEPTH = 7; // 2^7 = 128 leaves, 64 leaf-parents (one per lane) per brute-forced subtree
 constexpr int FRONTIER_CAP = 256; // frontier entries per wave and level (LDS); overflow -> exact walk
 
-// Per-lane query state + the emission rules shared by both kernels.
-template <class L, class N, class I, int MODE, bool WRITE, bool NARROW> struct Query {
+// Per-lane query state + the emission rules shared by both kernels.  Q: the query leaves' volume type — the walked tree's leaf
+// type L except in a pair walk of two BVHs of different types (IBVH_PAIR_MIXED_TYPES), which reads the work items as Q, tests
+// nodes with q_node = N(q_leaf) and leaves with iscontact(q_leaf, leaf) on the raw mixed types (lvt/traverse_pair.jl:196-197).
+template <class L, class N, class I, int MODE, bool WRITE, bool NARROW, class Q = L> struct Query {
     using Cnt = typename std::conditional<sizeof(I) == 8, int64_t, int32_t>::type; // contact counters / offsets
     const Args<L, N, I> &a;
     PairCache<I> cache; // (a copy: the queue kernel's fallback switches the cache off for its wave)
     int64_t item;
     bool valid, lane_on;
-    L q_leaf;
+    Q q_leaf;
     N q_node;
     I q_index;
     uint64_t q_morton;
@@ -221,7 +225,7 @@ template <class L, class N, class I, int MODE, bool WRITE, bool NARROW> struct Q
             // a.items / a.items_lay, six scalar registers that would otherwise stay live through the whole kernel)
             const LeafLayout &il = MODE == MODE_SELF ? a.lay : a.items_lay;
             const char *rec = (MODE == MODE_SELF ? a.leaves : a.items) + item * il.stride;
-            q_leaf = load_vol<L>(rec);
+            q_leaf = load_vol<Q>(rec);
             q_node = convert_to(q_leaf, (N *)nullptr); // traverse_single.jl:154-155
             q_index = load_index<I>(rec, il);
             if constexpr (NARROW)
@@ -265,8 +269,8 @@ template <class L, class N, class I, int MODE, bool WRITE, bool NARROW> struct Q
 };
 
 // ---- (1) exact wave-uniform pre-order walk ------------------------------------------------------
-template <class L, class N, class I, int MODE, bool WRITE, bool NARROW>
-IBVH_D void joint_walk(Query<L, N, I, MODE, WRITE, NARROW> &q, const Args<L, N, I> &a) {
+template <class L, class N, class I, int MODE, bool WRITE, bool NARROW, class Q>
+IBVH_D void joint_walk(Query<L, N, I, MODE, WRITE, NARROW, Q> &q, const Args<L, N, I> &a) {
     const int64_t levels = a.tree.levels, vl = a.tree.virtual_leaves;
     const uint32_t leaf_first = 1u << (levels - 1);
     const uint64_t self_next = (uint64_t)q.item + leaf_first + 1; // SELF: implicit index of this leaf, plus one
@@ -355,9 +359,9 @@ IBVH_D void joint_walk(Query<L, N, I, MODE, WRITE, NARROW> &q, const Args<L, N, 
     }
 }
 
-template <class L, class N, class I, int MODE, bool WRITE, bool NARROW>
+template <class L, class N, class I, int MODE, bool WRITE, bool NARROW, class Q = L>
 __global__ __launch_bounds__(256) void lvt_joint_kernel(Args<L, N, I> a, PairCache<I> cache) {
-    Query<L, N, I, MODE, WRITE, NARROW> q(a, cache);
+    Query<L, N, I, MODE, WRITE, NARROW, Q> q(a, cache);
     if constexpr (WRITE)
         if (!q.begin_write()) return;
     joint_walk(q, a);
@@ -929,8 +933,9 @@ template <class L, class N> constexpr bool kRayBinTypes = std::is_same<typename 
 
 // ---- launchers, one per walker, each defined (and explicitly instantiated for every type combination the dispatch can
 // reach: IBVH_FOR_* below) in its own translation unit ------------------------------------------------------------------
-// walker 2: a.start_level < a.tree.levels <= 31, BBox nodes (ibvh_lvt_queue_self.hip / ibvh_lvt_queue_pair.hip)
-template <class L, class N, class I, int MODE>
+// walker 2: a.start_level < a.tree.levels <= 31, BBox nodes (ibvh_lvt_queue_self.hip / ibvh_lvt_queue_pair.hip; Q != L:
+// ibvh_lvt_mixed_*.hip)
+template <class L, class N, class I, int MODE, class Q = L>
 int launch_queue(const Args<L, N, I> &a, const PairCache<I> &cache, bool write, hipStream_t st, bool *agg_zeroed = nullptr);
 // walkers 3 and 4: the whole ray traversal of one pass (ibvh_lvt_rays.hip; it hands over to launch_rays_binned when rb.cap > 0)
 template <class L, class N, class I>
@@ -941,6 +946,40 @@ int launch_rays_standby(const Args<L, N, I> &standby, bool write, hipStream_t st
 // walker 4 (ibvh_lvt_raybins.hip)
 template <class L, class N, class I>
 int launch_rays_binned(const Args<L, N, I> &a, bool write, hipStream_t st, const RayBins &rb, int ray_block, unsigned rblocks);
+
+// Pair walks of two BVHs of different types (IBVH_PAIR_MIXED_TYPES): the queue walker serves queries of the walked leaves' float
+// type, the exact joint walk cross-float ones (the build-time budget: one set of queue instantiations instead of three)
+template <class Q, class L> constexpr bool kQueueQuery = std::is_same<typename Q::elt, typename L::elt>::value;
+
+// one pass of a SELF / PAIR / RAYS walk with the walker the tree and the query type call for (Q: the query leaves' type, Query)
+template <class L, class N, class I, int MODE, class Q = L>
+int launch(const Args<L, N, I> &a, const PairCache<I> &cache, bool write, hipStream_t st, const RayBins &rb = RayBins{}, bool *agg_zeroed = nullptr) {
+    static_assert(std::is_same<Q, L>::value || MODE == MODE_PAIR, "only a pair walk has queries of another type");
+    if (a.n_items == 0) return IBVH_OK;
+    const bool count_work = a.work != nullptr; // (the counting pass of the COUNT instantiation; nothing else is launched)
+    if (count_work && (!(kWorkTypes<L, N, I> && std::is_same<Q, L>::value) || write)) return IBVH_ERR_UNSUPPORTED;
+    unsigned blocks = (unsigned)ceil_div(a.n_items, 256);
+    if constexpr (MODE == MODE_RAYS) {
+        return launch_rays<L, N, I>(a, cache, write, st, rb);
+    } else {
+        // BBox nodes with at least one node level below the start level: frontier descent + candidate queue (walker 2;
+        // trees deeper than 31 levels excepted: its wave-uniform arithmetic is 32-bit); everything else (BSphere nodes,
+        // start_level == levels, cross-float queries): the exact joint walk
+        if constexpr (N::kind == IBVH_BBOX && kQueueQuery<Q, L>) {
+            if (a.start_level < a.tree.levels && a.tree.levels <= 31) return launch_queue<L, N, I, MODE, Q>(a, cache, write, st, agg_zeroed);
+        }
+        if (count_work) return IBVH_ERR_UNSUPPORTED; // (BSphere nodes / start at the leaf level: the exact walk has no counters)
+        // (the exact walk keeps the run-time narrow switch: NARROW = true covers both)
+        if (write) IBVH_LAUNCH((lvt_joint_kernel<L, N, I, MODE, true, true, Q>), dim3(blocks), dim3(256), 0, st, a, cache);
+        else IBVH_LAUNCH((lvt_joint_kernel<L, N, I, MODE, false, true, Q>), dim3(blocks), dim3(256), 0, st, a, cache);
+    }
+    IBVH_LAUNCH_CHECK();
+    return IBVH_OK;
+}
+// launch<L, N, I, MODE_PAIR, Q> for Q != L, instantiated in ibvh_lvt_mixed_*.hip (IBVH_FOR_MIXED_* below) so that ibvh_lvt.hip,
+// which dispatches to it, does not compile those walkers itself
+template <class Q, class L, class N, class I>
+int launch_pair_mixed(const Args<L, N, I> &a, const PairCache<I> &cache, bool write, hipStream_t st, bool *agg_zeroed);
 
 // The (leaf, node, index) combinations dispatch_leaf_node / dispatch_index reach (ibvh_common.hpp): X(L, N, I, extra...)
 #ifdef IBVH_ONLY_BENCH_TYPES
@@ -971,6 +1010,46 @@ int launch_rays_binned(const Args<L, N, I> &a, bool write, hipStream_t st, const
     IBVH_FOR_INDEX(X, BSphere<double>, BSphere<double>, __VA_ARGS__) \
     IBVH_FOR_INDEX(X, BSphere<double>, BBox<double>, __VA_ARGS__)    \
     IBVH_FOR_INDEX(X, BBox<double>, BBox<double>, __VA_ARGS__)
+#endif
+
+// The mixed pair walks (IBVH_PAIR_MIXED_TYPES): X(Q, L, N, I) for every driving leaf type Q != the walked tree's leaf type L that
+// N(Q) exists for (no BSphere(::BBox)): the same-float ones run walker 2 (QUEUE, BBox nodes), the cross-float ones and BSphere nodes
+// walker 1 (JOINT).  The development build keeps Float32 particles against Float32 boxes (tools/bench_pair_mixed.py).
+#ifdef IBVH_ONLY_BENCH_TYPES
+#define IBVH_MIXED_Q(X, Q_, L_, N_) X(Q_, L_, N_, int32_t)
+#define IBVH_FOR_MIXED_QUEUE_A(X) IBVH_MIXED_Q(X, BBox<float>, BSphere<float>, BBox<float>) IBVH_MIXED_Q(X, BSphere<float>, BBox<float>, BBox<float>)
+#define IBVH_FOR_MIXED_QUEUE_B(X)
+#define IBVH_FOR_MIXED_QUEUE_C(X)
+#define IBVH_FOR_MIXED_JOINT(X)
+#else
+#define IBVH_MIXED_Q(X, Q_, L_, N_) X(Q_, L_, N_, int32_t) X(Q_, L_, N_, int64_t)
+#define IBVH_FOR_MIXED_QUEUE_A(X)                                   \
+    IBVH_MIXED_Q(X, BBox<float>, BSphere<float>, BBox<float>)      \
+    IBVH_MIXED_Q(X, BSphere<float>, BBox<float>, BBox<float>)      \
+    IBVH_MIXED_Q(X, BBox<double>, BSphere<double>, BBox<float>)
+#define IBVH_FOR_MIXED_QUEUE_B(X)                                   \
+    IBVH_MIXED_Q(X, BSphere<double>, BBox<double>, BBox<float>)    \
+    IBVH_MIXED_Q(X, BBox<float>, BSphere<float>, BBox<double>)     \
+    IBVH_MIXED_Q(X, BSphere<float>, BBox<float>, BBox<double>)
+#define IBVH_FOR_MIXED_QUEUE_C(X)                                   \
+    IBVH_MIXED_Q(X, BBox<double>, BSphere<double>, BBox<double>)   \
+    IBVH_MIXED_Q(X, BSphere<double>, BBox<double>, BBox<double>)
+#define IBVH_FOR_MIXED_JOINT_N(X, N_)                           \
+    IBVH_MIXED_Q(X, BSphere<double>, BSphere<float>, N_)       \
+    IBVH_MIXED_Q(X, BBox<double>, BSphere<float>, N_)          \
+    IBVH_MIXED_Q(X, BSphere<double>, BBox<float>, N_)          \
+    IBVH_MIXED_Q(X, BBox<double>, BBox<float>, N_)             \
+    IBVH_MIXED_Q(X, BSphere<float>, BSphere<double>, N_)       \
+    IBVH_MIXED_Q(X, BBox<float>, BSphere<double>, N_)          \
+    IBVH_MIXED_Q(X, BSphere<float>, BBox<double>, N_)          \
+    IBVH_MIXED_Q(X, BBox<float>, BBox<double>, N_)
+#define IBVH_FOR_MIXED_JOINT(X)                                    \
+    IBVH_FOR_MIXED_JOINT_N(X, BBox<float>)                        \
+    IBVH_FOR_MIXED_JOINT_N(X, BBox<double>)                       \
+    IBVH_MIXED_Q(X, BSphere<double>, BSphere<float>, BSphere<float>)   \
+    IBVH_MIXED_Q(X, BSphere<float>, BSphere<double>, BSphere<float>)   \
+    IBVH_MIXED_Q(X, BSphere<double>, BSphere<float>, BSphere<double>)  \
+    IBVH_MIXED_Q(X, BSphere<float>, BSphere<double>, BSphere<double>)
 #endif
 
 } // namespace lvt

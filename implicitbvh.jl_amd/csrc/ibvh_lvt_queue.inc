@@ -546,12 +546,13 @@ template <class L, class N, class I, bool WIDE, bool WRITE = false> constexpr in
     return WRITE ? QUEUE_MINWAVES - 1 : QUEUE_MINWAVES;
 }
 // WIDE: 64-bit queue entries for trees of 29 .. 31 levels (leaf-parent indices beyond 2^26), see launch().
-template <class L, class N, class I, int MODE, bool WRITE, bool NARROW, bool WIDE, bool COUNT = false>
+// Q: the query leaves' volume type (Query); pair walks of two BVHs of different types only
+template <class L, class N, class I, int MODE, bool WRITE, bool NARROW, bool WIDE, bool COUNT = false, class Q = L>
 __global__ __launch_bounds__(64 * QUEUE_WAVES, (queue_min_waves<L, N, I, WIDE, WRITE>())) void lvt_queue_kernel(Args<L, N, I> a, PairCache<I> cache, int cut_level) {
     using TN = typename N::elt;
     Work<COUNT> work; // (COUNT: one lane-level box / sphere test = one count; lane 0 carries the wave-uniform parts)
-    using Q = Query<L, N, I, MODE, WRITE, NARROW>;
-    using Cnt = typename Q::Cnt;
+    using QS = Query<L, N, I, MODE, WRITE, NARROW, Q>;
+    using Cnt = typename QS::Cnt;
     __shared__ uint32_t s_frontier[QUEUE_WAVES][2][FRONTIER_CAP];
     using QE = typename std::conditional<WIDE, uint64_t, uint32_t>::type; // queue entry: query lane | leaf-parent index << 6
     __shared__ QE s_queue[QUEUE_WAVES][QUEUE_CAP];
@@ -560,7 +561,7 @@ __global__ __launch_bounds__(64 * QUEUE_WAVES, (queue_min_waves<L, N, I, WIDE, W
     Sections sec;
     sec.start();
     const bool dense_index = WRITE && a.q_index_dense != nullptr; // (the counting pass left every item's .index in a dense array)
-    Q q(a, cache, dense_index);
+    QS q(a, cache, dense_index);
     const int lane = threadIdx.x & 63, wv = __builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6)); // (uniform: LDS bases stay scalar)
     if constexpr (!WRITE && !COUNT) {
         if (a.q_index_dense != nullptr && q.valid) a.q_index_dense[q.item] = q.q_index;
@@ -823,7 +824,7 @@ __global__ __launch_bounds__(64 * QUEUE_WAVES, (queue_min_waves<L, N, I, WIDE, W
                 mor_b = load_morton(rec_b, a.lay);
             }
         }
-        const L ql = shuffle_from(q.q_leaf, qi);
+        const Q ql = shuffle_from(q.q_leaf, qi);
         const I qidx = __shfl(q.q_index, qi, 64);
         const uint32_t item_q = wave_item0 + (uint32_t)qi;
         bool hit_a = v & iscontact(ql, leaf_a), hit_b = has_b & iscontact(ql, leaf_b);
@@ -1174,7 +1175,7 @@ __global__ __launch_bounds__(64 * QUEUE_WAVES, (queue_min_waves<L, N, I, WIDE, W
     sec.flush();
 }
 
-template <class L, class N, class I, int MODE>
+template <class L, class N, class I, int MODE, class Q>
 int launch_queue(const Args<L, N, I> &a, const PairCache<I> &cache, bool write, hipStream_t st, bool *agg_zeroed) {
     static_assert(N::kind == IBVH_BBOX, "walker 2 needs nested node boxes");
     const bool count_work = a.work != nullptr;
@@ -1195,7 +1196,7 @@ int launch_queue(const Args<L, N, I> &a, const PairCache<I> &cache, bool write, 
     aq.start_level = top; // also when the caller named a HIGHER level: levels 1..6 hold < 64 nodes each
     const int64_t c = aq.tree.levels - BRUTE_DEPTH;
     const int cut = (int)(c > aq.start_level ? c : aq.start_level);
-    if constexpr (kWorkTypes<L, N, I>) {
+    if constexpr (kWorkTypes<L, N, I> && std::is_same<Q, L>::value) {
         if (count_work) {
             if (wide || aq.narrow != IBVH_NARROW_NONE) return IBVH_ERR_UNSUPPORTED;
             IBVH_LAUNCH((lvt_queue_kernel<L, N, I, MODE, false, false, false, true>), dim3(qblocks), dim3(64 * QUEUE_WAVES), 0, st,
@@ -1233,7 +1234,7 @@ int launch_queue(const Args<L, N, I> &a, const PairCache<I> &cache, bool write, 
     if (agg_zeroed) *agg_zeroed = !write && aq.scan_agg != nullptr;
     const int variant = (write ? 1 : 0) | (aq.narrow != IBVH_NARROW_NONE ? 2 : 0) | (wide ? 4 : 0);
 #define IBVH_QUEUE_LAUNCH(W_, N_, D_)                                                                                 \
-    IBVH_LAUNCH((lvt_queue_kernel<L, N, I, MODE, W_, N_, D_>), dim3(qblocks), dim3(64 * QUEUE_WAVES), 0, st, aq, cache, cut)
+    IBVH_LAUNCH((lvt_queue_kernel<L, N, I, MODE, W_, N_, D_, false, Q>), dim3(qblocks), dim3(64 * QUEUE_WAVES), 0, st, aq, cache, cut)
     switch (variant) {
     case 0: IBVH_QUEUE_LAUNCH(false, false, false); break;
     case 1: IBVH_QUEUE_LAUNCH(true, false, false); break;
@@ -1250,7 +1251,7 @@ int launch_queue(const Args<L, N, I> &a, const PairCache<I> &cache, bool write, 
 }
 
 #define IBVH_INSTANTIATE_QUEUE(L_, N_, I_, MODE_) \
-    template int launch_queue<L_, N_, I_, MODE_>(const Args<L_, N_, I_> &, const PairCache<I_> &, bool, hipStream_t, bool *);
+    template int launch_queue<L_, N_, I_, MODE_, L_>(const Args<L_, N_, I_> &, const PairCache<I_> &, bool, hipStream_t, bool *);
 
 } // namespace lvt
 } // namespace ibvh

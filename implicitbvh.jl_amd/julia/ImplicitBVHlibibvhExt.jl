@@ -37,7 +37,7 @@ const libibvh = get(ENV, "LIBIBVH", "libibvh.so")
 
 # The header this file was written against (include/ibvh.h, IBVH_ABI_VERSION).  A library with another struct layout or
 # argument list would make the GPU write through garbage pointers, so a mismatch is refused when the extension loads.
-const IBVH_ABI_VERSION = Int32(5)
+const IBVH_ABI_VERSION = Int32(6)
 function __init__()
     got = ccall((:ibvh_abi_version, libibvh), Int32, ())
     got == IBVH_ABI_VERSION ||
@@ -110,6 +110,7 @@ end
 
 const IBVH_ERR_UNSUPPORTED = Cint(3)
 const IBVH_ERR_CAPACITY = Cint(4)
+const IBVH_PAIR_MIXED_TYPES = Int32(0x400)   # pair LVT traversals of two BVHs of different leaf / node types (include/ibvh.h)
 
 # status -> the exception the reference throws in the same situation
 function check(status::Cint, what)
@@ -602,11 +603,17 @@ cached(cache, field::Symbol, ::Type{T}, n, like) where {T} =
     end
 
 # `count`, `write`, `enqueue`: closures over the entry points of one traversal shape; they take the buffers only.
-function lvt_two_pass(::Type{I}, like, n_items, types, slots, cache, count, write, enqueue; rays_of=nothing) where {I}
+# types2: the other BVH's types of a pair of two types (IBVH_PAIR_MIXED_TYPES): the scratch is the larger of the two sizes.
+function lvt_two_pass(::Type{I}, like, n_items, types, slots, cache, count, write, enqueue; rays_of=nothing, types2=nothing) where {I}
     counts = cached(cache, :cache2, I, n_items, like)
     need = Ref{Csize_t}(0)
     if isnothing(rays_of)
         check(c_lvt_scratch_bytes(types, n_items, slots, need), "ibvh_lvt_scratch_bytes")
+        if !isnothing(types2)
+            need2 = Ref{Csize_t}(0)
+            check(c_lvt_scratch_bytes(types2, n_items, slots, need2), "ibvh_lvt_scratch_bytes")
+            need[] = max(need[], need2[])
+        end
     else   # rays: room for the binned path's tables where it serves the batch (include/ibvh.h)
         check(c_rays_scratch_bytes(rays_of, n_items, slots, need), "ibvh_rays_scratch_bytes")
     end
@@ -663,6 +670,15 @@ function ImplicitBVH.traverse(
     BVHTraversal(Int(start_level), 0, total, contacts, counts)
 end
 
+# Two BVHs of different leaf / node types the library walks (IBVH_PAIR_MIXED_TYPES): one index type (:50-52), and the
+# driving BVH — the one with more leaves (:15-36) — has leaves the walked tree's node type can be made of (:196-197): there
+# is no BSphere(::BBox), so a BBox-leaf driver against BSphere nodes goes to the generic method, which raises its MethodError.
+function mixed_ok(d1, d2, n1, n2)
+    d1.types.index_type == d2.types.index_type || return false
+    drv, oth = n1 >= n2 ? (d1, d2) : (d2, d1)
+    !(drv.types.leaf_kind == kind(BBox) && oth.types.node_kind == kind(BSphere))
+end
+
 # traverse(bvh1, bvh2, LVTTraversal()) — lvt/traverse_pair.jl:1-116 (the library picks the BVH with more leaves as
 # the driver and flips the pairs back: contacts are always (index in bvh1, index in bvh2))
 function ImplicitBVH.traverse(
@@ -675,8 +691,8 @@ function ImplicitBVH.traverse(
 ) where {I}
     code = narrow_code(narrow)
     d1, d2 = bvh_desc(bvh1), bvh_desc(bvh2)
-    # closures, types without an instantiation, and pairs of different leaf / node types: generic method
-    if isnothing(code) || isnothing(d1) || isnothing(d2) || d1.types != d2.types
+    # closures, types without an instantiation, and pairs of different types the library refuses (mixed_ok): generic method
+    if isnothing(code) || isnothing(d1) || isnothing(d2) || (d1.types != d2.types && !mixed_ok(d1, d2, length(bvh1.leaves), length(bvh2.leaves)))
         return invoke(ImplicitBVH.traverse, Tuple{BVH, BVH, LVTTraversal}, bvh1, bvh2, alg;
                       start_level1=start_level1, start_level2=start_level2, narrow=narrow, cache=cache, options=options)
     end
@@ -685,12 +701,15 @@ function ImplicitBVH.traverse(
     bvh2.built_level <= start_level2 <= bvh2.tree.levels <= 32 ||
         throw(ArgumentError("bvh2.built_level <= start_level2 <= bvh2.tree.levels <= 32 must hold"))
     get_index_type(bvh2) === I || throw(ArgumentError("get_index_type(bvh2) === I must hold"))   # :50-52
+    mixed = d1.types != d2.types
+    pcode = mixed ? code | IBVH_PAIR_MIXED_TYPES : code
     s = stream_ptr()
     n_items = max(length(bvh1.leaves), length(bvh2.leaves))
     total, contacts, counts = lvt_two_pass(I, bvh1.nodes, n_items, d1.types, cache_slots(cache, n_items, LVT_CACHE_SLOTS), cache,
-        (cn, tot, sc, sb) -> c_traverse_pair_lvt_count(d1, d2, start_level1, start_level2, code, devptr(cn), tot, devptr(sc), sb, s),
-        (cn, ct, sc, sb) -> c_traverse_pair_lvt_write(d1, d2, start_level1, start_level2, code, devptr(cn), devptr(ct), devptr(sc), sb, s),
-        (cn, ct, cap, td, th, sc, sb) -> c_traverse_pair_lvt_enqueue(d1, d2, start_level1, start_level2, code, devptr(cn), devptr(ct), cap, td, th, devptr(sc), sb, s))
+        (cn, tot, sc, sb) -> c_traverse_pair_lvt_count(d1, d2, start_level1, start_level2, pcode, devptr(cn), tot, devptr(sc), sb, s),
+        (cn, ct, sc, sb) -> c_traverse_pair_lvt_write(d1, d2, start_level1, start_level2, pcode, devptr(cn), devptr(ct), devptr(sc), sb, s),
+        (cn, ct, cap, td, th, sc, sb) -> c_traverse_pair_lvt_enqueue(d1, d2, start_level1, start_level2, pcode, devptr(cn), devptr(ct), cap, td, th, devptr(sc), sb, s);
+        types2=mixed ? d2.types : nothing)
     BVHTraversal(Int(start_level1), Int(start_level2), 0, total, contacts, counts)
 end
 

@@ -39,8 +39,9 @@ extern "C" {
  *   1: round 1   2: ibvh_build_desc.sort_levels / skew_flag, ibvh_bfs_result.resume_*, *_enqueue(total_dev)
  *   3: *_enqueue(total_host), ibvh_set_tuning, ibvh_lvt_work_counters, ray `narrow`, contact positions
  *   4: the multi-GPU driver (ibvh_comm, ibvh_dist_*)
- *   5: ibvh_dist_cross_* (boundary leaves), ibvh_comm_release, ibvh_build_desc.sort_equalize (was reserved_: same layout) */
-#define IBVH_ABI_VERSION 5
+ *   5: ibvh_dist_cross_* (boundary leaves), ibvh_comm_release, ibvh_build_desc.sort_equalize (was reserved_: same layout)
+ *   6: IBVH_PAIR_MIXED_TYPES (pair LVT traversals of two BVHs of different leaf / node types) */
+#define IBVH_ABI_VERSION 6
 int32_t ibvh_abi_version(void);
 
 /* ----------------------------------------------------------------------------------- */
@@ -93,7 +94,17 @@ enum {
      * contact SET.  A handful of leaves against a large tree then costs (few leaves) x (tree depth) instead of one work item —
      * and 8 cached contacts of scratch — per leaf of the large tree; the cross-shard completion uses it (a slice's thin boundary
      * shell against the neighbour's whole slice).  Size the scratch and `counts` for min(n1, n2) items then. */
-    IBVH_PAIR_SMALLER_DRIVES = 0x200
+    IBVH_PAIR_SMALLER_DRIVES = 0x200,
+    /* Pair LVT traversals only (ibvh_traverse_pair_lvt_{count,write,enqueue}): accept two BVHs of DIFFERENT leaf / node / Morton
+     * types with one index type (lvt/traverse_pair.jl:50-52).  Without the flag such a pair returns IBVH_ERR_UNSUPPORTED.  The
+     * walk is the reference's: the driving BVH's leaves are tested against the walked tree's nodes as NodeType(leaf.volume)
+     * (:196-197) and against its leaves with iscontact on the raw mixed types (iscontact.jl:2-28, the comparisons promote);
+     * IBVH_NARROW_MORTON_LT compares the two Morton widths as uint64.  Same list, order included, as the reference.  A BBox
+     * query against a tree with BSphere nodes has no NodeType(query) (no BSphere(::BBox): the reference raises MethodError):
+     * IBVH_ERR_UNSUPPORTED, never a list — and since the BVH with more leaves drives, whether two types are refused can
+     * depend on the sizes (and on IBVH_PAIR_SMALLER_DRIVES).  Scratch: the larger of ibvh_lvt_scratch_bytes over the two
+     * BVHs' types, for n_items = max(n1, n2) (min(n1, n2) with IBVH_PAIR_SMALLER_DRIVES).  Composes with every other flag. */
+    IBVH_PAIR_MIXED_TYPES = 0x400
 };
 
 typedef struct ibvh_types {
@@ -286,7 +297,7 @@ ibvh_status ibvh_traverse_lvt_write(const ibvh_bvh *bvh, int64_t start_level, in
 
 /* traverse(bvh1, bvh2, LVTTraversal()) — lvt/traverse_pair.jl:1-244.  The BVH with more leaves
  * supplies the work items (:15-36); contacts are always (index in bvh1, index in bvh2).
- * counts needs max(n1, n2) entries. */
+ * counts needs max(n1, n2) entries.  Two BVHs of different types: IBVH_PAIR_MIXED_TYPES. */
 ibvh_status ibvh_traverse_pair_lvt_count(const ibvh_bvh *bvh1, const ibvh_bvh *bvh2,
                                          int64_t start_level1, int64_t start_level2,
                                          int32_t narrow, void *counts, int64_t *total_out,
