@@ -8,7 +8,7 @@ import ctypes as C
 
 import numpy as np
 
-ABI_VERSION = 6  # IBVH_ABI_VERSION of the include/ibvh.h this mirror was written against
+ABI_VERSION = 7  # IBVH_ABI_VERSION of the include/ibvh.h this mirror was written against
 
 # enums ---------------------------------------------------------------------------------------
 BSPHERE, BBOX = 0, 1

@@ -29,7 +29,7 @@ __all__ = [
     "load_obj_triangles", "BSphere", "BBox", "BoundingVolumes", "BVHOptions", "DefaultMortonAlgorithm", "ImplicitTree", "BVH",
     "BVHTraversal", "LVTTraversal", "BFSTraversal", "traverse", "traverse_rays", "default_start_level",
     "memory_index", "level_indices", "isvirtual", "bounding_volumes_from_triangles", "generate_spheres",
-    "NARROW_MORTON_LT", "NARROW_INDEX_LT", "NARROW_RAY_ORIGIN_OUTSIDE", "LeafBatch", "lvt_work_counters",
+    "NARROW_MORTON_LT", "NARROW_INDEX_LT", "NARROW_RAY_ORIGIN_OUTSIDE", "LeafBatch", "lvt_work_counters", "refit",
 ]
 
 NARROW_MORTON_LT = abi.NARROW_MORTON_LT
@@ -688,6 +688,45 @@ class BVH:
     def __repr__(self):
         return (f"BVH\n  built_level: {self.built_level}\n  tree:        {self.tree}\n  skips:       {tuple(self.skips.shape)}\n"
                 f"  nodes:       {tuple(self.nodes.shape)}\n  leaves:      ({len(self.leaves)},)\n")
+
+
+def refit(bvh, bounding_volumes=None):
+    """Refit `bvh` IN PLACE to moved leaves and return it (include/ibvh.h, ibvh_refit): the leaf order, .index, .morton,
+    skips, tree and extrema stay those of the last full build; every node is merged again bottom-up (aggregate_oibvh!,
+    build.jl:366-523), bit-identical to a build's merge over the same records.  No extrema, Morton codes or sort.
+
+        refit(bvh)                      bvh.leaves.volume was moved in place
+        refit(bvh, bounding_volumes)    (m, 4) / (m, 6) CUDA tensor of the leaf type in the USER's order: the leaf with
+                                        index k takes bounding_volumes[k - 1]
+
+    Traversals stay exact; they only get slower as the Morton order goes stale — rebuild with BVH(..., cache=bvh) when
+    they do.  The leaf indices are checked against m once per BVH object (one device reduction, one host read); an index
+    outside 1..m raises ValueError.  The device also checks every index before it reads (bvh._refit_flag turns non-zero
+    if it ever found one out of range: such a leaf keeps its volume)."""
+    torch = _require_gpu()
+    types = bvh.types
+    vol_ptr, m = C.c_void_p(0), 0
+    if bounding_volumes is not None:
+        v = bounding_volumes
+        if not isinstance(v, torch.Tensor) or v.dim() != 2 or v.shape[1] != abi.volume_width(types.leaf_kind):
+            raise ValueError(f"refit: bounding volumes must be an (m, {abi.volume_width(types.leaf_kind)}) tensor of the BVH's leaf kind")
+        if v.dtype != _torch_float(types.leaf_float):
+            raise ValueError(f"refit: bounding volumes must be {_torch_float(types.leaf_float)}, like the BVH's leaves")
+        if not v.is_cuda:
+            raise ValueError("refit: bounding volumes must live on the GPU (device='cuda')")
+        v = v.contiguous()
+        m = int(v.shape[0])
+        if getattr(bvh, "_refit_checked", None) != m:
+            lo, hi = (int(x) for x in torch.aminmax(bvh.leaves.index.to(torch.int64)))
+            if lo < 1 or hi > m:
+                raise ValueError(f"refit: leaf indices span {lo}..{hi}, outside 1..{m} (the number of bounding volumes given)")
+            bvh._refit_checked = m  # refit never changes the indices; a rebuild (cache=) is a new object
+        vol_ptr = _ptr(v)
+    flag = getattr(bvh, "_refit_flag", None)
+    if flag is None:
+        flag = bvh._refit_flag = torch.zeros(1, dtype=torch.int32, device="cuda")
+    lib.call("ibvh_refit", C.byref(bvh.struct()), vol_ptr, m, _ptr(flag), _stream())
+    return bvh
 
 
 def default_start_level(bvh, alg=None):

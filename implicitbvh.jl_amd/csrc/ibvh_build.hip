@@ -323,6 +323,32 @@ __global__ __launch_bounds__(256) void gather_kernel(const char *__restrict__ sr
 constexpr int AGG_TPB = 256;
 constexpr int CH_LEVELS = 9; // 2*256 inputs -> 256,128,...,1 nodes
 
+// The rest of a launch: fold the workgroup's nodes of `level` (`mine`; `nreal` of them on that level) upwards through LDS,
+// up to CH_LEVELS - 1 more levels and not above built_level, writing every node made.
+template <class N>
+IBVH_D void fold_up(N *s_nodes, N mine, int64_t level, int64_t nreal, const TreeDev &tree, int64_t built_level, N *__restrict__ nodes) {
+    const int t = threadIdx.x;
+    int count = AGG_TPB;
+#pragma unroll 1
+    for (int s = 1; s < CH_LEVELS; ++s) {
+        if (level - 1 < built_level) break; // uniform
+        __syncthreads();
+        if (t < count) s_nodes[t] = mine;
+        __syncthreads();
+        count >>= 1;
+        level -= 1;
+        const int64_t child_real = nreal;
+        nreal = level_num_real(tree.levels, tree.virtual_leaves, level);
+        const int64_t i = (int64_t)blockIdx.x * count + t;
+        if ((t < count) && (i < nreal)) {
+            N a = s_nodes[2 * t];
+            if (2 * i + 1 < child_real) mine = merge_to(a, s_nodes[2 * t + 1], (N *)nullptr);
+            else mine = a;
+            nodes[level_start(tree.levels, tree.virtual_leaves, level) - 1 + i] = mine;
+        }
+    }
+}
+
 template <class L, class N, bool FROM_LEAVES>
 __global__ __launch_bounds__(AGG_TPB) void aggregate_kernel(const char *__restrict__ in, int64_t in_stride, int64_t in_level,
                                                             TreeDev tree, int64_t built_level, N *__restrict__ nodes) {
@@ -331,11 +357,10 @@ __global__ __launch_bounds__(AGG_TPB) void aggregate_kernel(const char *__restri
     // level being produced first: in_level - 1
     int64_t level = in_level - 1;
     const int64_t in_real = FROM_LEAVES ? tree.real_leaves : level_num_real(tree.levels, tree.virtual_leaves, in_level);
-    int64_t i = (int64_t)blockIdx.x * AGG_TPB + t; // 0-based node index within `level`
-    int64_t nreal = level_num_real(tree.levels, tree.virtual_leaves, level);
+    const int64_t i = (int64_t)blockIdx.x * AGG_TPB + t; // 0-based node index within `level`
+    const int64_t nreal = level_num_real(tree.levels, tree.virtual_leaves, level);
     N mine;
-    bool real = i < nreal;
-    if (real) {
+    if (i < nreal) {
         int64_t l = 2 * i, r = 2 * i + 1; // 0-based children within in_level
         if constexpr (FROM_LEAVES) {
             L a = load_vol<L>(in + l * in_stride);
@@ -356,27 +381,48 @@ __global__ __launch_bounds__(AGG_TPB) void aggregate_kernel(const char *__restri
         }
         nodes[level_start(tree.levels, tree.virtual_leaves, level) - 1 + i] = mine;
     }
-    // fold upwards inside the workgroup
-    int count = AGG_TPB;
-#pragma unroll 1
-    for (int s = 1; s < CH_LEVELS; ++s) {
-        if (level - 1 < built_level) break; // uniform
-        __syncthreads();
-        if (t < count) s_nodes[t] = mine;
-        __syncthreads();
-        count >>= 1;
-        level -= 1;
-        const int64_t child_real = nreal;
-        nreal = level_num_real(tree.levels, tree.virtual_leaves, level);
-        i = (int64_t)blockIdx.x * count + t;
-        real = (t < count) && (i < nreal);
-        if (real) {
-            N a = s_nodes[2 * t];
-            if (2 * i + 1 < child_real) mine = merge_to(a, s_nodes[2 * t + 1], (N *)nullptr);
-            else mine = a;
-            nodes[level_start(tree.levels, tree.virtual_leaves, level) - 1 + i] = mine;
+    fold_up<N>(s_nodes, mine, level, nreal, tree, built_level, nodes);
+}
+
+// Refit from new volumes in the user's order (ibvh_refit): the first launch of aggregate<L, N>, with the gather fused in.
+// Each leaf takes volumes[.index - 1], stores it into its record (volume bytes only) and is merged exactly as in
+// aggregate_kernel<L, N, true>.  The index is checked BEFORE the load: a leaf whose index lies outside 1..m keeps its old
+// volume and stores 1 to *flag.  A 1-leaf tree has no nodes: its leaf is only gathered.
+template <class L, class N, class I>
+__global__ __launch_bounds__(AGG_TPB) void refit_kernel(char *__restrict__ leaves, LeafLayout lay, const char *__restrict__ volumes,
+                                                        int64_t m, uint32_t *flag, TreeDev tree, int64_t built_level,
+                                                        N *__restrict__ nodes) {
+    __shared__ N s_nodes[AGG_TPB];
+    const int64_t i = (int64_t)blockIdx.x * AGG_TPB + threadIdx.x;
+    const bool one_leaf = tree.levels == 1;
+    const int64_t level = tree.levels - 1;
+    const int64_t nreal = one_leaf ? 1 : level_num_real(tree.levels, tree.virtual_leaves, level);
+    N mine;
+    if (i < nreal) {
+        const bool has_b = !one_leaf && 2 * i + 1 < tree.real_leaves;
+        char *ra = leaves + 2 * i * lay.stride, *rb = ra + lay.stride;
+        // both indices, then both gathers, then both stores: two dependent round trips per item, not four
+        const I ia = load_index<I>(ra, lay), ib = has_b ? load_index<I>(rb, lay) : I(1);
+        const bool oka = ia >= 1 && (int64_t)ia <= m, okb = ib >= 1 && (int64_t)ib <= m;
+        const char *sa = oka ? volumes + ((int64_t)ia - 1) * (int64_t)sizeof(L) : ra;
+        const char *sb = okb ? volumes + ((int64_t)ib - 1) * (int64_t)sizeof(L) : rb;
+        L a, b;
+        if constexpr (sizeof(L) % 16 == 0) { // raw BSphere{F32}/{F64}, BBox{F64}: one 16-byte request per 16 bytes
+            a = oka && ((uintptr_t)volumes & 15) == 0 ? load_vol16<L>(sa) : load_vol<L>(sa);
+            if (has_b) b = okb && ((uintptr_t)volumes & 15) == 0 ? load_vol16<L>(sb) : load_vol<L>(sb);
+        } else {
+            a = load_vol<L>(sa);
+            if (has_b) b = load_vol<L>(sb);
         }
+        if (oka) store_vol(ra, a);
+        if (has_b && okb) store_vol(rb, b);
+        if (flag && !(oka && okb)) *flag = 1u;
+        if (one_leaf) return; // (uniform: a one-block launch)
+        mine = has_b ? merge_to(a, b, (N *)nullptr) : convert_to(a, (N *)nullptr);
+        nodes[level_start(tree.levels, tree.virtual_leaves, level) - 1 + i] = mine;
     }
+    if (one_leaf) return;
+    fold_up<N>(s_nodes, mine, level, nreal, tree, built_level, nodes);
 }
 
 // The top of the tree: one workgroup folds all levels above `in_level` (<= AGG_TOP_MAX inputs), a barrier per level; same
@@ -435,19 +481,40 @@ __global__ __launch_bounds__(AGG_TOP_TPB) void aggregate_top_kernel(TreeDev tree
     }
 }
 
+// ibvh_refit from volumes in the user's order: what the first launch of aggregate() gathers into the leaf records
+struct RefitGather {
+    LeafLayout lay;
+    int index_type;
+    const void *volumes; // m raw volumes of the leaf type
+    int64_t m;
+    uint32_t *flag;      // optional
+};
+
 template <class L, class N>
-int aggregate(const char *leaves, int64_t leaf_stride, const ibvh_tree &tree, int64_t built_level, N *nodes, hipStream_t st) {
-    if (tree.real_nodes < 2) return IBVH_OK; // build.jl:266
+int aggregate(const char *leaves, int64_t leaf_stride, const ibvh_tree &tree, int64_t built_level, N *nodes, hipStream_t st,
+              const RefitGather *gather = nullptr) {
+    if (tree.real_nodes < 2 && !gather) return IBVH_OK; // build.jl:266
     TreeDev td{tree.levels, tree.real_leaves, tree.virtual_leaves};
     // launch 1: leaves (level `levels`) -> levels-1 .. levels-CH_LEVELS.  The last-level merge always
     // runs (aggregate_last_level!, build.jl:369), even when built_level == levels.
     int64_t in_level = tree.levels;
     {
-        int64_t nreal = level_num_real(tree.levels, tree.virtual_leaves, in_level - 1);
+        int64_t nreal = tree.levels > 1 ? level_num_real(tree.levels, tree.virtual_leaves, in_level - 1) : 1;
         int64_t eff_built = built_level > tree.levels - 1 ? tree.levels - 1 : built_level;
-        IBVH_LAUNCH((aggregate_kernel<L, N, true>), dim3((unsigned)ceil_div(nreal, AGG_TPB)), dim3(AGG_TPB), 0, st,
-                           leaves, leaf_stride, in_level, td, eff_built, nodes);
+        if (gather) {
+            int e = dispatch_index(gather->index_type, [&](auto it) -> int {
+                using I = typename decltype(it)::type;
+                IBVH_LAUNCH((refit_kernel<L, N, I>), dim3((unsigned)ceil_div(nreal, AGG_TPB)), dim3(AGG_TPB), 0, st,
+                            (char *)leaves, gather->lay, (const char *)gather->volumes, gather->m, gather->flag, td, eff_built, nodes);
+                return IBVH_OK;
+            });
+            if (e) return e;
+        } else {
+            IBVH_LAUNCH((aggregate_kernel<L, N, true>), dim3((unsigned)ceil_div(nreal, AGG_TPB)), dim3(AGG_TPB), 0, st,
+                               leaves, leaf_stride, in_level, td, eff_built, nodes);
+        }
         IBVH_LAUNCH_CHECK();
+        if (tree.real_nodes < 2) return IBVH_OK; // (a refit of one leaf: gathered, no nodes)
         in_level = in_level - CH_LEVELS;
     }
     while (in_level - 1 >= built_level && in_level - 1 >= 1) {
@@ -610,6 +677,26 @@ ibvh_status ibvh_aggregate(const ibvh_types *types, const ibvh_tree *tree, int64
         using L = typename decltype(lt)::type;
         using N = typename decltype(nt)::type;
         return aggregate<L, N>((const char *)leaves, lay.leaf_bytes, *tree, built_level, (N *)nodes, (hipStream_t)stream);
+    });
+}
+
+ibvh_status ibvh_refit(const ibvh_bvh *bvh, const void *volumes, int64_t num_volumes, void *flag, void *stream) {
+    if (!bvh || !bvh->leaves) return IBVH_ERR_INVALID_ARG;
+    const ibvh_tree &tree = bvh->tree;
+    if (tree.real_leaves < 1 || tree.levels < 1) return IBVH_ERR_INVALID_ARG;
+    if (bvh->built_level < 1 || bvh->built_level > tree.levels) return IBVH_ERR_INVALID_ARG;
+    if (tree.real_nodes >= 2 && !bvh->nodes) return IBVH_ERR_INVALID_ARG;
+    if (volumes && (num_volumes < 0 || ((uintptr_t)volumes & 7) != 0)) return IBVH_ERR_INVALID_ARG;
+    ibvh_layout lay;
+    LeafLayout dlay;
+    if (!layout_of(bvh->types, lay, &dlay)) return IBVH_ERR_UNSUPPORTED;
+    const RefitGather g{dlay, bvh->types.index_type, volumes, num_volumes, (uint32_t *)flag};
+    return (ibvh_status)dispatch_leaf_node(bvh->types, [&](auto lt, auto nt) -> int {
+        using L = typename decltype(lt)::type;
+        using N = typename decltype(nt)::type;
+        // the in-place form is exactly aggregate_oibvh! over the records as they stand
+        return aggregate<L, N>((const char *)bvh->leaves, lay.leaf_bytes, tree, bvh->built_level, (N *)bvh->nodes,
+                               (hipStream_t)stream, volumes ? &g : nullptr);
     });
 }
 

@@ -37,7 +37,7 @@ const libibvh = get(ENV, "LIBIBVH", "libibvh.so")
 
 # The header this file was written against (include/ibvh.h, IBVH_ABI_VERSION).  A library with another struct layout or
 # argument list would make the GPU write through garbage pointers, so a mismatch is refused when the extension loads.
-const IBVH_ABI_VERSION = Int32(6)
+const IBVH_ABI_VERSION = Int32(7)
 function __init__()
     got = ccall((:ibvh_abi_version, libibvh), Int32, ())
     got == IBVH_ABI_VERSION ||
@@ -269,6 +269,10 @@ c_dist_cross_write(bvh, plan, import_buf, scratch, sb, totals, contacts, stream)
     ccall((:ibvh_dist_cross_write, libibvh), Cint,
           (Ref{IbvhBvh}, Ref{IbvhDistCrossPlan}, Ptr{Cvoid}, Ptr{Cvoid}, Csize_t, Ref{Int64}, Ptr{Cvoid}, Ptr{Cvoid}),
           bvh, plan, import_buf, scratch, sb, totals, contacts, stream)
+c_refit(bvh, volumes, num_volumes, flag, stream) =
+    ccall((:ibvh_refit, libibvh), Cint,
+          (Ref{IbvhBvh}, Ptr{Cvoid}, Int64, Ptr{Cvoid}, Ptr{Cvoid}),
+          bvh, volumes, num_volumes, flag, stream)
 c_lvt_scratch_bytes(types, n_items, cache_slots, out) =
     ccall((:ibvh_lvt_scratch_bytes, libibvh), Cint,
           (Ref{IbvhTypes}, Int64, Int32, Ref{Csize_t}),
@@ -520,6 +524,42 @@ end
 # a file); `local_volumes` this rank's share of the leaves.  Returns this rank's slice of the globally sorted sequence as an
 # ordinary BVH (leaf .index = GLOBAL 1-based number) that traverse() takes like any other; contacts across slices are NOT
 # found by it: dist_cross_contacts below completes them (the trees of touching slices travel over the same communicator).
+# ---- refit: new leaf volumes into the EXISTING leaf order (include/ibvh.h, ibvh_refit) --------------------------------
+leaf_volume_type(::AbstractVector{BoundingVolume{L, I, M}}) where {L, I, M} = L
+# bvh.leaves array => (number of volumes, number of leaves) its indices were last checked against: refit never changes the
+# indices, and a rebuild into the same array only permutes them
+const refit_checked = WeakKeyDict{Any, Tuple{Int, Int}}()
+
+"""
+    refit!(bvh::BVH, volumes::Union{Nothing, ROCVector}=nothing) -> bvh
+
+Refit `bvh` in place to moved leaves: the leaf order, `.index`, `.morton` (those of the last full build), skips and tree stay
+as they are, and every node is merged again bottom-up (aggregate_oibvh!, build.jl:366-523), bit-identical to what a build
+merges over the same records.  `refit!(bvh)`: `bvh.leaves` already hold the moved volumes.  `refit!(bvh, volumes)`: `volumes`
+holds the leaf volume type in the user's order, and the leaf with index `k` takes `volumes[k]`.  Traversals stay exact and only
+slow down as the Morton order goes stale; rebuild with `BVH(...; cache=bvh)` when they do.  Not a method of ImplicitBVH: the
+reference has no refit, so a BVH the library does not instantiate raises ArgumentError.
+"""
+function refit!(bvh::RocBVH{I}, volumes::Union{Nothing, ROCVector}=nothing) where {I}
+    d = bvh_desc(bvh)
+    isnothing(d) && throw(ArgumentError("refit!: no libibvh instantiation for this BVH's types (there is no generic refit)"))
+    m = 0
+    if !isnothing(volumes)
+        L = leaf_volume_type(bvh.leaves)
+        eltype(volumes) === L || throw(ArgumentError("refit!: volumes must be a ROCVector{$L}, the BVH's leaf volume type"))
+        m = length(volumes)
+        if get(refit_checked, bvh.leaves, nothing) != (m, length(bvh.leaves))
+            lo, hi = extrema(bv -> Int64(bv.index), bvh.leaves)       # one device reduction, one host read
+            1 <= lo && hi <= m || throw(ArgumentError("refit!: leaf indices span $lo:$hi, outside 1:$m"))
+            refit_checked[bvh.leaves] = (m, length(bvh.leaves))
+        end
+    end
+    # the device checks every index again before it reads (a leaf edited by hand since keeps its volume)
+    flag = scratch!(:refit_flag, 4)
+    check(c_refit(d, devptr(volumes), Int64(m), devptr(flag), stream_ptr()), "ibvh_refit")
+    bvh
+end
+
 """
     dist_comm(nccl_comm::Ptr{Cvoid}, rank, size) -> IbvhComm
 """

@@ -32,6 +32,7 @@ SIGNATURES = {
     "ibvh_sort_pairs": [_i32, _i32, _i64, _vp, _vp, _vp, _vp, _P(_i32), _vp, _sz, _vp],
     "ibvh_sort_scratch_bytes": [_i32, _i64, _P(_sz)],
     "ibvh_aggregate": [_P(abi.Types), _P(abi.Tree), _i64, _vp, _vp, _vp],
+    "ibvh_refit": [_P(abi.Bvh), _vp, _i64, _vp, _vp],
     "ibvh_lvt_scratch_bytes": [_P(abi.Types), _i64, _i32, _P(_sz)],
     "ibvh_traverse_lvt_count": [_P(abi.Bvh), _i64, _i32, _vp, _P(_i64), _vp, _sz, _vp],
     "ibvh_traverse_lvt_write": [_P(abi.Bvh), _i64, _i32, _vp, _vp, _vp, _sz, _vp],

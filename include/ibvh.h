@@ -40,8 +40,9 @@ extern "C" {
  *   3: *_enqueue(total_host), ibvh_set_tuning, ibvh_lvt_work_counters, ray `narrow`, contact positions
  *   4: the multi-GPU driver (ibvh_comm, ibvh_dist_*)
  *   5: ibvh_dist_cross_* (boundary leaves), ibvh_comm_release, ibvh_build_desc.sort_equalize (was reserved_: same layout)
- *   6: IBVH_PAIR_MIXED_TYPES (pair LVT traversals of two BVHs of different leaf / node types) */
-#define IBVH_ABI_VERSION 6
+ *   6: IBVH_PAIR_MIXED_TYPES (pair LVT traversals of two BVHs of different leaf / node types)
+ *   7: ibvh_refit */
+#define IBVH_ABI_VERSION 7
 int32_t ibvh_abi_version(void);
 
 /* ----------------------------------------------------------------------------------- */
@@ -258,6 +259,20 @@ ibvh_status ibvh_sort_scratch_bytes(int32_t key_bytes, int64_t n, size_t *bytes_
 /* aggregate_oibvh! alone (build.jl:366-523) over already-sorted leaves. */
 ibvh_status ibvh_aggregate(const ibvh_types *types, const ibvh_tree *tree, int64_t built_level,
                            const void *leaves, void *nodes, void *stream);
+
+/* Refit: new leaf volumes into bvh's EXISTING leaf order, then aggregate_oibvh! (build.jl:366-523) again down to
+ * bvh->built_level; no extrema, Morton codes or sort.  Leaf .index / .morton, the skips and the tree are unchanged (the
+ * Morton codes stay those of the last full build: they are the key the leaves are ORDERED by), and the nodes are
+ * bit-identical to ibvh_aggregate over the updated records.  Every traversal stays exact; only its cost grows as the
+ * leaf order drifts away from the Morton order of the new volumes — when to build again is the caller's decision.
+ * bvh->leaves and bvh->nodes are WRITTEN (the const of ibvh_bvh is the traversals' view).
+ *   volumes == NULL: bvh->leaves already hold the new volumes (moved in place): exactly ibvh_aggregate.
+ *   volumes != NULL: num_volumes raw volumes of the leaf type (8-byte aligned, not overlapping the leaves); the leaf
+ *                    with user index k receives volumes[k-1], in the first launch of the merge.
+ * flag (optional, may be NULL): 4 bytes the GPU can write (device memory or mapped pinned host memory).  A leaf whose
+ * .index lies outside 1..num_volumes keeps its volume, nothing outside the array is read, and the kernel stores a
+ * non-zero value there.  The library never clears it: zero it before the call.  No host synchronisation. */
+ibvh_status ibvh_refit(const ibvh_bvh *bvh, const void *volumes, int64_t num_volumes, void *flag, void *stream);
 
 /* ----------------------------------------------------------------------------------- */
 /* leaf-vs-tree traversal (LVTTraversal, the reference default)                          */
