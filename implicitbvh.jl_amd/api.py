@@ -1032,50 +1032,60 @@ def _lvt_scratch(cache, types, n_items, slots=None, rays_bvh=None, types2=None):
     return s
 
 
+def _check_start_level(bvh, start_level, lvt):
+    """The start level's @argcheck of the LVT (lvt/traverse_single.jl:10) or the BFS (bfs/traverse_single.jl) algorithm."""
+    if lvt and not (bvh.built_level <= start_level <= bvh.tree.levels <= 32):
+        raise ValueError("bvh.built_level <= start_level <= bvh.tree.levels <= 32 must hold")
+    if not lvt and not (bvh.tree.levels >= start_level >= bvh.built_level):
+        raise ValueError("bvh.tree.levels >= start_level >= bvh.built_level must hold")
+
+
+def _lvt_two_pass(entry, args, n_items, idt, cache, scratch, sl1, sl2=0, keep=None):
+    """The leaf-vs-tree protocol of every traversal shape (the Julia extension's lvt_two_pass).  `entry` names the shape's
+    family of entry points (ibvh_traverse_*_lvt_{count,write,enqueue}), `args` are their leading arguments, up to `narrow`.
+    With a contact buffer in `cache`, count, scan and a writing pass guarded by that buffer's size are enqueued without a
+    host read, and the total is read when first asked for (BVHTraversal._resolve); otherwise the blocking count, then the
+    write.  keep: what `args` point into that the deferred write still reads (the rays)."""
+    counts = _cache_tensor(cache.cache2 if cache else None, n_items, 0, idt, "cache2")
+    sp, sn = _ptr(scratch), scratch.numel()
+    spec = _speculative_buffer(cache, idt)
+    if spec is not None:
+        tdev, thost, pending = scratch.next_total()
+        lib.call(entry + "_enqueue", *args, _ptr(counts), _ptr(spec), spec.shape[0], tdev, thost, sp, sn, _stream())
+        pending.launched()
+
+        def finish(total, keep=keep):  # (keep: bound to the closure, alive until the write has run)
+            contacts = _torch().empty((total, 2), dtype=idt, device="cuda")
+            lib.call(entry + "_write", *args, _ptr(counts), _ptr(contacts), sp, sn, _stream())
+            return contacts
+        return BVHTraversal(sl1, sl2, 0, None, spec, counts, scratch, _pending=(pending, spec.shape[0], finish))
+    total = C.c_int64()
+    lib.call(entry + "_count", *args, _ptr(counts), C.byref(total), sp, sn, _stream())
+    contacts = _cache_tensor(cache.cache1 if cache else None, total.value, 2, idt, "cache1")
+    if total.value:
+        lib.call(entry + "_write", *args, _ptr(counts), _ptr(contacts), sp, sn, _stream())
+    return BVHTraversal(sl1, sl2, 0, total.value, contacts, counts, scratch)
+
+
 def _traverse_lvt_single(bvh, start_level, narrow, cache):
     torch = _require_gpu()
     idt = _torch_index(bvh.types.index_type)
-    if not (bvh.built_level <= start_level <= bvh.tree.levels <= 32):
-        raise ValueError("bvh.built_level <= start_level <= bvh.tree.levels <= 32 must hold")
+    _check_start_level(bvh, start_level, lvt=True)
     if bvh.tree.real_nodes <= 1:  # traverse_single.jl:17-21
         return BVHTraversal(start_level, 0, 0, 0, torch.empty((0, 2), dtype=idt, device="cuda"),
                             torch.empty(0, dtype=idt, device="cuda"))
     n = len(bvh.leaves)
-    counts = _cache_tensor(cache.cache2 if cache else None, n, 0, idt, "cache2")
-    scratch = _lvt_scratch(cache, bvh.types, n)
-    sp, sn = _ptr(scratch), scratch.numel()
-    s = bvh.struct()
-    spec = _speculative_buffer(cache, idt)
-    if spec is not None:
-        tdev, thost, pending = scratch.next_total()
-        lib.call("ibvh_traverse_lvt_enqueue", C.byref(s), start_level, narrow, _ptr(counts), _ptr(spec), spec.shape[0],
-                 tdev, thost, sp, sn, _stream())
-        pending.launched()
-
-        def finish(total):
-            contacts = torch.empty((total, 2), dtype=idt, device="cuda")
-            lib.call("ibvh_traverse_lvt_write", C.byref(s), start_level, narrow, _ptr(counts), _ptr(contacts), sp,
-                     sn, _stream())
-            return contacts
-        return BVHTraversal(start_level, 0, 0, None, spec, counts, scratch, _pending=(pending, spec.shape[0], finish))
-    total = C.c_int64()
-    lib.call("ibvh_traverse_lvt_count", C.byref(s), start_level, narrow, _ptr(counts), C.byref(total), sp,
-             sn, _stream())
-    contacts = _cache_tensor(cache.cache1 if cache else None, total.value, 2, idt, "cache1")
-    if total.value:
-        lib.call("ibvh_traverse_lvt_write", C.byref(s), start_level, narrow, _ptr(counts), _ptr(contacts), sp,
-                 sn, _stream())
-    return BVHTraversal(start_level, 0, 0, total.value, contacts, counts, scratch)
+    return _lvt_two_pass("ibvh_traverse_lvt", (C.byref(bvh.struct()), start_level, narrow), n, idt, cache,
+                         _lvt_scratch(cache, bvh.types, n), start_level)
 
 
 def _traverse_lvt_pair(bvh1, bvh2, sl1, sl2, narrow, cache):
-    torch = _require_gpu()
+    _require_gpu()
     if bvh1.types.index_type != bvh2.types.index_type:
         raise ValueError("get_index_type(bvh2) === I must hold")  # traverse_pair.jl:50-52
     idt = _torch_index(bvh1.types.index_type)
-    for b, sl in ((bvh1, sl1), (bvh2, sl2)):
-        if not (b.built_level <= sl <= b.tree.levels <= 32):
-            raise ValueError("bvh.built_level <= start_level <= bvh.tree.levels <= 32 must hold")
+    _check_start_level(bvh1, sl1, lvt=True)
+    _check_start_level(bvh2, sl2, lvt=True)
     n = max(len(bvh1.leaves), len(bvh2.leaves))
     mixed = bvh1.types.key() != bvh2.types.key()
     if mixed:  # two types (IBVH_PAIR_MIXED_TYPES): the walked tree's nodes are tested against NodeType(leaf) (traverse_pair.jl:196-197)
@@ -1086,31 +1096,16 @@ def _traverse_lvt_pair(bvh1, bvh2, sl1, sl2, narrow, cache):
             f = {abi.F32: "Float32", abi.F64: "Float64"}
             raise abi.MethodError(f"no method matching BSphere{{{f[oth.types.node_float]}}}(::BBox{{{f[drv.types.leaf_float]}}})")
         narrow |= abi.PAIR_MIXED_TYPES
-    counts = _cache_tensor(cache.cache2 if cache else None, n, 0, idt, "cache2")
-    scratch = _lvt_scratch(cache, bvh1.types, n, types2=bvh2.types if mixed else None)
-    sp, sn = _ptr(scratch), scratch.numel()
-    s1, s2 = bvh1.struct(), bvh2.struct()
-    spec = _speculative_buffer(cache, idt)
-    if spec is not None:
-        tdev, thost, pending = scratch.next_total()
-        lib.call("ibvh_traverse_pair_lvt_enqueue", C.byref(s1), C.byref(s2), sl1, sl2, narrow, _ptr(counts), _ptr(spec),
-                 spec.shape[0], tdev, thost, sp, sn, _stream())
-        pending.launched()
+    return _lvt_two_pass("ibvh_traverse_pair_lvt", (C.byref(bvh1.struct()), C.byref(bvh2.struct()), sl1, sl2, narrow), n, idt,
+                         cache, _lvt_scratch(cache, bvh1.types, n, types2=bvh2.types if mixed else None), sl1, sl2)
 
-        def finish(total):
-            contacts = torch.empty((total, 2), dtype=idt, device="cuda")
-            lib.call("ibvh_traverse_pair_lvt_write", C.byref(s1), C.byref(s2), sl1, sl2, narrow, _ptr(counts), _ptr(contacts),
-                     sp, sn, _stream())
-            return contacts
-        return BVHTraversal(sl1, sl2, 0, None, spec, counts, scratch, _pending=(pending, spec.shape[0], finish))
-    total = C.c_int64()
-    lib.call("ibvh_traverse_pair_lvt_count", C.byref(s1), C.byref(s2), sl1, sl2, narrow, _ptr(counts), C.byref(total),
-             sp, sn, _stream())
-    contacts = _cache_tensor(cache.cache1 if cache else None, total.value, 2, idt, "cache1")
-    if total.value:
-        lib.call("ibvh_traverse_pair_lvt_write", C.byref(s1), C.byref(s2), sl1, sl2, narrow, _ptr(counts), _ptr(contacts),
-                 sp, sn, _stream())
-    return BVHTraversal(sl1, sl2, 0, total.value, contacts, counts, scratch)
+
+def _traverse_lvt_rays(bvh, p, d, start_level, narrow, cache):
+    """p, d: the rays as (N, 3) row-major tensors of the leaf float type"""
+    nr = p.shape[0]
+    return _lvt_two_pass("ibvh_traverse_rays_lvt", (C.byref(bvh.struct()), _ptr(p), _ptr(d), nr, start_level, narrow), nr,
+                         _torch_index(bvh.types.index_type), cache,
+                         _lvt_scratch(cache, bvh.types, nr, slots=RAY_CACHE_SLOTS, rays_bvh=bvh), start_level, keep=(p, d))
 
 
 BFS_INITIAL_FACTOR = 4  # queues start at 4x the initial pair count (bfs/traverse_single.jl:73)
@@ -1159,8 +1154,7 @@ def _bfs_run(entry, types, initial_capacity, cache, levels_hint, *args):
 def _traverse_bfs_single(bvh, start_level, narrow, cache):
     torch = _require_gpu()
     idt = _torch_index(bvh.types.index_type)
-    if not (bvh.tree.levels >= start_level >= bvh.built_level):
-        raise ValueError("bvh.tree.levels >= start_level >= bvh.built_level must hold")
+    _check_start_level(bvh, start_level, lvt=False)
     if bvh.tree.real_nodes <= 1:
         e = torch.empty((0, 2), dtype=idt, device="cuda")
         return BVHTraversal(start_level, 0, 0, 0, e, e.clone())
@@ -1173,15 +1167,24 @@ def _traverse_bfs_single(bvh, start_level, narrow, cache):
 
 def _traverse_bfs_pair(bvh1, bvh2, sl1, sl2, narrow, cache):
     _require_gpu()
-    for b, sl in ((bvh1, sl1), (bvh2, sl2)):
-        if not (b.tree.levels >= sl >= b.built_level):
-            raise ValueError("bvh.tree.levels >= start_level >= bvh.built_level must hold")
+    _check_start_level(bvh1, sl1, lvt=False)
+    _check_start_level(bvh2, sl2, lvt=False)
     s1, s2 = bvh1.struct(), bvh2.struct()
     cap = C.c_int64()
     lib.call("ibvh_bfs_pair_initial_capacity", C.byref(s1), C.byref(s2), sl1, sl2, C.byref(cap))
     res, q1, q2 = _bfs_run("ibvh_traverse_pair_bfs", bvh1.types, cap.value, cache, bvh1.tree.levels + bvh2.tree.levels,
                            C.byref(s1), C.byref(s2), sl1, sl2, narrow)
     return BVHTraversal(sl1, sl2, res.num_checks, res.num_contacts, q1, q2)
+
+
+def _traverse_bfs_rays(bvh, p, d, start_level, narrow, cache):
+    s = bvh.struct()
+    nr = p.shape[0]
+    cap = C.c_int64()
+    lib.call("ibvh_bfs_rays_initial_capacity", C.byref(s), nr, start_level, C.byref(cap))
+    res, q1, q2 = _bfs_run("ibvh_traverse_rays_bfs", bvh.types, cap.value, cache, bvh.tree.levels, C.byref(s), _ptr(p),
+                           _ptr(d), nr, start_level, narrow)
+    return BVHTraversal(start_level, 0, res.num_checks, res.num_contacts, q1, q2)
 
 
 def traverse(bvh, *args, start_level=None, start_level1=None, start_level2=None, narrow=None, cache=None, options=None):
@@ -1199,19 +1202,14 @@ def traverse(bvh, *args, start_level=None, start_level1=None, start_level2=None,
             raise ValueError(f"Traversal algorithm not implemented: {a}")  # traverse.jl:217
     alg = alg or LVTTraversal()
     code, fn = _narrow_code(narrow)
+    lvt = isinstance(alg, LVTTraversal)
     if bvh2 is None:
         sl = default_start_level(bvh, alg) if start_level is None else int(start_level)
-        if isinstance(alg, LVTTraversal):
-            t = _traverse_lvt_single(bvh, sl, code, cache)
-        else:
-            t = _traverse_bfs_single(bvh, sl, code, cache)
-        return _post_filter(t, fn, bvh) if fn else t
-    sl1 = default_start_level(bvh, alg) if start_level1 is None else int(start_level1)
-    sl2 = default_start_level(bvh2, alg) if start_level2 is None else int(start_level2)
-    if isinstance(alg, LVTTraversal):
-        t = _traverse_lvt_pair(bvh, bvh2, sl1, sl2, code, cache)
+        t = (_traverse_lvt_single if lvt else _traverse_bfs_single)(bvh, sl, code, cache)
     else:
-        t = _traverse_bfs_pair(bvh, bvh2, sl1, sl2, code, cache)
+        sl1 = default_start_level(bvh, alg) if start_level1 is None else int(start_level1)
+        sl2 = default_start_level(bvh2, alg) if start_level2 is None else int(start_level2)
+        t = (_traverse_lvt_pair if lvt else _traverse_bfs_pair)(bvh, bvh2, sl1, sl2, code, cache)
     return _post_filter(t, fn, bvh, bvh2) if fn else t
 
 
@@ -1227,51 +1225,15 @@ def traverse_rays(bvh, points, directions, alg=None, start_level=1, narrow=None,
     if points.shape[1] != directions.shape[1]:
         raise ValueError("size(points, 2) == size(directions, 2) must hold")
     lvt = isinstance(alg, LVTTraversal)
-    if lvt and not (bvh.built_level <= start_level <= bvh.tree.levels <= 32):
-        raise ValueError("bvh.built_level <= start_level <= bvh.tree.levels <= 32 must hold")
-    if not lvt and not (bvh.tree.levels >= start_level >= bvh.built_level):
-        raise ValueError("bvh.tree.levels >= start_level >= bvh.built_level must hold")
+    _check_start_level(bvh, start_level, lvt)
     idt = _torch_index(bvh.types.index_type)
-    nr = points.shape[1]
-    if nr == 0:
+    if points.shape[1] == 0:
         e = torch.empty((0, 2), dtype=idt, device="cuda")
         return BVHTraversal(start_level, 0, 0, 0, e, e.clone())
     ft = _torch_float(bvh.types.leaf_float)
     p = points.to(device="cuda", dtype=ft).t().contiguous()  # (N, 3) row-major == (3, N) column-major
     d = directions.to(device="cuda", dtype=ft).t().contiguous()
-    s = bvh.struct()
-    if lvt:
-        counts = _cache_tensor(cache.cache2 if cache else None, nr, 0, idt, "cache2")
-        scratch = _lvt_scratch(cache, bvh.types, nr, slots=RAY_CACHE_SLOTS, rays_bvh=bvh)
-        sp, sn = _ptr(scratch), scratch.numel()
-        spec = _speculative_buffer(cache, idt)
-        if spec is not None:
-            tdev, thost, pending = scratch.next_total()
-            lib.call("ibvh_traverse_rays_lvt_enqueue", C.byref(s), _ptr(p), _ptr(d), nr, start_level, code, _ptr(counts), _ptr(spec),
-                     spec.shape[0], tdev, thost, sp, sn, _stream())
-            pending.launched()
-
-            def finish(total):
-                contacts = torch.empty((total, 2), dtype=idt, device="cuda")
-                lib.call("ibvh_traverse_rays_lvt_write", C.byref(s), _ptr(p), _ptr(d), nr, start_level, code, _ptr(counts),
-                         _ptr(contacts), sp, sn, _stream())
-                return contacts
-            t = BVHTraversal(start_level, 0, 0, None, spec, counts, scratch, _pending=(pending, spec.shape[0], finish))
-            return _post_filter(t, fn, bvh, rays=(p, d)) if fn else t
-        total = C.c_int64()
-        lib.call("ibvh_traverse_rays_lvt_count", C.byref(s), _ptr(p), _ptr(d), nr, start_level, code, _ptr(counts),
-                 C.byref(total), sp, sn, _stream())
-        contacts = _cache_tensor(cache.cache1 if cache else None, total.value, 2, idt, "cache1")
-        if total.value:
-            lib.call("ibvh_traverse_rays_lvt_write", C.byref(s), _ptr(p), _ptr(d), nr, start_level, code, _ptr(counts),
-                     _ptr(contacts), sp, sn, _stream())
-        t = BVHTraversal(start_level, 0, 0, total.value, contacts, counts, scratch)
-        return _post_filter(t, fn, bvh, rays=(p, d)) if fn else t
-    cap = C.c_int64()
-    lib.call("ibvh_bfs_rays_initial_capacity", C.byref(s), nr, start_level, C.byref(cap))
-    res, q1, q2 = _bfs_run("ibvh_traverse_rays_bfs", bvh.types, cap.value, cache, bvh.tree.levels, C.byref(s), _ptr(p),
-                           _ptr(d), nr, start_level, code)
-    t = BVHTraversal(start_level, 0, res.num_checks, res.num_contacts, q1, q2)
+    t = (_traverse_lvt_rays if lvt else _traverse_bfs_rays)(bvh, p, d, start_level, code, cache)
     return _post_filter(t, fn, bvh, rays=(p, d)) if fn else t
 
 

@@ -731,11 +731,6 @@ inline int64_t self_initial(const ibvh_bvh &b, int64_t start_level) {
     return start_level != b.tree.levels ? n * (n - 1) / 2 + n : n * (n - 1) / 2;
 }
 
-inline bool same_types(const ibvh_types &x, const ibvh_types &y) {
-    return x.leaf_kind == y.leaf_kind && x.leaf_float == y.leaf_float && x.node_kind == y.node_kind &&
-           x.node_float == y.node_float && x.index_type == y.index_type && x.morton_type == y.morton_type;
-}
-
 template <class L, class N, class I>
 int run_self(const ibvh_bvh &b, int64_t start_level, int narrow, void *bvtt1, void *bvtt2, int64_t capacity, void *counters,
              ibvh_bfs_result *res, hipStream_t st) {

@@ -433,6 +433,10 @@ inline bool combo_ok(const ibvh_types &t) {
     if (t.node_kind == IBVH_BSPHERE && t.leaf_kind != IBVH_BSPHERE) return false; // no BSphere(BBox) ctor
     return true; // (any node float type: narrower, equal or wider than the leaves', build.jl:198-205)
 }
+inline bool same_types(const ibvh_types &x, const ibvh_types &y) {
+    return x.leaf_kind == y.leaf_kind && x.leaf_float == y.leaf_float && x.node_kind == y.node_kind &&
+           x.node_float == y.node_float && x.index_type == y.index_type && x.morton_type == y.morton_type;
+}
 inline int64_t align_up(int64_t v, int64_t a) { return (v + a - 1) / a * a; }
 inline bool layout_of(const ibvh_types &t, ibvh_layout &out, LeafLayout *dev = nullptr) {
     if (!combo_ok(t)) return false;

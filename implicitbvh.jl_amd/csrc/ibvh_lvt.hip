@@ -12,14 +12,33 @@
 namespace ibvh {
 namespace lvt {
 
-// shared driver of the six entry points
-template <int MODE>
-int run(const ibvh_bvh *drv, const ibvh_bvh *walk, const void *points, const void *dirs, int64_t n_items,
-        int64_t start_level, int32_t narrow, int32_t flip, void *counts, int64_t *total_out, void *contacts, void *scratch,
-        size_t scratch_bytes, hipStream_t st, bool enqueue = false, int64_t capacity = 0, int64_t *total_dev = nullptr,
-        int64_t *total_host = nullptr, unsigned long long *work = nullptr) {
-    // three shapes: count (contacts == nullptr), write (contacts, !enqueue), enqueue = count + scan + guarded write
-    const bool write = contacts != nullptr && !enqueue;
+// What one call walks: n_items work items (drv's leaves; RAYS: the rays, drv == nullptr) against the tree `walk`; flip: bvh2 drives
+struct Walk {
+    const ibvh_bvh *drv, *walk;
+    const void *points, *dirs;
+    int64_t n_items, start_level;
+    int32_t narrow, flip;
+};
+// What the call does with it: the *_count, *_write or *_enqueue call below, or ibvh_lvt_work_counters' counting pass (no scratch).
+enum Op { OP_COUNT, OP_WRITE, OP_ENQUEUE, OP_WORK };
+struct Call {
+    Op op;
+    void *counts;
+    int64_t *total_out;
+    void *contacts;
+    int64_t capacity;
+    void *total_dev, *total_host;
+    unsigned long long *work;
+    void *scratch;
+    size_t scratch_bytes;
+    void *stream;
+};
+
+// shared driver of the nine entry points and ibvh_lvt_work_counters
+template <int MODE> int run(const Walk &w, const Call &c) {
+    const bool write = c.op == OP_WRITE, enqueue = c.op == OP_ENQUEUE, work = c.op == OP_WORK;
+    const hipStream_t st = (hipStream_t)c.stream;
+    int32_t narrow = w.narrow;
     const int32_t positions = (narrow & IBVH_OUTPUT_POSITIONS) ? 1 : 0;
     if (narrow & ~(IBVH_NARROW_MASK | IBVH_OUTPUT_POSITIONS)) return IBVH_ERR_INVALID_ARG;
     narrow &= IBVH_NARROW_MASK;
@@ -28,16 +47,16 @@ int run(const ibvh_bvh *drv, const ibvh_bvh *walk, const void *points, const voi
         return IBVH_ERR_INVALID_ARG;
     ibvh_layout lay;
     LeafLayout wl, dl;
-    if (!layout_of(walk->types, lay, &wl)) return IBVH_ERR_UNSUPPORTED;
+    if (!layout_of(w.walk->types, lay, &wl)) return IBVH_ERR_UNSUPPORTED;
     dl = wl;
-    if (drv && !layout_of(drv->types, lay, &dl)) return IBVH_ERR_UNSUPPORTED;
-    if (!work && (!scratch || scratch_bytes < scan_scratch_bytes(n_items))) return IBVH_ERR_SCRATCH;
+    if (w.drv && !layout_of(w.drv->types, lay, &dl)) return IBVH_ERR_UNSUPPORTED;
+    if (!work && (!c.scratch || c.scratch_bytes < scan_scratch_bytes(w.n_items))) return IBVH_ERR_SCRATCH;
     // RAYS: the binned path's region lives at the END of the scratch when the caller sized it with ibvh_rays_scratch_bytes
     // and the tree and the batch qualify; the contact cache gets what lies in between
     RayBinPlan bin_plan;
     if (MODE == MODE_RAYS && !work) {
-        bin_plan = rays_bin_plan(*walk, n_items);
-        if (bin_plan.cut_level < start_level || scratch_bytes < scan_scratch_bytes(n_items) + bin_plan.bytes + 256) bin_plan = RayBinPlan{};
+        bin_plan = rays_bin_plan(*w.walk, w.n_items);
+        if (bin_plan.cut_level < w.start_level || c.scratch_bytes < scan_scratch_bytes(w.n_items) + bin_plan.bytes + 256) bin_plan = RayBinPlan{};
     }
     // SELF / PAIR under BBox nodes: the rows of the shared descent (ibvh_lvt.hpp "BlockRows") live at the END of the scratch when
     // the caller sized it with ibvh_lvt_scratch_bytes; a smaller scratch simply has none (every wave descends on its own)
@@ -46,71 +65,71 @@ int run(const ibvh_bvh *drv, const ibvh_bvh *walk, const void *points, const voi
     // (the rows are covers of consecutive work items made of the DRIVING tree's nodes: only when those have the walked tree's node
     // type — a mixed pair's driving nodes of another kind or float type are not rounded into covers, a BBox{Float64} rounded to
     // Float32 may no longer contain its leaves)
-    const bool same_nodes = !drv || (drv->types.node_kind == walk->types.node_kind && drv->types.node_float == walk->types.node_float);
+    const bool same_nodes = !w.drv || (w.drv->types.node_kind == w.walk->types.node_kind && w.drv->types.node_float == w.walk->types.node_float);
     size_t rows_bytes = 0, qidx_bytes = 0;
-    if (MODE != MODE_RAYS && !work && walk->types.node_kind == IBVH_BBOX && same_nodes) {
-        rows_bytes = blk_rows_bytes(n_items, BLK_SHIFT_MIN);
-        qidx_bytes = (size_t)align_up(n_items * (int64_t)(lay.pair_bytes / 2), 256);
-        if (scratch_bytes < scan_scratch_bytes(n_items) + rows_bytes + qidx_bytes + 256) qidx_bytes = 0;
-        if (scratch_bytes < scan_scratch_bytes(n_items) + rows_bytes + 256) rows_bytes = 0;
+    if (MODE != MODE_RAYS && !work && w.walk->types.node_kind == IBVH_BBOX && same_nodes) {
+        rows_bytes = blk_rows_bytes(w.n_items, BLK_SHIFT_MIN);
+        qidx_bytes = (size_t)align_up(w.n_items * (int64_t)(lay.pair_bytes / 2), 256);
+        if (c.scratch_bytes < scan_scratch_bytes(w.n_items) + rows_bytes + qidx_bytes + 256) qidx_bytes = 0;
+        if (c.scratch_bytes < scan_scratch_bytes(w.n_items) + rows_bytes + 256) rows_bytes = 0;
         if (!rows_bytes) qidx_bytes = 0;
         rows_bytes += qidx_bytes; // (one tail: [index array | rows])
     }
     const size_t tail_bytes = bin_plan.depth ? bin_plan.bytes : rows_bytes;
-    const size_t cache_room = scratch_bytes - (tail_bytes ? tail_bytes + 256 : 0);
-    char *tail_ptr = tail_bytes ? (char *)scratch + ((scratch_bytes - tail_bytes) & ~(size_t)255) : nullptr;
+    const size_t cache_room = c.scratch_bytes - (tail_bytes ? tail_bytes + 256 : 0);
+    char *tail_ptr = tail_bytes ? (char *)c.scratch + ((c.scratch_bytes - tail_bytes) & ~(size_t)255) : nullptr;
     const RayBins bins = bin_plan.depth ? rays_bins_at(bin_plan, tail_ptr) : RayBins{};
-    const int K = work ? 0 : cache_slots_for(cache_room, n_items, lay.pair_bytes);
-    return dispatch_leaf_node(walk->types, [&](auto lt, auto nt) -> int {
+    const int K = work ? 0 : cache_slots_for(cache_room, w.n_items, lay.pair_bytes);
+    return dispatch_leaf_node(w.walk->types, [&](auto lt, auto nt) -> int {
         using L = typename decltype(lt)::type;
         using N = typename decltype(nt)::type;
         if constexpr (MODE == MODE_RAYS && !std::is_same<typename L::elt, typename N::elt>::value) {
             return (int)IBVH_ERR_UNSUPPORTED; // isintersection(::BBox{T}, ::NTuple{3,T}, ...) needs one T
         } else {
-            return dispatch_index(walk->types.index_type, [&](auto it) -> int {
+            return dispatch_index(w.walk->types.index_type, [&](auto it) -> int {
                 using I = typename decltype(it)::type;
                 Args<L, N, I> a;
-                a.items = drv ? (const char *)drv->leaves : nullptr;
+                a.items = w.drv ? (const char *)w.drv->leaves : nullptr;
                 a.items_lay = dl;
-                a.points = (const typename L::elt *)points;
-                a.dirs = (const typename L::elt *)dirs;
-                a.n_items = n_items;
-                a.leaves = (const char *)walk->leaves;
+                a.points = (const typename L::elt *)w.points;
+                a.dirs = (const typename L::elt *)w.dirs;
+                a.n_items = w.n_items;
+                a.leaves = (const char *)w.walk->leaves;
                 a.lay = wl;
-                a.nodes = (const N *)walk->nodes;
-                a.tree = TreeDev{walk->tree.levels, walk->tree.real_leaves, walk->tree.virtual_leaves};
-                a.start_level = start_level;
-                a.built_level = walk->built_level;
+                a.nodes = (const N *)w.walk->nodes;
+                a.tree = TreeDev{w.walk->tree.levels, w.walk->tree.real_leaves, w.walk->tree.virtual_leaves};
+                a.start_level = w.start_level;
+                a.built_level = w.walk->built_level;
                 a.narrow = narrow;
                 a.positions = positions;
-                a.flip = flip;
+                a.flip = w.flip;
                 const int xcd_env = g_tuning.lvt_xcd;
                 a.xcd_tiles = MODE != MODE_RAYS ? xcd_env : 0; // 0: round robin, 1: one contiguous range per XCD, n > 1: runs of n
-                a.counts = (I *)counts;
-                a.contacts = (IndexPair<I> *)contacts;
+                a.counts = (I *)c.counts;
+                a.contacts = (IndexPair<I> *)c.contacts;
                 a.guard_total = nullptr;
                 a.guard_capacity = 0;
-                a.work = work;
+                a.work = c.work;
                 a.gate = nullptr;
                 a.blk_rows = rows_bytes ? (uint32_t *)(tail_ptr + qidx_bytes) : nullptr;
                 a.q_index_dense = qidx_bytes ? (I *)tail_ptr : nullptr;
                 // (the scan's tile sums live behind the 64-byte header of the scratch: scan_counts)
                 const bool may_fuse = !write && !work && MODE != MODE_RAYS;
-                a.scan_agg = may_fuse ? (unsigned long long *)((int64_t *)scratch + 8) : nullptr;
-                a.scan_nparts = (int32_t)ceil_div(n_items, (int64_t)SCAN_TILE);
+                a.scan_agg = may_fuse ? (unsigned long long *)((int64_t *)c.scratch + 8) : nullptr;
+                a.scan_nparts = (int32_t)ceil_div(w.n_items, (int64_t)SCAN_TILE);
                 bool agg_zeroed = false;
                 a.blk_shift = 0;
-                const ibvh_bvh *qside = drv ? drv : walk;
+                const ibvh_bvh *qside = w.drv ? w.drv : w.walk;
                 a.q_nodes = same_nodes ? (const N *)qside->nodes : nullptr;
                 a.q_tree = TreeDev{qside->tree.levels, qside->tree.real_leaves, qside->tree.virtual_leaves};
                 a.q_built_level = qside->built_level;
-                PairCache<I> cache{K ? (IndexPair<I> *)((char *)scratch + scan_scratch_bytes(n_items)) : nullptr, K};
+                PairCache<I> cache{K ? (IndexPair<I> *)((char *)c.scratch + scan_scratch_bytes(w.n_items)) : nullptr, K};
                 // one pass: the walked leaves' own type, or (a mixed pair, IBVH_PAIR_MIXED_TYPES) the driving leaves' type Q
                 auto pass = [&](bool wr, bool *agg) -> int {
                     if constexpr (MODE != MODE_PAIR) {
                         return launch<L, N, I, MODE>(a, cache, wr, st, bins, agg);
                     } else {
-                        return dispatch_volume(drv->types.leaf_kind, drv->types.leaf_float, [&](auto qt) -> int {
+                        return dispatch_volume(w.drv->types.leaf_kind, w.drv->types.leaf_float, [&](auto qt) -> int {
                             using Q = typename decltype(qt)::type;
                             if constexpr (std::is_same<Q, L>::value) return launch<L, N, I, MODE>(a, cache, wr, st, bins, agg);
                             else if constexpr (N::kind == IBVH_BSPHERE && Q::kind != IBVH_BSPHERE) return (int)IBVH_ERR_UNSUPPORTED; // (pair_common refuses it first)
@@ -120,11 +139,11 @@ int run(const ibvh_bvh *drv, const ibvh_bvh *walk, const void *points, const voi
                 };
                 if (int e = pass(write, &agg_zeroed)) return e;
                 if (write || work) return (int)IBVH_OK;
-                if (int e = scan_counts<I>((I *)counts, n_items, enqueue ? nullptr : total_out, scratch, st, enqueue ? total_dev : nullptr,
-                                           enqueue ? total_host : nullptr, nullptr, agg_zeroed)) return e;
-                if (enqueue && capacity > 0) {
-                    a.guard_total = total_dev ? (const int64_t *)total_dev : (const int64_t *)scratch; // the total contacts
-                    a.guard_capacity = sizeof(I) == 4 && capacity > (int64_t)INT32_MAX ? (int64_t)INT32_MAX : capacity;
+                if (int e = scan_counts<I>((I *)c.counts, w.n_items, c.total_out, c.scratch, st, (int64_t *)c.total_dev,
+                                           (int64_t *)c.total_host, nullptr, agg_zeroed)) return e;
+                if (enqueue && c.capacity > 0) {
+                    a.guard_total = c.total_dev ? (const int64_t *)c.total_dev : (const int64_t *)c.scratch; // the total contacts
+                    a.guard_capacity = sizeof(I) == 4 && c.capacity > (int64_t)INT32_MAX ? (int64_t)INT32_MAX : c.capacity;
                     return pass(true, nullptr);
                 }
                 return (int)IBVH_OK;
@@ -172,26 +191,35 @@ ibvh_status ibvh_rays_scratch_bytes(const ibvh_bvh *bvh, int64_t num_rays, int32
     return IBVH_OK;
 }
 
-// traverse(bvh, LVTTraversal()) — lvt/traverse_single.jl:1-79
+// nothing to walk (a single leaf, no rays): no contacts, and *_enqueue leaves a total of 0 where it would have left the count
+static ibvh_status nothing_to_walk(const Call &c) {
+    if (c.op != OP_ENQUEUE) return IBVH_OK;
+    if (hipMemsetAsync(c.total_dev ? c.total_dev : c.scratch, 0, 8, (hipStream_t)c.stream) != hipSuccess) return IBVH_ERR_HIP;
+    if (c.total_host) *(volatile int64_t *)c.total_host = 0; // (host memory: nothing was launched that could write it later)
+    return IBVH_OK;
+}
+
+// traverse(bvh, LVTTraversal()) — lvt/traverse_single.jl:1-79.  buffers: the caller's own, needed only if there is a walk (:17-21)
+static ibvh_status self_common(const ibvh_bvh *bvh, int64_t sl, int32_t narrow, bool buffers, const Call &c) {
+    if (int e = check_levels(*bvh, sl)) return (ibvh_status)e;
+    // (*_enqueue: the scratch header holds the total even when there is nothing to walk)
+    if (c.op == OP_ENQUEUE && (!c.scratch || c.scratch_bytes < scan_scratch_bytes(bvh->tree.real_leaves))) return IBVH_ERR_SCRATCH;
+    if (bvh->tree.real_nodes <= 1) return nothing_to_walk(c);
+    if (!buffers) return IBVH_ERR_INVALID_ARG;
+    return (ibvh_status)run<MODE_SELF>({.drv = bvh, .walk = bvh, .n_items = bvh->tree.real_leaves, .start_level = sl, .narrow = narrow}, c);
+}
 ibvh_status ibvh_traverse_lvt_count(const ibvh_bvh *bvh, int64_t start_level, int32_t narrow, void *counts,
                                     int64_t *total_out, void *scratch, size_t scratch_bytes, void *stream) {
     if (!bvh || !total_out) return IBVH_ERR_INVALID_ARG;
     *total_out = 0;
-    if (int e = check_levels(*bvh, start_level)) return (ibvh_status)e;
-    if (bvh->tree.real_nodes <= 1) return IBVH_OK; // traverse_single.jl:17-21
-    if (!counts || !scratch) return IBVH_ERR_INVALID_ARG;
-    return (ibvh_status)run<MODE_SELF>(bvh, bvh, nullptr, nullptr, bvh->tree.real_leaves, start_level, narrow, 0, counts,
-                                       total_out, nullptr, scratch, scratch_bytes, (hipStream_t)stream);
+    return self_common(bvh, start_level, narrow, counts && scratch, {.op = OP_COUNT, .counts = counts, .total_out = total_out,
+                       .scratch = scratch, .scratch_bytes = scratch_bytes, .stream = stream});
 }
 ibvh_status ibvh_traverse_lvt_write(const ibvh_bvh *bvh, int64_t start_level, int32_t narrow, const void *counts,
                                     void *contacts, void *scratch, size_t scratch_bytes, void *stream) {
     if (!bvh) return IBVH_ERR_INVALID_ARG;
-    if (int e = check_levels(*bvh, start_level)) return (ibvh_status)e;
-    if (bvh->tree.real_nodes <= 1) return IBVH_OK;
-    if (!counts || !contacts) return IBVH_ERR_INVALID_ARG;
-    int64_t dummy;
-    return (ibvh_status)run<MODE_SELF>(bvh, bvh, nullptr, nullptr, bvh->tree.real_leaves, start_level, narrow, 0,
-                                       (void *)counts, &dummy, contacts, scratch, scratch_bytes, (hipStream_t)stream);
+    return self_common(bvh, start_level, narrow, counts && contacts, {.op = OP_WRITE, .counts = (void *)counts, .contacts = contacts,
+                       .scratch = scratch, .scratch_bytes = scratch_bytes, .stream = stream});
 }
 
 // count + scan + writing pass in one go, WITHOUT the host read of the total in between (the reference blocks there,
@@ -202,17 +230,9 @@ ibvh_status ibvh_traverse_lvt_enqueue(const ibvh_bvh *bvh, int64_t start_level, 
                                       int64_t capacity, void *total_dev, void *total_host, void *scratch, size_t scratch_bytes,
                                       void *stream) {
     if (!bvh || capacity < 0) return IBVH_ERR_INVALID_ARG;
-    if (int e = check_levels(*bvh, start_level)) return (ibvh_status)e;
-    if (!scratch || scratch_bytes < scan_scratch_bytes(bvh->tree.real_leaves)) return IBVH_ERR_SCRATCH;
-    if (bvh->tree.real_nodes <= 1) { // traverse_single.jl:17-21: no contacts
-        if (hipMemsetAsync(total_dev ? total_dev : scratch, 0, 8, (hipStream_t)stream) != hipSuccess) return IBVH_ERR_HIP;
-        if (total_host) *(volatile int64_t *)total_host = 0; // (host memory: nothing was launched that could write it later)
-        return IBVH_OK;
-    }
-    if (!counts || (capacity > 0 && !contacts)) return IBVH_ERR_INVALID_ARG;
-    return (ibvh_status)run<MODE_SELF>(bvh, bvh, nullptr, nullptr, bvh->tree.real_leaves, start_level, narrow, 0, counts,
-                                       nullptr, contacts, scratch, scratch_bytes, (hipStream_t)stream, true, capacity,
-                                       (int64_t *)total_dev, (int64_t *)total_host);
+    return self_common(bvh, start_level, narrow, counts && (capacity == 0 || contacts),
+                       {.op = OP_ENQUEUE, .counts = counts, .contacts = contacts, .capacity = capacity, .total_dev = total_dev,
+                        .total_host = total_host, .scratch = scratch, .scratch_bytes = scratch_bytes, .stream = stream});
 }
 // blocking read of the total contact count a *_count / *_enqueue call left in the scratch header
 ibvh_status ibvh_lvt_total(const void *scratch, int64_t *total_out, void *stream) {
@@ -226,14 +246,13 @@ ibvh_status ibvh_lvt_total(const void *scratch, int64_t *total_out, void *stream
 ibvh_status ibvh_lvt_work_counters(const ibvh_bvh *bvh, const ibvh_bvh *bvh2, const void *points, const void *directions,
                                    int64_t num_rays, void *counts, void *work_out, void *stream) {
     if (!bvh || !counts || !work_out) return IBVH_ERR_INVALID_ARG;
-    hipStream_t st = (hipStream_t)stream;
-    if (hipMemsetAsync(work_out, 0, 4 * sizeof(unsigned long long), st) != hipSuccess) return IBVH_ERR_HIP;
+    const Call c{.op = OP_WORK, .counts = counts, .work = (unsigned long long *)work_out, .stream = stream};
+    if (hipMemsetAsync(work_out, 0, 4 * sizeof(unsigned long long), (hipStream_t)stream) != hipSuccess) return IBVH_ERR_HIP;
     const int64_t sl = bvh->built_level > 1 ? bvh->built_level : 1;
     if (int e = check_levels(*bvh, sl)) return (ibvh_status)e; // (all three shapes: levels <= 32, built_level <= start level)
     if (points) {
         if (!directions || num_rays <= 0) return IBVH_ERR_INVALID_ARG;
-        return (ibvh_status)run<MODE_RAYS>(nullptr, bvh, points, directions, num_rays, sl, 0, 0, counts, nullptr, nullptr, nullptr,
-                                           0, st, false, 0, nullptr, nullptr, (unsigned long long *)work_out);
+        return (ibvh_status)run<MODE_RAYS>({.walk = bvh, .points = points, .dirs = directions, .n_items = num_rays, .start_level = sl}, c);
     }
     if (bvh2) {
         if (!same_types(bvh->types, bvh2->types)) return IBVH_ERR_UNSUPPORTED;
@@ -241,19 +260,13 @@ ibvh_status ibvh_lvt_work_counters(const ibvh_bvh *bvh, const ibvh_bvh *bvh2, co
         const ibvh_bvh *drv = flip ? bvh2 : bvh, *oth = flip ? bvh : bvh2;
         const int64_t slo = oth->built_level > 1 ? oth->built_level : 1;
         if (int e = check_levels(*oth, slo)) return (ibvh_status)e;
-        return (ibvh_status)run<MODE_PAIR>(drv, oth, nullptr, nullptr, drv->tree.real_leaves, slo, 0, flip ? 1 : 0, counts, nullptr,
-                                           nullptr, nullptr, 0, st, false, 0, nullptr, nullptr, (unsigned long long *)work_out);
+        return (ibvh_status)run<MODE_PAIR>({.drv = drv, .walk = oth, .n_items = drv->tree.real_leaves, .start_level = slo, .flip = flip ? 1 : 0}, c);
     }
-    if (bvh->tree.real_nodes <= 1) return IBVH_OK;
-    return (ibvh_status)run<MODE_SELF>(bvh, bvh, nullptr, nullptr, bvh->tree.real_leaves, sl, 0, 0, counts, nullptr, nullptr, nullptr, 0,
-                                       st, false, 0, nullptr, nullptr, (unsigned long long *)work_out);
+    return self_common(bvh, sl, IBVH_NARROW_NONE, true, c);
 }
 
 // traverse(bvh1, bvh2, LVTTraversal()) — lvt/traverse_pair.jl:1-116
-static ibvh_status pair_common(const ibvh_bvh *bvh1, const ibvh_bvh *bvh2, int64_t sl1, int64_t sl2, int32_t narrow,
-                               void *counts, int64_t *total_out, void *contacts, void *scratch, size_t scratch_bytes,
-                               void *stream, bool enqueue = false, int64_t capacity = 0, void *total_dev = nullptr,
-                               void *total_host = nullptr) {
+static ibvh_status pair_common(const ibvh_bvh *bvh1, const ibvh_bvh *bvh2, int64_t sl1, int64_t sl2, int32_t narrow, const Call &c) {
     if (!bvh1 || !bvh2) return IBVH_ERR_INVALID_ARG;
     if (int e = check_levels(*bvh1, sl1)) return (ibvh_status)e;
     if (int e = check_levels(*bvh2, sl2)) return (ibvh_status)e;
@@ -261,7 +274,7 @@ static ibvh_status pair_common(const ibvh_bvh *bvh1, const ibvh_bvh *bvh2, int64
     const bool mixed = (narrow & IBVH_PAIR_MIXED_TYPES) != 0;
     narrow &= ~IBVH_PAIR_MIXED_TYPES;
     if (mixed ? bvh1->types.index_type != bvh2->types.index_type : !same_types(bvh1->types, bvh2->types)) return IBVH_ERR_UNSUPPORTED;
-    if (!counts) return IBVH_ERR_INVALID_ARG;
+    if (!c.counts) return IBVH_ERR_INVALID_ARG;
     // the BVH with more leaves supplies the work items; flip restores (bvh1, bvh2) order (:15-36).  IBVH_PAIR_SMALLER_DRIVES: the
     // other way round (the contact SET is the same; the list's order is the smaller BVH's leaf order)
     const bool smaller = (narrow & IBVH_PAIR_SMALLER_DRIVES) != 0;
@@ -270,51 +283,41 @@ static ibvh_status pair_common(const ibvh_bvh *bvh1, const ibvh_bvh *bvh2, int64
     const ibvh_bvh *drv = flip ? bvh2 : bvh1, *oth = flip ? bvh1 : bvh2;
     // the walked tree's nodes are tested against NodeType(query) (:196-197): there is no BSphere(::BBox), the reference raises
     if (drv->types.leaf_kind == IBVH_BBOX && oth->types.node_kind == IBVH_BSPHERE) return IBVH_ERR_UNSUPPORTED;
-    return (ibvh_status)run<MODE_PAIR>(drv, oth, nullptr, nullptr, drv->tree.real_leaves, flip ? sl1 : sl2, narrow,
-                                       flip ? 1 : 0, counts, total_out, contacts, scratch, scratch_bytes,
-                                       (hipStream_t)stream, enqueue, capacity, (int64_t *)total_dev, (int64_t *)total_host);
+    return (ibvh_status)run<MODE_PAIR>({.drv = drv, .walk = oth, .n_items = drv->tree.real_leaves, .start_level = flip ? sl1 : sl2,
+                                        .narrow = narrow, .flip = flip ? 1 : 0}, c);
 }
 ibvh_status ibvh_traverse_pair_lvt_count(const ibvh_bvh *bvh1, const ibvh_bvh *bvh2, int64_t sl1, int64_t sl2,
                                          int32_t narrow, void *counts, int64_t *total_out, void *scratch,
                                          size_t scratch_bytes, void *stream) {
     if (!total_out || !scratch) return IBVH_ERR_INVALID_ARG;
     *total_out = 0;
-    return pair_common(bvh1, bvh2, sl1, sl2, narrow, counts, total_out, nullptr, scratch, scratch_bytes, stream);
+    return pair_common(bvh1, bvh2, sl1, sl2, narrow, {.op = OP_COUNT, .counts = counts, .total_out = total_out, .scratch = scratch,
+                       .scratch_bytes = scratch_bytes, .stream = stream});
 }
 ibvh_status ibvh_traverse_pair_lvt_write(const ibvh_bvh *bvh1, const ibvh_bvh *bvh2, int64_t sl1, int64_t sl2,
                                          int32_t narrow, const void *counts, void *contacts, void *scratch,
                                          size_t scratch_bytes, void *stream) {
     if (!contacts) return IBVH_ERR_INVALID_ARG;
-    int64_t dummy;
-    return pair_common(bvh1, bvh2, sl1, sl2, narrow, (void *)counts, &dummy, contacts, scratch, scratch_bytes, stream);
+    return pair_common(bvh1, bvh2, sl1, sl2, narrow, {.op = OP_WRITE, .counts = (void *)counts, .contacts = contacts, .scratch = scratch,
+                       .scratch_bytes = scratch_bytes, .stream = stream});
 }
-
 ibvh_status ibvh_traverse_pair_lvt_enqueue(const ibvh_bvh *bvh1, const ibvh_bvh *bvh2, int64_t sl1, int64_t sl2,
                                            int32_t narrow, void *counts, void *contacts, int64_t capacity, void *total_dev,
                                            void *total_host, void *scratch, size_t scratch_bytes, void *stream) {
     if (!scratch || capacity < 0 || (capacity > 0 && !contacts)) return IBVH_ERR_INVALID_ARG;
-    return pair_common(bvh1, bvh2, sl1, sl2, narrow, counts, nullptr, contacts, scratch, scratch_bytes, stream, true, capacity,
-                       total_dev, total_host);
+    return pair_common(bvh1, bvh2, sl1, sl2, narrow, {.op = OP_ENQUEUE, .counts = counts, .contacts = contacts, .capacity = capacity,
+                       .total_dev = total_dev, .total_host = total_host, .scratch = scratch, .scratch_bytes = scratch_bytes, .stream = stream});
 }
 
 // traverse_rays(bvh, points, directions, LVTTraversal()) — raytrace/leaf_vs_tree/leaf_vs_tree.jl:1-90
 static ibvh_status rays_common(const ibvh_bvh *bvh, const void *points, const void *dirs, int64_t num_rays, int64_t sl,
-                               int32_t narrow, void *counts, int64_t *total_out, void *contacts, void *scratch, size_t scratch_bytes,
-                               void *stream, bool enqueue = false, int64_t capacity = 0, void *total_dev = nullptr,
-                               void *total_host = nullptr) {
+                               int32_t narrow, const Call &c) {
     if (!bvh || num_rays < 0) return IBVH_ERR_INVALID_ARG;
     if (int e = check_levels(*bvh, sl)) return (ibvh_status)e;
     if (bvh->types.leaf_float != bvh->types.node_float) return IBVH_ERR_UNSUPPORTED;
-    if (num_rays == 0) { // :22-26
-        if (enqueue && (total_dev || scratch) && hipMemsetAsync(total_dev ? total_dev : scratch, 0, 8, (hipStream_t)stream) != hipSuccess)
-            return IBVH_ERR_HIP;
-        if (enqueue && total_host) *(volatile int64_t *)total_host = 0;
-        return IBVH_OK;
-    }
-    if (!points || !dirs || !counts) return IBVH_ERR_INVALID_ARG;
-    return (ibvh_status)run<MODE_RAYS>(nullptr, bvh, points, dirs, num_rays, sl, narrow, 0, counts, total_out, contacts,
-                                       scratch, scratch_bytes, (hipStream_t)stream, enqueue, capacity, (int64_t *)total_dev,
-                                       (int64_t *)total_host);
+    if (num_rays == 0) return nothing_to_walk(c); // :22-26
+    if (!points || !dirs || !c.counts) return IBVH_ERR_INVALID_ARG;
+    return (ibvh_status)run<MODE_RAYS>({.walk = bvh, .points = points, .dirs = dirs, .n_items = num_rays, .start_level = sl, .narrow = narrow}, c);
 }
 ibvh_status ibvh_traverse_rays_lvt_count(const ibvh_bvh *bvh, const void *points, const void *dirs, int64_t num_rays,
                                          int64_t sl, int32_t narrow, void *counts, int64_t *total_out, void *scratch,
@@ -322,21 +325,23 @@ ibvh_status ibvh_traverse_rays_lvt_count(const ibvh_bvh *bvh, const void *points
     if (!total_out) return IBVH_ERR_INVALID_ARG;
     *total_out = 0;
     if (num_rays > 0 && !scratch) return IBVH_ERR_INVALID_ARG;
-    return rays_common(bvh, points, dirs, num_rays, sl, narrow, counts, total_out, nullptr, scratch, scratch_bytes, stream);
+    return rays_common(bvh, points, dirs, num_rays, sl, narrow, {.op = OP_COUNT, .counts = counts, .total_out = total_out,
+                       .scratch = scratch, .scratch_bytes = scratch_bytes, .stream = stream});
 }
 ibvh_status ibvh_traverse_rays_lvt_write(const ibvh_bvh *bvh, const void *points, const void *dirs, int64_t num_rays,
                                          int64_t sl, int32_t narrow, const void *counts, void *contacts, void *scratch,
                                          size_t scratch_bytes, void *stream) {
     if (num_rays > 0 && !contacts) return IBVH_ERR_INVALID_ARG;
-    int64_t dummy;
-    return rays_common(bvh, points, dirs, num_rays, sl, narrow, (void *)counts, &dummy, contacts, scratch, scratch_bytes, stream);
+    return rays_common(bvh, points, dirs, num_rays, sl, narrow, {.op = OP_WRITE, .counts = (void *)counts, .contacts = contacts,
+                       .scratch = scratch, .scratch_bytes = scratch_bytes, .stream = stream});
 }
 ibvh_status ibvh_traverse_rays_lvt_enqueue(const ibvh_bvh *bvh, const void *points, const void *dirs, int64_t num_rays,
                                            int64_t sl, int32_t narrow, void *counts, void *contacts, int64_t capacity,
                                            void *total_dev, void *total_host, void *scratch, size_t scratch_bytes, void *stream) {
     if (!scratch || capacity < 0 || (capacity > 0 && !contacts)) return IBVH_ERR_INVALID_ARG;
-    return rays_common(bvh, points, dirs, num_rays, sl, narrow, counts, nullptr, contacts, scratch, scratch_bytes, stream, true, capacity,
-                       total_dev, total_host);
+    return rays_common(bvh, points, dirs, num_rays, sl, narrow, {.op = OP_ENQUEUE, .counts = counts, .contacts = contacts,
+                       .capacity = capacity, .total_dev = total_dev, .total_host = total_host, .scratch = scratch,
+                       .scratch_bytes = scratch_bytes, .stream = stream});
 }
 
 } // extern "C"

@@ -808,10 +808,6 @@ inline int check_levels(const ibvh_bvh &b, int64_t start_level) {
     if (start_level < 1) return IBVH_ERR_INVALID_ARG;
     return IBVH_OK;
 }
-inline bool same_types(const ibvh_types &x, const ibvh_types &y) {
-    return x.leaf_kind == y.leaf_kind && x.leaf_float == y.leaf_float && x.node_kind == y.node_kind &&
-           x.node_float == y.node_float && x.index_type == y.index_type && x.morton_type == y.morton_type;
-}
 
 // the instantiations ibvh_lvt_work_counters may ask for: the bench types only
 template <class L, class N, class I> constexpr bool kWorkTypes =
