@@ -515,18 +515,15 @@ struct Tuning {
     int lvt_blocks_paired_below = -1; // block grids smaller than this take two levels per trip (-1 = 4096)
     int lvt_blocks_min_items = 0; // fewest work items for the shared descent (0 = 2^17)
     int lvt_xcd = 64;       // LVT item placement: 0 = round robin, 1 = one range per XCD, n = runs of n workgroups
-    int sort_tile = 0;      // LSD path: keys per tile (0 = by size; 2048, 4096, 8192, 16384)
+    // The sort's knobs (sort_lsd, sort_msd_avg, msd, msd_avg, msd_equalize, msd_rescue) only move a threshold or pick
+    // between shipped routes: whatever their values, the planners still take their geometry from the tables the kernels
+    // are compiled from (kFinish in ibvh_msd_impl.hpp, IBVH_SORT_TILES / IBVH_SORT_BUCKETS in ibvh_sort.hip).
     int sort_lsd = 0;       // 1 = ibvh_sort_pairs always takes the plain LSD passes
     int sort_msd_avg = 1536; // ibvh_sort_pairs: largest average bucket before another partition bit is taken
-    int bucket_tpb = 0;     // ibvh_sort_pairs: threads of a bucket workgroup (0 = by capacity)
     int msd = 1;            // 0 = the build never takes the MSD partition path
-    int msd_bits = 0, msd_cap = 0, msd_tile = 0, msd_ftpb = 0; // forced partition geometry (0 = chosen from n)
     int msd_avg = 1024;     // largest average cell before another first-level bit is taken
     int lvt_scan_fused = 1; // the scan behind walker 2's counting pass in one kernel (scan_fused_kernel / scan_fused_grouped_kernel); 0 = reduce + apply; N > 1 = at most N workgroups (development: the default is half of what the device holds at once)
     int msd_equalize = 0;   // equalised cells (ibvh_msd.hip): 0 = when the build asks (ibvh_build_desc.sort_equalize), 1 = always, -1 = never
-    int msd_finish_pad_kb = 0; // LDS (KiB) a finish workgroup asks for at least: limits the workgroups per CU (0 = what it needs)
-    int msd_resident_kb = 0; // LDS budget (KiB) of a finish workgroup that keeps its range's RECORDS in LDS: 0 = the plan decides
-                             // (8,192-record geometry only), > 0 = every geometry with this budget, < 0 = never
     int bfs_wg_per_cu = 4;  // workgroups per CU of the BFS level kernels' fixed grid (ibvh_bfs.hip, level_grid)
     int rays_binned = 1;    // ray traversals (F32 trees) cut the walk at a level and finish it subtree by subtree out of LDS:
                             // 1 = where it pays (rays_bin_plan: >= 17 levels, or >= 13 under <= 8,192 rays; not a small tree under many

@@ -64,13 +64,11 @@ struct Knob {
 };
 const Knob kKnobs[] = {
     {"ray_block", &Tuning::ray_block},   {"lvt_wide", &Tuning::lvt_wide},     {"lvt_xcd", &Tuning::lvt_xcd},
-    {"sort_tile", &Tuning::sort_tile},   {"sort_lsd", &Tuning::sort_lsd},     {"sort_msd_avg", &Tuning::sort_msd_avg},
-    {"bucket_tpb", &Tuning::bucket_tpb}, {"msd", &Tuning::msd},               {"msd_bits", &Tuning::msd_bits},
-    {"msd_cap", &Tuning::msd_cap},       {"msd_tile", &Tuning::msd_tile},     {"msd_ftpb", &Tuning::msd_ftpb},
+    {"sort_lsd", &Tuning::sort_lsd},     {"sort_msd_avg", &Tuning::sort_msd_avg}, {"msd", &Tuning::msd},
     {"msd_avg", &Tuning::msd_avg},       {"msd_equalize", &Tuning::msd_equalize}, {"msd_rescue", &Tuning::msd_rescue}, {"lvt_scan_fused", &Tuning::lvt_scan_fused}, {"bfs_wg_per_cu", &Tuning::bfs_wg_per_cu},
     {"lvt_blocks", &Tuning::lvt_blocks}, {"lvt_block_shift", &Tuning::lvt_block_shift}, {"lvt_blocks_min_items", &Tuning::lvt_blocks_min_items}, {"lvt_blocks_paired_below", &Tuning::lvt_blocks_paired_below},
     {"rays_binned", &Tuning::rays_binned}, {"rays_subtree_depth", &Tuning::rays_subtree_depth},
-    {"rays_items_per_ray", &Tuning::rays_items_per_ray}, {"rays_tail", &Tuning::rays_tail}, {"msd_resident_kb", &Tuning::msd_resident_kb}, {"msd_finish_pad_kb", &Tuning::msd_finish_pad_kb},
+    {"rays_items_per_ray", &Tuning::rays_items_per_ray}, {"rays_tail", &Tuning::rays_tail},
 };
 inline int64_t ilog2_down(int64_t n) { return 63 - __builtin_clzll((unsigned long long)n); }
 } // namespace

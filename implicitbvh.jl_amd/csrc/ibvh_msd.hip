@@ -979,36 +979,45 @@ static size_t carve_tables(Tables *tb, char *base, int radix, int num_tiles, int
 }
 
 Plan make_plan(int64_t n, int key_bits, int key_bytes, int leaf_bytes, void *sort_scratch) {
-    // development knobs (ibvh_set_tuning): msd = 0 disables the path, msd_bits / _cap / _tile / _ftpb force a geometry
-    const int enabled = g_tuning.msd, f_bits = g_tuning.msd_bits, f_cap = g_tuning.msd_cap, f_tile = g_tuning.msd_tile,
-              f_avg = g_tuning.msd_avg, f_ftpb = g_tuning.msd_ftpb;
+    // development knobs (ibvh_set_tuning): msd = 0 disables the path, msd_avg moves the digit width (the finish geometry is
+    // still a row of kFinish)
     Plan p{};
-    if (!enabled || n < 4096 || key_bits <= 8 || n >= ((int64_t)1 << 32) - 65536) return p;
+    if (!g_tuning.msd || n < 4096 || key_bits <= 8 || n >= ((int64_t)1 << 32) - 65536) return p;
     int bits = 6; // (>= 6: the scan kernel works on blocks of 64 digits)
-    while (bits < 11 && bits < key_bits - 1 && (n >> bits) > f_avg) ++bits;
+    while (bits < 11 && bits < key_bits - 1 && (n >> bits) > g_tuning.msd_avg) ++bits;
     // 1.3e7 .. 2.7e7 leaves: 4,096 cells keep the average cell within the 8,192-record finish workgroup (the 16,384-
     // record one runs one workgroup per CU: 2e7 leaves 0.73 -> 0.40 ms for the finish, +0.05 for the wider partition)
     constexpr int64_t kCellMax8k = 8192 * 8 / 10;
     if (bits == 11 && key_bits > 13 && (n >> 11) > kCellMax8k && (n >> 12) <= kCellMax8k) bits = 12;
-    if (f_bits) bits = f_bits;
-    if (bits > MSD_MAX_BITS) bits = MSD_MAX_BITS;
     if (bits >= key_bits) bits = key_bits - 1;
     if (bits < 6) return p;
     const int64_t avg = n >> bits;
     // capacity of the finish workgroup: the average cell fills at most 5/8 of it (uniform clouds vary by a few per
     // cent; denser cells get the rest of the headroom before the second partition level takes them)
-    int cap = 2048;
-    const int cap_max = key_bytes == 8 ? 8192 : 16384; // (16384 x 10 B does not fit the LDS)
     // (the last step is taken later — the average cell may fill 8/10 of the 8,192-record workgroup, a Poisson cell count
     // then stays below it — because the 16,384-record workgroup is so much slower: 1.25e7 leaves 0.43 -> 0.26 ms)
-    while (cap < cap_max && (cap < 8192 ? avg * 8 > (int64_t)cap * 5 : avg * 10 > (int64_t)cap * 8)) cap *= 2;
-    if (f_cap) cap = f_cap;
-    if (cap > cap_max) cap = cap_max;
+    const FinishGeometry *fin = nullptr;
+    for (const FinishGeometry &f : kFinish) {
+        if (f.key_bytes != key_bytes || f.resident) continue;
+        fin = &f;
+        if (f.cap < 8192 ? avg * 8 <= (int64_t)f.cap * 5 : avg * 10 <= (int64_t)f.cap * 8) break;
+    }
+    if (!fin) return p;
+    // Round 4: cells of the 8,192-record geometry (~2.5 .. 6.5 k records of 24 bytes: 1e7-leaf builds) are finished with
+    // their RECORDS resident in LDS — read from memory once instead of ~2.8 times (finish_range, resident path) — by one
+    // 1,024-thread workgroup per CU (the memory phases of a lone workgroup need that many loads in flight); cells beyond the
+    // ~5,000 records that fit beside the sort's arrays take the plain path inside the same kernel.  Measured at 1e7 leaves:
+    // finish 212 -> 196 us, Morton+sort 463 -> 448 us; smaller geometries lose (1e6: 24 -> 32 us: fewer workgroups per CU)
+    // and keep the plain kernel.  kFinish has that form for 32-bit keys only.
+    // (cells of ~3,000 records — 1.25e7 leaves at 12 bits — lose: 289 against 265 us; the rule asks for >= 4,096 on average)
+    if (fin->cap == 8192 && avg >= 4096 && leaf_bytes <= 24)
+        for (const FinishGeometry &f : kFinish)
+            if (f.key_bytes == key_bytes && f.cap == fin->cap && f.resident) fin = &f;
+    const int cap = fin->cap;
     // partition tile: its records are staged in LDS (tile * leaf_bytes + 2 tables of 2^bits words <= 160 KiB)
     int tile = (n >= (int64_t(1) << 22) && leaf_bytes <= 32) ? 4096 : 2048;
-    if (f_tile) tile = f_tile;
     while (tile > 1024 && (size_t)tile * leaf_bytes + ((size_t)8 << bits) + 128 > 160 * 1024) tile >>= 1;
-    while (!f_tile && tile > 1024 && tile > cap / 2) tile >>= 1; // a window of sub-cells (< tile + one sub-cell) should fit the LDS sort
+    while (tile > 1024 && tile > cap / 2) tile >>= 1; // a window of sub-cells (< tile + one sub-cell) should fit the LDS sort
     switch (tile) {
     case 1024: p.ptpb = 256, p.pipt = 4; break;
     case 2048: p.ptpb = 256, p.pipt = 8; break;
@@ -1016,23 +1025,8 @@ Plan make_plan(int64_t n, int key_bits, int key_bytes, int leaf_bytes, void *sor
     }
     if ((size_t)tile * leaf_bytes + ((size_t)8 << bits) + 128 > 160 * 1024) return p;
     // finish workgroups are small (4 or 8 waves, many keys per thread): several ranges per CU at different phases
-    switch (cap) {
-    case 2048: p.ftpb = 256; break;
-    case 4096: p.ftpb = 256; break;
-    case 8192: p.ftpb = 512; break;
-    default: p.ftpb = 512; break;
-    }
-    // Round 4: cells of the 8,192-record geometry (~2.5 .. 6.5 k records of 24 bytes: 1e7-leaf builds) are finished with
-    // their RECORDS resident in LDS — read from memory once instead of ~2.8 times (finish_range, resident path) — by one
-    // 1,024-thread workgroup per CU (the memory phases of a lone workgroup need that many loads in flight); cells beyond the
-    // ~5,000 records that fit beside the sort's arrays take the plain path inside the same kernel.  Measured at 1e7 leaves:
-    // finish 212 -> 196 us, Morton+sort 463 -> 448 us (tools/ab_sort.py); smaller geometries lose (1e6: 24 -> 32 us: fewer
-    // workgroups per CU) and keep the plain kernel.
-    // (cells of ~3,000 records — 1.25e7 leaves at 12 bits — lose: 289 against 265 us; the rule asks for >= 4,096 on average)
-    p.resident = cap == 8192 && avg >= 4096 && key_bytes == 4 && leaf_bytes <= 24 && g_tuning.msd_resident_kb >= 0 && !f_ftpb;
-    if (p.resident) p.ftpb = 1024;
-    if (f_ftpb) p.ftpb = f_ftpb;
-    p.fipt = cap / p.ftpb;
+    p.ftpb = fin->threads;
+    p.fipt = cap / fin->threads;
     p.bits = bits;
     p.shift = key_bits - bits;
     p.num_tiles = (int)ceil_div(n, (int64_t)tile);

@@ -47,8 +47,7 @@ struct Plan {
     int shift;           // key_bits - bits: the cell is key >> shift
     int ptpb, pipt;      // partition (and histogram) tile geometry
     int num_tiles;
-    int ftpb, fipt;      // finish workgroup: threads, keys per thread (capacity = ftpb * fipt)
-    bool resident;       // the finish keeps a cell's records in LDS (ibvh_msd.hip, finish_range)
+    int ftpb, fipt;      // finish workgroup: threads, keys per thread (capacity = ftpb * fipt): a row of kFinish (ibvh_msd_impl.hpp)
     int max_seg;         // S
     int max_tiles2;      // T2
     int rescuers;        // H: rescue workgroups at the end of the finish grid (scratch is carved for them)

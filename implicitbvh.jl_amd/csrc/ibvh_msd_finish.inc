@@ -1,8 +1,8 @@
 // ibvh_msd_finish.inc — the finish kernel of the build's sort and its launcher, as templates: every cell of the partitioned
 // records (and every window of sub-cells of a crowded cell) is sorted by one workgroup in LDS and written to its final place.
-// Included by the translation units that instantiate its geometries (ibvh_msd_finish_a / _b / _c.hip: the 26 geometries take
-// three minutes to compile in one unit) — see ibvh_msd_finish.hip for the list and ibvh_msd.hip for the whole picture
-// (replaces AK.sort!(leaves, by = bv -> bv.morton), reference src/build.jl:248-253).  gfx950 only.
+// Included by ibvh_msd_finish.hip, whose dispatcher instantiates the geometries of kFinish (ibvh_msd_impl.hpp) — see
+// ibvh_msd.hip for the whole picture (replaces AK.sort!(leaves, by = bv -> bv.morton), reference src/build.jl:248-253).
+// gfx950 only.
 #include "ibvh_msd_impl.hpp"
 
 namespace ibvh {
@@ -662,27 +662,24 @@ template <class K, int TPB, int IPT> constexpr size_t finish_smem() {
     return (size_t)TPB * IPT * (sizeof(K) + 2) + 2 * 256 * 4 + 64 + (size_t)(TPB / 64) * 256 * 2 + 64;
 }
 
-template <class K, int FT, int FI>
+template <class K, int FT, int FI, bool RES>
 int launch_finish(const Plan &p, const FinishArgs &fa_in, hipStream_t st) {
     FinishArgs fa = fa_in;
     size_t smem = finish_smem<K, FT, FI>();
-    // resident path: room for a full range of records behind the sort's arrays, as long as the workgroup stays within the
-    // LDS budget (tuning msd_resident_kb; 0 = off: the records are then gathered from memory as in rounds 2 and 3)
-    if (sizeof(K) == 4 && (g_tuning.msd_resident_kb > 0 || p.resident)) {
+    // resident geometry (kFinish): room for a full range of records behind the sort's arrays, as long as the workgroup
+    // stays within the LDS (what does not fit takes the plain path)
+    if constexpr (RES) {
+        static_assert(sizeof(K) == 4, "the resident finish keeps 32-bit keys");
         const size_t cap = (size_t)FT * FI;
         const size_t off = (size_t)align_up((int64_t)(smem - cap * 2), 16); // (no 16-bit positions in front of the record area)
-        const size_t want = g_tuning.msd_resident_kb > 0 ? (size_t)g_tuning.msd_resident_kb * 1024 : (size_t)kMaxLds;
-        const size_t budget = want < (size_t)kMaxLds ? want : (size_t)kMaxLds;
-        size_t rec = cap * (size_t)fa.lay.stride;  // a full range, or what the budget leaves (larger ranges take the plain path)
-        if (off + rec > budget) rec = budget > off ? ((budget - off) / 8) * 8 : 0;
+        size_t rec = cap * (size_t)fa.lay.stride;  // a full range, or what the LDS leaves (larger ranges take the plain path)
+        if (off + rec > (size_t)kMaxLds) rec = (size_t)kMaxLds > off ? (((size_t)kMaxLds - off) / 8) * 8 : 0;
         if (rec >= cap * 2 && rec >= 1024 * (size_t)fa.lay.stride) {
             fa.resident_off = (uint32_t)off;
             fa.resident_words = (uint32_t)(rec / 8);
             smem = off + rec;
         }
     }
-    // (development knob: ask for more LDS than needed, i.e. fewer workgroups per CU — a smaller footprint in flight per L2)
-    if ((size_t)g_tuning.msd_finish_pad_kb * 1024 > smem && g_tuning.msd_finish_pad_kb <= 160) smem = (size_t)g_tuning.msd_finish_pad_kb * 1024;
     const int f2 = fa.levels <= 0 ? 0 : (p.max_tiles2 < 1024 ? p.max_tiles2 : 1024); // workgroups that stride over the extra levels' windows
     fa.normal_wgs = (1u << p.bits) + (uint32_t)f2;
     // the rescue workgroups WAIT for the ordinary ones: never more of them than HALF the workgroups of this kernel the device
@@ -706,7 +703,7 @@ int launch_finish(const Plan &p, const FinishArgs &fa_in, hipStream_t st) {
         if (fa.rescuers > memo.room) fa.rescuers = memo.room;
         return IBVH_OK;
     };
-    if constexpr (sizeof(K) == 4) {
+    if constexpr (RES) {
         if (fa.resident_words) { // (a kernel of its own: the resident branch must not cost the plain one registers)
             IBVH_HIP_CHECK(hipFuncSetAttribute((const void *)finish_kernel<K, FT, FI, true>, hipFuncAttributeMaxDynamicSharedMemorySize, kMaxLds));
             if (fa.rescuers) { if (int e = clamp_rescuers((const void *)finish_kernel<K, FT, FI, true>)) return e; }

@@ -1,5 +1,5 @@
 // ibvh_msd_impl.hpp — what ibvh_msd.hip (tables, sample, partition, host driver) and ibvh_msd_finish.hip (the in-LDS finish) share:
-// two translation units because the finish kernel's 26 geometries alone take a minute to compile.  Not an interface: see ibvh_msd.hpp.
+// two translation units because the finish kernel's geometries take half a minute to compile.  Not an interface: see ibvh_msd.hpp.
 #pragma once
 #include <cstdlib>
 
@@ -80,6 +80,22 @@ template <class K> IBVH_D void cell_range(const Tables &tb, uint32_t d, int radi
     *lo_out = lo;
     *nbits_out = span == 0 ? 0 : 64 - __builtin_clzll(span);
 }
+
+// Every finish workgroup make_plan() can choose: X(key type, capacity, threads, resident); keys per thread = capacity / threads.
+// run_finish() (ibvh_msd_finish.hip) dispatches over this table and so instantiates exactly its kernels; `resident` marks the
+// geometry whose launch may keep a range's RECORDS in LDS (its kernel exists in that form as well as the plain one).  For each
+// key type the plain rows are in ascending capacity: make_plan takes the first one the average cell fits, else the last
+// (64-bit keys stop at 8,192: 16,384 x 10 B does not fit the LDS).
+#define IBVH_FINISH_GEOMETRIES(X)                                                                                             \
+    X(uint32_t, 2048, 256, false) X(uint32_t, 4096, 256, false) X(uint32_t, 8192, 512, false) X(uint32_t, 8192, 1024, true)    \
+    X(uint32_t, 16384, 512, false) X(uint64_t, 2048, 256, false) X(uint64_t, 4096, 256, false) X(uint64_t, 8192, 512, false)
+struct FinishGeometry {
+    int key_bytes, cap, threads;
+    bool resident;
+};
+#define IBVH_FINISH_ROW(K, C, T, R) FinishGeometry{(int)sizeof(K), C, T, R},
+constexpr FinishGeometry kFinish[] = {IBVH_FINISH_GEOMETRIES(IBVH_FINISH_ROW)};
+#undef IBVH_FINISH_ROW
 
 constexpr int kMaxLds = 160 * 1024; // LDS of a gfx950 CU
 constexpr int kRescuers = 512;       // rescue workgroups of the finish kernel that scratch is carved for; a launch uses at most half of what the device holds at once (they WAIT for the ordinary workgroups)

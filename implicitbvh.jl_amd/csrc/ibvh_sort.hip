@@ -508,28 +508,29 @@ struct FirstPassPlan {
     uint32_t mask;
     int shift, bits; // the digit the first pass sorts on: (key >> shift) & mask
 };
+// The geometries (threads, keys per thread) the kernels below are compiled for.  The planners pick an entry of these
+// tables and sort_pairs() dispatches over the same tables, so every plan has its kernels.  (X-macros: X(args..., T, P).)
+//   tiles of the LSD passes and of the hybrid's partition: small, large (choose_geometry)
+//   workgroups of the hybrid's bucket sort, by capacity: 2,048 and 4,096 keys (choose_msd)
+#define IBVH_SORT_TILES(X, ...) X(__VA_ARGS__, 256, 8) X(__VA_ARGS__, 512, 16)
+#define IBVH_SORT_BUCKETS(X, ...) X(__VA_ARGS__, 256, 8) X(__VA_ARGS__, 512, 8)
+#define IBVH_GEOMETRY(_, T, P) Geometry{T, P},
+constexpr Geometry kTiles[] = {IBVH_SORT_TILES(IBVH_GEOMETRY, _)};
+constexpr Geometry kBuckets[] = {IBVH_SORT_BUCKETS(IBVH_GEOMETRY, _)};
+#undef IBVH_GEOMETRY
+
 // Small inputs get small tiles so the grid still covers the 256 CUs; large inputs get 8192-element
 // tiles so that one digit's run in a tile is >= 128 B on average.
-inline Geometry choose_geometry(int64_t n) {
-    const int forced = g_tuning.sort_tile; // 2048, 4096, 8192 or 16384 keys per tile
-    switch (forced) {
-    case 2048: return Geometry{256, 8};
-    case 4096: return Geometry{256, 16};
-    case 8192: return Geometry{512, 16};
-    case 16384: return Geometry{1024, 16};
-    }
-    return n >= (int64_t(1) << 22) ? Geometry{512, 16} : Geometry{256, 8};
-}
+inline Geometry choose_geometry(int64_t n) { return kTiles[n >= (int64_t(1) << 22) ? 1 : 0]; }
 
-// MSD + in-LDS hybrid: which digit width and which bucket-kernel capacity, or {0, 0} for plain LSD
+// MSD + in-LDS hybrid: which digit width and which bucket workgroup, or bits = 0 for plain LSD
 struct MsdPlan {
-    int bits;     // MSD digit width (0 = do not use the hybrid)
-    int capacity; // keys a bucket workgroup sorts in LDS: 2048, 4096 or 8192
-    int btpb;     // threads of the bucket workgroup (capacity / btpb keys per thread)
+    int bits;        // MSD digit width (0 = do not use the hybrid)
+    Geometry bucket; // the workgroup that sorts a bucket in LDS (an entry of kBuckets)
 };
 inline MsdPlan choose_msd(int64_t n, int key_bits, int key_bytes) {
     const int mode = g_tuning.sort_lsd ? 1 : 0;
-    if (mode == 1 || n < 2048 || key_bits <= 8) return {0, 0, 0};
+    if (mode == 1 || n < 2048 || key_bits <= 8) return {0, {}};
     const int msd_avg_max = g_tuning.sort_msd_avg;
     int bits = 1;
     while (bits < MSD_MAX_BITS && bits < key_bits && (n >> bits) > msd_avg_max) ++bits;
@@ -537,16 +538,9 @@ inline MsdPlan choose_msd(int64_t n, int key_bits, int key_bytes) {
     // Measured on MI355X (round 1): the hybrid beats plain LSD while buckets fit 4096-key workgroups
     // (Morton+sort phase 0.366 vs 0.422 ms at 6e6 leaves, 0.109 vs 0.139 ms at 1e6) and loses with 8192-key
     // workgroups (0.652 vs 0.589 ms at 1e7: the bucket kernel is barrier-bound), so larger inputs keep LSD.
-    const int cap_max = 4096;
-    int cap = 2048;
-    while (cap < cap_max && avg * 4 > cap * 3) cap *= 2; // average bucket <= 3/4 of the capacity
-    if (avg * 4 > (int64_t)cap * 3) return {0, 0, 0};   // too many keys for one partition level: LSD
-    const int forced_tpb = g_tuning.bucket_tpb;
-    int btpb = cap == 2048 ? 256 : (cap == 4096 ? 512 : 1024);
-    if (forced_tpb == 256 || forced_tpb == 512 || forced_tpb == 1024) btpb = forced_tpb;
-    if (cap / btpb < 8) btpb = cap / 8;
-    if (cap / btpb > 32) btpb = cap / 32;
-    return {bits, cap, btpb};
+    for (const Geometry &b : kBuckets)
+        if (avg * 4 <= (int64_t)b.tile() * 3) return {bits, b}; // average bucket <= 3/4 of the capacity
+    return {0, {}};                                               // too many keys for one partition level: LSD
 }
 
 size_t scratch_bytes(int64_t n) {
@@ -600,13 +594,13 @@ int run_passes(K *keys, uint32_t *vals, K *keys_alt, uint32_t *vals_alt, int64_t
 
 template <class K, int TPB, int IPT, int BT, int BI>
 int run_msd(K *keys, uint32_t *vals, K *keys_alt, uint32_t *vals_alt, int64_t n, int key_bits, bool vals_implicit,
-            int32_t *result_in_alt, void *scratch, hipStream_t st, bool first_hist_done, const RecordArgs *records, int msd_bits) {
+            int32_t *result_in_alt, void *scratch, hipStream_t st, bool first_hist_done, const RecordArgs *records, int digit_bits) {
     const int num_tiles = (int)ceil_div(n, TPB * IPT);
-    const int radix = 1 << msd_bits;
-    const int shift = key_bits - msd_bits;
+    const int radix = 1 << digit_bits;
+    const int shift = key_bits - digit_bits;
     uint32_t *tile_hist = (uint32_t *)scratch;
     uint32_t *digit_total = (uint32_t *)((char *)scratch + align_up((int64_t)radix * num_tiles * 4, 256));
-    const size_t ssm = scatter_wide_smem<K, TPB, IPT>(msd_bits);
+    const size_t ssm = scatter_wide_smem<K, TPB, IPT>(digit_bits);
     constexpr size_t bsm = bucket_smem<K, BT, BI>();
     IBVH_HIP_CHECK(hipFuncSetAttribute((const void *)scatter_wide_kernel<K, TPB, IPT>,
                                        hipFuncAttributeMaxDynamicSharedMemorySize, (int)scatter_wide_smem<K, TPB, IPT>(MSD_MAX_BITS)));
@@ -615,11 +609,11 @@ int run_msd(K *keys, uint32_t *vals, K *keys_alt, uint32_t *vals_alt, int64_t n,
     IBVH_HIP_CHECK(hipFuncSetAttribute((const void *)bucket_sort_kernel<K, BT, BI, true>,
                                        hipFuncAttributeMaxDynamicSharedMemorySize, (int)bsm));
     if (!first_hist_done)
-        IBVH_LAUNCH((hist_wide_kernel<K, TPB, IPT>), dim3(num_tiles), dim3(TPB), (size_t)radix * 4, st, keys, n, shift, msd_bits,
+        IBVH_LAUNCH((hist_wide_kernel<K, TPB, IPT>), dim3(num_tiles), dim3(TPB), (size_t)radix * 4, st, keys, n, shift, digit_bits,
                     tile_hist, num_tiles);
     IBVH_LAUNCH((scan_kernel<256>), dim3(radix), dim3(256), 0, st, tile_hist, num_tiles, digit_total);
     IBVH_LAUNCH((scatter_wide_kernel<K, TPB, IPT>), dim3(num_tiles), dim3(TPB), ssm, st, keys,
-                vals_implicit ? (const uint32_t *)nullptr : vals, keys_alt, vals_alt, n, shift, msd_bits, tile_hist, digit_total,
+                vals_implicit ? (const uint32_t *)nullptr : vals, keys_alt, vals_alt, n, shift, digit_bits, tile_hist, digit_total,
                 num_tiles);
     if (records)
         IBVH_LAUNCH((bucket_sort_kernel<K, BT, BI, true>), dim3(radix), dim3(BT), bsm, st, keys_alt, vals_alt, keys, vals,
@@ -632,20 +626,17 @@ int run_msd(K *keys, uint32_t *vals, K *keys_alt, uint32_t *vals_alt, int64_t n,
     return IBVH_OK;
 }
 
-bool uses_hybrid(int64_t n, int key_bits, int key_bytes);
-
 // vals_implicit: the values of the first pass are the element positions 0..n-1 (vals is not read).
 // Where the first pass expects its per-tile histogram ([RADIX][num_tiles], digit-major) and the tile
 // geometry it will use, for a producer that fuses that histogram into its own pass (ibvh_build.hip).
 FirstPassPlan first_pass_plan(int64_t n, int key_bits, int key_bytes, void *scratch) {
-    Geometry g = choose_geometry(n);
-    if (key_bytes == 8 && g.tpb == 1024) g = Geometry{512, 16}; // same fallback as sort_pairs
+    const Geometry g = choose_geometry(n);
     FirstPassPlan p;
     p.tpb = g.tpb;
     p.ipt = g.ipt;
     p.num_tiles = (int)ceil_div(n, g.tile());
     p.tile_hist = (uint32_t *)scratch;
-    const MsdPlan mp = uses_hybrid(n, key_bits, key_bytes) ? choose_msd(n, key_bits, key_bytes) : MsdPlan{0, 0, 0};
+    const MsdPlan mp = choose_msd(n, key_bits, key_bytes);
     if (mp.bits) { // MSD partition first: histogram of the TOP digit
         p.bits = mp.bits;
         p.shift = key_bits - mp.bits;
@@ -657,11 +648,7 @@ FirstPassPlan first_pass_plan(int64_t n, int key_bits, int key_bytes, void *scra
     return p;
 }
 
-bool uses_hybrid(int64_t n, int key_bits, int key_bytes) {
-    if (choose_msd(n, key_bits, key_bytes).bits == 0) return false;
-    Geometry g = choose_geometry(n);
-    return g.tpb != 1024; // forced 16384-key tiles have no partition instantiation
-}
+bool uses_hybrid(int64_t n, int key_bits, int key_bytes) { return choose_msd(n, key_bits, key_bytes).bits != 0; }
 
 int sort_pairs(int key_bytes, int key_bits, int64_t n, void *keys, void *vals, void *keys_alt, void *vals_alt,
                bool vals_implicit, int32_t *result_in_alt, void *scratch, size_t scratch_sz, hipStream_t st,
@@ -670,56 +657,30 @@ int sort_pairs(int key_bytes, int key_bits, int64_t n, void *keys, void *vals, v
     if (scratch_sz < scratch_bytes(n)) return IBVH_ERR_SCRATCH;
     *result_in_alt = 0;
     if (n == 0) return IBVH_OK;
-    Geometry g = choose_geometry(n);
-    const MsdPlan mp = uses_hybrid(n, key_bits, key_bytes) ? choose_msd(n, key_bits, key_bytes) : MsdPlan{0, 0, 0};
-    if (mp.bits) {
-        if (key_bytes == 8 && g.tpb == 1024) g = Geometry{512, 16};
+    const Geometry g = choose_geometry(n);
+    const MsdPlan mp = choose_msd(n, key_bits, key_bytes);
+    // (g and mp.bucket are entries of the tables these cases expand from: one of them matches)
 #define IBVH_MSD_CASE(K, T, P, BT, BI)                                                                                \
-    if (g.tpb == T && g.ipt == P && mp.capacity == BT * BI && mp.btpb == BT)                                          \
+    if (g.tpb == T && g.ipt == P && mp.bucket.tpb == BT && mp.bucket.ipt == BI)                                       \
         return run_msd<K, T, P, BT, BI>((K *)keys, (uint32_t *)vals, (K *)keys_alt, (uint32_t *)vals_alt, n, key_bits, \
                                         vals_implicit, result_in_alt, scratch, st, first_hist_done, records, mp.bits);
-#define IBVH_MSD_GEOM(K, T, P)                                                                                         \
-    IBVH_MSD_CASE(K, T, P, 256, 8) IBVH_MSD_CASE(K, T, P, 512, 8) IBVH_MSD_CASE(K, T, P, 1024, 8) IBVH_MSD_CASE(K, T, P, 256, 16) \
-    IBVH_MSD_CASE(K, T, P, 256, 32) IBVH_MSD_CASE(K, T, P, 512, 16)
-        if (key_bytes == 4) {
-            IBVH_MSD_GEOM(uint32_t, 256, 8)
-            IBVH_MSD_GEOM(uint32_t, 256, 16)
-            IBVH_MSD_GEOM(uint32_t, 512, 16)
-        } else {
-            IBVH_MSD_CASE(uint64_t, 256, 8, 256, 8)
-            IBVH_MSD_CASE(uint64_t, 256, 8, 512, 8)
-            IBVH_MSD_CASE(uint64_t, 256, 8, 256, 16)
-            IBVH_MSD_CASE(uint64_t, 256, 16, 256, 8)
-            IBVH_MSD_CASE(uint64_t, 256, 16, 512, 8)
-            IBVH_MSD_CASE(uint64_t, 256, 16, 256, 16)
-            IBVH_MSD_CASE(uint64_t, 512, 16, 256, 8)
-            IBVH_MSD_CASE(uint64_t, 512, 16, 512, 8)
-            IBVH_MSD_CASE(uint64_t, 512, 16, 256, 16)
-        }
-#undef IBVH_MSD_GEOM
-#undef IBVH_MSD_CASE
-        // (forced 16384-key tiles have no partition instantiation: fall through to LSD)
-    }
+#define IBVH_MSD_TILE(K, T, P) IBVH_SORT_BUCKETS(IBVH_MSD_CASE, K, T, P)
 #define IBVH_SORT_CASE(K, T, P)                                                                                       \
     if (g.tpb == T && g.ipt == P)                                                                                     \
         return run_passes<K, T, P>((K *)keys, (uint32_t *)vals, (K *)keys_alt, (uint32_t *)vals_alt, n, key_bits,     \
                                    vals_implicit, result_in_alt, scratch, st, first_hist_done, records);
     if (key_bytes == 4) {
-        IBVH_SORT_CASE(uint32_t, 256, 8)
-        IBVH_SORT_CASE(uint32_t, 256, 16)
-        IBVH_SORT_CASE(uint32_t, 512, 16)
-        IBVH_SORT_CASE(uint32_t, 1024, 16)
+        if (mp.bits) { IBVH_SORT_TILES(IBVH_MSD_TILE, uint32_t) }
+        IBVH_SORT_TILES(IBVH_SORT_CASE, uint32_t)
     }
     if (key_bytes == 8) {
-        IBVH_SORT_CASE(uint64_t, 256, 8)
-        IBVH_SORT_CASE(uint64_t, 256, 16)
-        IBVH_SORT_CASE(uint64_t, 512, 16)
-        if (g.tpb == 1024) // 16384 x 12 B does not fit the LDS: fall back to 8192
-            return run_passes<uint64_t, 512, 16>((uint64_t *)keys, (uint32_t *)vals, (uint64_t *)keys_alt, (uint32_t *)vals_alt, n,
-                                                 key_bits, vals_implicit, result_in_alt, scratch, st, first_hist_done, records);
+        if (mp.bits) { IBVH_SORT_TILES(IBVH_MSD_TILE, uint64_t) }
+        IBVH_SORT_TILES(IBVH_SORT_CASE, uint64_t)
     }
 #undef IBVH_SORT_CASE
-    return IBVH_ERR_INVALID_ARG;
+#undef IBVH_MSD_TILE
+#undef IBVH_MSD_CASE
+    return IBVH_ERR_INVALID_ARG; // (key_bytes other than 4 or 8)
 }
 
 } // namespace rsort

@@ -419,7 +419,8 @@ def test_header_lists_exactly_the_knobs_the_library_has():
     v = C.c_int32()
     for name in sorted(product):
         assert L.ibvh_get_tuning(name.encode(), C.byref(v)) == 0, name
-    for name in ("lvt_dual", "rays_shadow", "msd_range", "rays_fast_slab", "nope"):
+    for name in ("lvt_dual", "rays_shadow", "msd_range", "rays_fast_slab", "sort_tile", "bucket_tpb", "msd_bits", "msd_cap",
+                 "msd_tile", "msd_ftpb", "msd_resident_kb", "msd_finish_pad_kb", "nope"):
         assert L.ibvh_get_tuning(name.encode(), C.byref(v)) != 0
 
 

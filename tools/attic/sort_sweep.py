@@ -1,6 +1,6 @@
 #!/usr/bin/env python3
 """Run ON THE GPU BOX: time the build's sort kernels under different development knobs (ibvh_set_tuning names, e.g.
-msd_bits=10,msd_tile=2048; one bench.py child per setting, handed over as IBVH_TUNING, which the Python binding applies
+msd_avg=2048,msd_equalize=1; one bench.py child per setting, handed over as IBVH_TUNING, which the Python binding applies
 when it loads the library).  usage: python tools/sort_sweep.py N "name=V,name=V" "name=V" ...
 Prints one line per setting: Morton+sort phase ms and the per-kernel averages (us)."""
 import json
