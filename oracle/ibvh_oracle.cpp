@@ -92,6 +92,14 @@ template <class Rec> inline bool narrow_eval(int narrow, const Rec &a, const Rec
     default: return true;
     }
 }
+// two record types (a mixed pair, IBVH_PAIR_MIXED_TYPES): Julia promotes two Morton widths, so compare them as uint64
+template <class RA, class RB> inline bool narrow_eval(int narrow, const RA &a, const RB &b) {
+    switch (narrow) {
+    case IBVH_NARROW_MORTON_LT: return uint64_t(a.morton) < uint64_t(b.morton);
+    case IBVH_NARROW_INDEX_LT: return a.index < b.index;
+    default: return true;
+    }
+}
 
 // ------------------------------------------------------------------------------------------
 // build — build.jl
@@ -296,14 +304,16 @@ inline void lvt_single_leaf(const View<L, N, I, M> &bvh, int64_t ileaf, int64_t 
     lvt_walk_counted<I>(bvh, start_level, p, tc);
 }
 
-// traverse_lvt_pair! — bv from the driving BVH against the other tree; FLIP restores order.
-template <class L, class N, class I, class M, class Emit>
-inline void lvt_pair_leaf(const BoundingVolume<L, I, M> &bv, const View<L, N, I, M> &bvh, int64_t start_level,
+// traverse_lvt_pair! — bv from the driving BVH against the other tree; FLIP restores order.  BV: the driving tree's record
+// (BoundingVolume<L, I, M>), or one of another volume type (IBVH_PAIR_MIXED_TYPES, widen_leaves): nodes are tested against
+// NodeType(bv.volume), leaves with iscontact on the raw mixed types (lvt/traverse_pair.jl:196-201)
+template <class BV, class L, class N, class I, class M, class Emit>
+inline void lvt_pair_leaf(const BV &bv, const View<L, N, I, M> &bvh, int64_t start_level,
                           int narrow, bool flip, Emit &&emit, TestCounts *tc = nullptr) {
     N bv_node = convert_to(bv.volume, (N *)nullptr);
     struct P {
         const View<L, N, I, M> &bvh;
-        const BoundingVolume<L, I, M> &bv;
+        const BV &bv;
         const N &bv_node;
         int narrow;
         bool flip;
@@ -361,6 +371,54 @@ inline int check_levels(const ibvh_bvh &b, int64_t start_level, bool lvt) {
     return IBVH_OK;
 }
 inline bool same_types(const ibvh_types &a, const ibvh_types &b) { return std::memcmp(&a, &b, sizeof(a)) == 0; }
+
+// a mixed pair's leaves with their Morton codes widened to uint64 (only NARROW_MORTON_LT reads them, and Julia promotes
+// two Morton widths): both trees' leaves are read once into such records, so the walk is instantiated per volume and
+// index type only, not per pair of Morton widths
+template <class V, class I> int widen_leaves(const ibvh_bvh &b, std::vector<BoundingVolume<V, I, uint64_t>> &out) {
+    out.resize(b.tree.real_leaves);
+    return dispatch_morton(b.types.morton_type, [&](auto mt) -> int {
+        const auto *rec = (const BoundingVolume<V, I, typename decltype(mt)::type> *)b.leaves;
+        for (size_t i = 0; i < out.size(); ++i) out[i] = {rec[i].volume, rec[i].index, uint64_t(rec[i].morton)};
+        return IBVH_OK;
+    });
+}
+
+// the two passes of the pair walk over n driving records q[0..n) against the walked tree vo
+template <class BV, class L, class N, class I, class M>
+static int pair_lvt_walk(const BV *q, int64_t n, const View<L, N, I, M> &vo, int64_t sl_other, int32_t narrow, bool flip,
+                         void *counts, int64_t *total_out, void *contacts, int threads, TestCounts *tc_out) {
+    I *c = (I *)counts;
+    // (threads > 1: contiguous chunks handed out dynamically, lvt/traverse_pair.jl:119-173's task ranges; every
+    // driving leaf writes its own count / its own output range, so the result does not depend on the team)
+    if (!contacts) {
+        std::mutex mu;
+        parallel_chunks(n, threads, 2048, [&](int, int64_t lo, int64_t hi) {
+            TestCounts tc;
+            for (int64_t i = lo + 1; i <= hi; ++i) {
+                int64_t cnt = 0;
+                auto emit = [&](I, I) { ++cnt; };
+                lvt_pair_leaf(q[i - 1], vo, sl_other, narrow, flip, emit, tc_out ? &tc : nullptr);
+                c[i - 1] = I(cnt);
+            }
+            if (tc_out) {
+                std::lock_guard<std::mutex> g(mu);
+                tc_out->node += tc.node;
+                tc_out->leaf += tc.leaf;
+            }
+        });
+        return scan_counts(c, n, total_out);
+    }
+    IndexPair<I> *out = (IndexPair<I> *)contacts;
+    parallel_chunks(n, threads, 2048, [&](int, int64_t lo, int64_t hi) {
+        for (int64_t i = lo + 1; i <= hi; ++i) {
+            int64_t w = (i == 1) ? 0 : (int64_t)c[i - 2];
+            auto emit = [&](I a, I b) { out[w++] = {a, b}; };
+            lvt_pair_leaf(q[i - 1], vo, sl_other, narrow, flip, emit);
+        }
+    });
+    return IBVH_OK;
+}
 
 // ------------------------------------------------------------------------------------------
 // BFS — bfs/traverse_single.jl + traverse_single_cpu.jl (single-task order),
@@ -848,53 +906,51 @@ int oracle_traverse_lvt_write(const ibvh_bvh *bvh, int64_t start_level, int32_t 
     });
 }
 
+// narrow: a pair code, optionally with IBVH_PAIR_SMALLER_DRIVES and IBVH_PAIR_MIXED_TYPES (their meaning in include/ibvh.h)
 static int pair_lvt(const ibvh_bvh *bvh1, const ibvh_bvh *bvh2, int64_t sl1, int64_t sl2, int32_t narrow,
                     void *counts, int64_t *total_out, void *contacts, int threads = 1, TestCounts *tc_out = nullptr) {
     if (int e = check_levels(*bvh1, sl1, true)) return e;
     if (int e = check_levels(*bvh2, sl2, true)) return e;
-    if (!same_types(bvh1->types, bvh2->types)) return IBVH_ERR_UNSUPPORTED;
-    // traverse_pair.jl:15-36: the BVH with more leaves drives; flip restores (bvh1, bvh2) order
-    bool flip = !(bvh1->tree.real_leaves >= bvh2->tree.real_leaves);
+    const bool mixed = (narrow & IBVH_PAIR_MIXED_TYPES) != 0, smaller = (narrow & IBVH_PAIR_SMALLER_DRIVES) != 0;
+    narrow &= ~(IBVH_PAIR_MIXED_TYPES | IBVH_PAIR_SMALLER_DRIVES);
+    // mixed: any two types with one index type (traverse_pair.jl:50-52)
+    if (mixed ? bvh1->types.index_type != bvh2->types.index_type : !same_types(bvh1->types, bvh2->types))
+        return IBVH_ERR_UNSUPPORTED;
+    // traverse_pair.jl:15-36: the BVH with more leaves drives (IBVH_PAIR_SMALLER_DRIVES: fewer); flip restores (bvh1, bvh2) order
+    bool flip = smaller ? bvh1->tree.real_leaves > bvh2->tree.real_leaves : !(bvh1->tree.real_leaves >= bvh2->tree.real_leaves);
     const ibvh_bvh *drv = flip ? bvh2 : bvh1, *oth = flip ? bvh1 : bvh2;
     int64_t sl_other = flip ? sl1 : sl2;
-    return dispatch_all(bvh1->types, [&](auto lt, auto nt, auto it, auto mt) -> int {
+    int64_t n = drv->tree.real_leaves;
+    if (!mixed)
+        return dispatch_all(bvh1->types, [&](auto lt, auto nt, auto it, auto mt) -> int {
+            using L = typename decltype(lt)::type;
+            using N = typename decltype(nt)::type;
+            using I = typename decltype(it)::type;
+            using M = typename decltype(mt)::type;
+            return pair_lvt_walk(view_of<L, N, I, M>(*drv).leaves, n, view_of<L, N, I, M>(*oth), sl_other, narrow, flip,
+                                 counts, total_out, contacts, threads, tc_out);
+        });
+    // the walked tree's volume types, the query's volume type, one index type; Morton codes widened (widen_leaves)
+    return dispatch_leaf_node(oth->types, [&](auto lt, auto nt) -> int {
         using L = typename decltype(lt)::type;
         using N = typename decltype(nt)::type;
-        using I = typename decltype(it)::type;
-        using M = typename decltype(mt)::type;
-        auto vd = view_of<L, N, I, M>(*drv);
-        auto vo = view_of<L, N, I, M>(*oth);
-        I *c = (I *)counts;
-        int64_t n = drv->tree.real_leaves;
-        // (threads > 1: contiguous chunks handed out dynamically, lvt/traverse_pair.jl:119-173's task ranges; every
-        // driving leaf writes its own count / its own output range, so the result does not depend on the team)
-        if (!contacts) {
-            std::mutex mu;
-            parallel_chunks(n, threads, 2048, [&](int, int64_t lo, int64_t hi) {
-                TestCounts tc;
-                for (int64_t i = lo + 1; i <= hi; ++i) {
-                    int64_t cnt = 0;
-                    auto emit = [&](I, I) { ++cnt; };
-                    lvt_pair_leaf(vd.leaves[i - 1], vo, sl_other, narrow, flip, emit, tc_out ? &tc : nullptr);
-                    c[i - 1] = I(cnt);
-                }
-                if (tc_out) {
-                    std::lock_guard<std::mutex> g(mu);
-                    tc_out->node += tc.node;
-                    tc_out->leaf += tc.leaf;
+        return dispatch_index(oth->types.index_type, [&](auto it) -> int {
+            using I = typename decltype(it)::type;
+            return dispatch_volume(drv->types.leaf_kind, drv->types.leaf_float, [&](auto qt) -> int {
+                using Q = typename decltype(qt)::type;
+                // no NodeType(query) for a BBox query against BSphere nodes (no BSphere(::BBox): the reference raises)
+                if constexpr (N::kind == IBVH_BSPHERE && Q::kind != IBVH_BSPHERE) {
+                    return IBVH_ERR_UNSUPPORTED;
+                } else {
+                    std::vector<BoundingVolume<Q, I, uint64_t>> q;
+                    std::vector<BoundingVolume<L, I, uint64_t>> w;
+                    if (int e = widen_leaves(*drv, q)) return e;
+                    if (int e = widen_leaves(*oth, w)) return e;
+                    View<L, N, I, uint64_t> vo{oth->tree, w.data(), (const N *)oth->nodes, (const I *)oth->skips};
+                    return pair_lvt_walk(q.data(), n, vo, sl_other, narrow, flip, counts, total_out, contacts, threads, tc_out);
                 }
             });
-            return scan_counts(c, n, total_out);
-        }
-        IndexPair<I> *out = (IndexPair<I> *)contacts;
-        parallel_chunks(n, threads, 2048, [&](int, int64_t lo, int64_t hi) {
-            for (int64_t i = lo + 1; i <= hi; ++i) {
-                int64_t w = (i == 1) ? 0 : (int64_t)c[i - 2];
-                auto emit = [&](I a, I b) { out[w++] = {a, b}; };
-                lvt_pair_leaf(vd.leaves[i - 1], vo, sl_other, narrow, flip, emit);
-            }
         });
-        return IBVH_OK;
     });
 }
 int oracle_traverse_pair_lvt_count(const ibvh_bvh *bvh1, const ibvh_bvh *bvh2, int64_t sl1, int64_t sl2,

@@ -1,7 +1,8 @@
 """Randomised differential testing of the HIP library against the oracle (run on a GPU box):
     python tests/fuzz_gpu.py [seconds] [seed]
 Random sizes, type combinations, densities (sparse ... everything overlaps), clustered / duplicated inputs, start levels,
-narrow menu, cache reuse chains, pair traversals in both orders and ray batches; every LVT list must equal the
+narrow menu, cache reuse chains, pair traversals in both orders, mixed-type pairs (IBVH_PAIR_MIXED_TYPES: the second BVH of
+another leaf / node / Morton type, drawn from a generator of their own) and ray batches; every LVT list must equal the
 oracle's INCLUDING order, every BFS list as a sorted set with the same num_checks.  tests/test_gpu_fuzz.py runs a
 short, seeded slice of it in the suite."""
 import os
@@ -13,10 +14,11 @@ import numpy as np
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))  # repo root, when run as a script
 
 import oracle_lib as orc
+from mixed_pair_checker import LEAF_NODE_COMBOS
 
 import torch
 import implicitbvh_amd as ibvh
-from implicitbvh_amd import abi
+from implicitbvh_amd import abi, api
 
 NP_F = {abi.F32: np.float32, abi.F64: np.float64}
 TOKENS = {abi.BSPHERE: ibvh.BSphere, abi.BBOX: ibvh.BBox}
@@ -77,7 +79,43 @@ def build(vols, types, built_level=1):
     return o, g
 
 
-def one_case(rng, log, light=False):
+MIXED_DONE = {"lists": 0, "refused": 0}  # mixed-pair lists compared so far, and refused combinations checked
+
+
+def mixed_leg(mrng, o, g, log, light):
+    """A mixed pair: g against a BVH of a type drawn from LEAF_NODE_COMBOS (g's index type, any Morton width), both argument
+    orders, random start levels, narrow codes and IBVH_PAIR_SMALLER_DRIVES; the list equals the oracle's mixed walk in order,
+    and the combination without NodeType(query) is refused."""
+    it = g.types.index_type
+    lk, lf, nk, nf = LEAF_NODE_COMBOS[mrng.integers(0, len(LEAF_NODE_COMBOS))]
+    types2 = abi.make_types(lk, lf, nk, nf, it, (abi.U16, abi.U32, abi.U64)[mrng.integers(0, 3)])
+    n2 = int(mrng.choice([1, 5, 64, 300, 4000] if light else [1, 5, 64, 300, 4000, 15000]))
+    o2, g2 = build(cloud(mrng, n2, lk, lf), types2)
+    log.append(f"mixed: types2={(lk, lf, nk, nf, types2.morton_type)} n2={n2}")
+    for (oa, ga, ob, gb) in ((o, g, o2, g2), (o2, g2, o, g)):
+        sl1 = int(mrng.integers(oa.built_level, oa.tree.levels + 1))
+        sl2 = int(mrng.integers(ob.built_level, ob.tree.levels + 1))
+        code = int(mrng.choice([abi.NARROW_NONE, abi.NARROW_MORTON_LT, abi.NARROW_INDEX_LT]))
+        code |= abi.PAIR_SMALLER_DRIVES if mrng.random() < 0.3 else 0
+        na, nb = oa.tree.real_leaves, ob.tree.real_leaves
+        flip = na > nb if code & abi.PAIR_SMALLER_DRIVES else not na >= nb
+        drv, oth = (ob, oa) if flip else (oa, ob)
+        if drv.types.leaf_kind == abi.BBOX and oth.types.node_kind == abi.BSPHERE:  # no BSphere(::BBox)
+            try:
+                api._traverse_lvt_pair(ga, gb, sl1, sl2, code, None)
+            except abi.MethodError:
+                MIXED_DONE["refused"] += 1
+                continue
+            raise AssertionError(f"mixed pair not refused: code={code}")
+        exp = orc.traverse_pair_lvt(oa, ob, sl1, sl2, narrow=code | abi.PAIR_MIXED_TYPES)[0]
+        if len(exp) > 6_000_000:
+            continue
+        t = api._traverse_lvt_pair(ga, gb, sl1, sl2, code, None)
+        assert (got(t) == pairs(exp)).all(), f"lvt mixed pair sl=({sl1},{sl2}) code={code}"
+        MIXED_DONE["lists"] += 1
+
+
+def one_case(rng, log, light=False, mrng=None):
     combo = COMBOS[rng.integers(0, len(COMBOS))]
     it, mt = [(abi.I32, abi.U32), (abi.I64, abi.U64), (abi.I32, abi.U16), (abi.I64, abi.U32)][rng.integers(0, 4)]
     types = abi.make_types(*combo, it, mt)
@@ -132,6 +170,8 @@ def one_case(rng, log, light=False):
                           cache=cache if rng.random() < 0.5 else None)
         assert (got(t) == pairs(exp)).all(), f"lvt pair sl=({sl1},{sl2}) narrow={nar}"
         cache = t
+    if mrng is not None:
+        mixed_leg(mrng, o, g, log, light)
     # rays (same float type for leaves and nodes only)
     if combo[1] == combo[3]:
         f = NP_F[combo[1]]
@@ -150,17 +190,18 @@ def one_case(rng, log, light=False):
 
 def main(seconds=60.0, seed=0, verbose=True, light=False):
     rng = np.random.default_rng(seed)
+    mrng = np.random.default_rng([seed, 0x6D78])  # (the mixed leg's own stream: the other legs draw what they always drew)
     t0, cases = time.time(), 0
     while time.time() - t0 < seconds:
         log = []
         try:
-            one_case(rng, log, light)
+            one_case(rng, log, light, mrng)
         except Exception:
             print("FAILED case", cases, "seed", seed, *log, file=sys.stderr)
             raise
         cases += 1
     if verbose:
-        print(f"fuzz ok: {cases} cases in {time.time() - t0:.1f} s (seed {seed})")
+        print(f"fuzz ok: {cases} cases in {time.time() - t0:.1f} s (seed {seed}); mixed pairs: {MIXED_DONE}")
     return cases
 
 

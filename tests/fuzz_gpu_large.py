@@ -4,7 +4,8 @@
 cells and rescue workgroups, `cache=` chains whose input changes ABRUPTLY between two builds (the hint is one build old), the
 shared descent per block of the LVT count pass, the one-kernel scans, the binned ray path with its tail as units.  Every build
 is compared with the oracle's byte for byte (order, codes, node volumes), every LVT list INCLUDING its order and its inclusive
-counts, every ray list including order.  tests/test_gpu_fuzz.py runs one short seeded slice of it."""
+counts, every ray list including order.  Each case ends with a mixed-type pair (IBVH_PAIR_MIXED_TYPES), drawn from a generator
+of its own, in order against the oracle's mixed walk.  tests/test_gpu_fuzz.py runs one short seeded slice of it."""
 import os
 import sys
 import time
@@ -14,10 +15,11 @@ import numpy as np
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))  # repo root, when run as a script
 
 import oracle_lib as orc
+from mixed_pair_checker import LEAF_NODE_COMBOS
 
 import torch
 import implicitbvh_amd as ibvh
-from implicitbvh_amd import abi
+from implicitbvh_amd import abi, api
 from implicitbvh_amd.synthetic import sphere_radius_law, torus_mesh
 
 NP_F = {abi.F32: np.float32, abi.F64: np.float64}
@@ -31,7 +33,8 @@ STYLES = ["uniform", "uniform", "clusters", "sheet", "torus", "one_cell", "all_e
 SPARSE = {"uniform", "clusters", "sheet", "torus"}  # styles whose contact lists stay near n with the radius law
 
 
-DONE = {"builds": 0, "lvt_self_lists": 0, "lvt_pair_lists": 0, "ray_lists": 0, "overflows": 0}  # what was compared so far
+DONE = {"builds": 0, "lvt_self_lists": 0, "lvt_pair_lists": 0, "ray_lists": 0, "overflows": 0,  # what was compared so far
+        "mixed_pair_lists": 0, "mixed_refused": 0}
 
 
 def cuda(a):
@@ -101,7 +104,46 @@ def check_build(o, g, what):
     assert gn.tobytes() == o.nodes.view(gn.dtype).reshape(gn.shape).tobytes(), f"{what}: nodes"
 
 
-def one_case(rng, log, sizes):
+def mixed_leg(mrng, o, g, log):
+    """The chain's last BVH (of a sparse style) against one of a type drawn from LEAF_NODE_COMBOS (its index type, any Morton width):
+    both argument orders, IBVH_PAIR_SMALLER_DRIVES now and then; the list equals the oracle's mixed walk in order, and the
+    combination without NodeType(query) is refused."""
+    it = g.types.index_type
+    lk, lf, nk, nf = LEAF_NODE_COMBOS[mrng.integers(0, len(LEAF_NODE_COMBOS))]
+    types2 = abi.make_types(lk, lf, nk, nf, it, (abi.U16, abi.U32, abi.U64)[mrng.integers(0, 3)])
+    n2 = int(mrng.choice([70_000, 140_000, 400_000]))
+    style2 = [s for s in STYLES if s in SPARSE][mrng.integers(0, 4)]
+    v2 = volumes(mrng, style2, n2, lk, lf)
+    o2 = orc.build(v2, types2)
+    opts = ibvh.BVHOptions(index=abi.INDEX_DTYPES[it], morton=ibvh.DefaultMortonAlgorithm(abi.MORTON_DTYPES[types2.morton_type]))
+    g2 = ibvh.BVH(cuda(v2), TOKENS[nk](torch.float32 if nf == abi.F32 else torch.float64), options=opts)
+    check_build(o2, g2, f"build mixed ({style2})")
+    log.append(f"mixed: types2={(lk, lf, nk, nf, types2.morton_type)} n2={n2} style2={style2}")
+    for (oa, ga, ob, gb) in ((o, g, o2, g2), (o2, g2, o, g)):
+        code = int(mrng.choice([abi.NARROW_NONE, abi.NARROW_NONE, abi.NARROW_MORTON_LT, abi.NARROW_INDEX_LT]))
+        code |= abi.PAIR_SMALLER_DRIVES if mrng.random() < 0.3 else 0
+        na, nb = oa.tree.real_leaves, ob.tree.real_leaves
+        flip = na > nb if code & abi.PAIR_SMALLER_DRIVES else not na >= nb
+        drv, oth = (ob, oa) if flip else (oa, ob)
+        if drv.types.leaf_kind == abi.BBOX and oth.types.node_kind == abi.BSPHERE:  # no BSphere(::BBox)
+            try:
+                api._traverse_lvt_pair(ga, gb, 1, 1, code, None)
+            except abi.MethodError:
+                DONE["mixed_refused"] += 1
+                continue
+            raise AssertionError(f"mixed pair not refused: code={code}")
+        try:
+            tp = api._traverse_lvt_pair(ga, gb, 1, 1, code, None)
+        except OverflowError:
+            assert it == abi.I32
+            continue
+        if tp.num_contacts <= 30_000_000:
+            exp = orc.traverse_pair_lvt(oa, ob, None, None, narrow=code | abi.PAIR_MIXED_TYPES)[0]
+            assert np.array_equal(tp.contacts.cpu().numpy().astype(np.int64), pairs(exp)), f"lvt mixed pair, code={code}"
+            DONE["mixed_pair_lists"] += 1
+
+
+def one_case(rng, log, sizes, mrng=None):
     t = TYPES[rng.integers(0, len(TYPES))]
     types = abi.make_types(*t)
     node_type = TOKENS[t[2]](torch.float32 if t[3] == abi.F32 else torch.float64)
@@ -165,15 +207,18 @@ def one_case(rng, log, sizes):
                 assert np.array_equal(tr.contacts.cpu().numpy().astype(np.int64), pairs(exp)), f"rays, step {step} ({style}, {nr} rays)"
                 DONE["ray_lists"] += 1
             rays_cache = tr
+    if mrng is not None and chain[-1] in SPARSE:  # (the chain's last build: an earlier one's buffers were reused by the next)
+        mixed_leg(mrng, o, g, log)
 
 
 def main(seconds=120.0, seed=0, verbose=True, sizes=(131_072, 200_000, 524_289, 1_000_000, 2_500_000)):
     rng = np.random.default_rng(seed)
+    mrng = np.random.default_rng([seed, 0x6D78])  # (the mixed leg's own stream: the other legs draw what they always drew)
     t0, cases = time.time(), 0
     while time.time() - t0 < seconds:
         log = []
         try:
-            one_case(rng, log, sizes)
+            one_case(rng, log, sizes, mrng)
         except Exception:
             print("FAILED case", cases, "seed", seed, *log, file=sys.stderr)
             raise

@@ -1,6 +1,7 @@
 """A numpy restatement of the reference's leaf-vs-tree pair walk (lvt/traverse_pair.jl:1-52, 176-244) for two BVHs of any
-two volume types: the checker of IBVH_PAIR_MIXED_TYPES.  The pinned oracle (oracle/ibvh_oracle.cpp) refuses pairs of two
-types, so this module stands in for it there; tests/test_host_mixed_pair.py pins it to the oracle on every same-type pair.
+two volume types: the checker of IBVH_PAIR_MIXED_TYPES.  It is the independent statement the oracle's own mixed walk
+(oracle/ibvh_oracle.cpp, pair_lvt with IBVH_PAIR_MIXED_TYPES) is pinned to: tests/test_host_mixed_pair.py pins it to the
+oracle on every same-type pair, and the oracle's mixed lists to it on every pair of two types.
 
 A plain module, not a conftest: the tests import it.  Works on oracle_lib.HostBVH (numpy records).
 

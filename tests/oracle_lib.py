@@ -221,10 +221,13 @@ def traverse_lvt(bvh, start_level=None, narrow=0):
 
 
 def traverse_pair_lvt(bvh1, bvh2, start_level1=None, start_level2=None, narrow=0):
+    """narrow: a pair code, optionally with abi.PAIR_SMALLER_DRIVES and abi.PAIR_MIXED_TYPES (then bvh1 and bvh2 may be of
+    two types with one index type).  -> (contacts, counts); counts has one entry per leaf of the driving BVH."""
     sl1 = max(1, bvh1.built_level) if start_level1 is None else start_level1
     sl2 = max(1, bvh2.built_level) if start_level2 is None else start_level2
     s1, s2 = bvh1.struct(), bvh2.struct()
-    n = max(bvh1.tree.real_leaves, bvh2.tree.real_leaves)
+    n1, n2 = bvh1.tree.real_leaves, bvh2.tree.real_leaves
+    n = min(n1, n2) if narrow & abi.PAIR_SMALLER_DRIVES else max(n1, n2)
     counts = np.zeros(n, abi.INDEX_DTYPES[bvh1.types.index_type])
     total = C.c_int64()
     abi.check(lib.oracle_traverse_pair_lvt_count(C.byref(s1), C.byref(s2), C.c_int64(sl1), C.c_int64(sl2), narrow,

@@ -3,7 +3,9 @@ of consecutive sorted leaves, the waves of the block start at the cut level.  By
 here the knob lvt_blocks_min_items = 1 forces it onto trees the oracle walks in seconds, and the lists must be the oracle's IN
 ORDER for every block size, both descents of the block kernel (one / two levels per trip), self and pair walks, ragged trees,
 partially built trees, both index types, Float64 volumes, the narrow menu, positions, rows that overflow (the waves then
-descend on their own), leaves with NaN / infinite components (the containment check), and a scratch without room for rows."""
+descend on their own), leaves with NaN / infinite components (the containment check), and a scratch without room for rows.
+The block-size and scratch tests also walk mixed pairs (IBVH_PAIR_MIXED_TYPES) of one node type against the oracle's mixed walk;
+tests/test_gpu_pair_mixed_paths.py has the rest of the mixed pairs' size-chosen paths."""
 import ctypes as C
 
 import numpy as np
@@ -51,6 +53,22 @@ def _kernels_of(fn):
     return names
 
 
+def rows_rule(drv, walk, n_items, shift=11, min_items=1, same_nodes=True):
+    """Whether launch_queue (csrc/ibvh_lvt_queue.inc) launches lvt_block_frontier_kernel for a walk of `walk` (an oracle
+    HostBVH) by the n_items leaves of `drv`: BBox nodes on both sides of one float type (run<>'s same_nodes), enough work
+    items, the block level present in the driving tree, at least two levels between the start of the descent (level 7 or the
+    walked tree's built level) and its cut (BRUTE_DEPTH = 7 above the leaves)."""
+    start = min(max(walk.built_level, 7), walk.tree.levels - 1)
+    cut = max(walk.tree.levels - 7, start)
+    blevel = drv.tree.levels - shift
+    return (same_nodes and walk.types.node_kind == abi.BBOX and n_items >= min_items and blevel >= 1 and
+            blevel >= drv.built_level and cut - start >= 2 and walk.tree.levels <= 28)
+
+
+def _ran_frontier(names):
+    return any("lvt_block_frontier_kernel" in k for k in names)
+
+
 @pytest.mark.parametrize("shift", [9, 10, 11, 12])
 @pytest.mark.parametrize("paired", [0, 1 << 30], ids=["one-level-trips", "two-level-trips"])
 def test_self_and_pair_lists_in_order_for_every_block_size(forced_rows, shift, paired):
@@ -71,6 +89,20 @@ def test_self_and_pair_lists_in_order_for_every_block_size(forced_rows, shift, p
         o2, g2 = build_both(other, types)
         assert (contacts_np(ibvh.traverse(g, g2)) == oracle_pairs(orc.traverse_pair_lvt(o, o2)[0])).all(), n
         assert (contacts_np(ibvh.traverse(g2, g)) == oracle_pairs(orc.traverse_pair_lvt(o2, o)[0])).all(), n  # flipped: g drives again
+        # a mixed pair (IBVH_PAIR_MIXED_TYPES, one node type): g's spheres against BBox{Float32} leaves, and those boxes driving
+        # against g's tree (own generator: the draws above stay what they were)
+        mrng = np.random.default_rng(1000 * shift + n)
+        o3, g3 = build_both(random_volumes(mrng, n // 3 + 5, abi.BBOX, abi.F32, scale=0.9 * n ** (1 / 3)),
+                            abi.make_types(abi.BBOX, abi.F32, abi.BBOX, abi.F32))
+        o4, g4 = build_both(random_volumes(mrng, n + 9, abi.BBOX, abi.F32, scale=0.9 * n ** (1 / 3)),
+                            abi.make_types(abi.BBOX, abi.F32, abi.BBOX, abi.F32))
+        for (oa, ga), (ob, gb), (od, ow) in (((o, g), (o3, g3), (o, o3)), ((o3, g3), (o, g), (o, o3)), ((o4, g4), (o, g), (o4, o))):
+            exp = oracle_pairs(orc.traverse_pair_lvt(oa, ob, narrow=abi.PAIR_MIXED_TYPES)[0])
+            names = _kernels_of(lambda: ibvh.traverse(ga, gb))
+            assert _ran_frontier(names) == rows_rule(od, ow, od.tree.real_leaves, shift), (n, names)
+            t = ibvh.traverse(ga, gb)
+            assert (contacts_np(t) == exp).all(), ("mixed", n)
+            assert (contacts_np(ibvh.traverse(ga, gb, cache=t)) == exp).all(), ("mixed enqueue", n)
 
 
 @pytest.mark.parametrize("combo", BOX_COMBOS, ids=str)
@@ -195,3 +227,32 @@ def test_a_scratch_without_room_for_rows_is_served_without_them(forced_rows):
         lib.call("ibvh_traverse_lvt_write", C.byref(s), 1, 0, counts.data_ptr(), out.data_ptr(), scratch.data_ptr(), nbytes, None)
         torch.cuda.synchronize()
         assert (out.cpu().numpy().astype(np.int64) == exp).all()
+    # a mixed pair: g's spheres driving against a BBox{Float32} tree; the scratch from the larger of the two types' sizes
+    o2, g2 = build_both(random_volumes(np.random.default_rng(14), 40_000, abi.BBOX, abi.F32, scale=30.0),
+                        abi.make_types(abi.BBOX, abi.F32, abi.BBOX, abi.F32))
+    exp = oracle_pairs(orc.traverse_pair_lvt(o, o2, narrow=abi.PAIR_MIXED_TYPES)[0])
+    assert len(exp) > 10_000 and rows_rule(o, o2, n)
+    s2 = g2.struct()
+    sizes = {}
+    for slots in (8, 0):
+        need = 0
+        for t in (g.types, g2.types):
+            sz = C.c_size_t()
+            lib.call("ibvh_lvt_scratch_bytes", C.byref(t), n, slots, C.byref(sz))
+            need = max(need, sz.value)
+        sizes[slots] = need
+    code = abi.PAIR_MIXED_TYPES
+    for nbytes, rows in ((sizes[8], True), (sizes[0], True), (sizes[0] - qidx_bytes, True),
+                         (sizes[0] - qidx_bytes - rows_bytes - 512, False)):
+        counts = torch.zeros(n, dtype=torch.int32, device="cuda")
+        scratch = torch.zeros(nbytes, dtype=torch.uint8, device="cuda")
+        total = C.c_int64()
+        names = _kernels_of(lambda: lib.call("ibvh_traverse_pair_lvt_count", C.byref(s), C.byref(s2), 1, 1, code, counts.data_ptr(),
+                                             C.byref(total), scratch.data_ptr(), nbytes, None))
+        assert _ran_frontier(names) == rows, ("mixed", nbytes)
+        assert total.value == len(exp)
+        out = torch.zeros((total.value, 2), dtype=torch.int32, device="cuda")
+        lib.call("ibvh_traverse_pair_lvt_write", C.byref(s), C.byref(s2), 1, 1, code, counts.data_ptr(), out.data_ptr(),
+                 scratch.data_ptr(), nbytes, None)
+        torch.cuda.synchronize()
+        assert (out.cpu().numpy().astype(np.int64) == exp).all(), ("mixed", nbytes)

@@ -43,6 +43,20 @@ class Built:
         self.h = orc.HostBVH(types, orc.tree_shape(n), self.g.built_level, self.g.leaves.to_numpy(), nodes, None, None)
 
 
+def host_of(g):
+    """A device-built BVH as oracle_lib.HostBVH records (its own leaves and nodes; skips computed): the oracle walks it."""
+    t, tree = g.types, orc.tree_shape(len(g.leaves))
+    nodes = np.ascontiguousarray(g.nodes.cpu().numpy()).view(abi.node_dtype(t)).reshape(-1)
+    skips = orc.compute_skips(tree).astype(abi.INDEX_DTYPES[t.index_type])
+    return orc.HostBVH(t, tree, g.built_level, np.ascontiguousarray(g.leaves.to_numpy()), nodes, skips, None)
+
+
+def oracle_list(h1, h2, code=0):
+    """The oracle's mixed list (IBVH_PAIR_MIXED_TYPES) of two HostBVHs as an (m, 2) int64 array."""
+    c = orc.traverse_pair_lvt(h1, h2, narrow=code | abi.PAIR_MIXED_TYPES)[0]
+    return np.stack([c["a"], c["b"]], axis=1).astype(np.int64) if len(c) else np.zeros((0, 2), np.int64)
+
+
 _built = {}
 
 
@@ -185,7 +199,8 @@ def test_abi_contract_of_the_flag():
 def test_particles_against_the_published_surface():
     """2e5 BSphere{Float32} particles against the 249,882-triangle torus as BBox{Float32} leaves (a checker at this size would
     be slow): the contact set equals the same-type run with the particles given as their BBox{Float32} boxes (the box
-    iscontact(::BSphere, ::BBox) forms), every contact passes the exact leaf test, and the two argument orders agree."""
+    iscontact(::BSphere, ::BBox) forms), every contact passes the exact leaf test, and the two argument orders agree; and the
+    lists equal the oracle's mixed walk in order, with the default knobs' shared descent."""
     from implicitbvh_amd.synthetic import sphere_radius_law, torus_mesh
     tris = torch.from_numpy(torus_mesh(354, 353)[:249_882].copy()).cuda()
     surf_vols = ibvh.bounding_volumes_from_triangles(tris, ibvh.BBox(torch.float32))
@@ -212,3 +227,16 @@ def test_particles_against_the_published_surface():
     for k in range(3):
         hit &= (s[:, k] + s[:, 3] >= t[:, k]) & (s[:, k] - s[:, 3] <= t[:, 3 + k])
     assert hit.all()
+    # the full lists, in order, against the oracle's mixed walk: both argument orders and the particles driving
+    # (IBVH_PAIR_SMALLER_DRIVES); more than 2^17 driving leaves and one node type, so the default knobs take the shared
+    # descent (the profile shows lvt_block_frontier_kernel), the one-kernel scan and the dense .index copy
+    from test_gpu_lvt_blocks import _kernels_of
+    hs, ht = host_of(sph), host_of(surf)
+    for (a, ha), (b, hb) in (((sph, hs), (surf, ht)), ((surf, ht), (sph, hs))):
+        for code in (0, abi.PAIR_SMALLER_DRIVES):
+            exp = oracle_list(ha, hb, code)
+            names = _kernels_of(lambda: api._traverse_lvt_pair(a, b, 1, 1, code, None))
+            assert any("lvt_block_frontier_kernel" in k for k in names), (code, names)
+            t = api._traverse_lvt_pair(a, b, 1, 1, code, None)
+            assert contacts_np(t).shape == exp.shape and (contacts_np(t) == exp).all(), code
+            assert (contacts_np(api._traverse_lvt_pair(a, b, 1, 1, code, t)) == exp).all(), ("enqueue", code)

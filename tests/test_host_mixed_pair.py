@@ -1,6 +1,7 @@
 """IBVH_PAIR_MIXED_TYPES on the host: the numpy checker of the mixed-type pair walk (tests/mixed_pair_checker.py) is pinned
 to the oracle on every same-type pair, its leaf test to the oracle's iscontact on mixed kinds, and the Julia extension is
-checked statically for binding the flag.  No GPU."""
+checked statically for binding the flag; the oracle's own mixed walk (IBVH_PAIR_MIXED_TYPES in oracle_traverse_pair_lvt_*) is
+pinned to the checker on all 144 ordered pairs of two types.  No GPU."""
 import itertools
 import re
 
@@ -143,3 +144,138 @@ def test_julia_ext_binds_the_mixed_flag():
     assert "index_type" in ok and "kind(BBox)" in ok and "kind(BSphere)" in ok and "n1 >= n2" in ok
     bfs = re.search(r"function ImplicitBVH\.traverse\(\s*bvh1::RocBVH\{I\}, bvh2::RocBVH, alg::BFSTraversal;(.*?)\nend\n", src, re.S).group(1)
     assert "d1.types != d2.types\n" in bfs and "mixed_ok" not in bfs
+
+
+# ---- the oracle's own mixed walk (IBVH_PAIR_MIXED_TYPES in oracle_traverse_pair_lvt_*), pinned to the checker ----------
+MORTONS = (abi.U16, abi.U32, abi.U64)
+_COMBO_ID = lambda c: "%s%d%s%d" % ("SB"[c[0]], 32 << c[1], "SB"[c[2]], 32 << c[3])  # noqa: E731
+
+
+def _mixed_types(i, j):
+    """Types of the ordered combo pair (i, j) of LEAF_NODE_COMBOS: two different Morton widths, one index type."""
+    idx = (abi.I32, abi.I64)[(i + j) % 2]
+    m1 = i % 3
+    return (abi.make_types(*mpc.LEAF_NODE_COMBOS[i], idx, MORTONS[m1]),
+            abi.make_types(*mpc.LEAF_NODE_COMBOS[j], idx, MORTONS[(m1 + 1 + j % 2) % 3]))
+
+
+def _pair_status(o1, o2, narrow, sl1=None, sl2=None):
+    """The raw status of oracle_traverse_pair_lvt_count."""
+    import ctypes as C
+    sl1 = max(1, o1.built_level) if sl1 is None else sl1
+    sl2 = max(1, o2.built_level) if sl2 is None else sl2
+    s1, s2 = o1.struct(), o2.struct()
+    counts = np.zeros(max(o1.tree.real_leaves, o2.tree.real_leaves), abi.INDEX_DTYPES[o1.types.index_type])
+    total = C.c_int64()
+    return orc.lib.oracle_traverse_pair_lvt_count(C.byref(s1), C.byref(s2), C.c_int64(sl1), C.c_int64(sl2), narrow,
+                                                  C.c_void_p(counts.ctypes.data), C.byref(total))
+
+
+def _check_against_checker(o1, o2, sl1, sl2, narrow, smaller):
+    """-> number of pairs compared, or None when the combination is refused (by both)."""
+    flags = abi.PAIR_MIXED_TYPES | (abi.PAIR_SMALLER_DRIVES if smaller else 0)
+    try:
+        exp = mpc.traverse_pair_lvt(o1, o2, sl1, sl2, narrow, smaller_drives=smaller)
+    except mpc.Refused:
+        assert _pair_status(o1, o2, narrow | flags, sl1, sl2) == abi.ERR_UNSUPPORTED
+        return None
+    got = _oracle_list(o1, o2, sl1, sl2, narrow | flags)
+    assert got.shape == exp.shape and (got == exp).all(), (sl1, sl2, narrow, smaller)
+    return len(exp)
+
+
+@pytest.mark.parametrize("pair", list(itertools.product(range(len(mpc.LEAF_NODE_COMBOS)), repeat=2)),
+                         ids=lambda p: _COMBO_ID(mpc.LEAF_NODE_COMBOS[p[0]]) + "_" + _COMBO_ID(mpc.LEAF_NODE_COMBOS[p[1]]))
+def test_oracle_mixed_list_equals_the_checker(pair):
+    """All 144 ordered pairs of leaf / node combinations, two Morton widths, either index type: sizes 1 and larger with
+    either BVH driving, built_level 1 and 2, every start level of the walked tree, every pair narrow code, with and without
+    IBVH_PAIR_SMALLER_DRIVES: the oracle's mixed list equals the checker's, order included; refused exactly where the
+    checker has no NodeType(query)."""
+    i, j = pair
+    t1, t2 = _mixed_types(i, j)
+    c1, c2 = mpc.LEAF_NODE_COMBOS[i], mpc.LEAF_NODE_COMBOS[j]
+    rng = np.random.default_rng(7919 + 12 * i + j)
+    compared = refused = 0
+    for n1, n2 in ((1, 37), (37, 1), (150, 61), (61, 150)):
+        a = mpc.random_volumes(rng, n1, c1[0], c1[1], scale=4.0, size=0.5)
+        b = mpc.random_volumes(rng, n2, c2[0], c2[1], scale=4.0, size=0.5, origin=0.5)
+        for bl in (1, 2):
+            o1 = orc.build(a, t1, built_level=min(bl, orc.tree_shape(n1).levels))
+            o2 = orc.build(b, t2, built_level=min(bl, orc.tree_shape(n2).levels))
+            b1, b2 = o1.built_level, o2.built_level
+            for narrow in (abi.NARROW_NONE, abi.NARROW_MORTON_LT, abi.NARROW_INDEX_LT):
+                for smaller in (False, True):
+                    r = _check_against_checker(o1, o2, b1, b2, narrow, smaller)
+                    refused += r is None
+                    compared += r or 0
+            # every start level of either tree (only the walked tree's matters), narrow code and driver rotating
+            sls = [(b1, s) for s in range(b2, o2.tree.levels + 1)] + [(s, b2) for s in range(b1 + 1, o1.tree.levels + 1)]
+            for k, (sl1, sl2) in enumerate(sls):
+                r = _check_against_checker(o1, o2, sl1, sl2, k % 3, (k // 3) % 2 == 1)
+                refused += r is None
+                compared += r or 0
+    box_vs_spheres = (c1[0] == abi.BBOX and c2[2] == abi.BSPHERE) or (c2[0] == abi.BBOX and c1[2] == abi.BSPHERE)
+    assert (refused > 0) == box_vs_spheres
+    assert compared > 100
+
+
+@pytest.mark.parametrize("idx", (abi.I32, abi.I64), ids=("i32", "i64"))
+def test_oracle_mixed_list_with_nan_and_infinite_volumes(idx):
+    """NaN and infinite radii and box bounds are data: on every ordered pair of combinations the oracle's mixed list equals
+    the checker's."""
+    rng = np.random.default_rng(23 + idx)
+    for i, j in itertools.product(range(len(mpc.LEAF_NODE_COMBOS)), repeat=2):
+        (lk1, lf1, nk1, nf1), (lk2, lf2, nk2, nf2) = mpc.LEAF_NODE_COMBOS[i], mpc.LEAF_NODE_COMBOS[j]
+        t1 = abi.make_types(lk1, lf1, nk1, nf1, idx, MORTONS[i % 3])
+        t2 = abi.make_types(lk2, lf2, nk2, nf2, idx, MORTONS[(i + 1) % 3])
+        a = mpc.random_volumes(rng, 90, lk1, lf1, scale=3.0, size=0.5)
+        b = mpc.random_volumes(rng, 70, lk2, lf2, scale=3.0, size=0.5)
+        for v, k in ((a, lk1), (b, lk2)):
+            rows = rng.choice(len(v), 12, replace=False)
+            col = 3 if k == abi.BSPHERE else rng.integers(0, 6, 12)
+            v[rows[:4], col if np.isscalar(col) else col[:4]] = np.inf
+            v[rows[4:8], col if np.isscalar(col) else col[4:8]] = np.nan
+            v[rows[8:], col if np.isscalar(col) else col[8:]] = -np.inf
+        o1, o2 = orc.build(a, t1), orc.build(b, t2)
+        for narrow in (abi.NARROW_NONE, abi.NARROW_MORTON_LT):
+            for smaller in (False, True):
+                _check_against_checker(o1, o2, o1.built_level, o2.built_level, narrow, smaller)
+
+
+def test_oracle_refuses_what_the_library_refuses():
+    """Two index types (with or without the flag), two types without the flag, and a BBox query against BSphere nodes
+    (which BVH drives decides, IBVH_PAIR_SMALLER_DRIVES included): IBVH_ERR_UNSUPPORTED."""
+    rng = np.random.default_rng(29)
+    ts = abi.make_types(abi.BSPHERE, abi.F32, abi.BSPHERE, abi.F32, abi.I32, abi.U32)
+    tb = abi.make_types(abi.BBOX, abi.F64, abi.BBOX, abi.F64, abi.I32, abi.U64)
+    tb64 = abi.make_types(abi.BBOX, abi.F64, abi.BBOX, abi.F64, abi.I64, abi.U64)
+    spheres = orc.build(mpc.random_volumes(rng, 40, abi.BSPHERE, abi.F32, 3, 0.3), ts)
+    boxes = orc.build(mpc.random_volumes(rng, 90, abi.BBOX, abi.F64, 3, 0.3), tb)
+    boxes64 = orc.build(mpc.random_volumes(rng, 20, abi.BBOX, abi.F64, 3, 0.3), tb64)
+    M, S = abi.PAIR_MIXED_TYPES, abi.PAIR_SMALLER_DRIVES
+    U = abi.ERR_UNSUPPORTED
+    assert _pair_status(spheres, boxes, 0) == U and _pair_status(boxes, spheres, abi.NARROW_INDEX_LT) == U
+    assert _pair_status(spheres, boxes64, M) == U and _pair_status(boxes64, spheres, M | S) == U
+    assert _pair_status(boxes, spheres, M) == U and _pair_status(spheres, boxes, M) == U  # boxes drive
+    assert _pair_status(spheres, boxes, M | S) == abi.OK and _pair_status(boxes, spheres, M | S) == abi.OK  # spheres drive
+    assert _pair_status(boxes64, spheres, M) == U  # (index types differ)
+    few = orc.build(mpc.random_volumes(rng, 10, abi.BBOX, abi.F64, 3, 0.3), tb)
+    assert _pair_status(spheres, few, M) == abi.OK and _pair_status(spheres, few, M | S) == U  # now the spheres have more
+
+
+@pytest.mark.parametrize("combo", mpc.LEAF_NODE_COMBOS, ids=_COMBO_ID)
+def test_oracle_mixed_flag_changes_nothing_on_same_type_pairs(combo):
+    """One type on both sides: the flag set gives the same contacts and the same counts, byte for byte, as the flag unset
+    (every narrow code, either driver, IBVH_PAIR_SMALLER_DRIVES, both index types)."""
+    rng = np.random.default_rng(31 + sum(combo))
+    for idx, (n1, n2) in ((abi.I32, (120, 47)), (abi.I64, (33, 200)), (abi.I32, (1, 9))):
+        t = abi.make_types(*combo, idx, MORTONS[n1 % 3])
+        o1 = orc.build(mpc.random_volumes(rng, n1, combo[0], combo[1], 4, 0.5), t)
+        o2 = orc.build(mpc.random_volumes(rng, n2, combo[0], combo[1], 4, 0.5, origin=0.5), t)
+        for narrow in (abi.NARROW_NONE, abi.NARROW_MORTON_LT, abi.NARROW_INDEX_LT):
+            for extra in (0, abi.PAIR_SMALLER_DRIVES):
+                c0, k0 = orc.traverse_pair_lvt(o1, o2, narrow=narrow | extra)
+                c1, k1 = orc.traverse_pair_lvt(o1, o2, narrow=narrow | extra | abi.PAIR_MIXED_TYPES)
+                assert c0.tobytes() == c1.tobytes() and k0.tobytes() == k1.tobytes(), (idx, n1, n2, narrow, extra)
+                exp = mpc.traverse_pair_lvt(o1, o2, narrow=narrow, smaller_drives=bool(extra))
+                assert (_oracle_list(o1, o2, None, None, narrow | extra) == exp).all()
