@@ -50,36 +50,27 @@ template <int MODE> int run(const Walk &w, const Call &c) {
     if (!layout_of(w.walk->types, lay, &wl)) return IBVH_ERR_UNSUPPORTED;
     dl = wl;
     if (w.drv && !layout_of(w.drv->types, lay, &dl)) return IBVH_ERR_UNSUPPORTED;
-    if (!work && (!c.scratch || c.scratch_bytes < scan_scratch_bytes(w.n_items))) return IBVH_ERR_SCRATCH;
-    // RAYS: the binned path's region lives at the END of the scratch when the caller sized it with ibvh_rays_scratch_bytes
-    // and the tree and the batch qualify; the contact cache gets what lies in between
-    RayBinPlan bin_plan;
-    if (MODE == MODE_RAYS && !work) {
-        bin_plan = rays_bin_plan(*w.walk, w.n_items);
-        if (bin_plan.cut_level < w.start_level || c.scratch_bytes < scan_scratch_bytes(w.n_items) + bin_plan.bytes + 256) bin_plan = RayBinPlan{};
-    }
-    // SELF / PAIR under BBox nodes: the rows of the shared descent (ibvh_lvt.hpp "BlockRows") live at the END of the scratch when
-    // the caller sized it with ibvh_lvt_scratch_bytes; a smaller scratch simply has none (every wave descends on its own)
-    // ... in front of them, every work item's .index (the counting pass writes it for the writing pass: Args::q_index_dense), when there
-    // is room for both
+    if (!work && (!c.scratch || !scratch_holds_front(w.n_items, c.scratch_bytes))) return IBVH_ERR_SCRATCH;
+    // The tail of the scratch this call is entitled to (whether it fits, and where everything goes: scratch_plan).
+    // RAYS: the binned path's tables, when the tree and the batch qualify and the cut lies at or below the start level.
+    // SELF / PAIR under BBox nodes: the rows of the shared descent (ibvh_lvt.hpp "BlockRows") and, in front of them, every work
+    // item's .index (the counting pass writes it for the writing pass: Args::q_index_dense); without rows every wave descends on its own
     // (the rows are covers of consecutive work items made of the DRIVING tree's nodes: only when those have the walked tree's node
     // type — a mixed pair's driving nodes of another kind or float type are not rounded into covers, a BBox{Float64} rounded to
     // Float32 may no longer contain its leaves)
     const bool same_nodes = !w.drv || (w.drv->types.node_kind == w.walk->types.node_kind && w.drv->types.node_float == w.walk->types.node_float);
-    size_t rows_bytes = 0, qidx_bytes = 0;
-    if (MODE != MODE_RAYS && !work && w.walk->types.node_kind == IBVH_BBOX && same_nodes) {
-        rows_bytes = blk_rows_bytes(w.n_items, BLK_SHIFT_MIN);
-        qidx_bytes = (size_t)align_up(w.n_items * (int64_t)(lay.pair_bytes / 2), 256);
-        if (c.scratch_bytes < scan_scratch_bytes(w.n_items) + rows_bytes + qidx_bytes + 256) qidx_bytes = 0;
-        if (c.scratch_bytes < scan_scratch_bytes(w.n_items) + rows_bytes + 256) rows_bytes = 0;
-        if (!rows_bytes) qidx_bytes = 0;
-        rows_bytes += qidx_bytes; // (one tail: [index array | rows])
+    RayBinPlan bin_plan;
+    ScratchTail tail = TAIL_NONE;
+    if (MODE == MODE_RAYS && !work) {
+        bin_plan = rays_bin_plan(*w.walk, w.n_items);
+        if (bin_plan.depth && bin_plan.cut_level >= w.start_level) tail = TAIL_BINS;
+    } else if (MODE != MODE_RAYS && w.walk->types.node_kind == IBVH_BBOX && same_nodes) {
+        tail = TAIL_ROWS;
     }
-    const size_t tail_bytes = bin_plan.depth ? bin_plan.bytes : rows_bytes;
-    const size_t cache_room = c.scratch_bytes - (tail_bytes ? tail_bytes + 256 : 0);
-    char *tail_ptr = tail_bytes ? (char *)c.scratch + ((c.scratch_bytes - tail_bytes) & ~(size_t)255) : nullptr;
-    const RayBins bins = bin_plan.depth ? rays_bins_at(bin_plan, tail_ptr) : RayBins{};
-    const int K = work ? 0 : cache_slots_for(cache_room, w.n_items, lay.pair_bytes);
+    // (OP_WORK uses no scratch at all)
+    const ScratchPlan plan = work ? ScratchPlan{} : scratch_plan(w.n_items, lay.pair_bytes, tail, bin_plan.bytes, c.scratch_bytes);
+    auto at = [&](size_t offset) { return offset == ABSENT ? nullptr : (char *)c.scratch + offset; };
+    const RayBins bins = plan.bins != ABSENT ? rays_bins_at(bin_plan, at(plan.bins)) : RayBins{};
     return dispatch_leaf_node(w.walk->types, [&](auto lt, auto nt) -> int {
         using L = typename decltype(lt)::type;
         using N = typename decltype(nt)::type;
@@ -111,11 +102,11 @@ template <int MODE> int run(const Walk &w, const Call &c) {
                 a.guard_capacity = 0;
                 a.work = c.work;
                 a.gate = nullptr;
-                a.blk_rows = rows_bytes ? (uint32_t *)(tail_ptr + qidx_bytes) : nullptr;
-                a.q_index_dense = qidx_bytes ? (I *)tail_ptr : nullptr;
-                // (the scan's tile sums live behind the 64-byte header of the scratch: scan_counts)
+                a.blk_rows = (uint32_t *)at(plan.rows);
+                a.q_index_dense = (I *)at(plan.index);
+                // (the scan's tile sums, behind the header of the scratch: scan_counts)
                 const bool may_fuse = !write && !work && MODE != MODE_RAYS;
-                a.scan_agg = may_fuse ? (unsigned long long *)((int64_t *)c.scratch + 8) : nullptr;
+                a.scan_agg = may_fuse ? (unsigned long long *)at(SCRATCH_HEADER_BYTES) : nullptr;
                 a.scan_nparts = (int32_t)ceil_div(w.n_items, (int64_t)SCAN_TILE);
                 bool agg_zeroed = false;
                 a.blk_shift = 0;
@@ -123,7 +114,7 @@ template <int MODE> int run(const Walk &w, const Call &c) {
                 a.q_nodes = same_nodes ? (const N *)qside->nodes : nullptr;
                 a.q_tree = TreeDev{qside->tree.levels, qside->tree.real_leaves, qside->tree.virtual_leaves};
                 a.q_built_level = qside->built_level;
-                PairCache<I> cache{K ? (IndexPair<I> *)((char *)c.scratch + scan_scratch_bytes(w.n_items)) : nullptr, K};
+                PairCache<I> cache{(IndexPair<I> *)at(plan.cache), plan.K};
                 // one pass: the walked leaves' own type, or (a mixed pair, IBVH_PAIR_MIXED_TYPES) the driving leaves' type Q
                 auto pass = [&](bool wr, bool *agg) -> int {
                     if constexpr (MODE != MODE_PAIR) {
@@ -168,33 +159,28 @@ ibvh_status ibvh_lvt_scratch_bytes(const ibvh_types *types, int64_t n_items, int
     ibvh_layout lay;
     if (!layout_of(*types, lay)) return IBVH_ERR_UNSUPPORTED;
     if (cache_slots > MAX_CACHE_SLOTS) cache_slots = MAX_CACHE_SLOTS;
-    *bytes_out = scan_scratch_bytes(n_items) + (size_t)cache_slots * (size_t)n_items * (size_t)lay.pair_bytes;
-    if (types->node_kind == IBVH_BBOX) // room for the rows of the shared descent (2 bytes per work item), behind the contact cache
-        *bytes_out = (size_t)align_up((int64_t)*bytes_out, 256) + blk_rows_bytes(n_items, BLK_SHIFT_MIN) + 512 +
-                     (size_t)align_up(n_items * (int64_t)(lay.pair_bytes / 2), 256); // (+ every work item's .index, for the writing pass)
+    // (BBox nodes: room for the rows of the shared descent and every work item's .index, behind the contact cache)
+    *bytes_out = scratch_size(n_items, lay.pair_bytes, cache_slots, types->node_kind == IBVH_BBOX, 0);
     return IBVH_OK;
 }
 
 // Scratch for the ray traversal entry points: ibvh_lvt_scratch_bytes for num_rays work items, or, when the binned path
 // serves the batch, that path's region behind a scratch without contact cache (see include/ibvh.h).
 ibvh_status ibvh_rays_scratch_bytes(const ibvh_bvh *bvh, int64_t num_rays, int32_t cache_slots, size_t *bytes_out) {
-    if (!bvh || !bytes_out || num_rays < 0) return IBVH_ERR_INVALID_ARG;
-    size_t base = 0;
-    if (ibvh_status e = ibvh_lvt_scratch_bytes(&bvh->types, num_rays, cache_slots, &base)) return e;
+    if (!bvh || !bytes_out || num_rays < 0 || cache_slots < 0) return IBVH_ERR_INVALID_ARG;
     const RayBinPlan bp = rays_bin_plan(*bvh, num_rays);
-    if (bp.depth) { // the binned path keeps no contact cache: its writing pass walks the subtrees out of LDS again
-        if (ibvh_status e = ibvh_lvt_scratch_bytes(&bvh->types, num_rays, 0, &base)) return e;
-        *bytes_out = (size_t)align_up((int64_t)base, 256) + bp.bytes + 512;
-        return IBVH_OK;
-    }
-    *bytes_out = base;
+    if (!bp.depth) return ibvh_lvt_scratch_bytes(&bvh->types, num_rays, cache_slots, bytes_out);
+    ibvh_layout lay; // (a tree the binned path serves has a supported layout: rays_bin_plan)
+    layout_of(bvh->types, lay);
+    // the binned path keeps no contact cache: its writing pass walks the subtrees out of LDS again
+    *bytes_out = scratch_size(num_rays, lay.pair_bytes, 0, bvh->types.node_kind == IBVH_BBOX, bp.bytes);
     return IBVH_OK;
 }
 
 // nothing to walk (a single leaf, no rays): no contacts, and *_enqueue leaves a total of 0 where it would have left the count
 static ibvh_status nothing_to_walk(const Call &c) {
     if (c.op != OP_ENQUEUE) return IBVH_OK;
-    if (hipMemsetAsync(c.total_dev ? c.total_dev : c.scratch, 0, 8, (hipStream_t)c.stream) != hipSuccess) return IBVH_ERR_HIP;
+    if (hipMemsetAsync(c.total_dev ? c.total_dev : c.scratch, 0, sizeof(int64_t), (hipStream_t)c.stream) != hipSuccess) return IBVH_ERR_HIP; // (header word 0)
     if (c.total_host) *(volatile int64_t *)c.total_host = 0; // (host memory: nothing was launched that could write it later)
     return IBVH_OK;
 }
@@ -203,7 +189,7 @@ static ibvh_status nothing_to_walk(const Call &c) {
 static ibvh_status self_common(const ibvh_bvh *bvh, int64_t sl, int32_t narrow, bool buffers, const Call &c) {
     if (int e = check_levels(*bvh, sl)) return (ibvh_status)e;
     // (*_enqueue: the scratch header holds the total even when there is nothing to walk)
-    if (c.op == OP_ENQUEUE && (!c.scratch || c.scratch_bytes < scan_scratch_bytes(bvh->tree.real_leaves))) return IBVH_ERR_SCRATCH;
+    if (c.op == OP_ENQUEUE && (!c.scratch || !scratch_holds_front(bvh->tree.real_leaves, c.scratch_bytes))) return IBVH_ERR_SCRATCH;
     if (bvh->tree.real_nodes <= 1) return nothing_to_walk(c);
     if (!buffers) return IBVH_ERR_INVALID_ARG;
     return (ibvh_status)run<MODE_SELF>({.drv = bvh, .walk = bvh, .n_items = bvh->tree.real_leaves, .start_level = sl, .narrow = narrow}, c);

@@ -18,6 +18,7 @@
 #include <type_traits>
 
 #include "ibvh_common.hpp"
+#include "ibvh_lvt_scratch.hpp" // the layout of the calls' scratch buffer: ScratchPlan
 
 namespace ibvh {
 namespace lvt {
@@ -84,12 +85,10 @@ template <class L, class N, class I> struct Args {
 // containment of its valid queries (six compares per lane) and descends on its own when it fails, when the block's list
 // overflowed its row, or when there are no rows (small trees, the writing pass, the work-counter instantiation).  Any
 // conservative enumeration is exact here (ibvh_lvt.hpp header: box tests are monotone along a root-to-leaf path).
-constexpr int BLK_ROW = 512;   // 32-bit words per row: [0] count (-1: no list), [2 .. 2 + sizeof(N) / 4) the block's box, [BLK_HEAD ..) nodes
+// A row is BLK_ROW 32-bit words (ibvh_lvt_scratch.hpp): [0] count (-1: no list), [2 .. 2 + sizeof(N) / 4) the block's box, [BLK_HEAD ..) nodes
 constexpr int BLK_HEAD = 16;
 constexpr int BLK_CAP = BLK_ROW - BLK_HEAD;
 constexpr int BLK_FCAP = 512;  // frontier entries of a block's descent per level (LDS)
-inline size_t blk_rows_bytes(int64_t n_items, int shift) { return (size_t)ceil_div(n_items > 0 ? n_items : 1, (int64_t)1 << shift) * BLK_ROW * 4; }
-constexpr int BLK_SHIFT_MIN = 9; // (the scratch is sized for the smallest block the launch code may choose)
 
 // per-lane work counters of the COUNT instantiations (nothing at all otherwise)
 template <bool COUNT> struct Work {
@@ -445,7 +444,7 @@ IBVH_HD size_t rays_subtree_lds(int depth, size_t node_bytes, size_t leaf_bytes,
 
 
 // ---- inclusive scan of the per-item counts (AK.accumulate!, traverse_single.jl:57) ---------------
-constexpr int SCAN_TPB = 256, SCAN_IPT = 16, SCAN_TILE = SCAN_TPB * SCAN_IPT;
+constexpr int SCAN_TPB = 256, SCAN_IPT = SCAN_TILE / SCAN_TPB; // (SCAN_TILE: ibvh_lvt_scratch.hpp, one tile sum each)
 
 IBVH_D int64_t block_sum(int64_t v, int64_t *s_w) {
 #pragma unroll
@@ -755,28 +754,14 @@ template <class I> inline int64_t resident_scan_workgroups() {
     return memo;
 }
 
-// scratch layout of the *_count / *_write calls:
-//   [0, 64)            int64 header: [0] total contacts, [1] contact-cache slots K in use
-//   [64, scan_bytes)   scan tile sums
-//   [scan_bytes, ...)  contact cache: K * n_items IndexPair{I}, slot-major
-inline size_t scan_scratch_bytes(int64_t n) {
-    return (size_t)align_up((ceil_div(n > 0 ? n : 1, SCAN_TILE) + 9) * 8, 256); // header, one aggregate per tile, the fused scan's ticket
-}
-constexpr int MAX_CACHE_SLOTS = 64;
-inline int cache_slots_for(size_t scratch_bytes, int64_t n_items, int64_t pair_bytes) {
-    size_t sb = scan_scratch_bytes(n_items);
-    if (scratch_bytes <= sb || n_items <= 0) return 0;
-    int64_t k = (int64_t)((scratch_bytes - sb) / ((size_t)n_items * (size_t)pair_bytes));
-    return (int)(k > MAX_CACHE_SLOTS ? MAX_CACHE_SLOTS : k);
-}
-
 // inclusive scan in place + (total_out != nullptr) blocking read of the total (the reference's @allowscalar, :60)
+// scratch: scan_scratch_bytes(n) — the header and the tile sums of ibvh_lvt_scratch.hpp
 template <class I>
 int scan_counts(I *counts, int64_t n, int64_t *total_out, void *scratch, hipStream_t st, int64_t *total_dev = nullptr,
                 int64_t *total_host = nullptr, const int32_t *limit = nullptr, bool aggregates_zeroed = false) {
     int64_t nparts = ceil_div(n, SCAN_TILE);
-    int64_t *totals = total_dev ? total_dev : (int64_t *)scratch; // where the device-side total goes
-    int64_t *partials = (int64_t *)scratch + 8;
+    int64_t *totals = total_dev ? total_dev : (int64_t *)scratch; // where the device-side total goes (header word 0)
+    int64_t *partials = (int64_t *)((char *)scratch + SCRATCH_HEADER_BYTES);
     if (aggregates_zeroed && g_tuning.lvt_scan_fused != 0) {
         int64_t room = resident_scan_workgroups<I>();
         if (g_tuning.lvt_scan_fused > 1 && g_tuning.lvt_scan_fused < room) room = g_tuning.lvt_scan_fused; // (development knob: a smaller grid)

@@ -288,6 +288,12 @@ ibvh_status ibvh_refit(const ibvh_bvh *bvh, const void *volumes, int64_t num_vol
  *          in front of the counting pass and read by both passes (csrc/ibvh_lvt.hpp "BlockRows"), and a dense copy of the
  *          work items' .index (4 / 8 bytes an item) that the counting pass leaves for the writing pass, which then does not
  *          touch the leaf records at all; a scratch without room for either is served without it.
+ *          Layout (csrc/ibvh_lvt_scratch.hpp, ScratchPlan — one description for the size queries and the launches):
+ *            [ 64-byte header | scan tile sums | contact cache: K slots x n_items pairs | ...gap... | tail ]
+ *          The tail is anchored at the END of `scratch_bytes`, aligned down to 256: [index array | rows] (self / pair under
+ *          BBox nodes) or the binned ray path's tables.  A buffer smaller than the size query's answer loses the index array
+ *          first, then the rows (the ray tables as a whole); the contact cache gets the slots (<= 64) that fit between the
+ *          scan sums and the tail; below header + scan sums the call answers IBVH_ERR_SCRATCH.
  * NaN: with BBox nodes the walkers rely on parents being the exact minima / maxima of their children (merge.jl:30-40): a
  *      contact is decided by the leaf parent's box and the leaf test, the levels above only prune.  On volumes whose boxes
  *      hold no NaN that is the reference's list, element for element.  A NaN leaf box (a NaN radius; Inf - Inf in the
