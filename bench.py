@@ -17,10 +17,15 @@ distributed radix-sort exchange (implicitbvh_amd.dist); each rank then builds an
 (BASELINE.json configs[4]: 1e8 leaves over 8 GPUs = 12.5 M leaves per GPU, the default for N > 1).  Weak
 scaling: --n is the per-GPU leaf count, value = all ranks' leaves / max-over-ranks time.
 
-Prints ONE JSON line (rank 0) with `roofline` (dominant kernel, HIP-event timed inside the library),
-`cpu_baseline` (the CPU oracle's multi-threaded restatement, timed on this box's host cores) and — at one
-GPU — `configs`: BASELINE.json configs 2 (BFS), 3 (mesh: build, self-traverse, 1e6 rays) and 4 (two 5e6
-clouds: pair LVT and BFS), each with its own roofline and, for rays and pair, its own CPU baseline.
+Prints ONE JSON line (rank 0).  A plain run does what the headline needs and nothing else: set-up, W warm-up
+steps, K timed steps, the outputs if --dump-outputs asks for them, the line (`value`, `ms_per_step`, the
+workload).  `--full` adds everything else the benchmark measures, each in runs of its own around the same
+headline: the north-star size (1e7 leaves), `value_enqueue_only`, the per-kernel table and `roofline`
+(dominant kernel, HIP-event timed inside the library), `cpu_baseline` (the CPU oracle's multi-threaded
+restatement, timed on the host's cores), `work`, at N > 1 the exchange statistics and the cross-shard
+completion (`exchange`, `dist`) and — at one GPU — `configs`: BASELINE.json configs 2 (BFS), 3 (mesh: build,
+self-traverse, 1e6 rays) and 4 (two 5e6 clouds: pair LVT and BFS), each with its own roofline and, for rays
+and pair, its own CPU baseline.  --no-cpu-baseline, --no-configs and --extra-n 0 take legs out of a --full run.
 """
 import argparse
 import ctypes as C
@@ -679,7 +684,7 @@ def compact_line(line, detail_path):
     """The ONE line the driver records (<= 4 KB): the contract's fields, the north-star size and one {ms, frac} per config;
     everything else is in `detail_path` (a 17 KB line lost its head in the driver's tail)."""
     keep = ("metric", "value", "unit", "n_gpus", "steps", "warmup", "ms_per_step", "higher_is_better", "scaling", "vs_baseline",
-            "dtype", "data", "value_enqueue_only", "ms_per_step_enqueue_only", "mcontacts_per_s", "profiled_ms_per_step")
+            "dtype", "data", "full", "value_enqueue_only", "ms_per_step_enqueue_only", "mcontacts_per_s", "profiled_ms_per_step")
     out = {k: line[k] for k in keep if k in line}
     cfg = line.get("config") or {}
     out["config"] = _pick(cfg, ("workload", "leaves_per_gpu", "leaves_total", "contacts_total", "parallelism"))
@@ -939,12 +944,17 @@ def main():
                     help="leaves per GPU (default: 1e6 at one GPU = BASELINE.json configs[1]; 12.5e6 at N > 1 = configs[4], "
                          "1e8 leaves over 8 GPUs)")
     ap.add_argument("--seed", type=int, default=42)
-    ap.add_argument("--no-cpu-baseline", action="store_true")
-    ap.add_argument("--no-configs", action="store_true", help="skip BASELINE.json configs 2 (BFS), 3 and 4")
+    ap.add_argument("--full", action="store_true",
+                    help="besides the headline, measure everything else: the north-star size, the steps without the count read, "
+                         "per-kernel times and roofline, CPU baselines, work counters, BASELINE.json configs 2 (BFS), 3 and 4, "
+                         "at N > 1 the exchange statistics and the cross-shard completion (off by default: a plain run sets "
+                         "up, warms up, times the steps and prints the line)")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="with --full: skip the CPU baselines and the work counters")
+    ap.add_argument("--no-configs", action="store_true", help="with --full: skip BASELINE.json configs 2 (BFS), 3 and 4")
     ap.add_argument("--force-dist", action="store_true", help="use the multi-GPU build path even with one rank")
     ap.add_argument("--extra-n", type=int, default=10_000_000,
-                    help="also report the north-star size (1e7 leaves) at N=1; 0 disables")
-    ap.add_argument("--cpu-n", type=int, default=0, help="leaves of the CPU baseline sample (0 = same as --n, capped)")
+                    help="with --full: also report the north-star size (1e7 leaves) at N=1; 0 disables")
+    ap.add_argument("--cpu-n", type=int, default=0, help="with --full: leaves of the CPU baseline sample (0 = same as --n, capped)")
     ap.add_argument("--detail", default="bench_detail.json", help="where the full (long) record goes; stdout carries the compact line")
     ap.add_argument("--virtual-ranks", type=int, default=0,
                     help="EMULATE BASELINE.json configs[4] on ONE GPU: this many virtual ranks (threads) x --n leaves (default 1.25e7) run the "
@@ -1010,12 +1020,14 @@ def main():
             trav = ibvh.traverse(bvh, cache=state[1])
             return bvh, trav
 
-    # ---- north-star size (1e7 leaves, single GPU): same step, fewer repetitions.  Runs BEFORE the headline's warm-up and timed
+    # ---- --full: north-star size (1e7 leaves, single GPU): same step, fewer repetitions.  Runs BEFORE the headline's warm-up and timed
     # steps on purpose: a GPU that has just been idle runs a 5 ms burst ~12 % slower than its steady state (round 3: 0.2494 ms
     # in the driver's 20-step record against 0.223 ms over 200 steps), and these ~30 ms of work bring it to steady clocks; the
-    # headline below is still W untimed warm-up steps followed by exactly K timed steps ---------------------
+    # headline below is still W untimed warm-up steps followed by exactly K timed steps.  (A plain run goes without it: with
+    # today's library, runs of 20 steps after 5 measured 0.2161 - 0.2189 ms without this leg and 0.2157 - 0.2208 ms with it,
+    # three runs each, alternating; 200 steps after 30: 0.2119 / 0.2120 against 0.2114 / 0.2120) -----------------------
     north_star = None
-    if world == 1 and dist is None and args.extra_n and args.extra_n != n:
+    if args.full and world == 1 and dist is None and args.extra_n and args.extra_n != n:
         n2 = args.extra_n
         r02 = 0.5 * (3 * 8 / (4 * math.pi * n2)) ** (1 / 3)
         vols2 = ibvh.generate_spheres(n2, args.seed, r0=r02)
@@ -1099,27 +1111,31 @@ def main():
     # (the last timed step's results, copied on the device; written to disk once everything is timed)
     snapshot = snapshot_outputs(*state) if args.dump_outputs and rank == 0 else None
 
-    # The same K steps chained through cache= WITHOUT the read (a caller that sizes nothing from the count need not
-    # wait for it; the count is read once, at the end)
-    barrier()
-    t0 = time.perf_counter()
-    for _ in range(args.steps):
-        state = one_step(state)
-    barrier()
-    elapsed_eq = max_over_ranks(time.perf_counter() - t0)
-    _ = state[1].num_contacts
+    # ---- --full: the same K steps chained through cache= WITHOUT the read (a caller that sizes nothing from the count need
+    # not wait for it; the count is read once, at the end)
+    elapsed_eq = None
+    if args.full:
+        barrier()
+        t0 = time.perf_counter()
+        for _ in range(args.steps):
+            state = one_step(state)
+        barrier()
+        elapsed_eq = max_over_ranks(time.perf_counter() - t0)
+        _ = state[1].num_contacts
 
-    # ---- per-kernel timing pass (HIP events inside the library, on the launch stream) -------------
-    prof_steps = max(3, min(10, args.steps))
-    lib.call("ibvh_profile_enable", 1)
-    torch.cuda.synchronize()
-    tp0 = time.perf_counter()
-    for _ in range(prof_steps):
-        state = one_step(state)
-    torch.cuda.synchronize()
-    tp = time.perf_counter() - tp0
-    prof = collect_profile(lib)
-    lib.call("ibvh_profile_enable", 0)
+    # ---- --full: per-kernel timing pass (HIP events inside the library, on the launch stream) -------------
+    prof, prof_steps, tp = {}, 0, 0.0
+    if args.full:
+        prof_steps = max(3, min(10, args.steps))
+        lib.call("ibvh_profile_enable", 1)
+        torch.cuda.synchronize()
+        tp0 = time.perf_counter()
+        for _ in range(prof_steps):
+            state = one_step(state)
+        torch.cuda.synchronize()
+        tp = time.perf_counter() - tp0
+        prof = collect_profile(lib)
+        lib.call("ibvh_profile_enable", 0)
 
     roofline, kernels = None, {}
     if prof:
@@ -1154,10 +1170,10 @@ def main():
             roofline["cache_residency"] = ("infinity-cache-resident: the step's working set (~130 MB) fits the 256 MB Infinity Cache, so the "
                                            "'hbm' fraction at this size is a label, not a bound; north_star_1e7.roofline is the HBM-sized figure")
 
-    # ---- per-rank exchange statistics of the distributed build (config 5): what the first real multi-GPU run needs to
+    # ---- --full: per-rank exchange statistics of the distributed build (config 5): what the first real multi-GPU run needs to
     # price the all-to-all against xGMI (7 links x ~153 GB/s per GPU) -------------------------------------------------
     exchange = None
-    if builder is not None:
+    if args.full and builder is not None:
         stats = builder.exchange_stats(vols, repeats=3)  # {"exchange_ms", "bytes_sent", "bytes_received", "peers"}
         rows = [None] * world
         dist.all_gather_object(rows, stats)
@@ -1170,12 +1186,12 @@ def main():
                         "note": "all-to-all of 24-byte records, timed with HIP events around the collective on every rank; "
                                 "xgmi_frac_per_link = bytes one GPU ships to ONE peer / time / 153 GB/s"}
 
-    # ---- what makes the result GLOBAL: the contacts between leaves of different slices, which the
+    # ---- --full: what makes the result GLOBAL: the contacts between leaves of different slices, which the
     # per-slice self-traversals of the timed step cannot see — timed on their own, every rank, max over
     # ranks; the phases of one step with a synchronisation between them; and, while the whole cloud fits one GPU, a self-check:
     # own + cross contacts of all ranks == the single-device contact count --------------------------------------------
     dist_detail = None
-    if builder is not None:
+    if args.full and builder is not None:
         import torch.distributed as tdist
         cross = builder.cross_contacts(state[0])  # (untimed: sizes the buffers)
         barrier()
@@ -1227,9 +1243,9 @@ def main():
                                    "cross_ms is what completing the contact set costs on top"
                                    + ("" if world > 1 else "; ONE rank: no peers, nothing crosses")}
 
-    # ---- CPU baseline: the oracle's multi-threaded restatement, rank 0 only, bounded sample --------
+    # ---- --full: CPU baseline: the oracle's multi-threaded restatement, rank 0 only, bounded sample --------
     cpu_baseline, cpu = None, None
-    if rank == 0 and world == 1 and not args.no_cpu_baseline:
+    if args.full and rank == 0 and world == 1 and not args.no_cpu_baseline:
         sys.path.insert(0, os.path.join(ROOT, "tests"))
         import oracle_lib as orc  # the checker, here only as the timed CPU baseline
         ncpu = os.cpu_count() or 1
@@ -1289,7 +1305,7 @@ def main():
             north_star["gpu_over_cpu"] = round(north_star["value"] / north_star["cpu_baseline"]["value"], 1)
             del host2
 
-    # ---- work inflation of the headline traversal (SURVEY.md §8d "touched bytes"): node + leaf tests of the HIP walk (a
+    # ---- --full: work inflation of the headline traversal (SURVEY.md §8d "touched bytes"): node + leaf tests of the HIP walk (a
     # counting instantiation of the same kernel) next to the reference walk's (instrumented oracle), same input ----------
     work = None
     if cpu is not None and dist is None and n <= 2_000_000:
@@ -1298,9 +1314,9 @@ def main():
         work = _work(ibvh, orc, ((state[0],), {}), ((ob,), {}), n, cores, native)
         del ob
 
-    # ---- BASELINE.json configs 2 (BFS), 3, 4 ------------------------------------------------------------------------
+    # ---- --full: BASELINE.json configs 2 (BFS), 3, 4 ----------------------------------------------------------------
     configs = None
-    if rank == 0 and world == 1 and dist is None and not args.no_configs:
+    if args.full and rank == 0 and world == 1 and dist is None and not args.no_configs:
         del vols
         state = (None, None)
         torch.cuda.empty_cache()
@@ -1311,7 +1327,7 @@ def main():
         line = {
             "metric": "BVH build+traverse throughput", "value": round(value, 3), "unit": "Mleaves/s",
             "n_gpus": world, "steps": args.steps, "warmup": args.warmup, "ms_per_step": round(ms_per_step, 4),
-            "higher_is_better": True, "scaling": "weak", "vs_baseline": None, "dtype": "f32", "data": "synthetic",
+            "higher_is_better": True, "scaling": "weak", "vs_baseline": None, "dtype": "f32", "data": "synthetic", "full": args.full,
             "config": {"workload": f"{n} random BSphere{{Float32}} leaves per GPU, BBox{{Float32}} nodes, UInt32 Morton, "
                                    f"Int32 index, build + LVT self-traverse + read of the contact count "
                                    + ("(BASELINE.json configs[1])" if world == 1 and n == 1_000_000 else
@@ -1321,14 +1337,17 @@ def main():
                        "leaves_per_gpu": n, "leaves_total": leaves_total, "contacts_total": contacts_total,
                        "parallelism": "single GPU" if world == 1 else f"leaves sharded over {world} GPUs (RCCL build), per-GPU traversal"},
             "value_definition": "every timed step ends with the host's read of the contact count, as the reference's traverse() does "
-                                "(lvt/traverse_single.jl:60); value_enqueue_only chains the same steps without it",
-            "value_enqueue_only": round(leaves_total * args.steps / elapsed_eq / 1e6, 3),
-            "ms_per_step_enqueue_only": round(elapsed_eq / args.steps * 1e3, 4),
+                                "(lvt/traverse_single.jl:60); value_enqueue_only (--full) chains the same steps without it",
             "mcontacts_per_s": round(contacts_total * args.steps / elapsed / 1e6, 3),
-            "mcontacts_per_s_traverse_only": round(contacts / (t_trav * 1e-3) / 1e6, 3) if t_trav else None,
-            "roofline": roofline, "cpu_baseline": cpu_baseline, "work": work, "north_star_1e7": north_star, "configs": configs,
-            "exchange": exchange, "dist": dist_detail, "kernels": kernels, "profiled_ms_per_step": round(tp / prof_steps * 1e3, 4),
         }
+        if args.full:
+            line.update({
+                "value_enqueue_only": round(leaves_total * args.steps / elapsed_eq / 1e6, 3),
+                "ms_per_step_enqueue_only": round(elapsed_eq / args.steps * 1e3, 4),
+                "mcontacts_per_s_traverse_only": round(contacts / (t_trav * 1e-3) / 1e6, 3) if t_trav else None,
+                "roofline": roofline, "cpu_baseline": cpu_baseline, "work": work, "north_star_1e7": north_star, "configs": configs,
+                "exchange": exchange, "dist": dist_detail, "kernels": kernels, "profiled_ms_per_step": round(tp / prof_steps * 1e3, 4),
+            })
         # full detail beside the script (gitignored; tools/profile_round.sh copies it under profiles/), ONE compact line on stdout
         detail_path = args.detail
         try:

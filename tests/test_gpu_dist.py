@@ -47,13 +47,13 @@ def test_c_abi_collective_vtable_over_rccl_and_dist_build_through_it():
 
 
 def test_bench_self_launches_its_ranks():
-    """`python bench.py --gpus 1 --force-dist`: the distributed path of the bench on one rank, and the self-launcher's
+    """`python bench.py --gpus 1 --force-dist --full`: the distributed path of the bench on one rank, and the self-launcher's
     plumbing (a parent that never touches the GPU) via --gpus 2 on a box with one GPU is NOT attempted here: only that the
     launcher code path parses and the one-rank distributed bench line carries n_gpus = 1."""
     import json
     root = os.path.dirname(HERE)
     env = dict(os.environ, MASTER_PORT=_free_port())
-    r = subprocess.run([sys.executable, os.path.join(root, "bench.py"), "--force-dist", "--n", "200000", "--steps", "3", "--warmup", "1",
+    r = subprocess.run([sys.executable, os.path.join(root, "bench.py"), "--force-dist", "--full", "--n", "200000", "--steps", "3", "--warmup", "1",
                         "--no-cpu-baseline", "--extra-n", "0"], env=env, capture_output=True, text=True, timeout=600)
     assert r.returncode == 0, r.stderr[-3000:]
     line = json.loads([l for l in r.stdout.splitlines() if l.startswith("{")][-1])

@@ -5,7 +5,7 @@ out=$1; shift
 mkdir -p $out
 for tag in "$@"; do
   if [ "$tag" = main ]; then unset IBVH_LIB; else export IBVH_LIB=$PWD/variants/libibvh_$tag.so; fi
-  python bench.py --no-cpu-baseline --no-configs > $out/ab_$tag.json 2> $out/ab_$tag.err
+  python bench.py --full --no-cpu-baseline --no-configs > $out/ab_$tag.json 2> $out/ab_$tag.err
   python - $out/ab_$tag.json $tag <<'PY'
 import json, sys
 d = json.loads([l for l in open(sys.argv[1]) if l.startswith("{")][-1])

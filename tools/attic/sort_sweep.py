@@ -12,7 +12,7 @@ ROOT = os.path.dirname(os.path.dirname(os.path.dirname(os.path.abspath(__file__)
 n = sys.argv[1]
 for setting in sys.argv[2:] or [""]:
     env = dict(os.environ, IBVH_TUNING=setting)
-    out = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--n", n, "--no-cpu-baseline", "--extra-n", "0",
+    out = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--full", "--n", n, "--no-cpu-baseline", "--extra-n", "0",
                           "--steps", "5", "--warmup", "2"], env=env, capture_output=True, text=True)
     lines = [l for l in out.stdout.splitlines() if l.startswith("{")]
     if not lines:

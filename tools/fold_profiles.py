@@ -1,6 +1,6 @@
 #!/usr/bin/env python3
 """Turn what one GPU run of
-    python bench.py > gpurun_out/final_bench.json; tools/profile_round.sh TAG; tools/profile_sq.sh TAG;
+    python bench.py --full > final_bench.json; tools/profile_round.sh TAG; tools/profile_sq.sh TAG;
     tools/profile_workloads.sh TAG; tools/sq_rays.sh TAG
 left under gpurun_out/ into the committed files of profiles/ (all stamped with the hash of the kernel sources they were
 taken at).  usage: python tools/fold_profiles.py r04"""
