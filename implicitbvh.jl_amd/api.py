@@ -30,6 +30,7 @@ __all__ = [
     "BVHTraversal", "LVTTraversal", "BFSTraversal", "traverse", "traverse_rays", "default_start_level",
     "memory_index", "level_indices", "isvirtual", "bounding_volumes_from_triangles", "generate_spheres",
     "NARROW_MORTON_LT", "NARROW_INDEX_LT", "NARROW_RAY_ORIGIN_OUTSIDE", "LeafBatch", "lvt_work_counters", "refit",
+    "resolve_triangles", "raycast", "RayHits",
 ]
 
 NARROW_MORTON_LT = abi.NARROW_MORTON_LT
@@ -761,6 +762,7 @@ class BVHTraversal:
         self._scratch = _scratch
         self._pending = _pending  # (total: _PendingTotal, capacity, finish(total) -> contacts tensor)
         self._donated = False
+        self._ray_list = None  # ray traversals: "lvt" (grouped by ray, user indices: what resolve_triangles takes), "bfs", "positions"
 
     def _resolve(self):
         if self._pending is None:
@@ -1103,9 +1105,11 @@ def _traverse_lvt_pair(bvh1, bvh2, sl1, sl2, narrow, cache):
 def _traverse_lvt_rays(bvh, p, d, start_level, narrow, cache):
     """p, d: the rays as (N, 3) row-major tensors of the leaf float type"""
     nr = p.shape[0]
-    return _lvt_two_pass("ibvh_traverse_rays_lvt", (C.byref(bvh.struct()), _ptr(p), _ptr(d), nr, start_level, narrow), nr,
-                         _torch_index(bvh.types.index_type), cache,
-                         _lvt_scratch(cache, bvh.types, nr, slots=RAY_CACHE_SLOTS, rays_bvh=bvh), start_level, keep=(p, d))
+    t = _lvt_two_pass("ibvh_traverse_rays_lvt", (C.byref(bvh.struct()), _ptr(p), _ptr(d), nr, start_level, narrow), nr,
+                      _torch_index(bvh.types.index_type), cache,
+                      _lvt_scratch(cache, bvh.types, nr, slots=RAY_CACHE_SLOTS, rays_bvh=bvh), start_level, keep=(p, d))
+    t._ray_list = "positions" if narrow & abi.OUTPUT_POSITIONS else "lvt"
+    return t
 
 
 BFS_INITIAL_FACTOR = 4  # queues start at 4x the initial pair count (bfs/traverse_single.jl:73)
@@ -1184,7 +1188,9 @@ def _traverse_bfs_rays(bvh, p, d, start_level, narrow, cache):
     lib.call("ibvh_bfs_rays_initial_capacity", C.byref(s), nr, start_level, C.byref(cap))
     res, q1, q2 = _bfs_run("ibvh_traverse_rays_bfs", bvh.types, cap.value, cache, bvh.tree.levels, C.byref(s), _ptr(p),
                            _ptr(d), nr, start_level, narrow)
-    return BVHTraversal(start_level, 0, res.num_checks, res.num_contacts, q1, q2)
+    t = BVHTraversal(start_level, 0, res.num_checks, res.num_contacts, q1, q2)
+    t._ray_list = "bfs"
+    return t
 
 
 def traverse(bvh, *args, start_level=None, start_level1=None, start_level2=None, narrow=None, cache=None, options=None):
@@ -1229,12 +1235,113 @@ def traverse_rays(bvh, points, directions, alg=None, start_level=1, narrow=None,
     idt = _torch_index(bvh.types.index_type)
     if points.shape[1] == 0:
         e = torch.empty((0, 2), dtype=idt, device="cuda")
-        return BVHTraversal(start_level, 0, 0, 0, e, e.clone())
+        t = BVHTraversal(start_level, 0, 0, 0, e, e.clone())
+        t._ray_list = "lvt" if lvt else "bfs"
+        return t
     ft = _torch_float(bvh.types.leaf_float)
     p = points.to(device="cuda", dtype=ft).t().contiguous()  # (N, 3) row-major == (3, N) column-major
     d = directions.to(device="cuda", dtype=ft).t().contiguous()
     t = (_traverse_lvt_rays if lvt else _traverse_bfs_rays)(bvh, p, d, start_level, code, cache)
     return _post_filter(t, fn, bvh, rays=(p, d)) if fn else t
+
+
+# ---------------------------------------------------------------------------------------------
+# ray hit lists against the mesh's triangles (ibvh_rays_resolve_triangles; no reference counterpart)
+# ---------------------------------------------------------------------------------------------
+class RayHits:
+    """Per ray: .index (N,) the nearest exactly hit triangle's user index (0 = miss), .t (N,) (+Inf = miss), .uv (N, 2)
+    (0, 0 on a miss); .candidate_t (num_contacts,) — t of every candidate that is an exact hit, +Inf otherwise — when
+    all_hits was asked for, else None."""
+
+    def __init__(self, index, t, uv, candidate_t=None):
+        self.index, self.t, self.uv, self.candidate_t = index, t, uv, candidate_t
+
+
+def _resolve_enqueue(flt, triangles, p, d, counts, contacts, index, t, uv, cand, flag):
+    """One ibvh_rays_resolve_triangles call on the current stream; reads nothing back.  p, d: (N, 3) row-major."""
+    lib.call("ibvh_rays_resolve_triangles", flt, _index_code(counts.dtype), _ptr(triangles), triangles.shape[0], _ptr(p), _ptr(d),
+             p.shape[0], _ptr(counts), _ptr(contacts), contacts.shape[0], _ptr(index), _ptr(t), _ptr(uv), _ptr(cand), _ptr(flag),
+             _stream())
+
+
+def _check_triangles(triangles, what):
+    torch = _torch()
+    if not isinstance(triangles, torch.Tensor) or not (
+            (triangles.dim() == 2 and triangles.shape[1] == 9) or (triangles.dim() == 3 and tuple(triangles.shape[1:]) == (3, 3))):
+        raise ValueError(f"{what}: triangles must be an (n, 9) or (n, 3, 3) tensor (p1 p2 p3 per triangle)")
+    if triangles.dtype not in (torch.float32, torch.float64):
+        raise ValueError(f"{what}: triangles must be float32 or float64, not {triangles.dtype}")
+    if not triangles.is_cuda:
+        raise ValueError(f"{what}: triangles must live on the GPU (device='cuda')")
+    return triangles.reshape(triangles.shape[0], 9).contiguous()
+
+
+def resolve_triangles(traversal, triangles, points, directions, all_hits=False):
+    """The exact ray-triangle test over the candidate list of traverse_rays(..., LVTTraversal()) and the nearest hit per ray
+    (include/ibvh.h, ibvh_rays_resolve_triangles: the arithmetic, the tie rule — smallest t, then the earlier candidate —
+    and the guards are spelled out there).  `triangles`: the (n, 9) / (n, 3, 3) CUDA tensor the BVH's bounding volumes were
+    made from (user index k = row k - 1), float32 or float64: the test runs in ITS dtype.  points, directions: the rays the
+    traversal was made with, (3, N) as for traverse_rays.  Returns a RayHits.
+
+    Exact on the candidate list it is given: a grazing hit that the broad phase's rounded slab / sphere test dropped is not
+    recovered.  ValueError: a BFS traversal (its list is not grouped by ray), a list of leaf positions or one a callable
+    `narrow` filtered (the counts no longer describe it), a wrong dtype, device or shape, and a candidate whose index lies
+    outside 1..n (flag bit 1; such candidates count as misses).  Reads traversal.cache1, i.e. the traversal's count, first."""
+    torch = _require_gpu()
+    kind = getattr(traversal, "_ray_list", None)
+    if kind != "lvt":
+        why = {"bfs": "a BFS ray traversal's list is not grouped by ray", "positions": "the list holds leaf positions, not triangle numbers",
+               None: "not an LVT ray traversal with a device narrow (a filtered list has no counts; traverse() lists hold no rays)"}[kind]
+        raise ValueError(f"resolve_triangles: {why}: use traverse_rays(..., LVTTraversal()) with narrow=None or a NARROW_* constant")
+    tris = _check_triangles(triangles, "resolve_triangles")
+    if not (isinstance(points, torch.Tensor) and isinstance(directions, torch.Tensor) and points.dim() == 2 and
+            directions.dim() == 2 and points.shape[0] == 3 and directions.shape[0] == 3):
+        raise ValueError("size(points, 1) == size(directions, 1) == 3 must hold")
+    if points.shape[1] != directions.shape[1]:
+        raise ValueError("size(points, 2) == size(directions, 2) must hold")
+    nr = int(points.shape[1])
+    contacts = traversal.cache1  # (resolves a pending count: the read a user makes anyway)
+    counts = traversal.cache2
+    ft, idt = tris.dtype, contacts.dtype
+    if nr == 0:
+        e = torch.empty(0, dtype=ft, device="cuda")
+        return RayHits(torch.empty(0, dtype=idt, device="cuda"), e, torch.empty((0, 2), dtype=ft, device="cuda"), e.clone() if all_hits else None)
+    if counts is None or counts.dim() != 1 or counts.shape[0] < nr or counts.dtype != idt or not counts.is_cuda:
+        raise ValueError(f"resolve_triangles: the traversal's counts (cache2) do not describe {nr} rays")
+    if contacts.dim() != 2 or contacts.shape[1] != 2 or not contacts.is_cuda:
+        raise ValueError("resolve_triangles: the traversal's contact list (cache1) must be an (m, 2) CUDA index tensor")
+    counts = counts[:nr]  # (a cached counts buffer may be longer than this batch)
+    index = torch.empty(nr, dtype=idt, device="cuda")
+    t = torch.empty(nr, dtype=ft, device="cuda")
+    uv = torch.empty((nr, 2), dtype=ft, device="cuda")
+    p = points.to(device="cuda", dtype=ft).t().contiguous()
+    d = directions.to(device="cuda", dtype=ft).t().contiguous()
+    cand = torch.empty(contacts.shape[0], dtype=ft, device="cuda") if all_hits else None
+    flag = torch.zeros(1, dtype=torch.int32, device="cuda")
+    _resolve_enqueue(_float_code(ft), tris, p, d, counts, contacts, index, t, uv, cand, flag)
+    raised = int(flag.item())
+    if raised & 1:
+        raise RuntimeError("resolve_triangles: the contact list is shorter than the traversal's count")
+    if raised & 2:
+        raise ValueError(f"resolve_triangles: a candidate's index lies outside 1..{tris.shape[0]} (the number of triangles given)")
+    return RayHits(index, t, uv, cand[: traversal.num_contacts] if all_hits else None)
+
+
+def raycast(bvh, triangles, points, directions, **kw):
+    """traverse_rays(bvh, points, directions, LVTTraversal(); **kw) followed by resolve_triangles: the nearest exactly hit
+    triangle per ray.  `triangles` must be of the BVH's leaf float type (the broad phase ran in it); kw: start_level,
+    narrow (None or a NARROW_* constant), cache, all_hits.  Returns (RayHits, the BVHTraversal — reusable as cache=)."""
+    tris = _check_triangles(triangles, "raycast")
+    if tris.dtype != _torch_float(bvh.types.leaf_float):
+        raise ValueError(f"raycast: triangles must be {_torch_float(bvh.types.leaf_float)}, the BVH's leaf float type")
+    all_hits = kw.pop("all_hits", False)
+    if "alg" in kw and not isinstance(kw["alg"], LVTTraversal):
+        raise ValueError("raycast: only LVTTraversal lists are grouped by ray")
+    kw.pop("alg", None)
+    if callable(kw.get("narrow")):
+        raise ValueError("raycast: narrow must be None or a NARROW_* constant (a filtered list has no counts)")
+    trav = traverse_rays(bvh, points, directions, LVTTraversal(), **kw)
+    return resolve_triangles(trav, tris, points, directions, all_hits=all_hits), trav
 
 
 def lvt_work_counters(bvh, bvh2=None, points=None, directions=None):

@@ -273,6 +273,13 @@ c_refit(bvh, volumes, num_volumes, flag, stream) =
     ccall((:ibvh_refit, libibvh), Cint,
           (Ref{IbvhBvh}, Ptr{Cvoid}, Int64, Ptr{Cvoid}, Ptr{Cvoid}),
           bvh, volumes, num_volumes, flag, stream)
+c_rays_resolve_triangles(flt, idx, triangles, num_triangles, points, directions, num_rays, counts, contacts, capacity,
+                         closest_index, closest_t, closest_uv, cand_t, flag, stream) =
+    ccall((:ibvh_rays_resolve_triangles, libibvh), Cint,
+          (Int32, Int32, Ptr{Cvoid}, Int64, Ptr{Cvoid}, Ptr{Cvoid}, Int64, Ptr{Cvoid}, Ptr{Cvoid}, Int64,
+           Ptr{Cvoid}, Ptr{Cvoid}, Ptr{Cvoid}, Ptr{Cvoid}, Ptr{Cvoid}, Ptr{Cvoid}),
+          flt, idx, triangles, num_triangles, points, directions, num_rays, counts, contacts, capacity,
+          closest_index, closest_t, closest_uv, cand_t, flag, stream)
 c_lvt_scratch_bytes(types, n_items, cache_slots, out) =
     ccall((:ibvh_lvt_scratch_bytes, libibvh), Cint,
           (Ref{IbvhTypes}, Int64, Int32, Ref{Csize_t}),
@@ -558,6 +565,52 @@ function refit!(bvh::RocBVH{I}, volumes::Union{Nothing, ROCVector}=nothing) wher
     flag = scratch!(:refit_flag, 4)
     check(c_refit(d, devptr(volumes), Int64(m), devptr(flag), stream_ptr()), "ibvh_refit")
     bvh
+end
+
+# ---- ray hit lists against the mesh's triangles (include/ibvh.h, ibvh_rays_resolve_triangles) ------------------------
+"""
+    resolve_triangles(traversal::BVHTraversal, triangles::ROCMatrix{T}, points, directions; all_hits=false)
+        -> (; index, t, uv, candidate_t)
+
+The exact ray-triangle test over the candidate list of `traverse_rays(bvh, points, directions, LVTTraversal())` and the nearest
+hit per ray: `index[i]` the winning triangle (0 = miss), `t[i]` (`Inf` = miss), `uv[:, i]` (0, 0 on a miss); with `all_hits`,
+`candidate_t[k]` is `t` of candidate `k` when it is an exact hit and `Inf` otherwise.  `triangles` is 9 x n (column k = p1 p2 p3
+of the triangle with user index k), of the float type the test runs in; the rays are the ones the traversal was made with.
+The arithmetic, the tie rule (smallest t, then the earlier candidate) and the guards are spelled out in include/ibvh.h.  Exact
+on the list it is given: what the broad phase's rounded slab / sphere test dropped is not recovered.  Only LVT lists of user
+indices: a BFS list is not grouped by ray and a list a closure `narrow` filtered has no counts — the caller must not pass
+them (neither can be told from the buffers).  Not a method of ImplicitBVH: the reference has no such function.
+"""
+pair_index_type(::ROCVector{IndexPair{I}}) where {I} = I
+pair_index_type(::Any) = nothing
+function resolve_triangles(traversal::BVHTraversal, triangles::ROCMatrix{T}, points::AbstractMatrix, directions::AbstractMatrix;
+                           all_hits::Bool=false) where {T}
+    fltcode(T) < 0 && throw(ArgumentError("resolve_triangles: triangles must be Float32 or Float64"))
+    size(triangles, 1) == 9 || throw(ArgumentError("resolve_triangles: triangles must be 9 x n (p1 p2 p3 per column)"))
+    size(points, 1) == size(directions, 1) == 3 || throw(ArgumentError("size(points, 1) == size(directions, 1) == 3 must hold"))
+    size(points, 2) == size(directions, 2) || throw(ArgumentError("size(points, 2) == size(directions, 2) must hold"))
+    contacts, counts = traversal.cache1, traversal.cache2
+    I = pair_index_type(contacts)
+    isnothing(I) && throw(ArgumentError("resolve_triangles: the traversal's contacts must be a ROCVector{IndexPair{I}}"))
+    nr = size(points, 2)
+    (counts isa ROCVector{I} && length(counts) >= nr && idxcode(I) >= 0) ||
+        throw(ArgumentError("resolve_triangles: the traversal's cache2 must hold the scanned counts of these rays (an LVT traversal)"))
+    p = points isa ROCMatrix{T} ? points : ROCMatrix{T}(points)
+    d = directions isa ROCMatrix{T} ? directions : ROCMatrix{T}(directions)
+    index = similar(triangles, I, nr)
+    t = similar(triangles, T, nr)
+    uv = similar(triangles, T, 2, nr)
+    cand = all_hits ? similar(triangles, T, length(contacts)) : nothing
+    nr == 0 && return (; index, t, uv, candidate_t=cand)
+    flag = scratch!(:resolve_flag, 4)
+    fill!(flag, 0x00)
+    check(c_rays_resolve_triangles(fltcode(T), idxcode(I), devptr(triangles), Int64(size(triangles, 2)), devptr(p), devptr(d),
+                                   Int64(nr), devptr(counts), devptr(contacts), Int64(length(contacts)), devptr(index), devptr(t),
+                                   devptr(uv), devptr(cand), devptr(flag), stream_ptr()), "ibvh_rays_resolve_triangles")
+    raised = Array(flag)[1]                                    # one host read
+    raised & 0x01 != 0 && error("resolve_triangles: the contact list is shorter than the traversal's count")
+    raised & 0x02 != 0 && throw(ArgumentError("resolve_triangles: a candidate's index lies outside 1:$(size(triangles, 2))"))
+    (; index, t, uv, candidate_t=isnothing(cand) ? nothing : view(cand, 1:traversal.num_contacts))
 end
 
 """

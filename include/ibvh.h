@@ -41,7 +41,8 @@ extern "C" {
  *   4: the multi-GPU driver (ibvh_comm, ibvh_dist_*)
  *   5: ibvh_dist_cross_* (boundary leaves), ibvh_comm_release, ibvh_build_desc.sort_equalize (was reserved_: same layout)
  *   6: IBVH_PAIR_MIXED_TYPES (pair LVT traversals of two BVHs of different leaf / node types)
- *   7: ibvh_refit */
+ *   7: ibvh_refit; ibvh_rays_resolve_triangles (additive under 7: a new entry point, no struct layout or existing
+ *      argument list moves, so a binding written against the earlier 7 keeps working) */
 #define IBVH_ABI_VERSION 7
 int32_t ibvh_abi_version(void);
 
@@ -380,6 +381,51 @@ ibvh_status ibvh_traverse_rays_lvt_enqueue(const ibvh_bvh *bvh, const void *poin
 /* blocking read of the total a _count / _enqueue call left behind: pass the call's `total_dev`, or its `scratch`
  * when total_dev was NULL */
 ibvh_status ibvh_lvt_total(const void *total_dev_or_scratch, int64_t *total_out, void *stream);
+
+/* ----------------------------------------------------------------------------------- */
+/* ray hit lists against the mesh's triangles                                           */
+/* ----------------------------------------------------------------------------------- */
+/* Resolve the (leaf.index, iray) list of an LVT ray traversal (ibvh_traverse_rays_lvt_{write,enqueue}) against the triangles
+ * the bounding volumes were made from (ibvh_volumes_from_triangles): the exact ray-triangle test per candidate, and per
+ * ray the nearest hit.  No reference counterpart (the reference stops at the candidate list); one launch, NO host
+ * synchronisation.  The leaf and node kinds of the BVH do not matter: only the list is read.
+ *   flt, index_type : IBVH_F32 | IBVH_F64, IBVH_I32 | IBVH_I64 (anything else: IBVH_ERR_UNSUPPORTED)
+ *   triangles  : num_triangles x 9 values of `flt` (p1 p2 p3); user index k is row k - 1
+ *   points, directions, num_rays : as for ibvh_traverse_rays_lvt_*
+ *   counts     : the traversal's inclusive scanned counts (num_rays x I): ray i (1-based) owns candidates
+ *                counts[i-1] .. counts[i] - 1 (0-based rows of `contacts`; counts[0] is taken as 0 for the first ray).
+ *                The total is counts[num_rays - 1], read on the device.
+ *   contacts   : the list, `capacity` rows of IndexPair{I}
+ * Outputs — every pointer optional, at least one non-NULL (else IBVH_ERR_INVALID_ARG, like NULL required pointers and
+ * negative sizes):
+ *   closest_index : num_rays x I, the winning triangle's user index; 0 = miss
+ *   closest_t     : num_rays x flt; +Inf = miss
+ *   closest_uv    : num_rays x 2 x flt, the hit's barycentric (u, v) (weights of p2, p3); 0, 0 on a miss
+ *   cand_t        : capacity x flt, per candidate: t of an exact hit, +Inf otherwise — for callers that want ALL exact hits;
+ *                   rows at and beyond the total are not written
+ * The test, in `flt`, every operation rounded once (nothing fused; correctly rounded divide), so that it can be pinned bit
+ * for bit: a = p1, b = p2, c = p3, ray p + t d:
+ *     e1 = b - a;  e2 = c - a;  pv = d x e2;  det = e1 . pv;  inv = 1 / det;  tv = p - a;
+ *     u = (tv . pv) * inv;  qv = tv x e1;  v = (d . qv) * inv;  t = (e2 . qv) * inv
+ *   with (x x y)[0] = x1*y2 - x2*y1 (cyclic) and x . y = (x0*y0 + x1*y1) + x2*y2.  A candidate is a hit iff
+ *     det != 0 && u >= 0 && v >= 0 && u + v <= 1 && t >= 0      (every comparison false on NaN)
+ *   two-sided (no back-face culling) and forwards only (like the reference's `tmax >= 0`, isintersection.jl:1-65).
+ * Closest hit: the smallest t wins; on equal t (-0 == +0 counts as equal) the candidate EARLIER in the list.  The outputs
+ * carry the winner's bits unchanged.  A segmented minimum over the ray's candidates: no atomics, deterministic.
+ * Guards: when the device total exceeds `capacity` the list was never written (see _enqueue): nothing is written except
+ * bit 0 of `flag`.  A candidate whose index lies outside 1..num_triangles is a miss, nothing outside the array is read,
+ * and bit 1 of `flag` is set.  flag (optional, may be NULL): 4 bytes the GPU can write, the contract of ibvh_refit's:
+ * the library never clears it: zero it before the call.
+ * Exact ON THE LIST IT IS GIVEN: the broad phase is the reference's rounded slab / sphere test (isintersection.jl), so a
+ * grazing triangle hit that the broad phase rounded away is not recovered here, and this test is not watertight along
+ * shared edges (a ray through an edge can miss both triangles or hit both).
+ * Not for BFS lists (not grouped by ray: `counts` does not describe them) nor IBVH_OUTPUT_POSITIONS lists (leaf positions,
+ * not triangle numbers): the library cannot tell either from the buffers, the caller must not pass them. */
+ibvh_status ibvh_rays_resolve_triangles(int32_t flt, int32_t index_type, const void *triangles, int64_t num_triangles,
+                                        const void *points, const void *directions, int64_t num_rays,
+                                        const void *counts, const void *contacts, int64_t capacity,
+                                        void *closest_index, void *closest_t, void *closest_uv, void *cand_t,
+                                        void *flag, void *stream);
 
 /* ----------------------------------------------------------------------------------- */
 /* breadth-first traversal (BFSTraversal): level-synchronous pair queues                 */
