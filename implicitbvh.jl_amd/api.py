@@ -30,7 +30,7 @@ __all__ = [
     "BVHTraversal", "LVTTraversal", "BFSTraversal", "traverse", "traverse_rays", "default_start_level",
     "memory_index", "level_indices", "isvirtual", "bounding_volumes_from_triangles", "generate_spheres",
     "NARROW_MORTON_LT", "NARROW_INDEX_LT", "NARROW_RAY_ORIGIN_OUTSIDE", "LeafBatch", "lvt_work_counters", "refit",
-    "resolve_triangles", "raycast", "RayHits",
+    "resolve_triangles", "raycast", "RayHits", "closest_points", "ClosestPoints",
 ]
 
 NARROW_MORTON_LT = abi.NARROW_MORTON_LT
@@ -1342,6 +1342,86 @@ def raycast(bvh, triangles, points, directions, **kw):
         raise ValueError("raycast: narrow must be None or a NARROW_* constant (a filtered list has no counts)")
     trav = traverse_rays(bvh, points, directions, LVTTraversal(), **kw)
     return resolve_triangles(trav, tris, points, directions, all_hits=all_hits), trav
+
+
+# ---------------------------------------------------------------------------------------------
+# closest point on the mesh for a batch of query points (ibvh_closest_triangles; no reference counterpart)
+# ---------------------------------------------------------------------------------------------
+class ClosestPoints:
+    """Per query point: .index (N,) the closest triangle's user index (0 = none within max_distance), .distance2 (N,) the
+    SQUARED distance (+Inf = none), .point (N, 3) the closest point on that triangle (0, 0, 0 = none)."""
+
+    def __init__(self, index, distance2, point):
+        self.index, self.distance2, self.point = index, distance2, point
+
+
+def _morton_order(p):
+    """Permutation that sorts the (N, 3) points along a 30-bit Morton curve through their own bounding box (NaN and
+    infinite coordinates land in a corner).  Only the ORDER the device walks the batch in: never the result."""
+    torch = _torch()
+    x = torch.nan_to_num(p.to(torch.float64), nan=0.0, posinf=0.0, neginf=0.0)
+    lo, hi = x.amin(dim=0), x.amax(dim=0)
+    cell = ((x - lo) / torch.clamp(hi - lo, min=1e-300) * 1023.0).to(torch.int64).clamp_(0, 1023)
+    for shift, mask in ((16, 0x30000ff), (8, 0x0300f00f), (4, 0x30c30c3), (2, 0x9249249)):  # split3, morton/default.jl:130-143
+        cell = (cell | (cell << shift)) & mask
+    return torch.argsort((cell[:, 0] << 2) | (cell[:, 1] << 1) | cell[:, 2])
+
+
+def closest_points(bvh, triangles, points, max_distance=None, presorted=False):
+    """For every query point the closest triangle of the mesh `bvh` was built over, the closest point on it and the squared
+    distance -> ClosestPoints (include/ibvh.h, ibvh_closest_triangles: the arithmetic, the tie rule — smallest distance, then
+    the smaller index — and why pruning loses nothing are spelled out there).  One launch, exact: bit-equal to a brute
+    force over all triangles.
+
+    bvh: BBox leaves made from `triangles` (bounding_volumes_from_triangles(triangles, BBox(dtype)); a skin margin and
+    refit are fine) under BBox nodes of the same or a wider float type.  triangles: (n, 9) / (n, 3, 3) CUDA tensor of the
+    leaves' dtype, user index k = row k - 1.  points: (3, N) CUDA tensor of that dtype, as for traverse_rays.
+    max_distance: search radius (None = unbounded); it is squared in the triangles' dtype on the host and a triangle
+    qualifies iff its squared distance <= that product.  The device walks the batch in Morton order of the points (lanes of
+    a wave then share nodes) and the outputs are put back in the caller's order; presorted=True walks it as given.
+
+    ValueError: sphere leaves or nodes, nodes narrower than the leaves, a wrong dtype, device or shape, and a leaf whose
+    index lies outside 1..n (flag bit 1; such leaves are skipped)."""
+    torch = _require_gpu()
+    t = bvh.types
+    if t.leaf_kind != abi.BBOX or t.node_kind != abi.BBOX:
+        raise ValueError("closest_points: the BVH must have BBox leaves under BBox nodes (the exact bound needs boxes that contain "
+                         "their triangles' boxes; sphere leaves are not supported)")
+    if t.leaf_float == abi.F64 and t.node_float == abi.F32:
+        raise ValueError("closest_points: Float32 nodes over Float64 leaves do not contain them exactly")
+    tris = _check_triangles(triangles, "closest_points")
+    ft = _torch_float(t.leaf_float)
+    if tris.dtype != ft:
+        raise ValueError(f"closest_points: triangles must be {ft}, the BVH's leaf float type")
+    if not (isinstance(points, torch.Tensor) and points.dim() == 2 and points.shape[0] == 3):
+        raise ValueError("closest_points: size(points, 1) == 3 must hold")
+    if points.dtype != ft or not points.is_cuda:
+        raise ValueError(f"closest_points: points must be a {ft} tensor on the GPU (device='cuda')")
+    n = int(points.shape[1])
+    idt = _torch_index(t.index_type)
+    index = torch.empty(n, dtype=idt, device="cuda")
+    d2 = torch.empty(n, dtype=ft, device="cuda")
+    q = torch.empty((n, 3), dtype=ft, device="cuda")
+    if n == 0:
+        return ClosestPoints(index, d2, q)
+    radius2 = None
+    if max_distance is not None:
+        npdt = np.float32 if t.leaf_float == abi.F32 else np.float64
+        with np.errstate(over="ignore"):
+            m = npdt(max_distance) * npdt(max_distance)
+        radius2 = C.byref((C.c_float if t.leaf_float == abi.F32 else C.c_double)(m))
+    p = points.t().contiguous()  # (N, 3) row-major == (3, N) column-major
+    order = None if presorted else _morton_order(p)
+    if order is not None:
+        p = p[order]
+    flag = torch.zeros(1, dtype=torch.int32, device="cuda")
+    lib.call("ibvh_closest_triangles", C.byref(bvh.struct()), _ptr(tris), tris.shape[0], _ptr(p), n, radius2, _ptr(index), _ptr(d2),
+             _ptr(q), _ptr(flag), _stream())
+    if int(flag.item()) & 2:
+        raise ValueError(f"closest_points: a leaf's index lies outside 1..{tris.shape[0]} (the number of triangles given)")
+    if order is not None:
+        index, d2, q = (torch.empty_like(x).index_copy_(0, order, x) for x in (index, d2, q))
+    return ClosestPoints(index, d2, q)
 
 
 def lvt_work_counters(bvh, bvh2=None, points=None, directions=None):

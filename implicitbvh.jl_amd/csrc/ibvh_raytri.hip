@@ -84,14 +84,7 @@ template <class T> IBVH_D bool ray_triangle(const Tri<T> &tr, const T *p, const 
     return (det != T(0)) & (u >= T(0)) & (v >= T(0)) & (u + v <= T(1)) & (t >= T(0));
 }
 
-// The flag word may be device memory or mapped pinned host memory: a plain read and a plain store of one word, no
-// read-modify-write instruction.  Within one launch only ONE bit is ever raised (bit 0 excludes all other work), so
-// racing raisers store the same word.
-IBVH_D void raise_flag(uint32_t *flag, uint32_t bit) {
-    const uint32_t old = __hip_atomic_load(flag, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);
-    if (!(old & bit)) __hip_atomic_store(flag, old | bit, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);
-}
-
+// (raise_flag: ibvh_common.hpp.  Within one launch only ONE bit is ever raised here: bit 0 excludes all other work.)
 constexpr int kBlock = 256;
 constexpr int kRaysPerBlock = kBlock / kGroup;
 

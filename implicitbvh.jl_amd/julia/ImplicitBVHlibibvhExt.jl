@@ -280,6 +280,12 @@ c_rays_resolve_triangles(flt, idx, triangles, num_triangles, points, directions,
            Ptr{Cvoid}, Ptr{Cvoid}, Ptr{Cvoid}, Ptr{Cvoid}, Ptr{Cvoid}, Ptr{Cvoid}),
           flt, idx, triangles, num_triangles, points, directions, num_rays, counts, contacts, capacity,
           closest_index, closest_t, closest_uv, cand_t, flag, stream)
+c_closest_triangles(bvh, triangles, num_triangles, points, num_points, max_distance2, closest_index, closest_d2, closest_point,
+                    flag, stream) =
+    ccall((:ibvh_closest_triangles, libibvh), Cint,
+          (Ref{IbvhBvh}, Ptr{Cvoid}, Int64, Ptr{Cvoid}, Int64, Ptr{Cvoid}, Ptr{Cvoid}, Ptr{Cvoid}, Ptr{Cvoid}, Ptr{Cvoid}, Ptr{Cvoid}),
+          bvh, triangles, num_triangles, points, num_points, max_distance2, closest_index, closest_d2, closest_point,
+          flag, stream)
 c_lvt_scratch_bytes(types, n_items, cache_slots, out) =
     ccall((:ibvh_lvt_scratch_bytes, libibvh), Cint,
           (Ref{IbvhTypes}, Int64, Int32, Ref{Csize_t}),
@@ -611,6 +617,59 @@ function resolve_triangles(traversal::BVHTraversal, triangles::ROCMatrix{T}, poi
     raised & 0x01 != 0 && error("resolve_triangles: the contact list is shorter than the traversal's count")
     raised & 0x02 != 0 && throw(ArgumentError("resolve_triangles: a candidate's index lies outside 1:$(size(triangles, 2))"))
     (; index, t, uv, candidate_t=isnothing(cand) ? nothing : view(cand, 1:traversal.num_contacts))
+end
+
+# ---- closest point on the mesh for a batch of query points (include/ibvh.h, ibvh_closest_triangles) ------------------
+function point_morton_order(points::ROCMatrix{T}) where {T}
+    h = Array(points)                                          # the order only: never the result
+    clean(x) = isfinite(x) ? Float64(x) : 0.0
+    lo = [minimum(clean, view(h, k, :)) for k in 1:3]
+    ext = [max(maximum(clean, view(h, k, :)) - lo[k], floatmin(Float64)) for k in 1:3]
+    split3(v::UInt32) = (v = (v | v << 16) & 0x030000ff; v = (v | v << 8) & 0x0300f00f; v = (v | v << 4) & 0x030c30c3; (v | v << 2) & 0x09249249)
+    cell(k, i) = split3(UInt32(clamp(floor(Int64, (clean(h[k, i]) - lo[k]) / ext[k] * 1023), 0, 1023)))
+    sortperm([(cell(1, i) << 2) | (cell(2, i) << 1) | cell(3, i) for i in axes(h, 2)])
+end
+"""
+    closest_points(bvh::BVH, triangles::ROCMatrix{T}, points::ROCMatrix{T}; max_distance=nothing, presorted=false)
+        -> (; index, distance2, point)
+
+For every query point (column of the 3 x N `points`) the closest triangle of the mesh `bvh` was built over: `index[i]` its user
+index (0 = none within `max_distance`), `distance2[i]` the squared distance (`Inf` = none), `point[:, i]` the closest point on
+it (zeros = none).  `triangles` is 9 x n (column k = p1 p2 p3 of the triangle with user index k).  The result is the
+lexicographic minimum of (squared distance, index) over ALL triangles — bit-equal to a brute force; the arithmetic, the tie
+rule and why pruning loses nothing are spelled out in include/ibvh.h.  The BVH must have `BBox{T}` leaves made from the
+triangles (a skin margin and `refit!` are fine) under `BBox` nodes of `T` or wider; anything else raises ArgumentError.
+`max_distance` is squared in `T` on the host.  The device walks the batch along a Morton curve through the points (lanes of a
+wave then share nodes) and the outputs come back in the caller's order; `presorted=true` walks it as given.  Not a method of
+ImplicitBVH: the reference has no such query.
+"""
+function closest_points(bvh::RocBVH{I}, triangles::ROCMatrix{T}, points::ROCMatrix{T}; max_distance=nothing,
+                        presorted::Bool=false) where {I, T}
+    d = bvh_desc(bvh)
+    isnothing(d) && throw(ArgumentError("closest_points: no libibvh instantiation for this BVH's types"))
+    leaf_volume_type(bvh.leaves) === BBox{T} && eltype(bvh.nodes) <: BBox && sizeof(eltype(bvh.nodes)) >= sizeof(BBox{T}) ||
+        throw(ArgumentError("closest_points: the BVH must have BBox{$T} leaves under BBox nodes of $T or wider"))
+    size(triangles, 1) == 9 || throw(ArgumentError("closest_points: triangles must be 9 x n (p1 p2 p3 per column)"))
+    size(points, 1) == 3 || throw(ArgumentError("size(points, 1) == 3 must hold"))
+    n = size(points, 2)
+    index = similar(points, I, n)
+    distance2 = similar(points, T, n)
+    point = similar(points, T, 3, n)
+    n == 0 && return (; index, distance2, point)
+    radius2 = isnothing(max_distance) ? C_NULL : Ref(T(max_distance) * T(max_distance))
+    order = presorted ? nothing : point_morton_order(points)
+    p = isnothing(order) ? points : points[:, ROCVector{Int64}(order)]
+    flag = scratch!(:closest_flag, 4)
+    fill!(flag, 0x00)
+    GC.@preserve radius2 begin
+        r2 = radius2 === C_NULL ? Ptr{Cvoid}(C_NULL) : Ptr{Cvoid}(Base.unsafe_convert(Ptr{T}, radius2))
+        check(c_closest_triangles(d, devptr(triangles), Int64(size(triangles, 2)), devptr(p), Int64(n), r2, devptr(index),
+                                  devptr(distance2), devptr(point), devptr(flag), stream_ptr()), "ibvh_closest_triangles")
+    end
+    Array(flag)[1] & 0x02 != 0 && throw(ArgumentError("closest_points: a leaf's index lies outside 1:$(size(triangles, 2))"))
+    isnothing(order) && return (; index, distance2, point)
+    inv = ROCVector{Int64}(invperm(order))
+    (; index=index[inv], distance2=distance2[inv], point=point[:, inv])
 end
 
 """

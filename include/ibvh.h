@@ -42,7 +42,8 @@ extern "C" {
  *   5: ibvh_dist_cross_* (boundary leaves), ibvh_comm_release, ibvh_build_desc.sort_equalize (was reserved_: same layout)
  *   6: IBVH_PAIR_MIXED_TYPES (pair LVT traversals of two BVHs of different leaf / node types)
  *   7: ibvh_refit; ibvh_rays_resolve_triangles (additive under 7: a new entry point, no struct layout or existing
- *      argument list moves, so a binding written against the earlier 7 keeps working) */
+ *      argument list moves, so a binding written against the earlier 7 keeps working); ibvh_closest_triangles (additive
+ *      under 7 in the same way) */
 #define IBVH_ABI_VERSION 7
 int32_t ibvh_abi_version(void);
 
@@ -426,6 +427,68 @@ ibvh_status ibvh_rays_resolve_triangles(int32_t flt, int32_t index_type, const v
                                         const void *counts, const void *contacts, int64_t capacity,
                                         void *closest_index, void *closest_t, void *closest_uv, void *cand_t,
                                         void *flag, void *stream);
+
+/* ----------------------------------------------------------------------------------- */
+/* closest point on the mesh for a batch of query points                                */
+/* ----------------------------------------------------------------------------------- */
+/* For every query point: the closest triangle of the mesh the BVH was built over (ibvh_volumes_from_triangles with
+ * IBVH_BBOX), the closest point on it and the squared distance.  No reference counterpart (every traversal of the reference
+ * is a fixed-volume overlap test); ONE launch, NO host synchronisation, no atomics, no scratch buffer.
+ *   triangles  : num_triangles x 9 values (p1 p2 p3) of bvh->types.leaf_float, `flt` below; user index k is row k - 1
+ *   points     : num_points x 3 row-major values of `flt`, processed in the order given (neighbours in memory that are
+ *                neighbours in space walk the same nodes: sort a scattered batch along a Morton curve first)
+ *   max_distance2 : HOST pointer to one value of `flt`, the SQUARED search radius; NULL = +Inf (unbounded)
+ * Outputs — every pointer optional, at least one non-NULL:
+ *   closest_index : num_points x I, the winning triangle's user index; 0 = no triangle within the radius
+ *   closest_d2    : num_points x flt; +Inf = none
+ *   closest_point : num_points x 3 x flt; 0, 0, 0 = none
+ * All arguments are validated before any launch: NULL required pointers, negative sizes, no output at all, a tree shape
+ * that is not an ImplicitTree's: IBVH_ERR_INVALID_ARG.  num_points == 0: IBVH_OK, nothing is touched.
+ * The result is defined independently of how it is found.  (d2_k, q_k) being the evaluation of triangle k below, the answer
+ * for p is the LEXICOGRAPHIC MINIMUM of (d2_k, k) over all k with d2_k <= max_distance2: the smallest distance, and among
+ * equal distances the SMALLER INDEX.  Every comparison is false on NaN: a triangle whose d2 is NaN never wins, a NaN query
+ * point has no answer.  The outputs carry the winner's d2 and q bits unchanged.
+ * The evaluation, in `flt`, every operation rounded once (nothing fused; correctly rounded divide), so that it can be
+ * pinned bit for bit: x . y = (x0*y0 + x1*y1) + x2*y2, a = p1, b = p2, c = p3, and (Ericson's region walk) with
+ *     ab = b - a;  ac = c - a;  ap = p - a;  d1 = ab . ap;  d2 = ac . ap
+ *     bp = p - b;  d3 = ab . bp;  d4 = ac . bp;  cp = p - c;  d5 = ab . cp;  d6 = ac . cp
+ *     vc = d1*d4 - d3*d2;  vb = d5*d2 - d1*d6;  va = d3*d6 - d5*d4
+ *   the FIRST matching case decides:
+ *     0: d1 <= 0 && d2 <= 0                        q = a
+ *     1: d3 >= 0 && d4 <= d3                       q = b
+ *     2: vc <= 0 && d1 >= 0 && d3 <= 0             v = d1 / (d1 - d3);  q = a + v*ab
+ *     3: d6 >= 0 && d5 <= d6                       q = c
+ *     4: vb <= 0 && d2 >= 0 && d6 <= 0             w = d2 / (d2 - d6);  q = a + w*ac
+ *     5: va <= 0 && (d4-d3) >= 0 && (d5-d6) >= 0   w = (d4-d3) / ((d4-d3) + (d5-d6));  q = b + w*(c - b)
+ *     6: otherwise                                 den = 1 / ((va + vb) + vc);  v = vb*den;  w = vc*den;  q = (a + v*ab) + w*ac
+ *   then, per component, q is clamped into the triangle's exact box, lo = min3(a, b, c), up = max3(a, b, c) (the
+ *   `x < y ? x : y` ternaries of BBox{T}(p1, p2, p3)):   q = q < lo ? lo : (q > up ? up : q)   (NaN stays NaN)
+ *   and   e = p - q;  d2 = (e0*e0 + e1*e1) + e2*e2.
+ * Why the clamp: it makes pruning lossless WITHOUT an epsilon.  For a box B that contains the triangle's box,
+ *     c = clamp(p, B.lo, B.up) per component;  f = p - c;  lb(B) = (f0*f0 + f1*f1) + f2*f2
+ *   is the same operation order as d2; round-to-nearest subtraction, squaring and addition are monotone and q lies inside
+ *   B per component, so the COMPUTED lb(B) <= the COMPUTED d2 of every triangle under B.  The walk skips a node or a leaf
+ *   iff lb > best d2 so far (which starts at max_distance2) — strictly: lb == best may hide an equal d2 of smaller index.
+ *   Traversal order and work mapping therefore cannot change the result.  (On ordinary meshes the clamp changes no q: it
+ *   is a guard for the proof.)
+ * Accepted BVHs — the bound needs boxes that contain their triangles' boxes exactly:
+ *   leaf_kind == node_kind == IBVH_BBOX, triangles and points of leaf_float, node_float the same as or wider than
+ *   leaf_float (box merges are min / max plus a widening conversion: exact); any index and Morton type.  Anything else —
+ *   sphere leaves, sphere nodes, F64 leaves under F32 nodes — is IBVH_ERR_UNSUPPORTED, never an answer.
+ *   Exact PROVIDED every leaf's box contains its triangle's box: a skin margin on the leaves is allowed, and so is a BVH
+ *   after ibvh_refit.  Levels above bvh->built_level are not read.
+ * NaN: a triangle with a NaN vertex has a NaN d2 and never wins, and a NaN query point (or radius) has no answer.  But, as
+ *   for the traversals above, a NaN leaf box can make merge.jl's `a < b ? a : b` produce a node box that does NOT contain
+ *   the NaN-free leaves below it (min(min(1, NaN), 5) = 5): on a mesh with NaN vertices the other triangles' answers are
+ *   only guaranteed in trees of at most two leaves.
+ * Guards: the triangle is read through the leaf record's .index, not its position.  A leaf whose index lies outside
+ * 1..num_triangles is skipped, nothing outside the array is read, and bit 1 of `flag` is set — the flag contract of
+ * ibvh_rays_resolve_triangles: optional, 4 bytes the GPU can write, a plain load and store, never cleared by the library
+ * (zero it before the call). */
+ibvh_status ibvh_closest_triangles(const ibvh_bvh *bvh, const void *triangles, int64_t num_triangles,
+                                   const void *points, int64_t num_points, const void *max_distance2,
+                                   void *closest_index, void *closest_d2, void *closest_point,
+                                   void *flag, void *stream);
 
 /* ----------------------------------------------------------------------------------- */
 /* breadth-first traversal (BFSTraversal): level-synchronous pair queues                 */
