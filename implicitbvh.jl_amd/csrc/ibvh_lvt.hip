@@ -104,10 +104,10 @@ template <int MODE> int run(const Walk &w, const Call &c) {
                 a.gate = nullptr;
                 a.blk_rows = (uint32_t *)at(plan.rows);
                 a.q_index_dense = (I *)at(plan.index);
-                // (the scan's tile sums, behind the header of the scratch: scan_counts)
+                // (the scan's tile aggregates, behind the header of the scratch: scan_counts)
                 const bool may_fuse = !write && !work && MODE != MODE_RAYS;
-                a.scan_agg = may_fuse ? (unsigned long long *)at(SCRATCH_HEADER_BYTES) : nullptr;
-                a.scan_nparts = (int32_t)ceil_div(w.n_items, (int64_t)SCAN_TILE);
+                a.scan_agg = may_fuse ? (unsigned long long *)at(SCAN_AGG_OFFSET) : nullptr;
+                a.scan_nparts = (int32_t)scan_tiles(w.n_items);
                 bool agg_zeroed = false;
                 a.blk_shift = 0;
                 const ibvh_bvh *qside = w.drv ? w.drv : w.walk;
@@ -130,8 +130,15 @@ template <int MODE> int run(const Walk &w, const Call &c) {
                 };
                 if (int e = pass(write, &agg_zeroed)) return e;
                 if (write || work) return (int)IBVH_OK;
-                if (int e = scan_counts<I>((I *)c.counts, w.n_items, c.total_out, c.scratch, st, (int64_t *)c.total_dev,
-                                           (int64_t *)c.total_host, nullptr, agg_zeroed)) return e;
+                ScanCall<I> scan;
+                scan.counts = (I *)c.counts;
+                scan.n = w.n_items;
+                scan.scratch = c.scratch;
+                scan.total_dev = (int64_t *)c.total_dev;
+                scan.total_host = (int64_t *)c.total_host;
+                scan.total_out = c.total_out;
+                scan.aggregates_zeroed = agg_zeroed;
+                if (int e = scan_counts(scan, st)) return e;
                 if (enqueue && c.capacity > 0) {
                     a.guard_total = c.total_dev ? (const int64_t *)c.total_dev : (const int64_t *)c.scratch; // the total contacts
                     a.guard_capacity = sizeof(I) == 4 && c.capacity > (int64_t)INT32_MAX ? (int64_t)INT32_MAX : c.capacity;

@@ -1,8 +1,9 @@
 // ibvh_lvt.hpp — what the translation units of the leaf-vs-tree traversal share (LVTTraversal on gfx950): the argument
-// block, the per-lane query state, the exact wave-uniform walk (walker 1, also the fall-back of walker 2), the scan of
-// the per-item counts, the geometry of the binned ray path, and the launchers each unit exports.
+// block, the per-lane query state, the exact wave-uniform walk (walker 1, also the fall-back of walker 2), the call of
+// the per-item counts' scan, the geometry of the binned ray path, and the launchers each unit exports.
 //
 //   ibvh_lvt.hip          entry points (extern "C"), type dispatch, the two-pass protocol (count -> scan -> write)
+//   ibvh_lvt_scan.hip     the scan of the per-item counts (scan_counts: two launches, or one behind a producer that zeroed its aggregates)
 //   ibvh_lvt_queue_*.hip  walker 2, lvt_queue_kernel (BBox nodes: frontier descent + candidate-pair queue), one unit
 //                         per mode (self / pair) — ibvh_lvt_queue.inc holds the kernel
 //   ibvh_lvt_mixed_*.hip  pair walks of two BVHs of different types (IBVH_PAIR_MIXED_TYPES): walkers 1 and 2 with the driving
@@ -443,349 +444,19 @@ IBVH_HD size_t rays_subtree_lds(int depth, size_t node_bytes, size_t leaf_bytes,
 }
 
 
-// ---- inclusive scan of the per-item counts (AK.accumulate!, traverse_single.jl:57) ---------------
-constexpr int SCAN_TPB = 256, SCAN_IPT = SCAN_TILE / SCAN_TPB; // (SCAN_TILE: ibvh_lvt_scratch.hpp, one tile sum each)
-
-IBVH_D int64_t block_sum(int64_t v, int64_t *s_w) {
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o, 64);
-    if ((threadIdx.x & 63) == 0) s_w[threadIdx.x >> 6] = v;
-    __syncthreads();
-    int64_t t = 0;
-#pragma unroll
-    for (int i = 0; i < SCAN_TPB / 64; ++i) t += s_w[i];
-    __syncthreads();
-    return t;
-}
-
-// (limit != nullptr: the array's length is min(n, *limit), known only on the device)
-template <class I> __global__ __launch_bounds__(SCAN_TPB) void scan_reduce_kernel(const I *c, int64_t n, int64_t *partials, const int32_t *limit) {
-    __shared__ int64_t s_w[SCAN_TPB / 64];
-    if (limit != nullptr) n = (int64_t)*limit < n ? (int64_t)*limit : n;
-    int64_t base = (int64_t)blockIdx.x * SCAN_TILE, v = 0;
-#pragma unroll
-    for (int j = 0; j < SCAN_IPT; ++j) {
-        int64_t i = base + j * SCAN_TPB + threadIdx.x;
-        if (i < n) v += (int64_t)c[i];
-    }
-    int64_t t = block_sum(v, s_w);
-    if (threadIdx.x == 0) partials[blockIdx.x] = t;
-}
-// one workgroup: exclusive scan of the tile sums in place; total -> totals[0]
-// Every workgroup derives its own tile offset from the raw tile sums (a redundant reduction of <= a few thousand
-// values) instead of waiting for a single-workgroup scan launch in between; the last tile also publishes the total.
-template <class I>
-__global__ __launch_bounds__(SCAN_TPB) void scan_apply_kernel(I *c, int64_t n, const int64_t *partials, int64_t *totals,
-                                                              int64_t *total_host, const int32_t *limit) {
-    __shared__ int64_t s_w[SCAN_TPB / 64], s_p[SCAN_TPB / 64];
-    if (limit != nullptr) n = (int64_t)*limit < n ? (int64_t)*limit : n;
-    int64_t before = 0;
-    for (int64_t j = threadIdx.x; j < (int64_t)blockIdx.x; j += SCAN_TPB) before += partials[j];
-    const int64_t tile_offset = block_sum(before, s_p);
-    // The grand total is known to the last workgroup before it scans anything (the tile sums are all there): publish it
-    // FIRST — the host may be polling its pinned copy (total_host), and every microsecond it learns the count earlier is
-    // a microsecond more of the next step's launch work hidden behind this step's writing pass.
-    if (blockIdx.x == gridDim.x - 1 && threadIdx.x == 0) {
-        const int64_t total = tile_offset + partials[blockIdx.x];
-        totals[0] = total;
-        if (total_host) __hip_atomic_store(total_host, total, __ATOMIC_RELEASE, __HIP_MEMORY_SCOPE_SYSTEM);
-    }
-    // thread owns SCAN_IPT consecutive items so the in-thread running sum is in memory order
-    int64_t base = (int64_t)blockIdx.x * SCAN_TILE + (int64_t)threadIdx.x * SCAN_IPT;
-    int64_t v[SCAN_IPT], sum = 0;
-    // a thread's SCAN_IPT items are 64 (or 128) contiguous bytes: 16-byte loads and stores when the array allows it
-    // (one 4-byte access per item makes every load instruction of a wave touch 64 different lines)
-    constexpr int NV = SCAN_IPT * (int)sizeof(I) / 16;
-    const bool vec = base + SCAN_IPT <= n && ((uintptr_t)c & 15) == 0;
-    if (vec) {
-        I raw[SCAN_IPT];
-        const uint4 *src = (const uint4 *)(c + base);
-#pragma unroll
-        for (int k = 0; k < NV; ++k) ((uint4 *)raw)[k] = src[k];
-#pragma unroll
-        for (int j = 0; j < SCAN_IPT; ++j) {
-            v[j] = (int64_t)raw[j];
-            sum += v[j];
-        }
-    } else {
-#pragma unroll
-        for (int j = 0; j < SCAN_IPT; ++j) {
-            int64_t i = base + j;
-            v[j] = i < n ? (int64_t)c[i] : 0;
-            sum += v[j];
-        }
-    }
-    int64_t inc = sum;
-    const int lane = threadIdx.x & 63, w = threadIdx.x >> 6;
-#pragma unroll
-    for (int o = 1; o < 64; o <<= 1) {
-        int64_t t = __shfl_up(inc, o, 64);
-        if (lane >= o) inc += t;
-    }
-    if (lane == 63) s_w[w] = inc;
-    __syncthreads();
-    int64_t wb = 0;
-#pragma unroll
-    for (int k = 0; k < SCAN_TPB / 64; ++k)
-        if (k < w) wb += s_w[k];
-    int64_t run = tile_offset + wb + inc - sum;
-    if (vec) {
-        I raw[SCAN_IPT];
-#pragma unroll
-        for (int j = 0; j < SCAN_IPT; ++j) {
-            run += v[j];
-            raw[j] = (I)run;
-        }
-        uint4 *dst = (uint4 *)(c + base);
-#pragma unroll
-        for (int k = 0; k < NV; ++k) dst[k] = ((const uint4 *)raw)[k];
-    } else {
-#pragma unroll
-        for (int j = 0; j < SCAN_IPT; ++j) {
-            int64_t i = base + j;
-            run += v[j];
-            if (i < n) c[i] = (I)run;
-        }
-    }
-}
-
-// The same scan in ONE kernel (round 5), for counts whose producer zeroed the tile aggregates (walker 2's counting pass): every
-// workgroup sums its tile, PUBLISHES the sum (bit 63 = "there"; one 64-bit agent-scope atomic store: value and flag travel together,
-// no fence — an agent-scope fence on this part writes back and invalidates an XCD's whole L2), adds up the aggregates of the tiles
-// before it (polling those that are not there yet) and scans its tile.  One launch and one dependent round trip less than reduce +
-// apply: they are launch- and latency-bound (245 workgroups at 1e6 leaves).
-// Whom a workgroup may wait for: only workgroups that are RUNNING OR DONE, whatever order the hardware starts them
-// in — the grid never exceeds what the device holds at once (scan_counts: resident_scan_workgroups()).  Larger inputs go through
-// scan_fused_grouped_kernel, whose workgroups own several consecutive tiles each: one aggregate and one look-back per group.
-// (Round 6 first took the tile from an atomic ticket instead: 2,442 returning atomics on one word serialise at ~11 ns each —
-// the 1e7-item scan 25 -> 56 us.)
-template <class I>
-__global__ __launch_bounds__(SCAN_TPB) void scan_fused_kernel(I *c, int64_t n, unsigned long long *agg, int64_t *totals, int64_t *total_host,
-                                                              const int32_t *limit) {
-    __shared__ int64_t s_w[SCAN_TPB / 64], s_p[SCAN_TPB / 64];
-    constexpr unsigned long long THERE = 1ull << 63;
-    // (limit: the array's length is min(n, *limit), known only on the device — tiles beyond it hold zeros and store nothing)
-    if (limit != nullptr) n = (int64_t)*limit < n ? (int64_t)*limit : n;
-    const uint32_t tile = blockIdx.x;
-    // thread owns SCAN_IPT consecutive items so the in-thread running sum is in memory order
-    const int64_t base = (int64_t)tile * SCAN_TILE + (int64_t)threadIdx.x * SCAN_IPT;
-    int64_t v[SCAN_IPT], sum = 0;
-    constexpr int NV = SCAN_IPT * (int)sizeof(I) / 16;
-    const bool vec = base + SCAN_IPT <= n && ((uintptr_t)c & 15) == 0;
-    if (vec) {
-        I raw[SCAN_IPT];
-        const uint4 *src = (const uint4 *)(c + base);
-#pragma unroll
-        for (int k = 0; k < NV; ++k) ((uint4 *)raw)[k] = src[k];
-#pragma unroll
-        for (int j = 0; j < SCAN_IPT; ++j) {
-            v[j] = (int64_t)raw[j];
-            sum += v[j];
-        }
-    } else {
-#pragma unroll
-        for (int j = 0; j < SCAN_IPT; ++j) {
-            const int64_t i = base + j;
-            v[j] = i < n ? (int64_t)c[i] : 0;
-            sum += v[j];
-        }
-    }
-    int64_t inc = sum;
-    const int lane = threadIdx.x & 63, w = threadIdx.x >> 6;
-#pragma unroll
-    for (int o = 1; o < 64; o <<= 1) {
-        const int64_t t = __shfl_up(inc, o, 64);
-        if (lane >= o) inc += t;
-    }
-    if (lane == 63) s_w[w] = inc;
-    __syncthreads();
-    int64_t wb = 0, tile_total = 0;
-#pragma unroll
-    for (int k = 0; k < SCAN_TPB / 64; ++k) {
-        if (k < w) wb += s_w[k];
-        tile_total += s_w[k];
-    }
-    if (threadIdx.x == 0) __hip_atomic_store(&agg[tile], THERE | (unsigned long long)tile_total, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-    int64_t before = 0;
-    for (int64_t j = threadIdx.x; j < (int64_t)tile; j += SCAN_TPB) {
-        unsigned long long a = __hip_atomic_load(&agg[j], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-        while (!(a & THERE)) {
-            __builtin_amdgcn_s_sleep(1);
-            a = __hip_atomic_load(&agg[j], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-        }
-        before += (int64_t)(a & ~THERE);
-    }
-    const int64_t tile_offset = block_sum(before, s_p);
-    if (tile == gridDim.x - 1 && threadIdx.x == 0) {
-        const int64_t total = tile_offset + tile_total;
-        totals[0] = total;
-        if (total_host) __hip_atomic_store(total_host, total, __ATOMIC_RELEASE, __HIP_MEMORY_SCOPE_SYSTEM);
-    }
-    int64_t run = tile_offset + wb + inc - sum;
-    if (vec) {
-        I raw[SCAN_IPT];
-#pragma unroll
-        for (int j = 0; j < SCAN_IPT; ++j) {
-            run += v[j];
-            raw[j] = (I)run;
-        }
-        uint4 *dst = (uint4 *)(c + base);
-#pragma unroll
-        for (int k = 0; k < NV; ++k) dst[k] = ((const uint4 *)raw)[k];
-    } else {
-#pragma unroll
-        for (int j = 0; j < SCAN_IPT; ++j) {
-            const int64_t i = base + j;
-            run += v[j];
-            if (i < n) c[i] = (I)run;
-        }
-    }
-}
-
-// The same scan for grids that would not be resident: a workgroup owns `tiles_per_group` CONSECUTIVE tiles.  Phase 1 sums them
-// (one pass over its items), publishes ONE aggregate and looks back over the groups before it; phase 2 reads the items again
-// (L2-hot) and scans tile by tile with a running base.  Grid = ceil(tiles / tiles_per_group) <= what the device holds at once.
-template <class I>
-__global__ __launch_bounds__(SCAN_TPB) void scan_fused_grouped_kernel(I *c, int64_t n, unsigned long long *agg, int64_t *totals, int64_t *total_host,
-                                                                      int tiles_per_group, const int32_t *limit) {
-    __shared__ int64_t s_w[SCAN_TPB / 64], s_p[SCAN_TPB / 64];
-    constexpr unsigned long long THERE = 1ull << 63;
-    const int64_t nparts = (n + SCAN_TILE - 1) / SCAN_TILE; // (of the launch: the grid was sized for it)
-    if (limit != nullptr) n = (int64_t)*limit < n ? (int64_t)*limit : n;
-    const int64_t t0 = (int64_t)blockIdx.x * tiles_per_group, t1 = t0 + tiles_per_group < nparts ? t0 + tiles_per_group : nparts;
-    const int lane = threadIdx.x & 63, w = threadIdx.x >> 6;
-    auto load16 = [&](int64_t base, int64_t (&v)[SCAN_IPT]) { // a thread's SCAN_IPT consecutive items of a tile
-        constexpr int NV = SCAN_IPT * (int)sizeof(I) / 16;
-        if (base + SCAN_IPT <= n && ((uintptr_t)c & 15) == 0) {
-            I raw[SCAN_IPT];
-            const uint4 *src = (const uint4 *)(c + base);
-#pragma unroll
-            for (int k = 0; k < NV; ++k) ((uint4 *)raw)[k] = src[k];
-#pragma unroll
-            for (int j = 0; j < SCAN_IPT; ++j) v[j] = (int64_t)raw[j];
-        } else {
-#pragma unroll
-            for (int j = 0; j < SCAN_IPT; ++j) v[j] = base + j < n ? (int64_t)c[base + j] : 0;
-        }
-    };
-    int64_t sum = 0;
-    for (int64_t t = t0; t < t1; ++t) {
-        int64_t v[SCAN_IPT];
-        load16(t * SCAN_TILE + (int64_t)threadIdx.x * SCAN_IPT, v);
-#pragma unroll
-        for (int j = 0; j < SCAN_IPT; ++j) sum += v[j];
-    }
-    const int64_t group_total = block_sum(sum, s_p);
-    if (threadIdx.x == 0) __hip_atomic_store(&agg[blockIdx.x], THERE | (unsigned long long)group_total, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-    int64_t before = 0;
-    for (int64_t j = threadIdx.x; j < (int64_t)blockIdx.x; j += SCAN_TPB) {
-        unsigned long long a = __hip_atomic_load(&agg[j], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-        while (!(a & THERE)) {
-            __builtin_amdgcn_s_sleep(1);
-            a = __hip_atomic_load(&agg[j], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-        }
-        before += (int64_t)(a & ~THERE);
-    }
-    __syncthreads(); // (s_p is reused)
-    int64_t run_base = block_sum(before, s_p);
-    if (blockIdx.x == gridDim.x - 1 && threadIdx.x == 0) {
-        const int64_t total = run_base + group_total;
-        totals[0] = total;
-        if (total_host) __hip_atomic_store(total_host, total, __ATOMIC_RELEASE, __HIP_MEMORY_SCOPE_SYSTEM);
-    }
-    for (int64_t t = t0; t < t1; ++t) {
-        const int64_t base = t * SCAN_TILE + (int64_t)threadIdx.x * SCAN_IPT;
-        int64_t v[SCAN_IPT], mine = 0;
-        load16(base, v);
-#pragma unroll
-        for (int j = 0; j < SCAN_IPT; ++j) mine += v[j];
-        int64_t inc = mine;
-#pragma unroll
-        for (int o = 1; o < 64; o <<= 1) {
-            const int64_t u = __shfl_up(inc, o, 64);
-            if (lane >= o) inc += u;
-        }
-        __syncthreads(); // (s_w is reused)
-        if (lane == 63) s_w[w] = inc;
-        __syncthreads();
-        int64_t wb = 0, tile_total = 0;
-#pragma unroll
-        for (int k = 0; k < SCAN_TPB / 64; ++k) {
-            if (k < w) wb += s_w[k];
-            tile_total += s_w[k];
-        }
-        int64_t run = run_base + wb + inc - mine;
-        const bool vec = base + SCAN_IPT <= n && ((uintptr_t)c & 15) == 0;
-        if (vec) {
-            constexpr int NV = SCAN_IPT * (int)sizeof(I) / 16;
-            I raw[SCAN_IPT];
-#pragma unroll
-            for (int j = 0; j < SCAN_IPT; ++j) {
-                run += v[j];
-                raw[j] = (I)run;
-            }
-            uint4 *dst = (uint4 *)(c + base);
-#pragma unroll
-            for (int k = 0; k < NV; ++k) dst[k] = ((const uint4 *)raw)[k];
-        } else {
-#pragma unroll
-            for (int j = 0; j < SCAN_IPT; ++j) {
-                run += v[j];
-                if (base + j < n) c[base + j] = (I)run;
-            }
-        }
-        run_base += tile_total;
-    }
-}
-// workgroups of SCAN_TPB threads the current device holds at once, halved (the margin for anything else that is running)
-template <class I> inline int64_t resident_scan_workgroups() {
-    static thread_local int memo_dev = -1;
-    static thread_local int64_t memo = 0;
-    int dev = 0;
-    if (hipGetDevice(&dev) != hipSuccess) return 256;
-    if (dev != memo_dev) {
-        int ncu = 0, per_cu = 0;
-        if (hipDeviceGetAttribute(&ncu, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess || ncu <= 0) ncu = 64;
-        if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, (const void *)scan_fused_grouped_kernel<I>, SCAN_TPB, 0) != hipSuccess || per_cu <= 0) per_cu = 2;
-        memo = (int64_t)ncu * per_cu / 2;
-        if (memo < 16) memo = 16;
-        memo_dev = dev;
-    }
-    return memo;
-}
-
-// inclusive scan in place + (total_out != nullptr) blocking read of the total (the reference's @allowscalar, :60)
-// scratch: scan_scratch_bytes(n) — the header and the tile sums of ibvh_lvt_scratch.hpp
-template <class I>
-int scan_counts(I *counts, int64_t n, int64_t *total_out, void *scratch, hipStream_t st, int64_t *total_dev = nullptr,
-                int64_t *total_host = nullptr, const int32_t *limit = nullptr, bool aggregates_zeroed = false) {
-    int64_t nparts = ceil_div(n, SCAN_TILE);
-    int64_t *totals = total_dev ? total_dev : (int64_t *)scratch; // where the device-side total goes (header word 0)
-    int64_t *partials = (int64_t *)((char *)scratch + SCRATCH_HEADER_BYTES);
-    if (aggregates_zeroed && g_tuning.lvt_scan_fused != 0) {
-        int64_t room = resident_scan_workgroups<I>();
-        if (g_tuning.lvt_scan_fused > 1 && g_tuning.lvt_scan_fused < room) room = g_tuning.lvt_scan_fused; // (development knob: a smaller grid)
-        if (nparts > room) {
-            const int64_t per = ceil_div(nparts, room);
-            IBVH_LAUNCH((scan_fused_grouped_kernel<I>), dim3((unsigned)ceil_div(nparts, per)), dim3(SCAN_TPB), 0, st, counts, n, (unsigned long long *)partials, totals,
-                        total_host, (int)per, limit);
-        } else {
-            IBVH_LAUNCH((scan_fused_kernel<I>), dim3((unsigned)nparts), dim3(SCAN_TPB), 0, st, counts, n, (unsigned long long *)partials, totals, total_host,
-                        limit);
-        }
-    } else {
-        IBVH_LAUNCH((scan_reduce_kernel<I>), dim3((unsigned)nparts), dim3(SCAN_TPB), 0, st, counts, n, partials, limit);
-        IBVH_LAUNCH((scan_apply_kernel<I>), dim3((unsigned)nparts), dim3(SCAN_TPB), 0, st, counts, n, partials, totals, total_host, limit);
-    }
-    IBVH_LAUNCH_CHECK();
-    if (!total_out) return IBVH_OK; // *_enqueue: the total stays in the scratch header, nobody waits
-    int64_t total = 0;
-    IBVH_HIP_CHECK(hipMemcpyAsync(&total, totals, sizeof(int64_t), hipMemcpyDeviceToHost, st));
-    IBVH_HIP_CHECK(hipStreamSynchronize(st));
-    *total_out = total;
-    if (sizeof(I) == 4 && total > (int64_t)INT32_MAX) return IBVH_ERR_OVERFLOW;
-    return IBVH_OK;
-}
+// ---- inclusive scan of the per-item counts (AK.accumulate!, traverse_single.jl:57): ibvh_lvt_scan.hip -----------------
+template <class I> struct ScanCall {
+    I *counts = nullptr;             // per-item counts in, their inclusive prefix out (in place)
+    int64_t n = 0;                   // items the launch is sized for
+    void *scratch = nullptr;         // scan_scratch_bytes(n): header + tile aggregates (ibvh_lvt_scratch.hpp)
+    const int32_t *limit = nullptr;  // device-side length: the array holds min(n, *limit) items (nullptr: n)
+    int64_t *total_dev = nullptr;    // where the device-side total goes (nullptr: word 0 of the scratch header)
+    int64_t *total_host = nullptr;   // pinned host memory the total is stored to as well (nullptr: nowhere)
+    int64_t *total_out = nullptr;    // != nullptr: blocking read of the total (the reference's @allowscalar, :60)
+    bool aggregates_zeroed = false;  // the producer of the counts zeroed the tile aggregates: the one-kernel routes may run
+};
+// IBVH_ERR_OVERFLOW when total_out is set and a 32-bit I cannot hold the total
+template <class I> int scan_counts(const ScanCall<I> &s, hipStream_t st);
 
 inline int check_levels(const ibvh_bvh &b, int64_t start_level) {
     // @argcheck bvh.built_level <= start_level <= bvh.tree.levels <= 32 (traverse_single.jl:10)

@@ -267,8 +267,8 @@ __global__ __launch_bounds__(1024) void rays_binscan_kernel(RayBins rb) {
     const unsigned long long cur = *rb.cursor;
     if (threadIdx.x == 0) *rb.n_items = (int32_t)(cur < (unsigned long long)rb.cap ? cur : (unsigned long long)rb.cap);
     { // the tile aggregates of the scan over the items' hits (scan_counts, one-kernel route): the scan over the rays' items has used them
-        unsigned long long *agg = (unsigned long long *)rb.scan_scratch + 8;
-        const int words = (rb.cap + SCAN_TILE - 1) / SCAN_TILE + 1;
+        unsigned long long *agg = (unsigned long long *)((char *)rb.scan_scratch + SCAN_AGG_OFFSET);
+        const int words = (int)scan_agg_words(rb.cap); // (cap > 0 here; at 0 this is 2 words where the hand-written form had 1: inside the scratch either way)
         for (int k = (int)threadIdx.x; k < words; k += 1024) agg[k] = 0ull;
     }
     if (*rb.flag != 0) {
@@ -783,8 +783,7 @@ int launch_rays_binned(const Args<L, N, I> &a, bool write, hipStream_t st, const
     if (!write) {
         // (header + the helper scans' header and tile aggregates right behind it: both scans take the one-kernel route, the second
         // one's aggregates are zeroed again by rays_binscan_kernel)
-        const int64_t scan_words = 8 + ceil_div((int64_t)rb.cap > a.n_items ? (int64_t)rb.cap : a.n_items, (int64_t)SCAN_TILE) + 1;
-        IBVH_HIP_CHECK(hipMemsetAsync(rb.cursor, 0, 2048 + (size_t)scan_words * 8, st));
+        IBVH_HIP_CHECK(hipMemsetAsync(rb.cursor, 0, 2048 + scan_used_bytes((int64_t)rb.cap > a.n_items ? (int64_t)rb.cap : a.n_items), st));
         IBVH_HIP_CHECK(hipMemsetAsync(rb.bin_count, 0, (size_t)((char *)rb.items - (char *)rb.bin_count), st)); // counts, starts, cursors
         if constexpr (N::kind == IBVH_BBOX && std::is_same<typename N::elt, float>::value) {
             const int64_t top_first = level_start(a.tree.levels, a.tree.virtual_leaves, a.built_level) - 1; // (memory index of the first node that exists)
@@ -793,7 +792,13 @@ int launch_rays_binned(const Args<L, N, I> &a, bool write, hipStream_t st, const
                         st, a.nodes + top_first, top_count, rb);
         }
         IBVH_LAUNCH((rays_top_kernel<L, N, I>), dim3(rblocks), dim3(64), 0, st, a, rb, ray_block);
-        if (int e = scan_counts<int32_t>(rb.ray_items, a.n_items, nullptr, rb.scan_scratch, st, rb.dummy_total, nullptr, nullptr, true)) return e;
+        ScanCall<int32_t> ray_scan; // items per ray -> where a ray's items start
+        ray_scan.counts = rb.ray_items;
+        ray_scan.n = a.n_items;
+        ray_scan.scratch = rb.scan_scratch;
+        ray_scan.total_dev = rb.dummy_total;
+        ray_scan.aggregates_zeroed = true; // (the memset above)
+        if (int e = scan_counts(ray_scan, st)) return e;
         const bool big_tiles = rb.cap >= (1 << 22);
         const unsigned tiles = (unsigned)ceil_div((int64_t)rb.cap, (big_tiles ? 1024 : 256) * RAYTILE_IPT);
         const size_t hist_lds = (size_t)rb.subtrees * 4;
@@ -806,7 +811,14 @@ int launch_rays_binned(const Args<L, N, I> &a, bool write, hipStream_t st, const
         if (lds > 64 * 1024)
             IBVH_HIP_CHECK(hipFuncSetAttribute((const void *)rays_subtree_kernel<L, N, I, false>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
         IBVH_LAUNCH((rays_subtree_kernel<L, N, I, false>), dim3(chunks), dim3(RAYSUB_TPB), lds, st, a, rb);
-        if (int e = scan_counts<I>((I *)rb.hits, (int64_t)rb.cap, nullptr, rb.scan_scratch, st, rb.dummy_total, nullptr, rb.n_items, true)) return e;
+        ScanCall<I> hit_scan; // hits per item, over the items in use -> where an item's hits go
+        hit_scan.counts = (I *)rb.hits;
+        hit_scan.n = (int64_t)rb.cap;
+        hit_scan.scratch = rb.scan_scratch;
+        hit_scan.limit = rb.n_items;
+        hit_scan.total_dev = rb.dummy_total;
+        hit_scan.aggregates_zeroed = true; // (rays_binscan_kernel)
+        if (int e = scan_counts(hit_scan, st)) return e;
         IBVH_LAUNCH((rays_counts_kernel<I>), dim3((unsigned)ceil_div(a.n_items, 256)), dim3(256), 0, st, rb, a.counts, a.n_items);
         if (int e = launch_rays_standby<L, N, I>(standby, false, st, ray_block, rblocks)) return e;
     } else {

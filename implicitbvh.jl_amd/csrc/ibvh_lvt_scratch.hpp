@@ -20,7 +20,7 @@
 namespace ibvh {
 namespace lvt {
 
-constexpr int SCAN_TILE = 4096;  // counts per tile of the scan (ibvh_lvt.hpp: SCAN_TPB * SCAN_IPT)
+constexpr int SCAN_TILE = 4096;  // counts per tile of the scan (ibvh_lvt_scan.hip: SCAN_TPB * SCAN_IPT)
 constexpr int BLK_ROW = 512;     // 32-bit words per block row (ibvh_lvt.hpp "the shared part of the descent")
 constexpr int BLK_SHIFT_MIN = 9; // (the scratch is sized for the smallest block the launch code may choose)
 constexpr int MAX_CACHE_SLOTS = 64;
@@ -33,8 +33,13 @@ constexpr size_t TAIL_FIT_SLACK = TAIL_ALIGN, TAIL_SIZE_SLACK = 2 * TAIL_ALIGN;
 constexpr size_t ABSENT = ~(size_t)0;
 
 inline size_t tail_align_up(size_t v) { return (v + TAIL_ALIGN - 1) / TAIL_ALIGN * TAIL_ALIGN; }
-// header, one aggregate per tile, the fused scan's ticket
-inline size_t scan_scratch_bytes(int64_t n) { return tail_align_up((size_t)(((n > 0 ? n : 1) + SCAN_TILE - 1) / SCAN_TILE + 9) * 8); }
+// The scan's scratch (scan_counts, ibvh_lvt_scan.hip), in 64-bit words: the header (word 0: the total), from SCAN_AGG_OFFSET on one
+// aggregate per tile, one spare word.  (constexpr: the kernels that zero the aggregates use the same arithmetic.)
+constexpr size_t SCAN_AGG_OFFSET = SCRATCH_HEADER_BYTES;
+constexpr int64_t scan_tiles(int64_t n) { return (n + SCAN_TILE - 1) / SCAN_TILE; }
+constexpr size_t scan_agg_words(int64_t n) { return (size_t)scan_tiles(n > 0 ? n : 1) + 1; }
+constexpr size_t scan_used_bytes(int64_t n) { return SCAN_AGG_OFFSET + scan_agg_words(n) * 8; }
+inline size_t scan_scratch_bytes(int64_t n) { return tail_align_up(scan_used_bytes(n)); }
 inline size_t blk_rows_bytes(int64_t n_items, int shift) {
     return (size_t)(((n_items > 0 ? n_items : 1) + ((int64_t)1 << shift) - 1) >> shift) * BLK_ROW * 4;
 }
