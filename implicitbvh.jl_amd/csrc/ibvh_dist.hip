@@ -85,11 +85,21 @@ template <class T> __global__ void unpack_extrema_kernel(const double *vec, T *e
 
 // Digit histograms for the splitter search: out[j][d] = #keys with (key >> prefix_shift) == prefix[j]
 // and digit d = (key >> shift) & mask; nprefix == 0: one histogram over all keys.  LDS-staged.
+// A prefix listed twice gets the count in both of its rows (every row is tested for every key).
 constexpr int HIST_TPB = 256;
 constexpr int MAX_PREFIX = 15;
+constexpr size_t HIST_LDS_BYTES = 160 * 1024; // the whole LDS of a CU: one workgroup may ask for all of it
 struct Prefixes {
     uint64_t v[MAX_PREFIX];
 };
+// Rows (prefixes) ONE ibvh_key_histogram call can count at a digit width: what fits the LDS staging, at most MAX_PREFIX
+// (10 at 12 bits, 15 below).  The argument check below and the batch loop and table sizes of ibvh_dist_plan
+// (ibvh_distdrv.hip) all ask here; 0 for a digit width the kernel does not take.
+int key_hist_max_rows(int bits) {
+    if (bits < 1 || bits > 12) return 0;
+    const size_t rows = HIST_LDS_BYTES / ((size_t)4 << bits);
+    return rows < (size_t)MAX_PREFIX ? (int)rows : MAX_PREFIX;
+}
 template <class K>
 __global__ __launch_bounds__(HIST_TPB) void key_hist_kernel(const K *__restrict__ keys, int64_t n, int shift, int bits,
                                                             int prefix_shift, Prefixes pre, int nprefix,
@@ -177,13 +187,16 @@ ibvh_status ibvh_dist_partition(int32_t key_bytes, const void *keys, int64_t n, 
                                 void *perm_out, void *counts_out, void *scratch, size_t scratch_bytes, void *stream) {
     if (n < 0 || nranks < 1 || (key_bytes != 4 && key_bytes != 8)) return IBVH_ERR_INVALID_ARG;
     if (nranks - 1 > distk::MAX_SPLITTERS) return IBVH_ERR_UNSUPPORTED;
-    if (counts_out && hipMemsetAsync(counts_out, 0, (size_t)nranks * 8, (hipStream_t)stream) != hipSuccess) return IBVH_ERR_HIP;
-    if (n == 0) return IBVH_OK;
-    if (!keys || !perm_out || !scratch || (nranks > 1 && !splitters)) return IBVH_ERR_INVALID_ARG;
-    size_t need;
-    ibvh_dist_partition_scratch_bytes(n, &need);
-    if (scratch_bytes < need) return IBVH_ERR_SCRATCH;
+    // (every check comes before the first HIP call: a refused call has touched nothing)
+    if (n > 0) {
+        if (!keys || !perm_out || !scratch || (nranks > 1 && !splitters)) return IBVH_ERR_INVALID_ARG;
+        size_t need;
+        ibvh_dist_partition_scratch_bytes(n, &need);
+        if (scratch_bytes < need) return IBVH_ERR_SCRATCH;
+    }
     hipStream_t st = (hipStream_t)stream;
+    if (counts_out && hipMemsetAsync(counts_out, 0, (size_t)nranks * 8, st) != hipSuccess) return IBVH_ERR_HIP;
+    if (n == 0) return IBVH_OK;
     const size_t slab = (size_t)align_up(n * 4, 256);
     uint32_t *dest = (uint32_t *)scratch, *dest_alt = (uint32_t *)((char *)scratch + slab), *vals_pri = (uint32_t *)((char *)scratch + 2 * slab);
     void *sort_scratch = (char *)scratch + 3 * slab;
@@ -206,12 +219,13 @@ ibvh_status ibvh_dist_partition(int32_t key_bytes, const void *keys, int64_t n, 
 
 ibvh_status ibvh_key_histogram(int32_t key_bytes, const void *keys, int64_t n, int32_t shift, int32_t bits,
                                int32_t prefix_shift, const uint64_t *prefixes, int32_t nprefix, void *out, void *stream) {
-    if (n < 0 || bits < 1 || bits > 12 || shift < 0 || nprefix < 0 || nprefix > distk::MAX_PREFIX || !out) return IBVH_ERR_INVALID_ARG;
+    if (n < 0 || bits < 1 || bits > 12 || nprefix < 0 || !out || (n > 0 && !keys)) return IBVH_ERR_INVALID_ARG;
+    if (shift < 0 || shift > 63) return IBVH_ERR_INVALID_ARG; // (the kernel shifts a 64-bit key by it)
     if (key_bytes != 4 && key_bytes != 8) return IBVH_ERR_INVALID_ARG;
-    if (nprefix > 0 && !prefixes) return IBVH_ERR_INVALID_ARG;
+    if (nprefix > 0 && (!prefixes || prefix_shift < 0)) return IBVH_ERR_INVALID_ARG; // (prefix_shift >= 64: every key has prefix 0)
     const int rows = nprefix > 0 ? nprefix : 1;
+    if (rows > distk::key_hist_max_rows(bits)) return IBVH_ERR_INVALID_ARG;
     const size_t smem = (size_t)rows * ((size_t)1 << bits) * 4;
-    if (smem > 160 * 1024) return IBVH_ERR_INVALID_ARG;
     hipStream_t st = (hipStream_t)stream;
     if (hipMemsetAsync(out, 0, smem, st) != hipSuccess) return IBVH_ERR_HIP;
     if (n == 0) return IBVH_OK;
@@ -221,13 +235,13 @@ ibvh_status ibvh_key_histogram(int32_t key_bytes, const void *keys, int64_t n, i
     unsigned blocks = (unsigned)(b < 1 ? 1 : (b > 1024 ? 1024 : b));
     if (key_bytes == 4) {
         if (hipFuncSetAttribute((const void *)distk::key_hist_kernel<uint32_t>, hipFuncAttributeMaxDynamicSharedMemorySize,
-                                160 * 1024) != hipSuccess) // (always the same value: concurrent callers cannot interleave badly)
+                                (int)distk::HIST_LDS_BYTES) != hipSuccess) // (always the same value: concurrent callers cannot interleave badly)
             return IBVH_ERR_HIP;
         IBVH_LAUNCH((distk::key_hist_kernel<uint32_t>), dim3(blocks), dim3(distk::HIST_TPB), smem, st, (const uint32_t *)keys, n,
                     shift, bits, prefix_shift, pre, nprefix, (uint32_t *)out);
     } else {
         if (hipFuncSetAttribute((const void *)distk::key_hist_kernel<uint64_t>, hipFuncAttributeMaxDynamicSharedMemorySize,
-                                160 * 1024) != hipSuccess) // (always the same value: concurrent callers cannot interleave badly)
+                                (int)distk::HIST_LDS_BYTES) != hipSuccess) // (always the same value: concurrent callers cannot interleave badly)
             return IBVH_ERR_HIP;
         IBVH_LAUNCH((distk::key_hist_kernel<uint64_t>), dim3(blocks), dim3(distk::HIST_TPB), smem, st, (const uint64_t *)keys, n,
                     shift, bits, prefix_shift, pre, nprefix, (uint32_t *)out);
@@ -237,12 +251,13 @@ ibvh_status ibvh_key_histogram(int32_t key_bytes, const void *keys, int64_t n, i
 
 ibvh_status ibvh_pack_records(const ibvh_types *types, const void *volumes, const void *keys, const void *perm,
                               int64_t index_base, int64_t n, void *records_out, void *stream) {
-    if (!types || n < 0) return IBVH_ERR_INVALID_ARG;
+    if (!types || n < 0 || index_base < 0) return IBVH_ERR_INVALID_ARG;
     if (n == 0) return IBVH_OK;
     if (!volumes || !keys || !records_out) return IBVH_ERR_INVALID_ARG;
     ibvh_layout lay;
     LeafLayout dl;
     if (!layout_of(*types, lay, &dl)) return IBVH_ERR_UNSUPPORTED;
+    if (types->index_type == IBVH_I32 && index_base > (int64_t)INT32_MAX - n) return IBVH_ERR_OVERFLOW; // the largest .index is index_base + n
     int64_t b = ceil_div(n, 256);
     unsigned blocks = (unsigned)(b > 4096 ? 4096 : b);
     hipStream_t st = (hipStream_t)stream;

@@ -28,6 +28,12 @@
 
 using namespace ibvh;
 
+namespace ibvh {
+namespace distk { // ibvh_dist.hip
+int key_hist_max_rows(int bits);
+} // namespace distk
+} // namespace ibvh
+
 namespace {
 
 constexpr int DIGIT_BITS = 12;
@@ -36,6 +42,15 @@ constexpr int MAX_RANKS = IBVH_DIST_MAX_RANKS;
 int key_bits_of(const ibvh_types &t) { return t.morton_type == IBVH_U16 ? 15 : (t.morton_type == IBVH_U32 ? 30 : 63); }
 int key_bytes_of(const ibvh_types &t) { return t.morton_type == IBVH_U64 ? 8 : 4; }
 int float_bytes(int flt) { return flt == IBVH_F64 ? 8 : 4; }
+// counters of the largest histogram one ibvh_key_histogram call of the splitter search fills (any digit width it uses)
+size_t hist_table_counters() {
+    size_t most = 0;
+    for (int bits = 1; bits <= DIGIT_BITS; ++bits) {
+        const size_t c = (size_t)distk::key_hist_max_rows(bits) << bits;
+        most = c > most ? c : most;
+    }
+    return most;
+}
 
 __global__ void widen_u32_i64_kernel(const uint32_t *in, long long *out, int64_t n) {
     const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
@@ -61,8 +76,8 @@ Layout make_layout(const ibvh_types &t, int64_t n, int size) {
     L.ext_local = take(64);
     L.vec = take((size_t)(7 + size) * 8); // (-mins, maxs, one-hot leaf counts, the largest status of all ranks)
     L.ext = take(64);
-    L.hist = take((size_t)16 * (1 << DIGIT_BITS) * 4);
-    L.hist64 = take((size_t)16 * (1 << DIGIT_BITS) * 8);
+    L.hist = take(hist_table_counters() * 4);
+    L.hist64 = take(hist_table_counters() * 8);
     L.allh = take((size_t)size * (1 << DIGIT_BITS) * 4);
     L.cnt = take((size_t)4 * size * 8);
     L.ext_scratch = take((size_t)1 << 17);
@@ -358,6 +373,7 @@ ibvh_status ibvh_dist_plan(const ibvh_types *types, const ibvh_comm *comm, const
     plan->base = before;
     for (int k = 0; k < 6; ++k) plan->extrema[k] = fb == 8 ? ((const double *)ext_raw)[k] : (double)((const float *)ext_raw)[k];
     if (n_global < P) return IBVH_ERR_DOMAIN; // fewer leaves than ranks
+    if (types->index_type == IBVH_I32 && n_global > (int64_t)INT32_MAX) return IBVH_ERR_OVERFLOW; // (the records' global 1-based .index; every rank reads the same counts)
     // 3. splitters
     ibvh_splitter_search ss;
     IBVH_TRY(ibvh_splitter_search_init(&ss, P, key_bits, n_global, tolerance));
@@ -370,10 +386,12 @@ ibvh_status ibvh_dist_plan(const ibvh_types *types, const ibvh_comm *comm, const
         while (!ss.all_done) { // (rare: a splitter landed in a bucket heavier than the tolerance allows)
             const int nr = ss.num_rows, width = 1 << ss.next_bits;
             rows_host.resize((size_t)nr * width);
-            // (the histogram tables hold 16 rows: more undecided prefixes than that — many ranks under tolerance 0, or a tightly
-            // clustered cloud — go through them 15 rows at a time, one all-reduce per batch)
-            for (int r0 = 0; r0 < nr; r0 += 15) {
-                const int nb = nr - r0 < 15 ? nr - r0 : 15;
+            // (one histogram call takes key_hist_max_rows(bits) rows — 10 at 12 bits, 15 below: more undecided prefixes than
+            // that — many ranks under tolerance 0, or a tightly clustered cloud — go through the tables a batch at a time,
+            // one all-reduce per batch)
+            const int batch = distk::key_hist_max_rows(ss.next_bits);
+            for (int r0 = 0; r0 < nr; r0 += batch) {
+                const int nb = nr - r0 < batch ? nr - r0 : batch;
                 if (n_local > 0)
                     IBVH_TRY(ibvh_key_histogram(kb, base + L.keys, n_local, ss.next_shift, ss.next_bits, ss.next_shift + ss.next_bits, ss.rows + r0, nb,
                                                 base + L.hist, stream));

@@ -43,7 +43,9 @@ extern "C" {
  *   6: IBVH_PAIR_MIXED_TYPES (pair LVT traversals of two BVHs of different leaf / node types)
  *   7: ibvh_refit; ibvh_rays_resolve_triangles (additive under 7: a new entry point, no struct layout or existing
  *      argument list moves, so a binding written against the earlier 7 keeps working); ibvh_closest_triangles (additive
- *      under 7 in the same way) */
+ *      under 7 in the same way); argument checks only, no layout or argument list moves: ibvh_key_histogram takes
+ *      what fits its LDS staging (10 rows at 12-bit digits) and refuses shift > 63 and a negative prefix_shift,
+ *      ibvh_pack_records / ibvh_dist_plan answer IBVH_ERR_OVERFLOW for an index past IBVH_I32 */
 #define IBVH_ABI_VERSION 7
 int32_t ibvh_abi_version(void);
 
@@ -565,7 +567,9 @@ ibvh_status ibvh_dist_unpack_extrema(int32_t flt, const void *vec, void *extrema
 /* Stable partition of the local leaves by destination rank (keys in [splitters[r-1], splitters[r]) go to rank r;
  * `splitters`: nranks - 1 ascending keys in HOST memory): perm_out[j] (DEVICE, n x uint32) = source position of the
  * j-th leaf in (destination, source position) order; counts_out (DEVICE, nranks x uint64, optional): leaves per
- * destination rank — for a caller that does not already know its row of the send matrix.  nranks <= 256. */
+ * destination rank — for a caller that does not already know its row of the send matrix.  nranks <= 256 (more:
+ * IBVH_ERR_UNSUPPORTED).  Keys equal to a splitter go to the rank on its right.  Every argument is checked before the
+ * first HIP call: a refused call has touched nothing; n == 0 zeroes counts_out and touches nothing else. */
 ibvh_status ibvh_dist_partition_scratch_bytes(int64_t n, size_t *bytes_out);
 ibvh_status ibvh_dist_partition(int32_t key_bytes, const void *keys, int64_t n, const uint64_t *splitters,
                                 int32_t nranks, void *perm_out, void *counts_out, void *scratch,
@@ -574,13 +578,19 @@ ibvh_status ibvh_dist_partition(int32_t key_bytes, const void *keys, int64_t n, 
 /* Digit histograms for the splitter search of the distributed radix sort.  out (DEVICE,
  * max(nprefix,1) x 2^bits uint32, zeroed here): out[j][d] = number of keys whose
  * (key >> prefix_shift) == prefixes[j] and whose digit (key >> shift) & (2^bits - 1) == d;
- * nprefix == 0 counts all keys.  bits <= 12, nprefix <= 15; `prefixes` is a HOST array. */
+ * nprefix == 0 counts all keys.  `prefixes` is a HOST array; a prefix listed twice gets the count in both rows.
+ * 1 <= bits <= 12, 0 <= shift <= 63; prefix_shift >= 0 when nprefix > 0, and prefix_shift >= 64 means "every key has
+ * prefix 0".  One call stages its rows in LDS (160 KB): nprefix <= 15 for bits <= 11, nprefix <= 10 for bits == 12
+ * (anything else: IBVH_ERR_INVALID_ARG) — ibvh_dist_plan batches its undecided prefixes by the same limit.  The
+ * largest configuration, 10 rows x 12 bits = exactly 160 KB of dynamic LDS, is the one verified on an MI355X: the
+ * device accepts the launch and the counts are right (tests/test_gpu_dist_pieces.py launches it in every run). */
 ibvh_status ibvh_key_histogram(int32_t key_bytes, const void *keys, int64_t n, int32_t shift,
                                int32_t bits, int32_t prefix_shift, const uint64_t *prefixes,
                                int32_t nprefix, void *out, void *stream);
 
 /* Pack BoundingVolume records for the exchange: out[i] = { volumes[p], index_base + p + 1,
- * keys[p] } with p = perm[i] (uint32) or i when perm == NULL. */
+ * keys[p] } with p = perm[i] (uint32, repeats allowed) or i when perm == NULL.  index_base < 0: IBVH_ERR_INVALID_ARG;
+ * index_base + n > INT32_MAX under IBVH_I32: IBVH_ERR_OVERFLOW (both before any HIP call). */
 ibvh_status ibvh_pack_records(const ibvh_types *types, const void *volumes, const void *keys,
                               const void *perm, int64_t index_base, int64_t n, void *records_out,
                               void *stream);
@@ -655,7 +665,7 @@ ibvh_status ibvh_dist_scratch_bytes(const ibvh_types *types, int64_t n_local, in
  * on `stream` once (twice when the send matrix does not follow from the first histogram): the record counts must reach the
  * host before RCCL can be told the transfer sizes — the reference's own "count, then size, then write" shape.
  * IBVH_ERR_DOMAIN (on EVERY rank, so that none is left waiting in a collective) when there are fewer leaves than ranks or a
- * rank would receive none. */
+ * rank would receive none; IBVH_ERR_OVERFLOW (on every rank as well) when the global leaf count does not fit IBVH_I32. */
 ibvh_status ibvh_dist_plan(const ibvh_types *types, const ibvh_comm *comm, const void *volumes, int64_t n_local, double tolerance,
                            void *scratch, size_t scratch_bytes, ibvh_dist_plan_t *plan_out, void *stream);
 
