@@ -1,33 +1,21 @@
-// ibvh_build.hip — BVH construction on gfx950: extrema -> Morton keys -> radix sort -> gather ->
-// bottom-up merge.  Replaces src/build.jl:198-271 and src/morton/*.jl of the reference.
+// ibvh_build.hip — BVH construction on gfx950: extrema -> Morton keys -> stable sort of the records -> bottom-up merge.
+// Replaces src/build.jl:198-271 and src/morton/*.jl of the reference.
 //
 // Data flow (BSphere{F32} leaves, n of them; bytes per leaf in brackets):
 //   extrema_partial   read volumes [16]                         -> per-workgroup min/max
-//   extrema_final     (1 workgroup) + epsilon expansion         -> 6 scalars in HBM (no host readback)
-//   encode            read volumes [16], write key [4]          (values are implicit positions)
-//   radix sort        ibvh_sort.hip
-//   gather            read perm [4] + key [4] + volume [16 random], write record [24]
+//   encode_hist       folds the partials + epsilon expansion    -> 6 scalars in HBM (no host readback; above 2^21 leaves
+//                     a one-workgroup extrema_final does it), read volumes [16], write key [4] (values are implicit
+//                     positions), and counts the sort's first digit per tile
+//   sort              n >= 4,096: ibvh_msd.hip — ONE partition of the finished records by the top bits of their key
+//                     (read key [4] + volume [16 random], write record [24]), every cell finished in LDS [24 + 24]
+//                     n <  4,096: ibvh_sort.hip — (key, position) pairs; the last pass writes the records
 //   aggregate         read records [24 stride, 16 used], write nodes [24 * ~1]
 #include "ibvh_common.hpp"
 #include "ibvh_radix.hpp"
 #include "ibvh_msd.hpp"
+#include "ibvh_sort.hpp"
 
 namespace ibvh {
-namespace rsort { // ibvh_sort.hip: LSD passes over (key, position) pairs (+ the MSD / in-LDS hybrid on pairs)
-struct FirstPassPlan {
-    int tpb, ipt, num_tiles;
-    uint32_t *tile_hist;
-    uint32_t mask;
-    int shift, bits;
-};
-FirstPassPlan first_pass_plan(int64_t n, int key_bits, int key_bytes, void *scratch);
-bool uses_hybrid(int64_t n, int key_bits, int key_bytes);
-int sort_pairs(int key_bytes, int key_bits, int64_t n, void *keys, void *vals, void *keys_alt, void *vals_alt,
-               bool vals_implicit, int32_t *result_in_alt, void *scratch, size_t scratch_sz, hipStream_t st,
-               bool first_hist_done, const RecordArgs *records);
-size_t scratch_bytes(int64_t n);
-} // namespace rsort
-
 namespace build {
 
 constexpr int EXT_TPB = 256;
@@ -268,49 +256,6 @@ __global__ __launch_bounds__(1024) void encode_hist_kernel(const char *__restric
         for (int d = threadIdx.x; d <= (int)mask; d += blockDim.x) tile_hist[(int64_t)blockIdx.x * (mask + 1) + d] = h[d];
     else
         for (int d = threadIdx.x; d <= (int)mask; d += blockDim.x) tile_hist[(int64_t)d * num_tiles + blockIdx.x] = h[d];
-}
-
-// ------------------------------------------------------------------------------------------
-// gather: sorted (key, position) -> BoundingVolume records in Morton order
-//   index = position + 1 for freshly wrapped volumes (wrap_bounding_volumes, build.jl:345-349)
-//           or the source record's own .index (build.jl:220-222)
-// ------------------------------------------------------------------------------------------
-// Each wave assembles 64 records in LDS and writes them as ONE contiguous byte range with fully coalesced
-// 8-byte stores (a record-per-lane store would touch every line of the range with each of its 3 partial
-// stores); the random volume fetch of the next chunk is issued before the current chunk is written out.
-template <class V, class I, class K>
-__global__ __launch_bounds__(256) void gather_kernel(const char *__restrict__ src, int64_t src_stride, int src_wrapped,
-                                                     LeafLayout lay, const K *__restrict__ keys,
-                                                     const uint32_t *__restrict__ perm, int64_t n, char *__restrict__ dst) {
-    extern __shared__ __attribute__((aligned(16))) unsigned char g_smem[];
-    const int lane = threadIdx.x & 63, wv = threadIdx.x >> 6;
-    const int words = lay.stride >> 3; // 8-byte words per record
-    uint64_t *stage = (uint64_t *)g_smem + (size_t)wv * 64 * words;
-    const int64_t nchunks = ceil_div_dev(n, 256);
-    for (int64_t c = blockIdx.x; c < nchunks; c += gridDim.x) {
-        const int64_t i = c * 256 + threadIdx.x;
-        const int64_t wave_first = c * 256 + wv * 64;
-        if (i < n) {
-            const uint32_t p = perm[i];
-            const char *s = src + (int64_t)p * src_stride;
-            V v;
-            if (sizeof(V) % 16 == 0 && (src_stride & 15) == 0) v = load_vol16<V>(s); // one 16-byte request per leaf
-            else v = load_vol<V>(s);
-            I idx = src_wrapped ? load_index<I>(s, lay) : (I)((int64_t)p + 1);
-            char *d = (char *)(stage + (size_t)lane * words);
-            store_vol(d, v);
-            *(I *)(d + lay.index_off) = idx;
-            store_morton(d, lay, (uint64_t)keys[i]);
-        }
-        __builtin_amdgcn_wave_barrier();
-        const int64_t wave_n = n - wave_first < 64 ? n - wave_first : 64; // records of this wave's chunk
-        if (wave_n > 0) {
-            uint64_t *out = (uint64_t *)(dst + wave_first * lay.stride);
-            const int total = (int)wave_n * words;
-            for (int g = lane; g < total; g += 64) out[g] = stage[g];
-        }
-        __builtin_amdgcn_wave_barrier();
-    }
 }
 
 // ------------------------------------------------------------------------------------------
@@ -557,7 +502,7 @@ struct Scratch {
     char *extrema;   // 6 * 8
     char *keys, *keys_alt; // n * key_bytes
     char *vals, *vals_alt; // n * 4
-    char *records;   // n * leaf_bytes: the partitioned records (and the staging of an in-place LSD build)
+    char *records;   // n * leaf_bytes: the partitioned records (and the staging of an in-place pair-sort build)
     char *records2;  // n * leaf_bytes: second partition level (oversized cells only)
     char *sort;      // rsort::scratch_bytes(n)
     size_t total;
@@ -607,17 +552,129 @@ int extrema(const char *recs, int64_t stride, int64_t n, int expand, typename V:
 template <class V>
 int encode(const char *recs, int64_t stride, int64_t n, const typename V::elt *ext, int morton_type, void *keys, hipStream_t st) {
     int blocks = grid_for(n, 256, 256 * 16);
-    if (morton_type == IBVH_U64)
-        IBVH_LAUNCH((encode_kernel<V, uint64_t>), dim3(blocks), dim3(256), 0, st, recs, stride, n, ext, morton_type,
-                           (uint64_t *)keys);
-    else
-        IBVH_LAUNCH((encode_kernel<V, uint32_t>), dim3(blocks), dim3(256), 0, st, recs, stride, n, ext, morton_type,
-                           (uint32_t *)keys);
-    IBVH_LAUNCH_CHECK();
-    return IBVH_OK;
+    return dispatch_key(morton_type == IBVH_U64 ? 8 : 4, [&](auto kt) -> int {
+        using K = typename decltype(kt)::type;
+        IBVH_LAUNCH((encode_kernel<V, K>), dim3(blocks), dim3(256), 0, st, recs, stride, n, ext, morton_type, (K *)keys);
+        IBVH_LAUNCH_CHECK();
+        return IBVH_OK;
+    });
 }
 
 inline int morton_key_bits(int morton_type) { return morton_type == IBVH_U16 ? 15 : (morton_type == IBVH_U32 ? 30 : 63); }
+
+// ------------------------------------------------------------------------------------------
+// ibvh_build: extrema -> keys + the sort's first tile histogram -> sort -> merge
+// ------------------------------------------------------------------------------------------
+// What ibvh_build has checked and derived from its arguments: the same for every leaf / node type
+struct BuildCall {
+    const ibvh_build_desc *desc;
+    ibvh_layout lay;
+    LeafLayout dlay;
+    ibvh_tree tree;
+    Scratch sc;
+    int64_t n;
+    int key_bytes, key_bits;
+    const char *src;        // raw volumes, or the source records of an already wrapped build
+    int64_t src_stride;
+    bool wrapped, in_place; // in_place: already wrapped, volumes == NULL: the caller's `leaves` are source and destination
+    void *leaves, *nodes, *skips, *extrema_out;
+    hipStream_t st;
+};
+
+// The sort of one build, chosen once: the record sort (ibvh_msd.hip) takes every build of 4,096 leaves or more, the pair
+// sort (ibvh_sort.hip) the smaller ones.  Both plans live in the sort region of the scratch (carve()).
+struct SortRoute {
+    msd::Plan records;      // bits != 0: the record sort
+    rsort::PairsPlan pairs; // otherwise
+    // The per-tile histogram the route's first pass expects from the key encoder: a workgroup of `tpb` threads per tile of
+    // `tile_elems` keys counts the digit (key >> shift) & mask; tile-major rows for the record sort, digit-major for the pairs.
+    int tpb, tile_elems, num_tiles, shift, tile_major;
+    uint32_t mask, *tile_hist;
+    bool by_records() const { return records.bits != 0; }
+};
+inline SortRoute choose_route(int64_t n, int key_bits, int key_bytes, int leaf_bytes, void *sort_scratch) {
+    SortRoute r{};
+    r.records = msd::make_plan(n, key_bits, key_bytes, leaf_bytes, sort_scratch);
+    if (r.by_records()) {
+        const msd::Plan &p = r.records;
+        r.tpb = p.ptpb, r.tile_elems = p.ptpb * p.pipt, r.num_tiles = p.num_tiles, r.shift = p.shift, r.tile_major = 1;
+        r.mask = (1u << p.bits) - 1u, r.tile_hist = p.tb.tile_hist;
+    } else {
+        const rsort::PairsPlan &p = r.pairs = rsort::plan_pairs(n, key_bits, key_bytes, sort_scratch);
+        r.tpb = p.tile.tpb, r.tile_elems = p.tile.tile(), r.num_tiles = p.num_tiles, r.shift = p.shift, r.tile_major = 0;
+        r.mask = p.mask, r.tile_hist = p.tile_hist;
+    }
+    return r;
+}
+
+// Extrema of the centres (or the caller's fixed bounds: morton/default.jl:52-57) and the skips: whatever is left for the
+// key encoder to do comes back in `fold`.
+template <class L> int launch_extrema(const BuildCall &b, ExtremaFold<typename L::elt> &fold) {
+    using T = typename L::elt;
+    T *ext = (T *)b.sc.extrema;
+    const TreeDev td{b.tree.levels, b.tree.real_leaves, b.tree.virtual_leaves};
+    const SkipsOut so{td, b.skips, b.desc->types.index_type == IBVH_I32 ? 4 : 8};
+    fold = ExtremaFold<T>{nullptr, 0, ext, (T *)b.extrema_out, so};
+    // Small builds are launch-latency bound: the encode kernel's workgroups fold the partial extrema themselves (one
+    // launch less on the critical path: -6 us at 1e6 leaves).  With thousands of encode workgroups the redundant folds
+    // cost more than the launch they save (1e7 leaves: encode 35 -> 45 us), so large builds keep the one-workgroup fold.
+    const bool fold_in_encode = b.n <= (int64_t)1 << 21;
+    if (b.desc->compute_extrema && fold_in_encode) {
+        int nparts = 0;
+        if (int e = extrema_partials<L>(b.src, b.src_stride, b.n, b.sc.partials, b.st, &nparts)) return e;
+        fold.partials = (const T *)b.sc.partials;
+        fold.nparts = nparts;
+    } else if (b.desc->compute_extrema) {
+        if (int e = extrema<L>(b.src, b.src_stride, b.n, 1, ext, b.sc.partials, b.st, (T *)b.extrema_out, so)) return e;
+    } else {
+        const double *mn = b.desc->mins, *mx = b.desc->maxs;
+        IBVH_LAUNCH((extrema_set_kernel<T>), dim3(1), dim3(64), 0, b.st, ext, (T *)b.extrema_out, mn[0], mn[1], mn[2], mx[0], mx[1],
+                    mx[2], so);
+    }
+    return IBVH_OK;
+}
+
+// Morton keys, fused with the first per-tile digit histogram of the sort
+template <class L> int launch_keys(const BuildCall &b, const SortRoute &h, const ExtremaFold<typename L::elt> &fold) {
+    using T = typename L::elt;
+    return dispatch_key(b.key_bytes, [&](auto kt) -> int {
+        using K = typename decltype(kt)::type;
+        IBVH_LAUNCH((encode_hist_kernel<L, K>), dim3(h.num_tiles), dim3(h.tpb), ((size_t)h.mask + 1) * 4, b.st, b.src, b.src_stride,
+                    b.n, (const T *)b.sc.extrema, b.desc->types.morton_type, (K *)b.sc.keys, h.tile_elems, h.shift, h.mask,
+                    h.tile_hist, h.num_tiles, h.tile_major, fold);
+        IBVH_LAUNCH_CHECK();
+        return IBVH_OK;
+    });
+}
+
+// The records in Morton order into `leaves` (index = position + 1 for fresh volumes, build.jl:345-349, or the source
+// record's own index, :220-222), then the merge.
+//   record sort: ONE partition of the finished records into scratch by the top bits of their key, cells finished in LDS
+//                into `leaves` (an in-place build reads `leaves`, stages in scratch and writes `leaves`: no extra copy)
+//   pair sort:   stable sort of (key, position); the last pass writes the records — into scratch for an in-place build,
+//                which then copies them back
+template <class L, class N> int sort_and_aggregate(const BuildCall &b, const SortRoute &route) {
+    const ibvh_build_desc &d = *b.desc;
+    const Scratch &sc = b.sc;
+    char *dst = (route.by_records() || b.in_place) ? sc.records : (char *)b.leaves;
+    const rsort::RecordArgs ra{b.src, dst, b.src_stride, b.wrapped ? 1 : 0, (int32_t)(b.lay.volume_bytes / 8),
+                               d.types.index_type == IBVH_I32 ? 4 : 8, b.dlay};
+    if (route.by_records()) {
+        if (int e = msd::sort_records(route.records, b.key_bytes, b.key_bits, sc.keys, b.n, ra, sc.records2, (char *)b.leaves,
+                                      sc.keys_alt, (uint32_t *)sc.vals_alt, sc.keys, (uint32_t *)sc.vals, d.sort_levels,
+                                      d.sort_equalize != 0, d.skew_flag, b.st))
+            return e;
+    } else {
+        if (d.skew_flag) IBVH_HIP_CHECK(hipMemsetAsync(d.skew_flag, 0, 4, b.st)); // (the pair sort does not care about skew)
+        int32_t in_alt = 0;
+        if (int e = rsort::sort_pairs(route.pairs, b.key_bytes, b.key_bits, b.n, sc.keys, sc.vals, sc.keys_alt, sc.vals_alt, true,
+                                      &in_alt, rsort::scratch_bytes(b.n), b.st, true, &ra))
+            return e;
+        if (b.in_place)
+            IBVH_HIP_CHECK(hipMemcpyAsync(b.leaves, sc.records, (size_t)b.n * b.lay.leaf_bytes, hipMemcpyDeviceToDevice, b.st));
+    }
+    return aggregate<L, N>((const char *)b.leaves, b.lay.leaf_bytes, b.tree, d.built_level, (N *)b.nodes, b.st);
+}
 
 } // namespace build
 } // namespace ibvh
@@ -714,110 +771,30 @@ ibvh_status ibvh_build(const ibvh_build_desc *desc, const void *volumes, void *l
     if (desc->built_level < 1 || desc->built_level > tree.levels) return IBVH_ERR_INVALID_ARG; // build.jl:314
     if (!desc->already_wrapped && !volumes) return IBVH_ERR_INVALID_ARG;
     if (tree.real_nodes >= 2 && !nodes) return IBVH_ERR_INVALID_ARG;
-    const int64_t n = desc->n;
-    const int key_bytes = ty.morton_type == IBVH_U64 ? 8 : 4;
-    const bool wrapped = desc->already_wrapped != 0;
-    Scratch sc = carve((char *)scratch, n, key_bytes, lay.leaf_bytes, ty.morton_type);
-    if (scratch_bytes < sc.total) return IBVH_ERR_SCRATCH;
-    hipStream_t st = (hipStream_t)stream;
-
+    BuildCall b{};
+    b.desc = desc, b.lay = lay, b.dlay = dlay, b.tree = tree, b.n = desc->n;
+    b.key_bytes = ty.morton_type == IBVH_U64 ? 8 : 4;
+    b.key_bits = morton_key_bits(ty.morton_type);
+    b.sc = carve((char *)scratch, b.n, b.key_bytes, lay.leaf_bytes, ty.morton_type);
+    if (scratch_bytes < b.sc.total) return IBVH_ERR_SCRATCH;
     // already_wrapped with a non-NULL `volumes`: `volumes` holds the source RECORDS and `leaves` receives the sorted
     // ones (out of place: no staging copy); with volumes == NULL the caller's `leaves` are sorted in place.
-    const bool out_of_place = wrapped && volumes != nullptr;
-    const char *src = wrapped ? (out_of_place ? (const char *)volumes : (const char *)leaves) : (const char *)volumes;
-    const int64_t src_stride = wrapped ? lay.leaf_bytes : lay.volume_bytes;
+    b.wrapped = desc->already_wrapped != 0;
+    b.in_place = b.wrapped && volumes == nullptr;
+    b.src = (const char *)(b.in_place ? leaves : volumes);
+    b.src_stride = b.wrapped ? lay.leaf_bytes : lay.volume_bytes;
+    b.leaves = leaves, b.nodes = nodes, b.skips = skips, b.extrema_out = extrema_out;
+    b.st = (hipStream_t)stream;
 
-    int rc = dispatch_leaf_node(ty, [&](auto lt, auto nt) -> int {
+    return (ibvh_status)dispatch_leaf_node(ty, [&](auto lt, auto nt) -> int {
         using L = typename decltype(lt)::type;
         using N = typename decltype(nt)::type;
-        using T = typename L::elt;
-        T *ext = (T *)sc.extrema;
-        // skips
-        TreeDev td{tree.levels, tree.real_leaves, tree.virtual_leaves};
-        const SkipsOut so{td, skips, ty.index_type == IBVH_I32 ? 4 : 8};
-        // extrema (or caller-fixed bounds: morton/default.jl:52-57)
-        ExtremaFold<T> fold{nullptr, 0, ext, (T *)extrema_out, so};
-        // Small builds are launch-latency bound: the encode kernel's workgroups fold the partial extrema themselves (one
-        // launch less on the critical path: -6 us at 1e6 leaves).  With thousands of encode workgroups the redundant folds
-        // cost more than the launch they save (1e7 leaves: encode 35 -> 45 us), so large builds keep the one-workgroup fold.
-        const bool fold_in_encode = n <= (int64_t)1 << 21;
-        if (desc->compute_extrema && fold_in_encode) {
-            int nparts = 0;
-            if (int e = extrema_partials<L>(src, src_stride, n, sc.partials, st, &nparts)) return e;
-            fold.partials = (const T *)sc.partials;
-            fold.nparts = nparts;
-        } else if (desc->compute_extrema) {
-            if (int e = extrema<L>(src, src_stride, n, 1, ext, sc.partials, st, (T *)extrema_out, so)) return e;
-        } else {
-            IBVH_LAUNCH((extrema_set_kernel<T>), dim3(1), dim3(64), 0, st, ext, (T *)extrema_out, desc->mins[0], desc->mins[1],
-                               desc->mins[2], desc->maxs[0], desc->maxs[1], desc->maxs[2], so);
-        }
-        // keys, fused with the first per-tile digit histogram of the sort
-        const int key_bits = morton_key_bits(ty.morton_type);
-        const msd::Plan mp = msd::make_plan(n, key_bits, key_bytes, (int)lay.leaf_bytes, sc.sort);
-        rsort::FirstPassPlan plan;
-        if (mp.bits) plan = rsort::FirstPassPlan{mp.ptpb, mp.pipt, mp.num_tiles, mp.tb.tile_hist, (1u << mp.bits) - 1u, mp.shift, mp.bits};
-        else plan = rsort::first_pass_plan(n, key_bits, key_bytes, sc.sort);
-        if (key_bytes == 8)
-            IBVH_LAUNCH((encode_hist_kernel<L, uint64_t>), dim3(plan.num_tiles), dim3(plan.tpb), ((size_t)plan.mask + 1) * 4, st,
-                        src, src_stride, n, ext, ty.morton_type, (uint64_t *)sc.keys, plan.tpb * plan.ipt, plan.shift, plan.mask,
-                        plan.tile_hist, plan.num_tiles, mp.bits ? 1 : 0, fold);
-        else
-            IBVH_LAUNCH((encode_hist_kernel<L, uint32_t>), dim3(plan.num_tiles), dim3(plan.tpb), ((size_t)plan.mask + 1) * 4, st,
-                        src, src_stride, n, ext, ty.morton_type, (uint32_t *)sc.keys, plan.tpb * plan.ipt, plan.shift, plan.mask,
-                        plan.tile_hist, plan.num_tiles, mp.bits ? 1 : 0, fold);
-        IBVH_LAUNCH_CHECK();
-        if (mp.bits) {
-            // the default: ONE partition of the finished records by the top bits of their key, buckets finished in LDS
-            // (ibvh_msd.hip).  index = position + 1 for fresh volumes (build.jl:345-349) or the source record's own
-            // index (:220-222); in-place builds read `leaves`, stage in scratch and write `leaves`: no extra copy.
-            rsort::RecordArgs ra{src, sc.records, src_stride, wrapped ? 1 : 0, (int32_t)(lay.volume_bytes / 8),
-                                 ty.index_type == IBVH_I32 ? 4 : 8, dlay};
-            if (int e = msd::sort_records(mp, key_bytes, key_bits, sc.keys, n, ra, sc.records2, (char *)leaves, sc.keys_alt, (uint32_t *)sc.vals_alt, sc.keys,
-                                          (uint32_t *)sc.vals, desc->sort_levels, desc->sort_equalize != 0, desc->skew_flag, st))
-                return e;
-            return aggregate<L, N>((const char *)leaves, lay.leaf_bytes, tree, desc->built_level, (N *)nodes, st);
-        }
-        if (desc->skew_flag) IBVH_HIP_CHECK(hipMemsetAsync(desc->skew_flag, 0, 4, st)); // (LSD passes do not care about skew)
-        // stable LSB radix sort of (key, position), then the records in Morton order
-        // (index = position + 1 for fresh volumes, build.jl:345-349, or the source record's own index, :220-222).
-        // In-place (already wrapped) builds go through scratch records.
-        // Below ~4 M leaves the LAST radix pass writes the finished records itself (one launch and one
-        // (key, position) round trip fewer: 0.157 -> 0.140 ms at 1e6); above, the dedicated gather kernel's higher
-        // occupancy serves the random volume reads better (measured at 1e7: 0.049 + 0.276 ms vs 0.350 ms fused).
-        char *dst = (wrapped && !out_of_place) ? sc.records : (char *)leaves;
-        // (with the MSD + in-LDS hybrid, the default up to ~6 M leaves, the bucket kernel always writes the records)
-        const bool fuse_records = rsort::uses_hybrid(n, key_bits, key_bytes) || n < (int64_t(1) << 22);
-        rsort::RecordArgs ra{src, dst, src_stride, wrapped ? 1 : 0, (int32_t)(lay.volume_bytes / 8),
-                             ty.index_type == IBVH_I32 ? 4 : 8, dlay};
-        int32_t in_alt = 0;
-        if (int e = rsort::sort_pairs(key_bytes, key_bits, n, sc.keys, sc.vals, sc.keys_alt, sc.vals_alt, true, &in_alt,
-                                      sc.sort, rsort::scratch_bytes(n), st, true, fuse_records ? &ra : nullptr))
-            return e;
-        if (!fuse_records) {
-            const void *skeys = in_alt ? sc.keys_alt : sc.keys;
-            const uint32_t *sperm = (const uint32_t *)(in_alt ? sc.vals_alt : sc.vals);
-            int gblocks = grid_for(n, 256, 256 * 16);
-            auto launch_gather = [&](auto it) -> int {
-                using I = typename decltype(it)::type;
-                const size_t gsm = (size_t)256 * lay.leaf_bytes;
-                if (key_bytes == 8)
-                    IBVH_LAUNCH((gather_kernel<L, I, uint64_t>), dim3(gblocks), dim3(256), gsm, st, src, src_stride,
-                                wrapped ? 1 : 0, dlay, (const uint64_t *)skeys, sperm, n, dst);
-                else
-                    IBVH_LAUNCH((gather_kernel<L, I, uint32_t>), dim3(gblocks), dim3(256), gsm, st, src, src_stride,
-                                wrapped ? 1 : 0, dlay, (const uint32_t *)skeys, sperm, n, dst);
-                return IBVH_OK;
-            };
-            if (int e = dispatch_index(ty.index_type, launch_gather)) return e;
-            IBVH_LAUNCH_CHECK();
-        }
-        if (wrapped && !out_of_place)
-            IBVH_HIP_CHECK(hipMemcpyAsync(leaves, sc.records, (size_t)n * lay.leaf_bytes, hipMemcpyDeviceToDevice, st));
-        // merge
-        return aggregate<L, N>((const char *)leaves, lay.leaf_bytes, tree, desc->built_level, (N *)nodes, st);
+        const SortRoute route = choose_route(b.n, b.key_bits, b.key_bytes, (int)lay.leaf_bytes, b.sc.sort);
+        ExtremaFold<typename L::elt> fold;
+        if (int e = launch_extrema<L>(b, fold)) return e;
+        if (int e = launch_keys<L>(b, route, fold)) return e;
+        return sort_and_aggregate<L, N>(b, route);
     });
-    return (ibvh_status)rc;
 }
 
 } // extern "C"

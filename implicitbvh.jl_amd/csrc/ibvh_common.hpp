@@ -489,6 +489,12 @@ template <class F> int dispatch_index(int index_type, F &&f) {
 #endif
     return IBVH_ERR_UNSUPPORTED;
 }
+// Morton keys (and the keys of ibvh_sort_pairs) are 4 or 8 bytes wide
+template <class F> int dispatch_key(int key_bytes, F &&f) {
+    if (key_bytes == 4) return f(Tag<uint32_t>{});
+    if (key_bytes == 8) return f(Tag<uint64_t>{});
+    return IBVH_ERR_INVALID_ARG;
+}
 
 #define IBVH_HIP_CHECK(expr)                                  \
     do {                                                      \
@@ -515,12 +521,11 @@ struct Tuning {
     int lvt_blocks_paired_below = -1; // block grids smaller than this take two levels per trip (-1 = 4096)
     int lvt_blocks_min_items = 0; // fewest work items for the shared descent (0 = 2^17)
     int lvt_xcd = 64;       // LVT item placement: 0 = round robin, 1 = one range per XCD, n = runs of n workgroups
-    // The sort's knobs (sort_lsd, sort_msd_avg, msd, msd_avg, msd_equalize, msd_rescue) only move a threshold or pick
+    // The sort's knobs (sort_lsd, sort_msd_avg, msd_avg, msd_equalize, msd_rescue) only move a threshold or pick
     // between shipped routes: whatever their values, the planners still take their geometry from the tables the kernels
     // are compiled from (kFinish in ibvh_msd_impl.hpp, IBVH_SORT_TILES / IBVH_SORT_BUCKETS in ibvh_sort.hip).
     int sort_lsd = 0;       // 1 = ibvh_sort_pairs always takes the plain LSD passes
     int sort_msd_avg = 1536; // ibvh_sort_pairs: largest average bucket before another partition bit is taken
-    int msd = 1;            // 0 = the build never takes the MSD partition path
     int msd_avg = 1024;     // largest average cell before another first-level bit is taken
     int lvt_scan_fused = 1; // the scan behind walker 2's counting pass in one kernel (scan_fused_kernel / scan_fused_grouped_kernel); 0 = reduce + apply; N > 1 = at most N workgroups (development: the default is half of what the device holds at once)
     int msd_equalize = 0;   // equalised cells (ibvh_msd.hip): 0 = when the build asks (ibvh_build_desc.sort_equalize), 1 = always, -1 = never

@@ -5,15 +5,9 @@
 // The collectives themselves are issued by the host side (implicitbvh.jl_amd/dist.py) through
 // torch.distributed (backend "nccl" = RCCL over xGMI); this file holds the kernels around them.
 #include "ibvh_common.hpp"
+#include "ibvh_sort.hpp"
 
 namespace ibvh {
-namespace rsort { // ibvh_sort.hip
-struct RecordArgs;
-int sort_pairs(int key_bytes, int key_bits, int64_t n, void *keys, void *vals, void *keys_alt, void *vals_alt, bool vals_implicit,
-               int32_t *result_in_alt, void *scratch, size_t scratch_sz, hipStream_t st, bool first_hist_done,
-               const RecordArgs *records);
-size_t scratch_bytes(int64_t n);
-} // namespace rsort
 namespace distk {
 
 // destination rank of every key: the number of splitters <= key (keys in [k_r, k_{r+1}) go to rank r)
@@ -204,13 +198,16 @@ ibvh_status ibvh_dist_partition(int32_t key_bytes, const void *keys, int64_t n, 
     for (int i = 0; i < nranks - 1; ++i) sp.v[i] = splitters[i];
     const int blocks = (int)(ceil_div(n, 256) < 4096 ? ceil_div(n, 256) : 4096);
     unsigned long long *cnt = (unsigned long long *)counts_out;
-    if (key_bytes == 8) IBVH_LAUNCH((distk::dest_kernel<uint64_t>), dim3(blocks), dim3(256), 0, st, (const uint64_t *)keys, n, sp, nranks - 1, dest, cnt);
-    else IBVH_LAUNCH((distk::dest_kernel<uint32_t>), dim3(blocks), dim3(256), 0, st, (const uint32_t *)keys, n, sp, nranks - 1, dest, cnt);
+    dispatch_key(key_bytes, [&](auto kt) -> int {
+        using K = typename decltype(kt)::type;
+        IBVH_LAUNCH((distk::dest_kernel<K>), dim3(blocks), dim3(256), 0, st, (const K *)keys, n, sp, nranks - 1, dest, cnt);
+        return IBVH_OK;
+    });
     int bits = 1;
     while ((1 << bits) < nranks) ++bits; // <= 8: exactly one LSD pass, whose output lands in the alternate buffers
     int32_t in_alt = 0;
-    if (int e = rsort::sort_pairs(4, bits, n, dest, vals_pri, dest_alt, perm_out, true, &in_alt, sort_scratch, rsort::scratch_bytes(n), st,
-                                  false, nullptr))
+    const rsort::PairsPlan plan = rsort::plan_pairs(n, bits, 4, sort_scratch);
+    if (int e = rsort::sort_pairs(plan, 4, bits, n, dest, vals_pri, dest_alt, perm_out, true, &in_alt, rsort::scratch_bytes(n), st, false, nullptr))
         return (ibvh_status)e;
     if (!in_alt) // (cannot happen for one pass; keep the contract anyway)
         if (hipMemcpyAsync(perm_out, vals_pri, (size_t)n * 4, hipMemcpyDeviceToDevice, st) != hipSuccess) return IBVH_ERR_HIP;
@@ -233,20 +230,16 @@ ibvh_status ibvh_key_histogram(int32_t key_bytes, const void *keys, int64_t n, i
     for (int j = 0; j < nprefix; ++j) pre.v[j] = prefixes[j];
     int64_t b = ceil_div(n, distk::HIST_TPB * 16);
     unsigned blocks = (unsigned)(b < 1 ? 1 : (b > 1024 ? 1024 : b));
-    if (key_bytes == 4) {
-        if (hipFuncSetAttribute((const void *)distk::key_hist_kernel<uint32_t>, hipFuncAttributeMaxDynamicSharedMemorySize,
-                                (int)distk::HIST_LDS_BYTES) != hipSuccess) // (always the same value: concurrent callers cannot interleave badly)
-            return IBVH_ERR_HIP;
-        IBVH_LAUNCH((distk::key_hist_kernel<uint32_t>), dim3(blocks), dim3(distk::HIST_TPB), smem, st, (const uint32_t *)keys, n,
-                    shift, bits, prefix_shift, pre, nprefix, (uint32_t *)out);
-    } else {
-        if (hipFuncSetAttribute((const void *)distk::key_hist_kernel<uint64_t>, hipFuncAttributeMaxDynamicSharedMemorySize,
-                                (int)distk::HIST_LDS_BYTES) != hipSuccess) // (always the same value: concurrent callers cannot interleave badly)
-            return IBVH_ERR_HIP;
-        IBVH_LAUNCH((distk::key_hist_kernel<uint64_t>), dim3(blocks), dim3(distk::HIST_TPB), smem, st, (const uint64_t *)keys, n,
-                    shift, bits, prefix_shift, pre, nprefix, (uint32_t *)out);
-    }
-    return hipGetLastError() == hipSuccess ? IBVH_OK : IBVH_ERR_HIP;
+    return (ibvh_status)dispatch_key(key_bytes, [&](auto kt) -> int {
+        using K = typename decltype(kt)::type;
+        // (always the same value: concurrent callers cannot interleave badly)
+        IBVH_HIP_CHECK(hipFuncSetAttribute((const void *)distk::key_hist_kernel<K>, hipFuncAttributeMaxDynamicSharedMemorySize,
+                                           (int)distk::HIST_LDS_BYTES));
+        IBVH_LAUNCH((distk::key_hist_kernel<K>), dim3(blocks), dim3(distk::HIST_TPB), smem, st, (const K *)keys, n, shift, bits,
+                    prefix_shift, pre, nprefix, (uint32_t *)out);
+        IBVH_LAUNCH_CHECK();
+        return IBVH_OK;
+    });
 }
 
 ibvh_status ibvh_pack_records(const ibvh_types *types, const void *volumes, const void *keys, const void *perm,
@@ -265,14 +258,13 @@ ibvh_status ibvh_pack_records(const ibvh_types *types, const void *volumes, cons
         using V = typename decltype(vt)::type;
         return dispatch_index(types->index_type, [&](auto it) -> int {
             using I = typename decltype(it)::type;
-            if (types->morton_type == IBVH_U64)
-                IBVH_LAUNCH((distk::pack_kernel<V, I, uint64_t>), dim3(blocks), dim3(256), 0, st, (const V *)volumes,
-                            (const uint64_t *)keys, (const uint32_t *)perm, index_base, n, dl, (char *)records_out);
-            else
-                IBVH_LAUNCH((distk::pack_kernel<V, I, uint32_t>), dim3(blocks), dim3(256), 0, st, (const V *)volumes,
-                            (const uint32_t *)keys, (const uint32_t *)perm, index_base, n, dl, (char *)records_out);
-            IBVH_LAUNCH_CHECK();
-            return (int)IBVH_OK;
+            return dispatch_key(types->morton_type == IBVH_U64 ? 8 : 4, [&](auto kt) -> int {
+                using K = typename decltype(kt)::type;
+                IBVH_LAUNCH((distk::pack_kernel<V, I, K>), dim3(blocks), dim3(256), 0, st, (const V *)volumes, (const K *)keys,
+                            (const uint32_t *)perm, index_base, n, dl, (char *)records_out);
+                IBVH_LAUNCH_CHECK();
+                return (int)IBVH_OK;
+            });
         });
     });
 }

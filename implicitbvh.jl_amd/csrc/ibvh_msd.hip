@@ -979,10 +979,9 @@ static size_t carve_tables(Tables *tb, char *base, int radix, int num_tiles, int
 }
 
 Plan make_plan(int64_t n, int key_bits, int key_bytes, int leaf_bytes, void *sort_scratch) {
-    // development knobs (ibvh_set_tuning): msd = 0 disables the path, msd_avg moves the digit width (the finish geometry is
-    // still a row of kFinish)
+    // development knob (ibvh_set_tuning): msd_avg moves the digit width (the finish geometry is still a row of kFinish)
     Plan p{};
-    if (!g_tuning.msd || n < 4096 || key_bits <= 8 || n >= ((int64_t)1 << 32) - 65536) return p;
+    if (n < 4096 || key_bits <= 8 || n >= ((int64_t)1 << 32) - 65536) return p;
     int bits = 6; // (>= 6: the scan kernel works on blocks of 64 digits)
     while (bits < 11 && bits < key_bits - 1 && (n >> bits) > g_tuning.msd_avg) ++bits;
     // 1.3e7 .. 2.7e7 leaves: 4,096 cells keep the average cell within the 8,192-record finish workgroup (the 16,384-
@@ -1109,8 +1108,8 @@ int sort_records(const Plan &p, int key_bytes, int key_bits, const void *keys, i
         // the encode kernel fused; the lists and the candidates live behind the splitters in the sort scratch)
         const size_t hsm = ((size_t)(2 * key_bytes + 4)) << p.bits;
         const uint32_t cap = (uint32_t)(p.ftpb * p.fipt);
-        auto run = [&](auto kt) -> int {
-            using K = decltype(kt);
+        const int e = dispatch_key(key_bytes, [&](auto kt) -> int {
+            using K = typename decltype(kt)::type;
             using SG = SampleGeom<K>;
             K *cand = (K *)p.tb.splitters + ((size_t)1 << p.bits) + 1, *lists = cand + ((size_t)1 << p.bits) + 1;
             IBVH_HIP_CHECK(hipFuncSetAttribute((const void *)sample_rank_kernel<K>, hipFuncAttributeMaxDynamicSharedMemorySize, kMaxLds));
@@ -1121,8 +1120,8 @@ int sort_records(const Plan &p, int key_bytes, int key_bits, const void *keys, i
             IBVH_LAUNCH((bucket_hist_kernel<K>), dim3(p.num_tiles), dim3(512), hsm, st, (const K *)keys, n, p.tb, (const K *)cand, p.bits, (int)tile_elems,
                         key_bits, cap);
             return IBVH_OK;
-        };
-        if (int e = key_bytes == 8 ? run(uint64_t{}) : run(uint32_t{})) return e;
+        });
+        if (e) return e;
     }
     {
         const int radix = 1 << p.bits, ndb = radix >> 6;

@@ -2,7 +2,8 @@
 //
 // Replaces AK.sort!(leaves, by = bv -> bv.morton) (reference src/build.jl:248-253).  The
 // reference sorts whole 24-byte records with a third-party merge sort; here only (key, position)
-// pairs move through the passes and the records are gathered once at the end (ibvh_build.hip).
+// pairs move through the passes, and for a build the last pass writes the records (RecordArgs).
+// Host interface: ibvh_sort.hpp (plan_pairs decides everything once, sort_pairs runs that plan).
 //
 // One pass (8-bit digit) = three launches, no inter-workgroup communication inside a launch:
 //   hist    : per-tile digit histogram, LDS-staged (ds_add_u32), written digit-major
@@ -14,8 +15,7 @@
 // reference).
 #include <cstdlib>
 
-#include "ibvh_common.hpp"
-#include "ibvh_radix.hpp"
+#include "ibvh_sort.hpp"
 
 namespace ibvh {
 namespace rsort {
@@ -498,17 +498,7 @@ template <class K, int TPB, int IPT> constexpr size_t scatter_smem() {
     return (size_t)TPB * IPT * (sizeof(K) + 4) + (size_t)(TPB / 64) * RADIX * 4 + RADIX * 8 + (TPB / 64) * 4 + 64;
 }
 
-struct Geometry {
-    int tpb, ipt;
-    int tile() const { return tpb * ipt; }
-};
-struct FirstPassPlan {
-    int tpb, ipt, num_tiles;
-    uint32_t *tile_hist;
-    uint32_t mask;
-    int shift, bits; // the digit the first pass sorts on: (key >> shift) & mask
-};
-// The geometries (threads, keys per thread) the kernels below are compiled for.  The planners pick an entry of these
+// The geometries (threads, keys per thread) the kernels below are compiled for.  plan_pairs() picks an entry of these
 // tables and sort_pairs() dispatches over the same tables, so every plan has its kernels.  (X-macros: X(args..., T, P).)
 //   tiles of the LSD passes and of the hybrid's partition: small, large (choose_geometry)
 //   workgroups of the hybrid's bucket sort, by capacity: 2,048 and 4,096 keys (choose_msd)
@@ -551,10 +541,9 @@ size_t scratch_bytes(int64_t n) {
 
 template <class K, int TPB, int IPT>
 int run_passes(K *keys, uint32_t *vals, K *keys_alt, uint32_t *vals_alt, int64_t n, int key_bits, bool vals_implicit,
-               int32_t *result_in_alt, void *scratch, hipStream_t st, bool first_hist_done, const RecordArgs *records) {
-    const int num_tiles = (int)ceil_div(n, TPB * IPT);
-    uint32_t *tile_hist = (uint32_t *)scratch;
-    uint32_t *digit_total = (uint32_t *)((char *)scratch + align_up((int64_t)RADIX * num_tiles * 4, 256));
+               int32_t *result_in_alt, uint32_t *tile_hist, int num_tiles, hipStream_t st, bool first_hist_done,
+               const RecordArgs *records) {
+    uint32_t *digit_total = (uint32_t *)((char *)tile_hist + align_up((int64_t)RADIX * num_tiles * 4, 256));
     constexpr size_t smem = scatter_smem<K, TPB, IPT>();
     // (per call, not once per process: the attribute is per DEVICE, and a host may drive several GPUs from one process)
     IBVH_HIP_CHECK(hipFuncSetAttribute((const void *)scatter_kernel<K, TPB, IPT, false>,
@@ -594,12 +583,11 @@ int run_passes(K *keys, uint32_t *vals, K *keys_alt, uint32_t *vals_alt, int64_t
 
 template <class K, int TPB, int IPT, int BT, int BI>
 int run_msd(K *keys, uint32_t *vals, K *keys_alt, uint32_t *vals_alt, int64_t n, int key_bits, bool vals_implicit,
-            int32_t *result_in_alt, void *scratch, hipStream_t st, bool first_hist_done, const RecordArgs *records, int digit_bits) {
-    const int num_tiles = (int)ceil_div(n, TPB * IPT);
+            int32_t *result_in_alt, uint32_t *tile_hist, int num_tiles, hipStream_t st, bool first_hist_done,
+            const RecordArgs *records, int digit_bits) {
     const int radix = 1 << digit_bits;
     const int shift = key_bits - digit_bits;
-    uint32_t *tile_hist = (uint32_t *)scratch;
-    uint32_t *digit_total = (uint32_t *)((char *)scratch + align_up((int64_t)radix * num_tiles * 4, 256));
+    uint32_t *digit_total = (uint32_t *)((char *)tile_hist + align_up((int64_t)radix * num_tiles * 4, 256));
     const size_t ssm = scatter_wide_smem<K, TPB, IPT>(digit_bits);
     constexpr size_t bsm = bucket_smem<K, BT, BI>();
     IBVH_HIP_CHECK(hipFuncSetAttribute((const void *)scatter_wide_kernel<K, TPB, IPT>,
@@ -626,17 +614,18 @@ int run_msd(K *keys, uint32_t *vals, K *keys_alt, uint32_t *vals_alt, int64_t n,
     return IBVH_OK;
 }
 
-// vals_implicit: the values of the first pass are the element positions 0..n-1 (vals is not read).
-// Where the first pass expects its per-tile histogram ([RADIX][num_tiles], digit-major) and the tile
-// geometry it will use, for a producer that fuses that histogram into its own pass (ibvh_build.hip).
-FirstPassPlan first_pass_plan(int64_t n, int key_bits, int key_bytes, void *scratch) {
-    const Geometry g = choose_geometry(n);
-    FirstPassPlan p;
-    p.tpb = g.tpb;
-    p.ipt = g.ipt;
-    p.num_tiles = (int)ceil_div(n, g.tile());
-    p.tile_hist = (uint32_t *)scratch;
+// what sort_pairs() takes (its own argument check; plan_pairs() plans nothing for anything else)
+static bool sortable(int64_t n, int key_bits, int key_bytes) {
+    return n >= 0 && n < (int64_t(1) << 32) && key_bits >= 1 && key_bits <= key_bytes * 8;
+}
+
+PairsPlan plan_pairs(int64_t n, int key_bits, int key_bytes, void *scratch) {
+    PairsPlan p{};
+    if (!sortable(n, key_bits, key_bytes)) return p;
+    p.tile = choose_geometry(n);
     const MsdPlan mp = choose_msd(n, key_bits, key_bytes);
+    p.msd_bits = mp.bits;
+    p.bucket = mp.bucket;
     if (mp.bits) { // MSD partition first: histogram of the TOP digit
         p.bits = mp.bits;
         p.shift = key_bits - mp.bits;
@@ -645,36 +634,35 @@ FirstPassPlan first_pass_plan(int64_t n, int key_bits, int key_bytes, void *scra
         p.shift = 0;
     }
     p.mask = (1u << p.bits) - 1u;
+    p.num_tiles = (int)ceil_div(n, p.tile.tile());
+    p.tile_hist = (uint32_t *)scratch;
     return p;
 }
 
-bool uses_hybrid(int64_t n, int key_bits, int key_bytes) { return choose_msd(n, key_bits, key_bytes).bits != 0; }
-
-int sort_pairs(int key_bytes, int key_bits, int64_t n, void *keys, void *vals, void *keys_alt, void *vals_alt,
-               bool vals_implicit, int32_t *result_in_alt, void *scratch, size_t scratch_sz, hipStream_t st,
-               bool first_hist_done, const RecordArgs *records) {
-    if (n < 0 || n >= (int64_t(1) << 32) || key_bits < 1 || key_bits > key_bytes * 8) return IBVH_ERR_INVALID_ARG;
+int sort_pairs(const PairsPlan &p, int key_bytes, int key_bits, int64_t n, void *keys, void *vals, void *keys_alt, void *vals_alt,
+               bool vals_implicit, int32_t *result_in_alt, size_t scratch_sz, hipStream_t st, bool first_hist_done,
+               const RecordArgs *records) {
+    if (!sortable(n, key_bits, key_bytes)) return IBVH_ERR_INVALID_ARG;
     if (scratch_sz < scratch_bytes(n)) return IBVH_ERR_SCRATCH;
     *result_in_alt = 0;
     if (n == 0) return IBVH_OK;
-    const Geometry g = choose_geometry(n);
-    const MsdPlan mp = choose_msd(n, key_bits, key_bytes);
-    // (g and mp.bucket are entries of the tables these cases expand from: one of them matches)
+    // (p.tile and p.bucket are entries of the tables these cases expand from: one of them matches)
 #define IBVH_MSD_CASE(K, T, P, BT, BI)                                                                                \
-    if (g.tpb == T && g.ipt == P && mp.bucket.tpb == BT && mp.bucket.ipt == BI)                                       \
+    if (p.tile.tpb == T && p.tile.ipt == P && p.bucket.tpb == BT && p.bucket.ipt == BI)                               \
         return run_msd<K, T, P, BT, BI>((K *)keys, (uint32_t *)vals, (K *)keys_alt, (uint32_t *)vals_alt, n, key_bits, \
-                                        vals_implicit, result_in_alt, scratch, st, first_hist_done, records, mp.bits);
+                                        vals_implicit, result_in_alt, p.tile_hist, p.num_tiles, st, first_hist_done,  \
+                                        records, p.msd_bits);
 #define IBVH_MSD_TILE(K, T, P) IBVH_SORT_BUCKETS(IBVH_MSD_CASE, K, T, P)
 #define IBVH_SORT_CASE(K, T, P)                                                                                       \
-    if (g.tpb == T && g.ipt == P)                                                                                     \
+    if (p.tile.tpb == T && p.tile.ipt == P)                                                                           \
         return run_passes<K, T, P>((K *)keys, (uint32_t *)vals, (K *)keys_alt, (uint32_t *)vals_alt, n, key_bits,     \
-                                   vals_implicit, result_in_alt, scratch, st, first_hist_done, records);
+                                   vals_implicit, result_in_alt, p.tile_hist, p.num_tiles, st, first_hist_done, records);
     if (key_bytes == 4) {
-        if (mp.bits) { IBVH_SORT_TILES(IBVH_MSD_TILE, uint32_t) }
+        if (p.msd_bits) { IBVH_SORT_TILES(IBVH_MSD_TILE, uint32_t) }
         IBVH_SORT_TILES(IBVH_SORT_CASE, uint32_t)
     }
     if (key_bytes == 8) {
-        if (mp.bits) { IBVH_SORT_TILES(IBVH_MSD_TILE, uint64_t) }
+        if (p.msd_bits) { IBVH_SORT_TILES(IBVH_MSD_TILE, uint64_t) }
         IBVH_SORT_TILES(IBVH_SORT_CASE, uint64_t)
     }
 #undef IBVH_SORT_CASE
@@ -698,8 +686,9 @@ ibvh_status ibvh_sort_pairs(int32_t key_bytes, int32_t key_bits, int64_t n, void
                             void *vals_alt, int32_t *result_in_alt, void *scratch, size_t scratch_bytes, void *stream) {
     if (!result_in_alt) return IBVH_ERR_INVALID_ARG;
     if (n > 0 && (!keys || !vals || !keys_alt || !vals_alt || !scratch)) return IBVH_ERR_INVALID_ARG;
-    return (ibvh_status)ibvh::rsort::sort_pairs(key_bytes, key_bits, n, keys, vals, keys_alt, vals_alt, false,
-                                                result_in_alt, scratch, scratch_bytes, (hipStream_t)stream, false, nullptr);
+    const ibvh::rsort::PairsPlan plan = ibvh::rsort::plan_pairs(n, key_bits, key_bytes, scratch);
+    return (ibvh_status)ibvh::rsort::sort_pairs(plan, key_bytes, key_bits, n, keys, vals, keys_alt, vals_alt, false, result_in_alt,
+                                                scratch_bytes, (hipStream_t)stream, false, nullptr);
 }
 
 } // extern "C"

@@ -175,7 +175,9 @@ def test_fixed_extrema_option():
 # stand-alone pieces through the raw C ABI
 # ---------------------------------------------------------------------------------------------
 @pytest.mark.parametrize("key_bytes,key_bits", [(4, 30), (4, 15), (4, 32), (8, 63), (8, 40)])
-@pytest.mark.parametrize("n", [1, 63, 2048, 2049, 100000, (1 << 22) + 77])
+# 2047 | 2048: LSD passes | hybrid; 3073 * 2048: the smallest n beyond the hybrid (its average bucket no longer fits 3/4 of a
+# 4,096-key workgroup at 11 bits): LSD passes with the large tile
+@pytest.mark.parametrize("n", [1, 63, 2047, 2048, 2049, 100000, (1 << 22) + 77, 3073 * 2048])
 def test_sort_pairs_matches_stable_sort(key_bytes, key_bits, n):
     rng = np.random.default_rng(n + key_bits)
     kdt = np.uint32 if key_bytes == 4 else np.uint64
