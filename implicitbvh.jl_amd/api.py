@@ -31,6 +31,7 @@ __all__ = [
     "memory_index", "level_indices", "isvirtual", "bounding_volumes_from_triangles", "generate_spheres",
     "NARROW_MORTON_LT", "NARROW_INDEX_LT", "NARROW_RAY_ORIGIN_OUTSIDE", "LeafBatch", "lvt_work_counters", "refit",
     "resolve_triangles", "raycast", "RayHits", "closest_points", "ClosestPoints",
+    "nearest_leaves", "NearestLeaves",
 ]
 
 NARROW_MORTON_LT = abi.NARROW_MORTON_LT
@@ -1422,6 +1423,63 @@ def closest_points(bvh, triangles, points, max_distance=None, presorted=False):
     if order is not None:
         index, d2, q = (torch.empty_like(x).index_copy_(0, order, x) for x in (index, d2, q))
     return ClosestPoints(index, d2, q)
+
+
+# ---------------------------------------------------------------------------------------------
+# k nearest leaves for a batch of query points (ibvh_nearest_leaves; no reference counterpart)
+# ---------------------------------------------------------------------------------------------
+class NearestLeaves:
+    """Per query point, nearest first: .index (N, k) the leaves' user indices, .d2 (N, k) the SQUARED distances to their
+    centres.  Slots beyond the answers (fewer than k leaves, or fewer within max_distance, or a NaN point) hold 0 / +Inf."""
+
+    def __init__(self, index, d2):
+        self.index, self.d2 = index, d2
+
+
+def nearest_leaves(bvh, points, k=1, max_distance=None, presorted=False):
+    """For every query point the k leaves of `bvh` whose centres are nearest -> NearestLeaves (include/ibvh.h,
+    ibvh_nearest_leaves: the arithmetic, the tie rule — smallest distance, then the smaller index — and why pruning loses
+    nothing are spelled out there).  One launch, exact: bit-equal to a brute force over all leaves.
+
+    bvh: BSphere or BBox leaves under BBox nodes of the same or a wider float type (refit is fine).  points: (3, N) CUDA
+    tensor of the leaves' dtype, as for traverse_rays.  k: 1 .. 16.  max_distance: search radius (None = unbounded); it is
+    squared in the leaves' dtype on the host and a leaf qualifies iff its squared centre distance <= that product.  The
+    device walks the batch in Morton order of the points (lanes of a wave then share nodes) and the rows are put back in the
+    caller's order; presorted=True walks it as given.
+
+    ValueError: sphere nodes, nodes narrower than the leaves, k out of range, a wrong dtype, device or shape."""
+    torch = _require_gpu()
+    t = bvh.types
+    if t.node_kind != abi.BBOX:
+        raise ValueError("nearest_leaves: the BVH must have BBox nodes (the exact bound needs boxes that contain the leaves' centres)")
+    if t.leaf_float == abi.F64 and t.node_float == abi.F32:
+        raise ValueError("nearest_leaves: Float32 nodes over Float64 leaves do not contain them exactly")
+    if not (isinstance(k, (int, np.integer)) and not isinstance(k, bool) and 1 <= k <= abi.NEAREST_MAX_K):
+        raise ValueError(f"nearest_leaves: k must be an integer in 1..{abi.NEAREST_MAX_K}")
+    ft = _torch_float(t.leaf_float)
+    if not (isinstance(points, torch.Tensor) and points.dim() == 2 and points.shape[0] == 3):
+        raise ValueError("nearest_leaves: size(points, 1) == 3 must hold")
+    if points.dtype != ft or not points.is_cuda:
+        raise ValueError(f"nearest_leaves: points must be a {ft} tensor on the GPU (device='cuda')")
+    n = int(points.shape[1])
+    index = torch.empty((n, k), dtype=_torch_index(t.index_type), device="cuda")
+    d2 = torch.empty((n, k), dtype=ft, device="cuda")
+    if n == 0:
+        return NearestLeaves(index, d2)
+    radius2 = None
+    if max_distance is not None:
+        npdt = np.float32 if t.leaf_float == abi.F32 else np.float64
+        with np.errstate(over="ignore"):
+            m = npdt(max_distance) * npdt(max_distance)
+        radius2 = C.byref((C.c_float if t.leaf_float == abi.F32 else C.c_double)(m))
+    p = points.t().contiguous()  # (N, 3) row-major == (3, N) column-major
+    order = None if presorted else _morton_order(p)
+    if order is not None:
+        p = p[order]
+    lib.call("ibvh_nearest_leaves", C.byref(bvh.struct()), _ptr(p), n, int(k), radius2, _ptr(index), _ptr(d2), _stream())
+    if order is not None:
+        index, d2 = (torch.empty_like(x).index_copy_(0, order, x) for x in (index, d2))
+    return NearestLeaves(index, d2)
 
 
 def lvt_work_counters(bvh, bvh2=None, points=None, directions=None):

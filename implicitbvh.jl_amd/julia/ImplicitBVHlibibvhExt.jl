@@ -286,6 +286,10 @@ c_closest_triangles(bvh, triangles, num_triangles, points, num_points, max_dista
           (Ref{IbvhBvh}, Ptr{Cvoid}, Int64, Ptr{Cvoid}, Int64, Ptr{Cvoid}, Ptr{Cvoid}, Ptr{Cvoid}, Ptr{Cvoid}, Ptr{Cvoid}, Ptr{Cvoid}),
           bvh, triangles, num_triangles, points, num_points, max_distance2, closest_index, closest_d2, closest_point,
           flag, stream)
+c_nearest_leaves(bvh, points, num_points, k, max_distance2, nearest_index, nearest_d2, stream) =
+    ccall((:ibvh_nearest_leaves, libibvh), Cint,
+          (Ref{IbvhBvh}, Ptr{Cvoid}, Int64, Int32, Ptr{Cvoid}, Ptr{Cvoid}, Ptr{Cvoid}, Ptr{Cvoid}),
+          bvh, points, num_points, k, max_distance2, nearest_index, nearest_d2, stream)
 c_lvt_scratch_bytes(types, n_items, cache_slots, out) =
     ccall((:ibvh_lvt_scratch_bytes, libibvh), Cint,
           (Ref{IbvhTypes}, Int64, Int32, Ref{Csize_t}),
@@ -670,6 +674,46 @@ function closest_points(bvh::RocBVH{I}, triangles::ROCMatrix{T}, points::ROCMatr
     isnothing(order) && return (; index, distance2, point)
     inv = ROCVector{Int64}(invperm(order))
     (; index=index[inv], distance2=distance2[inv], point=point[:, inv])
+end
+
+# ---- k nearest leaves for a batch of query points (include/ibvh.h, ibvh_nearest_leaves) ------------------------------
+const IBVH_NEAREST_MAX_K = 16
+"""
+    nearest_leaves(bvh::BVH, points::ROCMatrix{T}; k=1, max_distance=nothing, presorted=false) -> (; index, d2)
+
+For every query point (column of the 3 x N `points`) the `k` leaves of `bvh` whose centres are nearest, nearest first:
+`index[:, i]` their user indices and `d2[:, i]` the squared distances, both k x N.  Slots beyond the answers (fewer than `k`
+leaves, fewer within `max_distance`, a NaN point) hold 0 / `Inf`.  The result is the k lexicographically smallest
+(squared distance, index) over ALL leaves — bit-equal to a brute force; the arithmetic, the tie rule and why pruning loses
+nothing are spelled out in include/ibvh.h.  The BVH must have `BSphere{T}` or `BBox{T}` leaves under `BBox` nodes of `T` or
+wider (`refit!` is fine); anything else raises ArgumentError.  `max_distance` is squared in `T` on the host.  The device walks
+the batch along a Morton curve through the points and the outputs come back in the caller's order; `presorted=true` walks it
+as given.  Not a method of ImplicitBVH: the reference has no such query.
+"""
+function nearest_leaves(bvh::RocBVH{I}, points::ROCMatrix{T}; k::Integer=1, max_distance=nothing,
+                        presorted::Bool=false) where {I, T}
+    d = bvh_desc(bvh)
+    isnothing(d) && throw(ArgumentError("nearest_leaves: no libibvh instantiation for this BVH's types"))
+    L = leaf_volume_type(bvh.leaves)
+    (L === BSphere{T} || L === BBox{T}) && eltype(bvh.nodes) <: BBox && sizeof(eltype(bvh.nodes)) >= sizeof(BBox{T}) ||
+        throw(ArgumentError("nearest_leaves: the BVH must have BSphere{$T} or BBox{$T} leaves under BBox nodes of $T or wider"))
+    1 <= k <= IBVH_NEAREST_MAX_K || throw(ArgumentError("nearest_leaves: 1 <= k <= $IBVH_NEAREST_MAX_K must hold"))
+    size(points, 1) == 3 || throw(ArgumentError("size(points, 1) == 3 must hold"))
+    n = size(points, 2)
+    index = similar(points, I, Int(k), n)                      # k x N column-major == N x k row-major
+    d2 = similar(points, T, Int(k), n)
+    n == 0 && return (; index, d2)
+    radius2 = isnothing(max_distance) ? C_NULL : Ref(T(max_distance) * T(max_distance))
+    order = presorted ? nothing : point_morton_order(points)
+    p = isnothing(order) ? points : points[:, ROCVector{Int64}(order)]
+    GC.@preserve radius2 begin
+        r2 = radius2 === C_NULL ? Ptr{Cvoid}(C_NULL) : Ptr{Cvoid}(Base.unsafe_convert(Ptr{T}, radius2))
+        check(c_nearest_leaves(d, devptr(p), Int64(n), Int32(k), r2, devptr(index), devptr(d2), stream_ptr()),
+              "ibvh_nearest_leaves")
+    end
+    isnothing(order) && return (; index, d2)
+    inv = ROCVector{Int64}(invperm(order))
+    (; index=index[:, inv], d2=d2[:, inv])
 end
 
 """

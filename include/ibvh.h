@@ -43,7 +43,8 @@ extern "C" {
  *   6: IBVH_PAIR_MIXED_TYPES (pair LVT traversals of two BVHs of different leaf / node types)
  *   7: ibvh_refit; ibvh_rays_resolve_triangles (additive under 7: a new entry point, no struct layout or existing
  *      argument list moves, so a binding written against the earlier 7 keeps working); ibvh_closest_triangles (additive
- *      under 7 in the same way); argument checks only, no layout or argument list moves: ibvh_key_histogram takes
+ *      under 7 in the same way); ibvh_nearest_leaves and IBVH_NEAREST_MAX_K (additive under 7 in the same way);
+ *      argument checks only, no layout or argument list moves: ibvh_key_histogram takes
  *      what fits its LDS staging (10 rows at 12-bit digits) and refuses shift > 63 and a negative prefix_shift,
  *      ibvh_pack_records / ibvh_dist_plan answer IBVH_ERR_OVERFLOW for an index past IBVH_I32 */
 #define IBVH_ABI_VERSION 7
@@ -491,6 +492,58 @@ ibvh_status ibvh_closest_triangles(const ibvh_bvh *bvh, const void *triangles, i
                                    const void *points, int64_t num_points, const void *max_distance2,
                                    void *closest_index, void *closest_d2, void *closest_point,
                                    void *flag, void *stream);
+
+/* ----------------------------------------------------------------------------------- */
+/* k nearest leaves for a batch of query points                                         */
+/* ----------------------------------------------------------------------------------- */
+/* For every query point: the k leaves of the BVH whose CENTRES are nearest, and their squared distances, optionally within
+ * a search radius.  No reference counterpart (every traversal of the reference is a fixed-volume overlap test); ONE launch,
+ * NO host synchronisation, no atomics, no scratch buffer.  Sphere leaves and box leaves.
+ *   points     : num_points x 3 row-major values of bvh->types.leaf_float, `flt` below, processed in the order given
+ *                (neighbours in memory that are neighbours in space walk the same nodes: sort a scattered batch along a
+ *                Morton curve first)
+ *   k          : 1 .. IBVH_NEAREST_MAX_K
+ *   max_distance2 : HOST pointer to one value of `flt`, the SQUARED search radius; NULL = +Inf (unbounded)
+ * Outputs — each optional, at least one non-NULL:
+ *   nearest_index : num_points x k x I, row i = the user indices (.index of the leaf records) of point i's answers
+ *   nearest_d2    : num_points x k x flt, their squared distances
+ *   Row i holds the answers in ASCENDING (d2, index) order.  Slots beyond the answers hold 0 / +Inf = unfilled: fewer than k
+ *   leaves, fewer than k within the radius, a NaN query point (or radius).  (With caller-supplied indices that may be 0, or an
+ *   unbounded search in which a distance overflows to +Inf, the pair 0 / +Inf can also be an answer: a row has as many
+ *   answers as there are leaves with d2 <= max_distance2, capped at k.)
+ * All arguments are validated before any launch: NULL required pointers, negative sizes, k out of range, no output at all, a
+ * tree shape that is not an ImplicitTree's: IBVH_ERR_INVALID_ARG.  num_points == 0: IBVH_OK, nothing is touched.
+ * The result is defined independently of how it is found.  In `flt`, every operation rounded once (nothing fused):
+ *     c_j  = center(volume of leaf j): a sphere's x (bsphere.jl:142); a box's 0.5 * (lo + up) per component (bbox.jl:100-102)
+ *     e    = p - c_j;   d2_j = (e0*e0 + e1*e1) + e2*e2          (dist3sq's order, utils.jl:168-171)
+ *   and the answer for p is the k LEXICOGRAPHICALLY SMALLEST (d2_j, index_j) over ALL leaves j with d2_j <= max_distance2:
+ *   the smallest distances, and among equal distances the SMALLER INDEX.  Every comparison is false on NaN: a leaf whose d2
+ *   is NaN is never an answer, a NaN query point has none.  The outputs carry the winners' bits unchanged.
+ * Pruning is lossless WITHOUT an epsilon, by the argument of ibvh_closest_triangles.  For a box B that contains c_j,
+ *     c = clamp(p, B.lo, B.up) per component;  f = p - c;  lb(B) = (f0*f0 + f1*f1) + f2*f2
+ *   is the same operation order as d2_j, |p - c| <= |p - c_j| per component, and round-to-nearest subtraction, squaring and
+ *   addition are monotone: the COMPUTED lb(B) <= the COMPUTED d2_j.  The walk skips a node or a leaf iff lb > the k-th best
+ *   (d2) so far (which starts at max_distance2) — strictly: lb == that may hide an equal d2 of smaller index.  A leaf is
+ *   bounded by its stored volume's box — for a sphere x -/+ r computed in `flt`, as the merge forms it (merge.jl:47-51) —
+ *   and only then is its centre distance taken.  Traversal order and work mapping therefore cannot change the result.
+ * What makes it exact: EVERY LEAF CENTRE MUST LIE IN THE BOXES ABOVE IT (its own and every node's on its path).
+ *   Boxes with lo <= up whose lo + up does not overflow: holds (lo <= 0.5 * (lo + up) <= up after rounding; node boxes are
+ *   exact minima / maxima, merge.jl:30-40).  Spheres with r >= 0: x - r <= x <= x + r after rounding, and the parent of two
+ *   leaves is the minima / maxima of the two x -/+ r (merge.jl:58-81) — except where that merge takes its shortcut
+ *   `dist(a, b) + a.r <= b.r`: the parent is then b's box alone, and a's centre is inside it up to the rounding of that
+ *   distance (a sphere inside another with less than a few ulp to spare; exact again when the centres coincide, as for
+ *   duplicates).  Holds after ibvh_refit (the same merges over the moved volumes).  Infinite radii are fine (the box is all
+ *   of space).  A negative radius (x + r < x - r) voids it.
+ * Accepted BVHs: node_kind == IBVH_BBOX, leaf_kind IBVH_BSPHERE or IBVH_BBOX, node_float the same as or wider than leaf_float
+ *   (a widening conversion is exact); any index and Morton type.  Anything else — sphere nodes, F64 leaves under F32 nodes —
+ *   is IBVH_ERR_UNSUPPORTED, never an answer.  Levels above bvh->built_level are not read.
+ * NaN: a leaf whose centre holds a NaN has a NaN d2 and is never an answer.  But, as for ibvh_closest_triangles, a NaN leaf
+ *   box (a NaN radius; Inf - Inf) can make merge.jl's `a < b ? a : b` produce a node box that does NOT contain the NaN-free
+ *   leaves below it: on volumes with NaN the other leaves' answers are only guaranteed in trees of at most two leaves.
+ * No flag word: nothing is gathered through an index, there is nothing to guard. */
+#define IBVH_NEAREST_MAX_K 16
+ibvh_status ibvh_nearest_leaves(const ibvh_bvh *bvh, const void *points, int64_t num_points, int32_t k,
+                                const void *max_distance2, void *nearest_index, void *nearest_d2, void *stream);
 
 /* ----------------------------------------------------------------------------------- */
 /* breadth-first traversal (BFSTraversal): level-synchronous pair queues                 */
