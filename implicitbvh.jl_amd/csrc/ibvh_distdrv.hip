@@ -492,10 +492,10 @@ ibvh_status ibvh_dist_exchange(const ibvh_types *types, const ibvh_comm *comm, c
 } // extern "C"
 
 // ---- cross-shard contact completion behind the boundary ---------------------------------------------------
-// Per-slice trees do not see contacts between leaves of different slices.  Every rank publishes its slice's root box and leaf
-// count (ONE all-gather of 64 bytes a rank); for every pair of slices r < s whose boxes touch, rank s sends rank r the leaves
-// that can matter there — those whose own box touches r's root box (a thin shell of the slice: Morton slices of a cloud meet at
-// faces), NOT its tree: round 4 shipped whole trees, 600 MB a peer at config 5 for 0.5 % of the contacts — and rank r builds an
+// Per-slice trees do not see contacts between leaves of different slices.  Every rank publishes its slice's description — up to
+// 16 node boxes of its tree, see _plan below — and leaf count (ONE all-gather); for every pair of slices r < s whose boxes touch,
+// rank s sends rank r the leaves that can matter there — those whose own box touches one of r's boxes (a thin shell of the slice:
+// Morton slices of a cloud meet at faces), NOT its tree: round 4 shipped whole trees, 600 MB a peer at config 5 for 0.5 % of the contacts — and rank r builds an
 // ordinary BVH over what it received (ibvh_build: extrema, Morton sort, merge) and runs the ordinary pair traversal
 // (ibvh_traverse_pair_lvt_*) of its own tree against it.  Per-slice self contacts and these pairs together are the contact set
 // of the whole cloud, every pair exactly once (tests/test_gpu_dist_procs.py, test_gpu_parity.py, test_gpu_dist.py).
@@ -514,12 +514,13 @@ ibvh_status ibvh_dist_exchange(const ibvh_types *types, const ibvh_comm *comm, c
 // stable Morton sort then orders leaves of EQUAL codes differently from run to run, and with them the order of their cross
 // contacts — cross contacts are a SET (include/ibvh.h); the per-slice lists keep the reference's order.
 namespace {
-// the box a leaf is tested with, in double
+// the box a volume is tested with, in double: x -+ r AFTER the exact conversion to double (in T the difference rounds to nearest
+// — inwards half the time — and the published boxes would depend on the float type they were computed in)
 template <class T> IBVH_D void leaf_box(const BSphere<T> &s, double (&lo)[3], double (&up)[3]) {
 #pragma unroll
     for (int k = 0; k < 3; ++k) {
-        lo[k] = (double)(s.x[k] - s.r);
-        up[k] = (double)(s.x[k] + s.r);
+        lo[k] = (double)s.x[k] - (double)s.r;
+        up[k] = (double)s.x[k] + (double)s.r;
     }
 }
 template <class T> IBVH_D void leaf_box(const BBox<T> &b, double (&lo)[3], double (&up)[3]) {
@@ -538,7 +539,9 @@ struct CrossRec {
 };
 static_assert(sizeof(CrossRec) == IBVH_DIST_CROSS_BOXES * 48 + 16, "record layout (IBVH_DIST_CROSS_SCRATCH)");
 
-template <class V> IBVH_D void box_of(const V &v, double out[6]) { // the volume's box in double: never smaller than the box any node type would hold
+// the volume's box in double, exact.  The box a narrower node type holds for the same volume is this one rounded to nearest, so
+// it can be larger by half an ulp of that type: the filter's eps widening of the receiver's boxes covers it
+template <class V> IBVH_D void box_of(const V &v, double out[6]) {
     double lo[3], up[3];
     leaf_box(v, lo, up);
 #pragma unroll

@@ -730,7 +730,7 @@ ibvh_status ibvh_dist_exchange(const ibvh_types *types, const ibvh_comm *comm, c
                                void *scratch, size_t scratch_bytes, void *records_out, void *stream);
 
 /* Cross-shard contact completion: the contacts between leaves of DIFFERENT slices, which the
- * per-slice self-traversals cannot see.  Root boxes and leaf counts of all slices are all-gathered; for every pair of slices
+ * per-slice self-traversals cannot see.  Descriptions and leaf counts of all slices are all-gathered; for every pair of slices
  * r < s whose boxes touch, rank s sends rank r the leaves whose own box touches one of r's boxes (a slice is described by
  * <= 16 node boxes of its tree, refined from the root by always splitting the largest: a Morton slice is not convex) — a thin
  * shell of its slice, not its tree — in ONE all_to_all_v over the same vtable; rank r builds an ordinary BVH over each set it received
@@ -760,11 +760,11 @@ typedef struct ibvh_dist_cross_plan_t {
     int64_t recv_offset[IBVH_DIST_MAX_RANKS];    /* [n_recv] byte offset of that set's leaves in the import buffer (the sets are contiguous; the room for their trees' nodes and skips follows the last set) */
     int64_t scratch_offset[IBVH_DIST_MAX_RANKS]; /* [n_recv] byte offset of its counts + traversal scratch                   */
     int64_t slice_leaves[IBVH_DIST_MAX_RANKS];   /* [size] leaves of every rank's slice                                      */
-    int32_t touches[IBVH_DIST_MAX_RANKS];        /* [size] 1: this rank's root box touches rank r's (r != rank)              */
-    int64_t send_leaves[IBVH_DIST_MAX_RANKS];    /* [size] own leaves rank r gets (r < rank, boxes touching r's root box)    */
+    int32_t touches[IBVH_DIST_MAX_RANKS];        /* [size] 1: one of this rank's boxes (below) touches one of rank r's (r != rank) */
+    int64_t send_leaves[IBVH_DIST_MAX_RANKS];    /* [size] own leaves rank r gets (r < rank: those whose box touches one of r's boxes) */
     int64_t send_offset[IBVH_DIST_MAX_RANKS];    /* [size] where they are compacted in the export buffer (contiguous, by rank) */
     int32_t n_boxes[IBVH_DIST_MAX_RANKS];        /* [size] boxes that describe rank r's slice (1 .. IBVH_DIST_CROSS_BOXES)   */
-    double boxes[IBVH_DIST_MAX_RANKS][IBVH_DIST_CROSS_BOXES][6]; /* [size] ... node boxes of its tree, refined greedily (lo, up) */
+    double boxes[IBVH_DIST_MAX_RANKS][IBVH_DIST_CROSS_BOXES][6]; /* [size] ... node boxes of its tree, refined greedily (lo, up); a sphere's box is x -+ r in double */
 } ibvh_dist_cross_plan_t;
 /* device bytes _plan and _exchange need as `scratch` for `size` ranks */
 #define IBVH_DIST_CROSS_SCRATCH(size) ((size_t)(IBVH_DIST_CROSS_BOXES * 48 + 16) * ((size_t)(size) + 1) + (size_t)16 * (size_t)(size) + 512)
