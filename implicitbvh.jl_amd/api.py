@@ -1368,6 +1368,35 @@ def _morton_order(p):
     return torch.argsort((cell[:, 0] << 2) | (cell[:, 1] << 1) | cell[:, 2])
 
 
+def _query_points(points, ft, max_distance, presorted, what):
+    """The point queries' common input: the (3, N) CUDA tensor `points` of dtype ft, checked -> the (N, 3) contiguous tensor
+    the device walks (in Morton order unless presorted), N, max_distance squared in ft as a byref host scalar (None =
+    unbounded) and the permutation applied (None = none)."""
+    torch = _torch()
+    if not (isinstance(points, torch.Tensor) and points.dim() == 2 and points.shape[0] == 3):
+        raise ValueError(f"{what}: size(points, 1) == 3 must hold")
+    if points.dtype != ft or not points.is_cuda:
+        raise ValueError(f"{what}: points must be a {ft} tensor on the GPU (device='cuda')")
+    n = int(points.shape[1])
+    radius2 = None
+    if max_distance is not None:
+        npdt = np.float32 if ft == torch.float32 else np.float64
+        with np.errstate(over="ignore"):
+            m = npdt(max_distance) * npdt(max_distance)
+        radius2 = C.byref((C.c_float if ft == torch.float32 else C.c_double)(m))
+    p = points.t().contiguous()  # (N, 3) row-major == (3, N) column-major
+    order = None if presorted or n == 0 else _morton_order(p)
+    return (p if order is None else p[order]), n, radius2, order
+
+
+def _unpermute(order, outputs):
+    """The outputs' rows back in the caller's order (order: what _query_points returned)."""
+    if order is None:
+        return outputs
+    torch = _torch()
+    return tuple(torch.empty_like(x).index_copy_(0, order, x) for x in outputs)
+
+
 def closest_points(bvh, triangles, points, max_distance=None, presorted=False):
     """For every query point the closest triangle of the mesh `bvh` was built over, the closest point on it and the squared
     distance -> ClosestPoints (include/ibvh.h, ibvh_closest_triangles: the arithmetic, the tie rule — smallest distance, then
@@ -1394,35 +1423,19 @@ def closest_points(bvh, triangles, points, max_distance=None, presorted=False):
     ft = _torch_float(t.leaf_float)
     if tris.dtype != ft:
         raise ValueError(f"closest_points: triangles must be {ft}, the BVH's leaf float type")
-    if not (isinstance(points, torch.Tensor) and points.dim() == 2 and points.shape[0] == 3):
-        raise ValueError("closest_points: size(points, 1) == 3 must hold")
-    if points.dtype != ft or not points.is_cuda:
-        raise ValueError(f"closest_points: points must be a {ft} tensor on the GPU (device='cuda')")
-    n = int(points.shape[1])
+    p, n, radius2, order = _query_points(points, ft, max_distance, presorted, "closest_points")
     idt = _torch_index(t.index_type)
     index = torch.empty(n, dtype=idt, device="cuda")
     d2 = torch.empty(n, dtype=ft, device="cuda")
     q = torch.empty((n, 3), dtype=ft, device="cuda")
     if n == 0:
         return ClosestPoints(index, d2, q)
-    radius2 = None
-    if max_distance is not None:
-        npdt = np.float32 if t.leaf_float == abi.F32 else np.float64
-        with np.errstate(over="ignore"):
-            m = npdt(max_distance) * npdt(max_distance)
-        radius2 = C.byref((C.c_float if t.leaf_float == abi.F32 else C.c_double)(m))
-    p = points.t().contiguous()  # (N, 3) row-major == (3, N) column-major
-    order = None if presorted else _morton_order(p)
-    if order is not None:
-        p = p[order]
     flag = torch.zeros(1, dtype=torch.int32, device="cuda")
     lib.call("ibvh_closest_triangles", C.byref(bvh.struct()), _ptr(tris), tris.shape[0], _ptr(p), n, radius2, _ptr(index), _ptr(d2),
              _ptr(q), _ptr(flag), _stream())
     if int(flag.item()) & 2:
         raise ValueError(f"closest_points: a leaf's index lies outside 1..{tris.shape[0]} (the number of triangles given)")
-    if order is not None:
-        index, d2, q = (torch.empty_like(x).index_copy_(0, order, x) for x in (index, d2, q))
-    return ClosestPoints(index, d2, q)
+    return ClosestPoints(*_unpermute(order, (index, d2, q)))
 
 
 # ---------------------------------------------------------------------------------------------
@@ -1457,29 +1470,13 @@ def nearest_leaves(bvh, points, k=1, max_distance=None, presorted=False):
     if not (isinstance(k, (int, np.integer)) and not isinstance(k, bool) and 1 <= k <= abi.NEAREST_MAX_K):
         raise ValueError(f"nearest_leaves: k must be an integer in 1..{abi.NEAREST_MAX_K}")
     ft = _torch_float(t.leaf_float)
-    if not (isinstance(points, torch.Tensor) and points.dim() == 2 and points.shape[0] == 3):
-        raise ValueError("nearest_leaves: size(points, 1) == 3 must hold")
-    if points.dtype != ft or not points.is_cuda:
-        raise ValueError(f"nearest_leaves: points must be a {ft} tensor on the GPU (device='cuda')")
-    n = int(points.shape[1])
+    p, n, radius2, order = _query_points(points, ft, max_distance, presorted, "nearest_leaves")
     index = torch.empty((n, k), dtype=_torch_index(t.index_type), device="cuda")
     d2 = torch.empty((n, k), dtype=ft, device="cuda")
     if n == 0:
         return NearestLeaves(index, d2)
-    radius2 = None
-    if max_distance is not None:
-        npdt = np.float32 if t.leaf_float == abi.F32 else np.float64
-        with np.errstate(over="ignore"):
-            m = npdt(max_distance) * npdt(max_distance)
-        radius2 = C.byref((C.c_float if t.leaf_float == abi.F32 else C.c_double)(m))
-    p = points.t().contiguous()  # (N, 3) row-major == (3, N) column-major
-    order = None if presorted else _morton_order(p)
-    if order is not None:
-        p = p[order]
     lib.call("ibvh_nearest_leaves", C.byref(bvh.struct()), _ptr(p), n, int(k), radius2, _ptr(index), _ptr(d2), _stream())
-    if order is not None:
-        index, d2 = (torch.empty_like(x).index_copy_(0, order, x) for x in (index, d2))
-    return NearestLeaves(index, d2)
+    return NearestLeaves(*_unpermute(order, (index, d2)))
 
 
 def lvt_work_counters(bvh, bvh2=None, points=None, directions=None):

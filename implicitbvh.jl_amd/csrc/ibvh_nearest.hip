@@ -1,8 +1,7 @@
 // ibvh_nearest.hip — for a batch of query points, the k leaves of a BVH whose CENTRES are nearest: which ones and how far
 // (include/ibvh.h, ibvh_nearest_leaves).  No reference counterpart: every traversal of ImplicitBVH.jl is a fixed-volume
-// overlap test.  The walk is ibvh_closest.hip's — one lane per query, near child first, one owed bit per level in a 64-bit
-// trail word, a node or a leaf skipped iff its bound > the best so far, strictly — generalised from one best triangle to
-// the k best leaf centres, for sphere leaves and box leaves.
+// overlap test.  The walk is ibvh_pointwalk.hpp's — one lane per query, near child first, a node or a leaf skipped iff its
+// bound > the k-th best so far, strictly — here for the k best leaf centres, of sphere leaves and box leaves.
 //
 // The answer is defined over ALL leaves — the k lexicographically smallest (d2, index) — so the walk only has to be
 // lossless.  It is, without an epsilon: a leaf's centre lies in the leaf's own box (x -/+ r around x; lo <= 0.5 (lo + up)
@@ -16,25 +15,14 @@
 // the k-th best and the pruning bound is exact for every k, not only for k = K.  Slots not yet filled hold max_distance2:
 // the last slot is the bound from the first step on.  An insertion is K comparisons and a fully unrolled shift with
 // compile-time slot numbers only: nothing is indexed at run time, nothing lands in scratch memory.
-#include "ibvh_common.hpp"
+#include "ibvh_pointwalk.hpp"
 
 #include <limits>
 
 namespace ibvh {
 namespace nearest {
 
-constexpr int kBlock = 64; // one wave a workgroup: walks differ in length, and a wave that is done frees its slot at once
-
-// lb(B) of include/ibvh.h: the squared distance from p to the box, by the operations of the centre distance
-template <class T> IBVH_D T box_bound(const T *lo, const T *up, const T *p) {
-    T f[3];
-#pragma unroll
-    for (int k = 0; k < 3; ++k) {
-        const T c = p[k] < lo[k] ? lo[k] : (p[k] > up[k] ? up[k] : p[k]);
-        f[k] = p[k] - c;
-    }
-    return (f[0] * f[0] + f[1] * f[1]) + f[2] * f[2];
-}
+using pointwalk::kBlock;
 
 // VL: the leaves' volume type, T its float type; TN: the nodes' (the same or wider — a node box then holds values of T,
 // widened exactly, and narrows back exactly); K: slots of the list, 1 <= k <= K
@@ -45,10 +33,6 @@ __global__ __launch_bounds__(kBlock) void nearest_walk_kernel(TreeDev tree, int 
                                                               int k, typename VL::elt max_d2, I *__restrict__ out_index,
                                                               typename VL::elt *__restrict__ out_d2) {
     using T = typename VL::elt;
-    const int levels = (int)tree.levels;
-    const int64_t vl = tree.virtual_leaves;
-    const uint64_t leaf_first = uint64_t(1) << (levels - 1);
-    const int64_t roots = level_num_real(levels, vl, built_level);
     const int base = K - k; // the first slot of the answer
     for (int64_t item = (int64_t)blockIdx.x * kBlock + threadIdx.x; item < num_points; item += (int64_t)gridDim.x * kBlock) {
         const T p[3] = {points[3 * item], points[3 * item + 1], points[3 * item + 2]};
@@ -60,79 +44,31 @@ __global__ __launch_bounds__(kBlock) void nearest_walk_kernel(TreeDev tree, int 
             d[j] = j < base ? -std::numeric_limits<T>::infinity() : max_d2;
             ix[j] = 0;
         }
-
-        // bound of implicit node `i` of `level`: a node box, or at the last level the box of the leaf's stored volume
-        auto bound_of = [&](uint64_t i, int level) -> T {
-            if (level == levels) {
-                const BBox<T> b = convert_to(load_vol<VL>(leaves + (int64_t)(i - leaf_first) * lay.stride), (BBox<T> *)nullptr);
-                return box_bound(b.lo, b.up, p);
+        auto visit = [&](const char *rec) {
+            const I index = load_index<I>(rec, lay);
+            T c[3];
+            center(load_vol<VL>(rec), c);
+            const T e[3] = {p[0] - c[0], p[1] - c[1], p[2] - c[2]};
+            const T d2 = (e[0] * e[0] + e[1] * e[1]) + e[2] * e[2];
+            // (d2, index) against the k-th best; while slots are free anything within the radius enters
+            const bool full = cnt == k;
+            if ((d2 <= max_d2) & (!full | (d2 < d[K - 1]) | ((d2 == d[K - 1]) & (index < ix[K - 1])))) {
+                bool lt[K]; // the candidate sorts before slot j (a free slot is behind everything)
+#pragma unroll
+                for (int j = 0; j < K; ++j) lt[j] = (j >= base + cnt) | (d2 < d[j]) | ((d2 == d[j]) & (index < ix[j]));
+#pragma unroll
+                for (int j = K - 1; j > 0; --j) {
+                    d[j] = lt[j - 1] ? d[j - 1] : (lt[j] ? d2 : d[j]);
+                    ix[j] = lt[j - 1] ? ix[j - 1] : (lt[j] ? index : ix[j]);
+                }
+                d[0] = lt[0] ? d2 : d[0];
+                ix[0] = lt[0] ? index : ix[0];
+                cnt += full ? 0 : 1;
             }
-            const BBox<TN> n = load_vol<BBox<TN>>(nodes + ((int64_t)i - level_skips(levels, vl, level) - 1));
-            const T lo[3] = {T(n.lo[0]), T(n.lo[1]), T(n.lo[2])}, up[3] = {T(n.up[0]), T(n.up[1]), T(n.up[2])};
-            return box_bound(lo, up, p);
         };
-
         // a NaN coordinate makes every d2 NaN and a NaN radius admits nothing: no answer either way, and no bound could prune
         const bool hopeless = !((p[0] == p[0]) & (p[1] == p[1]) & (p[2] == p[2]) & (max_d2 == max_d2));
-        for (int64_t r = 0; r < roots && !hopeless; ++r) {
-            uint64_t node = (uint64_t(1) << (built_level - 1)) + (uint64_t)r;
-            int level = built_level;
-            uint64_t trail = 0; // bit l: the sibling of the path's node at level l is still owed
-            if (bound_of(node, level) > d[K - 1]) continue;
-            for (;;) {
-                bool descended = false;
-                if (level == levels) {
-                    const char *rec = leaves + (int64_t)(node - leaf_first) * lay.stride;
-                    const I index = load_index<I>(rec, lay);
-                    T c[3];
-                    center(load_vol<VL>(rec), c);
-                    const T e[3] = {p[0] - c[0], p[1] - c[1], p[2] - c[2]};
-                    const T d2 = (e[0] * e[0] + e[1] * e[1]) + e[2] * e[2];
-                    // (d2, index) against the k-th best; while slots are free anything within the radius enters
-                    const bool full = cnt == k;
-                    if ((d2 <= max_d2) & (!full | (d2 < d[K - 1]) | ((d2 == d[K - 1]) & (index < ix[K - 1])))) {
-                        bool lt[K]; // the candidate sorts before slot j (a free slot is behind everything)
-#pragma unroll
-                        for (int j = 0; j < K; ++j) lt[j] = (j >= base + cnt) | (d2 < d[j]) | ((d2 == d[j]) & (index < ix[j]));
-#pragma unroll
-                        for (int j = K - 1; j > 0; --j) {
-                            d[j] = lt[j - 1] ? d[j - 1] : (lt[j] ? d2 : d[j]);
-                            ix[j] = lt[j - 1] ? ix[j - 1] : (lt[j] ? index : ix[j]);
-                        }
-                        d[0] = lt[0] ? d2 : d[0];
-                        ix[0] = lt[0] ? index : ix[0];
-                        cnt += full ? 0 : 1;
-                    }
-                } else {
-                    const int cl = level + 1;
-                    const uint64_t c0 = 2 * node, c1 = c0 + 1; // (a real node's first child is real)
-                    const bool real1 = (int64_t)(c1 - (uint64_t(1) << (cl - 1))) < level_num_real(levels, vl, cl);
-                    const T lb0 = bound_of(c0, cl), lb1 = bound_of(real1 ? c1 : c0, cl);
-                    const bool go0 = !(lb0 > d[K - 1]), go1 = real1 && !(lb1 > d[K - 1]);
-                    if (go0 | go1) {
-                        node = go1 && (!go0 || lb1 < lb0) ? c1 : c0; // the nearer child first
-                        level = cl;
-                        if (go0 & go1) trail |= uint64_t(1) << cl;
-                        descended = true;
-                    }
-                }
-                if (descended) continue;
-                // pop: the deepest owed sibling whose bound still reaches the k-th best found since
-                bool found = false;
-                while (trail != 0) {
-                    const int l = 63 - __builtin_clzll(trail);
-                    trail &= ~(uint64_t(1) << l);
-                    const uint64_t sibling = (node >> (level - l)) ^ 1u;
-                    if (!(bound_of(sibling, l) > d[K - 1])) {
-                        node = sibling;
-                        level = l;
-                        found = true;
-                        break;
-                    }
-                }
-                if (!found) break;
-            }
-        }
+        if (!hopeless) pointwalk::walk<VL, TN>(tree, built_level, leaves, lay, nodes, p, [&]() { return d[K - 1]; }, visit);
 #pragma unroll
         for (int j = 0; j < K; ++j) {
             if (j >= base) {
@@ -157,22 +93,16 @@ ibvh_status ibvh_nearest_leaves(const ibvh_bvh *bvh, const void *points, int64_t
     if (!nearest_index && !nearest_d2) return IBVH_ERR_INVALID_ARG;
     const ibvh_types &t = bvh->types;
     if (!combo_ok(t)) return IBVH_ERR_UNSUPPORTED;
-    // the lossless bound needs boxes above the leaves, holding the leaves' values exactly
-    if (t.node_kind != IBVH_BBOX) return IBVH_ERR_UNSUPPORTED;
-    if (t.leaf_float == IBVH_F64 && t.node_float == IBVH_F32) return IBVH_ERR_UNSUPPORTED;
+    if (!pointwalk::box_nodes_hold_leaves(t)) return IBVH_ERR_UNSUPPORTED;
     const ibvh_tree &tr = bvh->tree;
-    if (tr.levels < 1 || tr.levels > 62 || tr.real_leaves < 1 || tr.virtual_leaves < 0) return IBVH_ERR_INVALID_ARG;
-    if (tr.real_leaves + tr.virtual_leaves != (int64_t(1) << (tr.levels - 1))) return IBVH_ERR_INVALID_ARG;
-    if (bvh->built_level < 1 || bvh->built_level > tr.levels) return IBVH_ERR_INVALID_ARG;
-    if (!bvh->leaves || (bvh->built_level < tr.levels && !bvh->nodes)) return IBVH_ERR_INVALID_ARG;
+    if (!pointwalk::tree_ok(bvh)) return IBVH_ERR_INVALID_ARG;
     if (num_points > 0 && !points) return IBVH_ERR_INVALID_ARG;
     if (num_points == 0) return IBVH_OK;
     ibvh_layout layout;
     LeafLayout lay;
     if (!layout_of(t, layout, &lay)) return IBVH_ERR_UNSUPPORTED;
     const TreeDev tree{tr.levels, tr.real_leaves, tr.virtual_leaves};
-    const int64_t b = ceil_div(num_points, nearest::kBlock);
-    const unsigned blocks = (unsigned)(b > (int64_t(1) << 22) ? (int64_t(1) << 22) : b);
+    const unsigned blocks = pointwalk::grid_blocks(num_points);
     return (ibvh_status)dispatch_volume(t.leaf_kind, t.leaf_float, [&](auto lt) -> int {
         using VL = typename decltype(lt)::type;
         using T = typename VL::elt;
@@ -182,7 +112,7 @@ ibvh_status ibvh_nearest_leaves(const ibvh_bvh *bvh, const void *points, int64_t
             auto launch = [&](auto nt, auto kt) -> int {
                 using TN = typename decltype(nt)::type;
                 constexpr int K = decltype(kt)::value;
-                IBVH_LAUNCH((nearest::nearest_walk_kernel<VL, TN, I, K>), dim3(blocks), dim3(nearest::kBlock), 0,
+                IBVH_LAUNCH((nearest::nearest_walk_kernel<VL, TN, I, K>), dim3(blocks), dim3(pointwalk::kBlock), 0,
                             (hipStream_t)stream, tree, (int)bvh->built_level, (const char *)bvh->leaves, lay,
                             (const BBox<TN> *)bvh->nodes, (const T *)points, num_points, (int)k, max_d2, (I *)nearest_index,
                             (T *)nearest_d2);

@@ -1,0 +1,125 @@
+// ibvh_pointwalk.hpp — the bounded walk of one query point through a BVH, shared by the point queries that prune on a bound
+// which shrinks while they walk: ibvh_closest.hip (the closest triangle) and ibvh_nearest.hip (the k nearest leaf centres),
+// and the argument checks their entry points have in common.  No reference counterpart: every traversal of ImplicitBVH.jl
+// is a fixed-volume overlap test (traverse/, raytrace/).
+//
+// A query hands the walk two things: limit(), the squared distance beyond which nothing can enter its answer any more, and
+// visit(rec), what to do with a leaf record that is still within it.  The walk is lossless if the COMPUTED bound of a box
+// never exceeds the COMPUTED distance of anything the query could find under it; each query argues that for its own
+// distance.  A box is skipped iff bound > limit(): strictly, because an equal distance under it may carry a smaller index.
+//
+// Work mapping: one lane per query, everything in registers.  The lane descends to the child with the smaller bound
+// first and keeps ONE bit per level — "the other child is still owed" — in a 64-bit trail word (levels <= 62): no
+// indexable private array, nothing in scratch memory.  A pop scans the trail for the deepest owed bit, finds the owed
+// sibling from the current path (node >> depth difference, ^ 1) and tests its bound again against the CURRENT limit: that is
+// where the shrinking bound pays.  Leaves are walked like nodes (the box of their stored volume is the bound); only a leaf
+// that passes is visited.  Lanes of a wave share nodes when neighbouring queries are neighbours in space: the entry points
+// keep the order they are given, the host mirrors sort the batch along a Morton curve first.
+#pragma once
+#include "ibvh_common.hpp"
+
+namespace ibvh {
+namespace pointwalk {
+
+constexpr int kBlock = 64; // one wave a workgroup: walks differ in length, and a wave that is done frees its slot at once
+
+// lb(B) of include/ibvh.h: the squared distance from p to the box, by the operations of the queries' own d2
+template <class T> IBVH_D T box_bound(const T *lo, const T *up, const T *p) {
+    T f[3];
+#pragma unroll
+    for (int k = 0; k < 3; ++k) {
+        const T c = p[k] < lo[k] ? lo[k] : (p[k] > up[k] ? up[k] : p[k]);
+        f[k] = p[k] - c;
+    }
+    return (f[0] * f[0] + f[1] * f[1]) + f[2] * f[2];
+}
+
+// The walk of query point p from every root of the built part of the tree.  VL: the leaves' volume type, T its float
+// type; TN: the nodes' (the same or wider — a node box then holds values of T, widened exactly, and narrows back exactly).
+// limit() -> T is read afresh at every test; visit(const char *rec) may lower it.
+template <class VL, class TN, class Limit, class Visit>
+IBVH_D void walk(const TreeDev &tree, int built_level, const char *__restrict__ leaves, const LeafLayout &lay,
+                 const BBox<TN> *__restrict__ nodes, const typename VL::elt *p, const Limit &limit, const Visit &visit) {
+    using T = typename VL::elt;
+    const int levels = (int)tree.levels;
+    const int64_t vl = tree.virtual_leaves;
+    const uint64_t leaf_first = uint64_t(1) << (levels - 1);
+    const int64_t roots = level_num_real(levels, vl, built_level);
+
+    // bound of implicit node `i` of `level`: a node box, or at the last level the box of the leaf's stored volume
+    auto bound_of = [&](uint64_t i, int level) -> T {
+        if (level == levels) {
+            const BBox<T> b = convert_to(load_vol<VL>(leaves + (int64_t)(i - leaf_first) * lay.stride), (BBox<T> *)nullptr);
+            return box_bound(b.lo, b.up, p);
+        }
+        const BBox<TN> n = load_vol<BBox<TN>>(nodes + ((int64_t)i - level_skips(levels, vl, level) - 1));
+        const T lo[3] = {T(n.lo[0]), T(n.lo[1]), T(n.lo[2])}, up[3] = {T(n.up[0]), T(n.up[1]), T(n.up[2])};
+        return box_bound(lo, up, p);
+    };
+
+    for (int64_t r = 0; r < roots; ++r) {
+        uint64_t node = (uint64_t(1) << (built_level - 1)) + (uint64_t)r;
+        int level = built_level;
+        uint64_t trail = 0; // bit l: the sibling of the path's node at level l is still owed
+        if (bound_of(node, level) > limit()) continue;
+        for (;;) {
+            bool descended = false;
+            if (level == levels) {
+                visit(leaves + (int64_t)(node - leaf_first) * lay.stride);
+            } else {
+                const int cl = level + 1;
+                const uint64_t c0 = 2 * node, c1 = c0 + 1; // (a real node's first child is real)
+                const bool real1 = (int64_t)(c1 - (uint64_t(1) << (cl - 1))) < level_num_real(levels, vl, cl);
+                const T lb0 = bound_of(c0, cl), lb1 = bound_of(real1 ? c1 : c0, cl);
+                const bool go0 = !(lb0 > limit()), go1 = real1 && !(lb1 > limit());
+                if (go0 | go1) {
+                    node = go1 && (!go0 || lb1 < lb0) ? c1 : c0; // the nearer child first
+                    level = cl;
+                    if (go0 & go1) trail |= uint64_t(1) << cl;
+                    descended = true;
+                }
+            }
+            if (descended) continue;
+            // pop: the deepest owed sibling whose bound still reaches the limit as it stands now
+            bool found = false;
+            while (trail != 0) {
+                const int l = 63 - __builtin_clzll(trail);
+                trail &= ~(uint64_t(1) << l);
+                const uint64_t sibling = (node >> (level - l)) ^ 1u;
+                if (!(bound_of(sibling, l) > limit())) {
+                    node = sibling;
+                    level = l;
+                    found = true;
+                    break;
+                }
+            }
+            if (!found) break;
+        }
+    }
+}
+
+// ---- the entry points' common argument checks (host) ---------------------------------------------------------------
+
+// the lossless bound needs boxes above the leaves, holding the leaves' values exactly (else IBVH_ERR_UNSUPPORTED)
+inline bool box_nodes_hold_leaves(const ibvh_types &t) {
+    return t.node_kind == IBVH_BBOX && !(t.leaf_float == IBVH_F64 && t.node_float == IBVH_F32);
+}
+
+// an ImplicitTree's shape the trail word can hold, built from a level that exists, with the arrays the walk reads (else
+// IBVH_ERR_INVALID_ARG)
+inline bool tree_ok(const ibvh_bvh *bvh) {
+    const ibvh_tree &tr = bvh->tree;
+    if (tr.levels < 1 || tr.levels > 62 || tr.real_leaves < 1 || tr.virtual_leaves < 0) return false;
+    if (tr.real_leaves + tr.virtual_leaves != (int64_t(1) << (tr.levels - 1))) return false;
+    if (bvh->built_level < 1 || bvh->built_level > tr.levels) return false;
+    return bvh->leaves && (bvh->built_level == tr.levels || bvh->nodes);
+}
+
+// workgroups for num_points queries; the kernels stride over what a clamped grid leaves
+inline unsigned grid_blocks(int64_t num_points) {
+    const int64_t b = ceil_div(num_points, kBlock);
+    return (unsigned)(b > (int64_t(1) << 22) ? (int64_t(1) << 22) : b);
+}
+
+} // namespace pointwalk
+} // namespace ibvh

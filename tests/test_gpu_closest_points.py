@@ -221,6 +221,19 @@ def test_hand_made_meshes_through_the_c_entry(n, built_level, flt, idx):
         _same(cut, cpc.brute_force(tris[:n - 2], p, idt=NP_I[idx]), "guard")
 
 
+def test_two_roots_one_over_a_virtual_sibling_and_a_batch_of_a_wave_and_one():
+    """built_level = 2 over 3 leaves: the walk starts from two roots, and the second root's other child is virtual; 65
+    points are a full wave and one lane of a second workgroup"""
+    tris = np.array(HAND[:3], np.float32)
+    rng = np.random.default_rng(65)
+    p = np.concatenate([np.array(HAND_POINTS[:11], np.float32), (rng.random((54, 3)) * 12 - 1).astype(np.float32)])
+    bvh, _ = _build(tris, built_level=2)
+    assert len(p) == 65 and (bvh.tree.levels, bvh.built_level, bvh.tree.real_leaves, bvh.tree.virtual_leaves) == (3, 2, 3, 1)
+    exp = cpc.brute_force(tris, p, idt=np.int32)
+    assert set(exp.index.tolist()) == {1, 2, 3}  # every leaf, hence either root, holds an answer
+    _same(_call(bvh, tris, p), exp)
+
+
 @pytest.mark.parametrize("flt", [abi.F32, abi.F64], ids=["f32", "f64"])
 @pytest.mark.parametrize("order", [(0, 1), (1, 0)], ids=["nan_second", "nan_first"])
 def test_a_triangle_with_a_nan_vertex_never_wins(order, flt):

@@ -71,9 +71,11 @@ def test_makefile_launch_and_python_surface():
     src = _read("implicitbvh.jl_amd", "csrc", "ibvh_nearest.hip")
     launches = re.findall(r"IBVH_LAUNCH\(\((nearest::\w+)<", src)
     assert launches == ["nearest::nearest_walk_kernel"], "ONE launch, through the profiling wrapper"
-    assert "hipLaunchKernelGGL" not in src and "<<<" not in src
-    assert "atomic" not in src and "hipStreamSynchronize" not in src and "hipDeviceSynchronize" not in src and "hipMemcpy" not in src
-    assert "fp-contract" not in src and "fma(" not in src   # the Makefile's -ffp-contract=off holds for this file
+    # (the walk the kernel calls lives in ibvh_pointwalk.hpp: the same holds for it)
+    for text in (src, _read("implicitbvh.jl_amd", "csrc", "ibvh_pointwalk.hpp")):
+        assert "hipLaunchKernelGGL" not in text and "<<<" not in text
+        assert "atomic" not in text and "hipStreamSynchronize" not in text and "hipDeviceSynchronize" not in text and "hipMemcpy" not in text
+        assert "fp-contract" not in text and "fma(" not in text   # the Makefile's -ffp-contract=off holds for this file
 
 
 def _fake_bvh(leaf_kind=abi.BSPHERE, leaf_float=abi.F32, node_kind=abi.BBOX, node_float=abi.F32, idx=abi.I32, morton=abi.U32, n=5,
