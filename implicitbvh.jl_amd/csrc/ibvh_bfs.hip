@@ -65,10 +65,6 @@ inline bool narrow_arg_ok(int32_t narrow, bool rays) {
     return rays ? (code == IBVH_NARROW_NONE || code == IBVH_NARROW_RAY_ORIGIN_OUTSIDE)
                 : (code == IBVH_NARROW_NONE || code == IBVH_NARROW_MORTON_LT || code == IBVH_NARROW_INDEX_LT);
 }
-template <class T> IBVH_D bool origin_outside(const BSphere<T> &s, const T *p) { return dist3sq(p, s.x) > s.r * s.r; }
-template <class T> IBVH_D bool origin_outside(const BBox<T> &b, const T *p) {
-    return (p[0] < b.lo[0]) | (p[0] > b.up[0]) | (p[1] < b.lo[1]) | (p[1] > b.up[1]) | (p[2] < b.lo[2]) | (p[2] > b.up[2]);
-}
 
 IBVH_D bool narrow_eval(int narrow, uint64_t ma, int64_t ia, uint64_t mb, int64_t ib) {
     if (narrow == IBVH_NARROW_MORTON_LT) return ma < mb;

@@ -273,6 +273,12 @@ template <class T> IBVH_HD bool isintersection(const BSphere<T> &s, const T *p, 
     }
     return false;
 }
+// IBVH_NARROW_RAY_ORIGIN_OUTSIDE: (bv, p, d) -> p lies outside bv.volume (strictly outside the sphere: distance > r;
+// outside the box: beyond a face on some axis), evaluated only for leaves the ray already hits
+template <class T> IBVH_HD bool origin_outside(const BSphere<T> &s, const T *p) { return dist3sq(p, s.x) > s.r * s.r; }
+template <class T> IBVH_HD bool origin_outside(const BBox<T> &b, const T *p) {
+    return (p[0] < b.lo[0]) | (p[0] > b.up[0]) | (p[1] < b.lo[1]) | (p[1] > b.up[1]) | (p[2] < b.lo[2]) | (p[2] > b.up[2]);
+}
 
 // ------------------------------------------------------------------------------------------
 // triangle constructors — bsphere.jl:43-112, bbox.jl:59-70

@@ -10,6 +10,7 @@
 //                         leaves' type Q as the query type, split over four units (ibvh_lvt_mixed.inc, IBVH_FOR_MIXED_* below)
 //   ibvh_lvt_rays.hip     walker 3, lvt_rays_kernel (per-lane ray walk)
 //   ibvh_lvt_raybins.hip  walker 4, rays binned by subtree (rays_top / tilehist / binscan / scatter / subtree / place)
+//   ibvh_raywalk.hpp      the pieces of the per-lane walk of one ray, once: what the kernels of walkers 3 and 4 compose
 //
 // Replaces src/traverse/leaf_vs_tree/traverse_single.jl, traverse_pair.jl and
 // src/raytrace/leaf_vs_tree/leaf_vs_tree.jl.  The reference's 32-entry per-thread index stack
@@ -118,15 +119,6 @@ IBVH_D bool narrow_eval(int narrow, uint64_t ma, int64_t ia, uint64_t mb, int64_
     if (narrow == IBVH_NARROW_MORTON_LT) return ma < mb;
     if (narrow == IBVH_NARROW_INDEX_LT) return ia < ib;
     return true;
-}
-
-// IBVH_NARROW_RAY_ORIGIN_OUTSIDE: (bv, p, d) -> p lies outside bv.volume (strictly outside the sphere: distance > r;
-// outside the box: beyond a face on some axis), evaluated only for leaves the ray already hits
-template <class T> IBVH_D bool origin_outside(const BSphere<T> &s, const T *p) {
-    return dist3sq(p, s.x) > s.r * s.r;
-}
-template <class T> IBVH_D bool origin_outside(const BBox<T> &b, const T *p) {
-    return (p[0] < b.lo[0]) | (p[0] > b.up[0]) | (p[1] < b.lo[1]) | (p[1] > b.up[1]) | (p[2] < b.lo[2]) | (p[2] > b.up[2]);
 }
 
 // ------------------------------------------------------------------------------------------

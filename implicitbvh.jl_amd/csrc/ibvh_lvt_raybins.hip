@@ -1,6 +1,7 @@
 // ibvh_lvt_raybins.hip — walker 4 of the leaf-vs-tree traversal: rays binned by subtree (the default ray path of large
 // trees).  raytrace/leaf_vs_tree/leaf_vs_tree.jl:170-228 cut in two at a level K.
 #include "ibvh_lvt.hpp"
+#include "ibvh_raywalk.hpp"
 
 namespace ibvh {
 namespace lvt {
@@ -75,33 +76,25 @@ __global__ __launch_bounds__(64) void rays_top_kernel(Args<L, N, I> a, RayBins r
     using T = typename L::elt;
     __shared__ uint64_t s_items[RAYTOP_STAGE];
     const int lane = threadIdx.x;
-    const int64_t first_item = (int64_t)blockIdx.x * ray_block;
-    const int64_t left = a.n_items - first_item;
-    const int items_here = (int)(left < ray_block ? left : ray_block);
+    raywalk::Block block(a.n_items, ray_block);
+    const int64_t first_item = block.first_item;
+    const int items_here = block.items_here;
     const int levels = (int)a.tree.levels;
     const uint32_t vl = (uint32_t)a.tree.virtual_leaves;
     const int K = rb.cut_level;
     const uint32_t kfirst = 1u << (K - 1);
-    const int plevel = (int)a.start_level - 1;
-    const int64_t roots = level_num_real(a.tree.levels, a.tree.virtual_leaves, a.start_level);
-    const uint32_t pfirst = plevel >= 1 ? (1u << (plevel - 1)) : 0u;
-    const uint32_t pcount = (uint32_t)((roots + 1) / 2);
+    const raywalk::Roots roots(a.tree, a.start_level);
 
-    T p[3] = {0, 0, 0}, d[3] = {0, 0, 0}, inv[3] = {0, 0, 0};
+    raywalk::Ray<T> r;
+    raywalk::Cursor cur;
     RayPk pk{};
     bool regular = true; // (idle lanes count as regular)
     constexpr bool kPacked = N::kind == IBVH_BBOX && std::is_same<T, float>::value; // (slab_fast is single precision)
     const bool top_clean = kPacked && *rb.top_nan == 0;
     int ray = -1;
-    uint32_t pi = 0, inode = 0, pend = 0, ord = 0;
-    int level = 0;
-    int next = 0; // wave-uniform: rays of the block handed out so far
+    uint32_t pi = 0, ord = 0;
     int fill = 0; // wave-uniform: items staged
 
-    auto node_hit = [&](const N &n) {
-        if constexpr (N::kind == IBVH_BBOX) return isintersection_inv(n, p, inv);
-        else return isintersection(n, p, d);
-    };
     auto flush = [&]() {
         if (fill == 0) return;
         __syncthreads(); // (one wave: orders the stage's writes before the reads below)
@@ -122,30 +115,19 @@ __global__ __launch_bounds__(64) void rays_top_kernel(Args<L, N, I> a, RayBins r
 
     for (;;) {
         const uint64_t idle = __builtin_amdgcn_ballot_w64(ray < 0);
-        if (idle != 0 && next < items_here) {
-            const int rank = (int)__builtin_amdgcn_mbcnt_hi((uint32_t)(idle >> 32), __builtin_amdgcn_mbcnt_lo((uint32_t)idle, 0u));
-            const int mine = next + rank;
+        if (idle != 0 && block.more()) {
+            const int mine = block.take(idle);
             if (ray < 0 && mine < items_here) {
-                const int64_t item = first_item + mine;
-#pragma unroll
-                for (int k = 0; k < 3; ++k) {
-                    p[k] = a.points[3 * item + k];
-                    d[k] = a.dirs[3 * item + k];
-                    inv[k] = T(1) / d[k];
-                }
+                r.load(a.points, a.dirs, first_item + mine);
                 if constexpr (kPacked) {
-                    regular = ray_is_regular(p, d, inv);
-                    pk = ray_pk(p, inv);
+                    regular = ray_is_regular(r.p, r.d, r.inv);
+                    pk = ray_pk(r.p, r.inv);
                 }
                 ray = mine;
                 pi = 0;
-                inode = pfirst;
-                level = plevel;
-                pend = 0;
+                roots.first(cur);
                 ord = 0;
             }
-            const int taken = __popcll(idle);
-            next = next + taken < items_here ? next + taken : items_here;
         }
         if (__builtin_amdgcn_ballot_w64(ray >= 0) == 0) break; // (every lane idle after a refill: the block is used up)
         // (wave-uniform, fixed between refills: slab_fast serves the wave while all its rays are regular)
@@ -154,36 +136,24 @@ __global__ __launch_bounds__(64) void rays_top_kernel(Args<L, N, I> a, RayBins r
             bool e0 = false, e1 = false;
             uint64_t it0 = 0, it1 = 0;
             if (ray >= 0) {
-                const int cl = level + 1;
-                const uint32_t c0 = 2u * inode, c1 = c0 + 1u;
-                const uint32_t first = 1u << (cl - 1);
-                const uint32_t nreal = first - (uint32_t)((uint64_t)vl >> (levels - cl));
-                const bool real0 = c0 != 0u, real1 = (c1 - first) < nreal; // (c0 == 0: the pseudo node above the root)
-                const uint64_t v = (uint64_t)vl >> (levels - cl + 1);
-                const uint32_t sk = (uint32_t)(2 * v) - (uint32_t)__popcll(v); // level_skips(cl)
-                const N *np = a.nodes + ((int64_t)c0 - (int64_t)sk - 1);
-                struct Two {
-                    N a, b;
-                };
-                Two ch;
-                if (real0 && real1) {
-                    __builtin_memcpy(&ch, __builtin_assume_aligned(np, 8), sizeof(Two));
-                } else {
-                    ch.a = load_vol<N>(real0 ? np : np + 1);
-                    ch.b = ch.a;
-                }
+                const raywalk::Children kids = raywalk::children(levels, vl, cur.node, cur.level);
+                const int cl = kids.cl;
+                const uint32_t c0 = kids.c0, c1 = kids.c1;
+                const bool real0 = kids.real0, real1 = kids.real1;
+                raywalk::Two<N> ch;
+                raywalk::load_two(ch, a.nodes + ((int64_t)c0 - (int64_t)kids.sk - 1), real0, real1);
                 bool h0, h1;
                 if constexpr (kPacked) {
                     if (fast) {
                         h0 = real0 && slab_fast(ch.a, pk);
                         h1 = real1 && slab_fast(ch.b, pk);
                     } else {
-                        h0 = real0 && node_hit(ch.a);
-                        h1 = real1 && node_hit(ch.b);
+                        h0 = real0 && raywalk::node_hit(ch.a, r);
+                        h1 = real1 && raywalk::node_hit(ch.b, r);
                     }
                 } else {
-                    h0 = real0 && node_hit(ch.a);
-                    h1 = real1 && node_hit(ch.b);
+                    h0 = real0 && raywalk::node_hit(ch.a, r);
+                    h1 = real1 && raywalk::node_hit(ch.b, r);
                 }
                 bool descended = false;
                 if (cl == K) { // the cut: hits become items, left before right
@@ -195,24 +165,17 @@ __global__ __launch_bounds__(64) void rays_top_kernel(Args<L, N, I> a, RayBins r
                     it1 = r64 | ((uint64_t)(c1 - kfirst) << 32) | ((uint64_t)ord << 48);
                     ord += h1 ? 1u : 0u;
                 } else if (h0) {
-                    if (h1) pend |= 1u << cl;
-                    inode = c0;
-                    level = cl;
+                    cur.descend(c0, cl, h1);
                     descended = true;
                 } else if (h1) {
-                    inode = c1;
-                    level = cl;
+                    cur.descend(c1, cl, false);
                     descended = true;
                 }
                 if (!descended) {
-                    if (pend != 0) {
-                        const int pl = 31 - __builtin_clz(pend);
-                        pend &= ~(1u << pl);
-                        inode = (inode >> (level - pl)) | 1u;
-                        level = pl;
-                    } else if (++pi < pcount) {
-                        inode = pfirst + pi;
-                        level = plevel;
+                    if (cur.pend != 0) {
+                        cur.pop();
+                    } else if (++pi < roots.pcount) {
+                        roots.next(cur, pi);
                     } else {
                         rb.ray_items[first_item + ray] = (int32_t)ord;
                         ray = -1;
@@ -230,7 +193,7 @@ __global__ __launch_bounds__(64) void rays_top_kernel(Args<L, N, I> a, RayBins r
             }
             const uint64_t idle_now = __builtin_amdgcn_ballot_w64(ray < 0);
             if (idle_now == ~(uint64_t)0) break;
-            if (next < items_here && __popcll(idle_now) >= 16) break;
+            if (block.more() && __popcll(idle_now) >= 16) break;
         }
     }
     flush();
@@ -397,32 +360,22 @@ IBVH_D void rays_tail_phase(const Args<L, N, I> &a, const RayBins &rb, unsigned 
     uint32_t *p_ray = masks + RAYSUB_TAIL_ITEMS * 16, *p_g = p_ray + RAYSUB_TAIL_ITEMS, *p_cnt = p_g + RAYSUB_TAIL_ITEMS;
     static_assert((2 * RAYSUB_TAIL_UNITS + RAYSUB_TAIL_ITEMS * 19) * 4 <= RAYSUB_WALKERS * RAYSUB_STAGE * 16, "the tail lives in the hit stages");
     // one unit down one level; returns the children that hit (node tests) or marks the leaves that hit (cd == D)
-    auto expand = [&](uint32_t pid, uint32_t t, int cd, const T (&up)[3], const T (&ud)[3], const T (&uinv)[3], bool &n0, bool &n1) {
+    auto expand = [&](uint32_t pid, uint32_t t, int cd, const raywalk::Ray<T> &ur, bool &n0, bool &n1) {
         const uint32_t c0 = 2u * t, c1 = c0 + 1u;
         n0 = n1 = false;
         if (cd == D) { // the two leaves under t
             const uint32_t li = c0 - S;
             const bool real1 = (j << D) + li + 1u < real_leaves;
             const L la = s_leaves[li], lb = s_leaves[li + 1];
-            bool h0 = isintersection(la, up, ud), h1 = real1 && isintersection(lb, up, ud);
-            if (a.narrow == IBVH_NARROW_RAY_ORIGIN_OUTSIDE) {
-                h0 = h0 && origin_outside(la, up);
-                h1 = h1 && origin_outside(lb, up);
-            }
+            bool h0, h1;
+            raywalk::leaf_hits(la, lb, ur, a.narrow, true, real1, h0, h1);
             const uint32_t bits = (h0 ? 1u << (li & 31u) : 0u) | (h1 ? 1u << ((li + 1u) & 31u) : 0u); // (li is even: one word)
             if (bits != 0) atomicOr(&masks[pid * mask_words + (li >> 5)], bits);
         } else {
-            const int level = K + cd;
-            const uint32_t nreal = (1u << (level - 1)) - (uint32_t)((uint64_t)vl >> (levels - level));
-            const bool real1 = (j << cd) + (c1 - (1u << cd)) < nreal;
+            const bool real1 = (j << cd) + (c1 - (1u << cd)) < raywalk::level_real32(levels, vl, K + cd);
             const N na = s_nodes[c0], nb = s_nodes[c1];
-            if constexpr (N::kind == IBVH_BBOX) {
-                n0 = isintersection_inv(na, up, uinv);
-                n1 = real1 && isintersection_inv(nb, up, uinv);
-            } else {
-                n0 = isintersection(na, up, ud);
-                n1 = real1 && isintersection(nb, up, ud);
-            }
+            n0 = raywalk::node_hit(na, ur);
+            n1 = real1 && raywalk::node_hit(nb, ur);
         }
     };
     __syncthreads(); // every wave has left the walking loop and flushed: the stages are free
@@ -451,61 +404,51 @@ IBVH_D void rays_tail_phase(const Args<L, N, I> &a, const RayBins &rb, unsigned 
         for (uint32_t u = tid; u < n_units; u += RAYSUB_TPB) {
             const uint32_t unit = in[u];
             const uint32_t pid = unit & 63u;
-            const int64_t r = (int64_t)p_ray[pid];
-            T up[3], ud[3], uinv[3];
-#pragma unroll
-            for (int k = 0; k < 3; ++k) {
-                up[k] = a.points[3 * r + k];
-                ud[k] = a.dirs[3 * r + k];
-                uinv[k] = T(1) / ud[k];
-            }
+            raywalk::Ray<T> ur;
+            ur.load(a.points, a.dirs, (int64_t)p_ray[pid]);
             // this unit one level down; a child that finds the next list full is walked depth-first, here and now
-            uint32_t t = (unit >> 10) & 1023u, spill_pend = 0;
-            int d = (int)((unit >> 6) & 15u);
+            raywalk::Cursor at; // (pend: the right siblings this lane's depth-first walk still owes)
+            at.start((unit >> 10) & 1023u, (int)((unit >> 6) & 15u));
             for (uint32_t up_pend = unit >> 20; up_pend != 0;) { // a parked walk's pending right siblings: units of their own
                 const int pl = 31 - __builtin_clz(up_pend);
                 up_pend &= ~(1u << pl);
                 const uint32_t slot = atomicAdd(&s_nunits[cur ^ 1], 1u);
-                if (slot < (uint32_t)UNITS) out[slot] = pid | ((uint32_t)pl << 6) | (((t >> (d - pl)) | 1u) << 10);
-                else spill_pend |= 1u << pl; // (no room: this lane's depth-first walk below takes it)
+                if (slot < (uint32_t)UNITS) out[slot] = pid | ((uint32_t)pl << 6) | (at.right_sibling(pl) << 10);
+                else at.pend |= 1u << pl; // (no room: this lane's depth-first walk below takes it)
             }
             bool first = true;
             for (;;) {
                 bool n0, n1;
-                expand(pid, t, d + 1, up, ud, uinv, n0, n1);
+                const int cd = at.level + 1;
+                const uint32_t t = at.node;
+                expand(pid, t, cd, ur, n0, n1);
                 bool descended = false;
                 if (first) {
                     first = false;
                     uint32_t keep = 0; // children that did not fit the next list
                     if (n0) {
                         const uint32_t slot = atomicAdd(&s_nunits[cur ^ 1], 1u);
-                        if (slot < (uint32_t)UNITS) out[slot] = pid | ((uint32_t)(d + 1) << 6) | ((2u * t) << 10);
+                        if (slot < (uint32_t)UNITS) out[slot] = pid | ((uint32_t)cd << 6) | ((2u * t) << 10);
                         else keep |= 1u;
                     }
                     if (n1) {
                         const uint32_t slot = atomicAdd(&s_nunits[cur ^ 1], 1u);
-                        if (slot < (uint32_t)UNITS) out[slot] = pid | ((uint32_t)(d + 1) << 6) | ((2u * t + 1u) << 10);
+                        if (slot < (uint32_t)UNITS) out[slot] = pid | ((uint32_t)cd << 6) | ((2u * t + 1u) << 10);
                         else keep |= 2u;
                     }
                     n0 = (keep & 1u) != 0;
                     n1 = (keep & 2u) != 0;
                 }
                 if (n0) { // (the walking loop's step, hits marked instead of staged)
-                    if (n1) spill_pend |= 1u << (d + 1);
-                    t = 2u * t;
-                    d += 1;
+                    at.descend(2u * t, cd, n1);
                     descended = true;
                 } else if (n1) {
-                    t = 2u * t + 1u;
-                    d += 1;
+                    at.descend(2u * t + 1u, cd, false);
                     descended = true;
                 }
                 if (!descended) {
-                    if (spill_pend == 0) break;
-                    const int pl = 31 - __builtin_clz(spill_pend);
-                    spill_pend &= ~(1u << pl);
-                    t = (t >> (d - pl)) | 1u;
-                    d = pl;
+                    if (at.pend == 0) break;
+                    at.pop();
                 }
             }
         }
@@ -587,9 +530,7 @@ __global__ __launch_bounds__(RAYSUB_TPB) void rays_subtree_kernel(Args<L, N, I> 
             const uint32_t h = wd / WPN, part = wd - h * WPN;
             const int dl = 31 - __builtin_clz(h), level = K + dl;
             const uint32_t gi = (j << dl) + (h - (1u << dl)), first = 1u << (level - 1);
-            const uint32_t nreal = first - (uint32_t)((uint64_t)vl >> (levels - level));
-            const uint64_t v = (uint64_t)vl >> (levels - level + 1);
-            const uint32_t sk = (uint32_t)(2 * v) - (uint32_t)__popcll(v);
+            const uint32_t nreal = raywalk::level_real32(levels, vl, level), sk = raywalk::level_skips32(levels, vl, level);
             if (gi < nreal) dst[wd] = src[((int64_t)first + (int64_t)gi - (int64_t)sk - 1) * WPN + part];
         }
         const uint32_t g0 = j << D;
@@ -611,17 +552,13 @@ __global__ __launch_bounds__(RAYSUB_TPB) void rays_subtree_kernel(Args<L, N, I> 
     const I *hits = (const I *)rb.hits;
     // (the list this wave appends to next — the records carry their place, any list serves: reserve_hits)
     uint32_t region = blockIdx.x & (uint32_t)(rb.regions - 1);
-    T p[3] = {0, 0, 0}, d[3] = {0, 0, 0}, inv[3] = {0, 0, 0};
+    raywalk::Ray<T> r;
+    raywalk::Cursor cur; // (node, level: heap index and depth inside the subtree)
     bool busy = false, more = true; // more: wave-uniform, the chunk may still hold items
-    uint32_t ray = 0, g = 0, tn = 1, pend = 0;
-    int dl = 0;
+    uint32_t ray = 0, g = 0;
     int64_t w = 0;
     uint32_t cnt = 0;
     int fill = 0; // wave-uniform: hit records staged
-    auto node_hit = [&](const N &n) {
-        if constexpr (N::kind == IBVH_BBOX) return isintersection_inv(n, p, inv);
-        else return isintersection(n, p, d);
-    };
     auto flush = [&]() {
         if (fill == 0) return;
         RayHit<I> *dst = nullptr;
@@ -639,21 +576,14 @@ __global__ __launch_bounds__(RAYSUB_TPB) void rays_subtree_kernel(Args<L, N, I> 
             if (lane == 0) base = atomicAdd(&s_next, (uint32_t)want);
             base = (uint32_t)__builtin_amdgcn_readfirstlane((int)base);
             more = base + (uint32_t)want < n_here;
-            const uint32_t mine = base + __builtin_amdgcn_mbcnt_hi((uint32_t)(idle >> 32), __builtin_amdgcn_mbcnt_lo((uint32_t)idle, 0u));
+            const uint32_t mine = (uint32_t)raywalk::deal(idle, (int)base);
             if (!busy && mine < n_here) {
                 const uint2 e = rb.bucket[b0 + mine];
                 ray = e.x;
                 g = e.y;
-#pragma unroll
-                for (int k = 0; k < 3; ++k) {
-                    p[k] = a.points[3 * (int64_t)ray + k];
-                    d[k] = a.dirs[3 * (int64_t)ray + k];
-                    inv[k] = T(1) / d[k];
-                }
+                r.load(a.points, a.dirs, (int64_t)ray);
                 busy = true;
-                tn = 1;
-                dl = 0;
-                pend = 0;
+                cur.start(1, 0);
                 cnt = 0;
                 if constexpr (WRITE) w = g > 0 ? (int64_t)hits[g - 1] : 0;
             }
@@ -663,47 +593,34 @@ __global__ __launch_bounds__(RAYSUB_TPB) void rays_subtree_kernel(Args<L, N, I> 
             bool h0 = false, h1 = false;
             uint32_t li = 0;
             if (busy) {
-                const int cd = dl + 1;
-                const uint32_t c0 = 2u * tn, c1 = c0 + 1u;
+                const int cd = cur.level + 1;
+                const uint32_t c0 = 2u * cur.node, c1 = c0 + 1u;
                 bool descended = false;
                 if (cd == D) { // the two leaves under tn
                     li = c0 - S;
                     const bool real1 = (j << D) + li + 1u < real_leaves; // (a real parent's left child is real)
                     const L la = s_leaves[li], lb = s_leaves[li + 1];
-                    h0 = isintersection(la, p, d);
-                    h1 = real1 && isintersection(lb, p, d);
-                    if (a.narrow == IBVH_NARROW_RAY_ORIGIN_OUTSIDE) { // raytrace/lvt:194: isintersection(...) && narrow(leaf, p, d)
-                        h0 = h0 && origin_outside(la, p);
-                        h1 = h1 && origin_outside(lb, p);
-                    }
+                    raywalk::leaf_hits(la, lb, r, a.narrow, true, real1, h0, h1);
                     if constexpr (WRITE) {
                         if (h0) a.contacts[w++] = IndexPair<I>{s_index[li], (I)((int64_t)ray + 1)};
                         if (h1) a.contacts[w++] = IndexPair<I>{s_index[li + 1], (I)((int64_t)ray + 1)};
                     }
                 } else {
-                    const int level = K + cd;
-                    const uint32_t nreal = (1u << (level - 1)) - (uint32_t)((uint64_t)vl >> (levels - level));
-                    const bool real1 = (j << cd) + (c1 - (1u << cd)) < nreal;
+                    const bool real1 = (j << cd) + (c1 - (1u << cd)) < raywalk::level_real32(levels, vl, K + cd);
                     const N na = s_nodes[c0], nb = s_nodes[c1];
                     // (the packed slab test of rays_top_kernel as a second code path in this loop made it slower: 1.65 against 1.55 ms)
-                    const bool n0 = node_hit(na), n1 = real1 && node_hit(nb);
+                    const bool n0 = raywalk::node_hit(na, r), n1 = real1 && raywalk::node_hit(nb, r);
                     if (n0) {
-                        if (n1) pend |= 1u << cd;
-                        tn = c0;
-                        dl = cd;
+                        cur.descend(c0, cd, n1);
                         descended = true;
                     } else if (n1) {
-                        tn = c1;
-                        dl = cd;
+                        cur.descend(c1, cd, false);
                         descended = true;
                     }
                 }
                 if (!descended) {
-                    if (pend != 0) {
-                        const int pl = 31 - __builtin_clz(pend);
-                        pend &= ~(1u << pl);
-                        tn = (tn >> (dl - pl)) | 1u;
-                        dl = pl;
+                    if (cur.pend != 0) {
+                        cur.pop();
                     } else {
                         if constexpr (!WRITE) ((I *)rb.hits)[g] = (I)(cnt + (h0 ? 1u : 0u) + (h1 ? 1u : 0u));
                         busy = false;
@@ -742,7 +659,7 @@ __global__ __launch_bounds__(RAYSUB_TPB) void rays_subtree_kernel(Args<L, N, I> 
     }
     if constexpr (!WRITE) {
         flush();
-        if (tail_lanes > 0) rays_tail_phase<L, N, I>(a, rb, s_raw + o, s_nodes, s_leaves, s_index, &s_npark, s_nunits, busy, ray, g, tn, dl, pend, cnt, j, region);
+        if (tail_lanes > 0) rays_tail_phase<L, N, I>(a, rb, s_raw + o, s_nodes, s_leaves, s_index, &s_npark, s_nunits, busy, ray, g, cur.node, cur.level, cur.pend, cnt, j, region);
     }
 }
 

@@ -1,6 +1,7 @@
 // ibvh_lvt_rays.hip — walker 3 of the leaf-vs-tree traversal: lvt_rays_kernel, the per-lane ray walk
 // (raytrace/leaf_vs_tree/leaf_vs_tree.jl:187-225), and the launcher of a whole ray pass.
 #include "ibvh_lvt.hpp"
+#include "ibvh_raywalk.hpp"
 
 namespace ibvh {
 namespace lvt {
@@ -44,9 +45,9 @@ __global__ __launch_bounds__(64) void lvt_rays_kernel(Args<L, N, I> a, PairCache
     __shared__ int s_fill;
     if (a.gate != nullptr && *(const __attribute__((address_space(4))) int32_t *)(uintptr_t)a.gate == 0) return;
     const int lane = threadIdx.x;
-    const int64_t first_item = (int64_t)blockIdx.x * ray_block;
-    const int64_t left = a.n_items - first_item;
-    const int items_here = (int)(left < ray_block ? left : ray_block);
+    raywalk::Block block(a.n_items, ray_block);
+    const int64_t first_item = block.first_item;
+    const int items_here = block.items_here;
     char *region = cache.K > 0 && items_here > 0 ? (char *)(cache.slots + first_item * (int64_t)cache.K) : nullptr;
     const int entry_cap = region ? (int)(((int64_t)items_here * cache.K * (int64_t)sizeof(IndexPair<I>) - 16) / (int64_t)sizeof(Entry)) : 0;
     Entry *entries = (Entry *)(region + 16);
@@ -69,28 +70,19 @@ __global__ __launch_bounds__(64) void lvt_rays_kernel(Args<L, N, I> a, PairCache
     const int levels = (int)a.tree.levels;
     const uint32_t vl = (uint32_t)a.tree.virtual_leaves; // < 2^(levels-1) <= 2^31
     const uint32_t leaf_first = 1u << (levels - 1);
-    const int plevel = (int)a.start_level - 1;
-    const int64_t roots = level_num_real(a.tree.levels, a.tree.virtual_leaves, a.start_level);
-    const uint32_t pfirst = plevel >= 1 ? (1u << (plevel - 1)) : 0u;
-    const uint32_t pcount = (uint32_t)((roots + 1) / 2); // pseudo-parents of the start-level roots
+    const raywalk::Roots roots(a.tree, a.start_level);
     // one fetch path for nodes and leaves when both are 24-byte records whose volume comes first
     constexpr bool SAME = sizeof(N) == 24 && sizeof(L) == 16;
     const bool unified = SAME && sizeof(I) == 4 && a.lay.stride == 24 && a.lay.index_off == 16;
 
     // per-lane ray state
-    T p[3] = {0, 0, 0}, d[3] = {0, 0, 0}, inv[3] = {0, 0, 0}; // inv = 1 / d, once per ray (isintersection.jl:2-4)
+    raywalk::Ray<T> r;
+    raywalk::Cursor cur;
     int ray = -1;          // ray-in-block this lane walks (-1: idle)
     uint32_t pi = 0;       // pseudo-parent being walked
-    uint32_t inode = 0, pend = 0;
-    int level = 0;
     int64_t w = 0, cnt = 0;
     bool meta_bad = false; // a position that does not fit the entry's meta field: the block walks again when writing
-    int next = 0;          // wave-uniform: rays of the block handed out so far
 
-    auto node_hit = [&](const N &n) {
-        if constexpr (N::kind == IBVH_BBOX) return isintersection_inv(n, p, inv);
-        else return isintersection(n, p, d);
-    };
     auto emit = [&](I lidx, uint32_t lpos) {
         // (leaf.index, iray), raytrace/lvt:200 — or the leaf's 1-based position (IBVH_OUTPUT_POSITIONS)
         const IndexPair<I> c2{a.positions ? (I)(lpos + 1u) : lidx, (I)(first_item + ray + 1)};
@@ -109,43 +101,30 @@ __global__ __launch_bounds__(64) void lvt_rays_kernel(Args<L, N, I> a, PairCache
     for (;;) {
         // ---- refill: idle lanes take the next rays of the block
         const uint64_t idle = __builtin_amdgcn_ballot_w64(ray < 0);
-        if (idle != 0 && next < items_here) {
-            const int rank = (int)__builtin_amdgcn_mbcnt_hi((uint32_t)(idle >> 32), __builtin_amdgcn_mbcnt_lo((uint32_t)idle, 0u));
-            const int mine = next + rank;
+        if (idle != 0 && block.more()) {
+            const int mine = block.take(idle);
             if (ray < 0 && mine < items_here) {
                 const int64_t item = first_item + mine;
-#pragma unroll
-                for (int k = 0; k < 3; ++k) {
-                    p[k] = a.points[3 * item + k];
-                    d[k] = a.dirs[3 * item + k];
-                    inv[k] = T(1) / d[k];
-                }
+                r.load(a.points, a.dirs, item);
                 ray = mine;
                 pi = 0;
-                inode = pfirst;
-                level = plevel;
-                pend = 0;
+                roots.first(cur);
                 cnt = 0;
                 if constexpr (WRITE) w = item > 0 ? (int64_t)a.counts[item - 1] : 0;
             }
-            const int taken = __popcll(idle);
-            next = next + taken < items_here ? next + taken : items_here;
         }
         if (__builtin_amdgcn_ballot_w64(ray >= 0) == 0) break; // (an idle wave after the refill: the block is used up)
         // ---- walk: every busy lane advances its ray until a quarter of the wave has gone idle (or the block is used up
         // and everybody is done)
         for (;;) {
             if (ray >= 0) {
-                const int cl = level + 1;
-                const uint32_t c0 = 2u * inode, c1 = c0 + 1u;
-                const uint32_t first = 1u << (cl - 1);
-                const uint32_t nreal = first - (uint32_t)((uint64_t)vl >> (levels - cl));
-                const bool real0 = c0 != 0u, real1 = (c1 - first) < nreal; // (c0 == 0: the pseudo node above the root)
+                const raywalk::Children ch = raywalk::children(levels, vl, cur.node, cur.level);
+                const int cl = ch.cl;
+                const uint32_t c0 = ch.c0, c1 = ch.c1, sk = ch.sk;
+                const bool real0 = ch.real0, real1 = ch.real1;
                 const bool at_leaves = cl == levels;
                 work.add(at_leaves ? 1 : 0, (uint32_t)real0 + (uint32_t)real1);
                 work.add(at_leaves ? 3 : 2, (uint32_t)real0 + (uint32_t)real1);
-                const uint64_t v = (uint64_t)vl >> (levels - cl + 1);
-                const uint32_t sk = (uint32_t)(2 * v) - (uint32_t)__popcll(v); // level_skips(cl)
                 bool h0 = false, h1 = false, descended = false;
                 I idx0 = 0, idx1 = 0;
                 if (unified) {
@@ -167,12 +146,7 @@ __global__ __launch_bounds__(64) void lvt_rays_kernel(Args<L, N, I> a, PairCache
                             L la, lb;
                             __builtin_memcpy(&la, &raw.w[0], 16);
                             __builtin_memcpy(&lb, &raw.w[6], 16);
-                            h0 = real0 && isintersection(la, p, d);
-                            h1 = real1 && isintersection(lb, p, d);
-                            if (a.narrow == IBVH_NARROW_RAY_ORIGIN_OUTSIDE) { // raytrace/lvt:194: isintersection(...) && narrow(leaf, p, d)
-                                h0 = h0 && origin_outside(la, p);
-                                h1 = h1 && origin_outside(lb, p);
-                            }
+                            raywalk::leaf_hits(la, lb, r, a.narrow, real0, real1, h0, h1);
                             // .index sits right behind the 16-byte volume (4 or 8 bytes)
                             // (a 24-byte record with a 16-byte volume: the index is the 4 bytes behind it — a CONSTANT offset; the
                             // run-time a.lay.index_off made the compiler keep `raw` in LDS: 18 LDS instructions a step, SQ counters)
@@ -184,58 +158,37 @@ __global__ __launch_bounds__(64) void lvt_rays_kernel(Args<L, N, I> a, PairCache
                             N na, nb;
                             __builtin_memcpy(&na, &raw.w[0], 24);
                             __builtin_memcpy(&nb, &raw.w[6], 24);
-                            h0 = real0 && node_hit(na);
-                            h1 = real1 && node_hit(nb);
+                            h0 = real0 && raywalk::node_hit(na, r);
+                            h1 = real1 && raywalk::node_hit(nb, r);
                         }
                     }
                 } else if (at_leaves) {
                     const char *rec = a.leaves + ((int64_t)c0 - (int64_t)leaf_first) * a.lay.stride;
                     const L la = load_vol<L>(real0 ? rec : rec + a.lay.stride), lb = load_vol<L>(real1 ? rec + a.lay.stride : rec);
-                    h0 = real0 && isintersection(la, p, d);
-                    h1 = real1 && isintersection(lb, p, d);
-                    if (a.narrow == IBVH_NARROW_RAY_ORIGIN_OUTSIDE) {
-                        h0 = h0 && origin_outside(la, p);
-                        h1 = h1 && origin_outside(lb, p);
-                    }
+                    raywalk::leaf_hits(la, lb, r, a.narrow, real0, real1, h0, h1);
                     if (h0) idx0 = load_index<I>(rec, a.lay);
                     if (h1) idx1 = load_index<I>(rec + a.lay.stride, a.lay);
                 } else {
-                    const N *np = a.nodes + ((int64_t)c0 - (int64_t)sk - 1);
-                    struct Two {
-                        N a, b;
-                    };
-                    Two ch;
-                    if (real0 && real1) {
-                        __builtin_memcpy(&ch, __builtin_assume_aligned(np, 8), sizeof(Two));
-                    } else {
-                        ch.a = load_vol<N>(real0 ? np : np + 1);
-                        ch.b = ch.a;
-                    }
-                    h0 = real0 && node_hit(ch.a);
-                    h1 = real1 && node_hit(ch.b);
+                    raywalk::Two<N> two;
+                    raywalk::load_two(two, a.nodes + ((int64_t)c0 - (int64_t)sk - 1), real0, real1);
+                    h0 = real0 && raywalk::node_hit(two.a, r);
+                    h1 = real1 && raywalk::node_hit(two.b, r);
                 }
                 if (at_leaves) {
                     if (h0) emit(idx0, c0 - leaf_first);
                     if (h1) emit(idx1, c1 - leaf_first);
                 } else if (h0) {
-                    if (h1) pend |= 1u << cl;
-                    inode = c0;
-                    level = cl;
+                    cur.descend(c0, cl, h1);
                     descended = true;
                 } else if (h1) {
-                    inode = c1;
-                    level = cl;
+                    cur.descend(c1, cl, false);
                     descended = true;
                 }
                 if (!descended) {
-                    if (pend != 0) { // back to the deepest pending right sibling
-                        const int pl = 31 - __builtin_clz(pend);
-                        pend &= ~(1u << pl);
-                        inode = (inode >> (level - pl)) | 1u;
-                        level = pl;
-                    } else if (++pi < pcount) { // next root pair of the start level
-                        inode = pfirst + pi;
-                        level = plevel;
+                    if (cur.pend != 0) { // back to the deepest pending right sibling
+                        cur.pop();
+                    } else if (++pi < roots.pcount) { // next root pair of the start level
+                        roots.next(cur, pi);
                     } else { // ray finished
                         if constexpr (!WRITE) a.counts[first_item + ray] = (I)cnt;
                         ray = -1;
@@ -244,7 +197,7 @@ __global__ __launch_bounds__(64) void lvt_rays_kernel(Args<L, N, I> a, PairCache
             }
             const uint64_t idle_now = __builtin_amdgcn_ballot_w64(ray < 0);
             if (idle_now == ~(uint64_t)0) break;
-            if (next < items_here && __popcll(idle_now) >= 16) break;
+            if (block.more() && __popcll(idle_now) >= 16) break;
         }
     }
     work.flush(a.work);

@@ -1,0 +1,164 @@
+// ibvh_raywalk.hpp — the per-lane walk of one ray through the implicit tree (raytrace/leaf_vs_tree/leaf_vs_tree.jl:187-225),
+// once, as the pieces the ray kernels compose: lvt_rays_kernel (ibvh_lvt_rays.hip: the whole tree from global memory),
+// rays_top_kernel (ibvh_lvt_raybins.hip: the same down to the cut level), rays_subtree_kernel and the tail of its
+// workgroup (same file: below the cut, out of the subtree's copy in LDS).
+//
+// The walk.  A lane stands at a node and tests BOTH its children in one step (they are adjacent in memory).  A left hit is
+// descended into, a right hit that has to wait sets the bit of its level in `pend`: the tree is implicit, so the pending
+// right siblings of the current path are one 32-bit mask where the reference keeps a 32-entry stack.  When nothing is
+// descended into, the deepest pending sibling is next (pop); when none is pending, the next pair of roots of the start
+// level (Roots), and after the last pair the ray is finished.  That is the reference's visit order — left subtree, then
+// the pending sibling, deepest first — so the hits of a ray come out in its order whichever kernel walks it.
+// A walk starts one level ABOVE its roots, at a pseudo-parent, so that a pair of roots is tested like any pair of
+// children; above the root of the whole tree that is node 0, whose "left child" 0 does not exist.
+// The reciprocals 1 / d are computed once per ray (isintersection_inv: the same operations in the same order).
+//
+// The wave.  A wave deals the rays of its range to its lanes as they become free: idle lanes are ranked with v_mbcnt (no
+// atomics inside the wave), and the walking loop is left for a refill when a quarter of the wave is idle.
+//
+// What a kernel does with a hit — write a contact, stage a record, emit an item, set a mask bit — stays in the kernel, and so
+// does the control flow of its walking loop (the if / else chain of a step, the two exits of the loop): the kernels' loops
+// compiled to other, slower code when that flow went through helpers that return a flag (LVT traversal, 3).
+#pragma once
+#include "ibvh_lvt.hpp"
+
+namespace ibvh {
+namespace lvt {
+namespace raywalk {
+
+// ---- the ray ---------------------------------------------------------------------------------------------------------
+template <class T> struct Ray {
+    T p[3] = {0, 0, 0}, d[3] = {0, 0, 0}, inv[3] = {0, 0, 0}; // inv = 1 / d, once per ray (isintersection.jl:2-4)
+    IBVH_D void load(const T *points, const T *dirs, int64_t item) {
+#pragma unroll
+        for (int k = 0; k < 3; ++k) {
+            p[k] = points[3 * item + k];
+            d[k] = dirs[3 * item + k];
+            inv[k] = T(1) / d[k];
+        }
+    }
+};
+// ray against a node volume: the slab test takes the reciprocals, the sphere test the direction
+template <class N, class T> IBVH_D bool node_hit(const N &n, const Ray<T> &r) {
+    if constexpr (N::kind == IBVH_BBOX) return isintersection_inv(n, r.p, r.inv);
+    else return isintersection(n, r.p, r.d);
+}
+// ray against the two leaves la, lb with the ray narrow of the menu (raytrace/lvt:194: isintersection(...) && narrow(leaf, p, d));
+// real0 / real1: whether the leaf exists
+template <class L, class T> IBVH_D void leaf_hits(const L &la, const L &lb, const Ray<T> &r, int narrow, bool real0, bool real1, bool &h0, bool &h1) {
+    h0 = real0 && isintersection(la, r.p, r.d);
+    h1 = real1 && isintersection(lb, r.p, r.d);
+    if (narrow == IBVH_NARROW_RAY_ORIGIN_OUTSIDE) {
+        h0 = h0 && origin_outside(la, r.p);
+        h1 = h1 && origin_outside(lb, r.p);
+    }
+}
+
+// ---- where a lane stands: node and level (implicit index and tree level, or heap index and depth inside a subtree) ------
+struct Cursor {
+    uint32_t node = 0, pend = 0; // pend bit l: the right sibling of the path's node at level l was hit and waits
+    int level = 0;
+    IBVH_D void start(uint32_t n, int l) {
+        node = n;
+        level = l;
+        pend = 0;
+    }
+    // into child c of level cl; sibling_waits: it is the left child and the right one was hit too
+    IBVH_D void descend(uint32_t c, int cl, bool sibling_waits) {
+        if (sibling_waits) pend |= 1u << cl;
+        node = c;
+        level = cl;
+    }
+    // the right sibling, at level pl, of the path's node there
+    IBVH_D uint32_t right_sibling(int pl) const { return (node >> (level - pl)) | 1u; }
+    // back to the deepest pending right sibling (pend != 0)
+    IBVH_D void pop() {
+        const int pl = 31 - __builtin_clz(pend);
+        pend &= ~(1u << pl);
+        node = right_sibling(pl);
+        level = pl;
+    }
+};
+
+// ---- the children of a node in global memory ----------------------------------------------------------------------------
+// real nodes of `level` and the virtual nodes skipped in memory before it (level_num_real, level_skips of ibvh_common.hpp in
+// the 32-bit arithmetic of a tree of <= 32 levels); levels, vl: the tree's levels and virtual leaves, wave-uniform
+IBVH_D uint32_t level_real32(int levels, uint32_t vl, int level) { return (1u << (level - 1)) - (uint32_t)((uint64_t)vl >> (levels - level)); }
+IBVH_D uint32_t level_skips32(int levels, uint32_t vl, int level) {
+    const uint64_t v = (uint64_t)vl >> (levels - level + 1);
+    return (uint32_t)(2 * v) - (uint32_t)__popcll(v);
+}
+struct Children {
+    int cl;             // their level
+    uint32_t c0, c1;    // implicit indices
+    bool real0, real1;  // (c0 == 0: the pseudo node above the root)
+    uint32_t sk;        // level_skips(cl): child c lives at nodes[c - sk - 1]
+};
+IBVH_D Children children(int levels, uint32_t vl, uint32_t node, int level) {
+    Children c;
+    c.cl = level + 1;
+    c.c0 = 2u * node;
+    c.c1 = c.c0 + 1u;
+    c.real0 = c.c0 != 0u;
+    c.real1 = (c.c1 - (1u << (c.cl - 1))) < level_real32(levels, vl, c.cl);
+    c.sk = level_skips32(levels, vl, c.cl);
+    return c;
+}
+// the two children at np, np + 1 in one fetch; a missing one re-reads its sibling (its hit is masked by real0 / real1)
+template <class N> struct Two {
+    N a, b;
+};
+template <class N> IBVH_D void load_two(Two<N> &ch, const N *np, bool real0, bool real1) {
+    if (real0 && real1) {
+        __builtin_memcpy(&ch, __builtin_assume_aligned(np, 8), sizeof(Two<N>));
+    } else {
+        ch.a = load_vol<N>(real0 ? np : np + 1);
+        ch.b = ch.a;
+    }
+}
+
+// ---- the roots of a walk: pairs of start-level nodes under their pseudo-parents (wave-uniform) ---------------------------
+struct Roots {
+    int plevel;
+    uint32_t pfirst, pcount; // a lane walks pseudo-parents pi = 0 .. pcount - 1; after the last one its ray is finished
+    IBVH_D Roots(const TreeDev &tree, int64_t start_level) {
+        plevel = (int)start_level - 1;
+        const int64_t roots = level_num_real(tree.levels, tree.virtual_leaves, start_level);
+        pfirst = plevel >= 1 ? (1u << (plevel - 1)) : 0u;
+        pcount = (uint32_t)((roots + 1) / 2);
+    }
+    IBVH_D void first(Cursor &c) const { c.start(pfirst, plevel); }
+    IBVH_D void next(Cursor &c, uint32_t pi) const { // (pi < pcount)
+        c.node = pfirst + pi;
+        c.level = plevel;
+    }
+};
+
+// ---- dealing work to idle lanes -------------------------------------------------------------------------------------------
+// the piece of [base, ...) for this lane when it is idle: base + its rank among the idle lanes (`idle`: their ballot); the
+// caller checks it against the end of what there is to hand out
+IBVH_D int deal(uint64_t idle, int base) {
+    return base + (int)__builtin_amdgcn_mbcnt_hi((uint32_t)(idle >> 32), __builtin_amdgcn_mbcnt_lo((uint32_t)idle, 0u));
+}
+// a wave's block of `ray_block` consecutive rays (one wave a workgroup), dealt in order
+struct Block {
+    int64_t first_item;
+    int items_here;
+    int next = 0; // wave-uniform: rays handed out so far
+    IBVH_D Block(int64_t n_items, int ray_block) {
+        first_item = (int64_t)blockIdx.x * ray_block;
+        const int64_t left = n_items - first_item;
+        items_here = (int)(left < ray_block ? left : ray_block);
+    }
+    IBVH_D bool more() const { return next < items_here; }
+    IBVH_D int take(uint64_t idle) { // (idle != 0 && more()); items_here or more: nothing left for this lane
+        const int mine = deal(idle, next);
+        const int taken = __popcll(idle);
+        next = next + taken < items_here ? next + taken : items_here;
+        return mine;
+    }
+};
+
+} // namespace raywalk
+} // namespace lvt
+} // namespace ibvh

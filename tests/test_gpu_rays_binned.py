@@ -279,3 +279,48 @@ def test_the_counting_pass_keeps_its_hits_for_the_writing_pass(n_leaves, n_rays)
         assert len(ms) == 2, ms
         best = ms if best is None or ms[1] / ms[0] < best[1] / best[0] else best
     assert best[1] < 0.3 * best[0] + 0.01, f"the writing pass walked again: count {best[0]:.3f} ms, write {best[1]:.3f} ms"
+
+
+RAY_BLOCK_TYPES = [  # (leaves, nodes, index, Morton): what of the per-lane walker each set reaches
+    (abi.BSPHERE, abi.F32, abi.BBOX, abi.F32, abi.I32, abi.U32),  # 24-byte leaf records: the unified fetch of nodes and leaves
+    (abi.BSPHERE, abi.F32, abi.BBOX, abi.F32, abi.I32, abi.U64),  # 32-byte leaf records: the two fetch paths
+    (abi.BBOX, abi.F64, abi.BBOX, abi.F64, abi.I64, abi.U32),     # the Float64 and Int64 forms
+]
+
+
+@pytest.mark.parametrize("tset", RAY_BLOCK_TYPES, ids=str)
+@pytest.mark.parametrize("ray_block", [128, 1024])
+def test_lanes_that_take_a_second_and_a_third_ray(tset, ray_block):
+    """Every lane of a wave takes its first ray in the first refill; lanes of the per-lane walker and of rays_top_kernel take
+    FURTHER rays of their block (raywalk::Block) only with blocks of 128+ rays, which the launcher picks from ~384,000 rays
+    on: forced here with the ray_block knob.  (rays_subtree_kernel deals a bucket's items, whatever the knob.)  Two full
+    blocks and a ragged one smaller than a wave, irregular rays, per-lane walker and binned path: the oracle's list in the
+    oracle's order."""
+    scale = 8.0
+    rng = np.random.default_rng(300 + ray_block)
+    types = abi.make_types(*tset[:4], index_type=tset[4], morton_type=tset[5])
+    vols = random_volumes(rng, 1000, tset[0], tset[1], scale=scale)
+    o, g = build_both(vols, types)
+    nr = 2 * ray_block + 37
+    p, d = _rays(rng, nr, scale)
+    p, d = p.astype(NP_F[tset[1]]), d.astype(NP_F[tset[1]])
+    P_, D_ = cuda(p).t(), cuda(d).t()
+    exp = {}
+    for sl in (1, o.tree.levels):
+        with np.errstate(all="ignore"):
+            exp[sl] = oracle_pairs(orc.traverse_rays_lvt(o, p, d, sl)[0]).reshape(-1, 2)
+        # not vacuous, by the oracle alone: lanes fall idle at different times (rays without a hit in every block, long rays)
+        per_ray = np.bincount(exp[sl][:, 1] - 1, minlength=nr)
+        assert len(exp[sl]) > 0 and per_ray.max() >= 8
+        assert all((per_ray[b:b + ray_block] == 0).any() for b in range(0, nr, ray_block))
+    pos = _positions(o.leaves)
+    for path in (dict(rays_binned=0), dict(rays_binned=2, rays_subtree_depth=3)):
+        with knobs(ray_block=ray_block, **path):
+            for sl in (1, o.tree.levels):
+                t1 = ibvh.traverse_rays(g, P_, D_, start_level=sl)
+                assert t1.num_contacts == len(exp[sl]), (path, sl)
+                assert (contacts_np(t1).reshape(-1, 2) == exp[sl]).all(), (path, sl)
+                t2 = ibvh.traverse_rays(g, P_, D_, start_level=sl, cache=t1)  # the cached write
+                assert (contacts_np(t2).reshape(-1, 2) == exp[sl]).all(), (path, sl)
+            raw = contacts_np(_rays_positions(g, P_, D_)).reshape(-1, 2)
+            assert (raw[:, 0] == pos[exp[1][:, 0]]).all() and (raw[:, 1] == exp[1][:, 1]).all(), path
