@@ -73,6 +73,9 @@ MAX_SORT_LEVELS = 4  # IBVH_MAX_SORT_LEVELS (include/ibvh.h)
 NEAREST_MAX_K = 16  # IBVH_NEAREST_MAX_K (include/ibvh.h)
 # ibvh_nearest_leaves(bvh, points, num_points, k, max_distance2, nearest_index, nearest_d2, stream)
 NEAREST_LEAVES_ARGTYPES = [C.POINTER(Bvh), C.c_void_p, C.c_int64, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
+# ibvh_point_crossings(bvh, triangles, num_triangles, points, num_points, axis, crossings, winding, flag, stream)
+POINT_CROSSINGS_ARGTYPES = [C.POINTER(Bvh), C.c_void_p, C.c_int64, C.c_void_p, C.c_int64, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p,
+                            C.c_void_p]
 
 
 class BuildDesc(C.Structure):

@@ -31,7 +31,7 @@ __all__ = [
     "memory_index", "level_indices", "isvirtual", "bounding_volumes_from_triangles", "generate_spheres",
     "NARROW_MORTON_LT", "NARROW_INDEX_LT", "NARROW_RAY_ORIGIN_OUTSIDE", "LeafBatch", "lvt_work_counters", "refit",
     "resolve_triangles", "raycast", "RayHits", "closest_points", "ClosestPoints",
-    "nearest_leaves", "NearestLeaves",
+    "nearest_leaves", "NearestLeaves", "point_crossings", "PointCrossings", "points_inside", "signed_distance",
 ]
 
 NARROW_MORTON_LT = abi.NARROW_MORTON_LT
@@ -1477,6 +1477,106 @@ def nearest_leaves(bvh, points, k=1, max_distance=None, presorted=False):
         return NearestLeaves(index, d2)
     lib.call("ibvh_nearest_leaves", C.byref(bvh.struct()), _ptr(p), n, int(k), radius2, _ptr(index), _ptr(d2), _stream())
     return NearestLeaves(*_unpermute(order, (index, d2)))
+
+
+# ---------------------------------------------------------------------------------------------
+# inside / outside of a closed mesh for a batch of query points (ibvh_point_crossings; no reference counterpart)
+# ---------------------------------------------------------------------------------------------
+class PointCrossings:
+    """Per query point: .crossings (N,) the number of triangles the axis ray from the point crosses, .winding (N,) the ccw
+    crossings minus the cw ones (+1 inside an outward-oriented closed mesh, -1 inside an inward-oriented one, 0 outside)."""
+
+    def __init__(self, crossings, winding):
+        self.crossings, self.winding = crossings, winding
+
+
+def _check_axis(axis, what):
+    if not (isinstance(axis, (int, np.integer)) and not isinstance(axis, bool) and 0 <= axis <= 2):
+        raise ValueError(f"{what}: axis must be 0, 1 or 2")
+    return int(axis)
+
+
+def _check_rule(rule, what):
+    if rule not in ("parity", "winding"):
+        raise ValueError(f"{what}: rule must be 'parity' or 'winding'")
+
+
+def point_crossings(bvh, triangles, points, axis=0, presorted=False):
+    """For every query point P the triangles of the mesh `bvh` was built over that the ray P + t*e_axis, t > 0, crosses
+    -> PointCrossings (include/ibvh.h, ibvh_point_crossings: the guard, the canonical edge order that makes a ray through a
+    shared edge or vertex cross the surface once, the depth test and why pruning loses nothing are spelled out there).  One
+    launch, exact: equal to a brute force over all triangles.
+
+    bvh: BBox leaves made from `triangles` (bounding_volumes_from_triangles(triangles, BBox(dtype)); a skin margin and
+    refit are fine) under BBox nodes of the same or a wider float type.  triangles: (n, 9) / (n, 3, 3) CUDA tensor of the
+    leaves' dtype, user index k = row k - 1.  points: (3, N) CUDA tensor of that dtype, as for traverse_rays.  axis: 0, 1
+    or 2.  The device walks the batch in Morton order of the points (lanes of a wave then share nodes) and the outputs are
+    put back in the caller's order; presorted=True walks it as given.
+
+    Points on the surface are ambiguous; shared vertices must be bit-identical (no T-junctions or cracks).
+
+    ValueError: sphere leaves or nodes, nodes narrower than the leaves, a wrong dtype, device or shape, an axis outside
+    0..2, and a leaf whose index lies outside 1..n (flag bit 1; such leaves are skipped)."""
+    torch = _require_gpu()
+    t = bvh.types
+    if t.leaf_kind != abi.BBOX or t.node_kind != abi.BBOX:
+        raise ValueError("point_crossings: the BVH must have BBox leaves under BBox nodes (the guard needs boxes that contain "
+                         "their triangles exactly; sphere leaves are not supported)")
+    if t.leaf_float == abi.F64 and t.node_float == abi.F32:
+        raise ValueError("point_crossings: Float32 nodes over Float64 leaves do not contain them exactly")
+    axis = _check_axis(axis, "point_crossings")
+    tris = _check_triangles(triangles, "point_crossings")
+    ft = _torch_float(t.leaf_float)
+    if tris.dtype != ft:
+        raise ValueError(f"point_crossings: triangles must be {ft}, the BVH's leaf float type")
+    p, n, _, order = _query_points(points, ft, None, presorted, "point_crossings")
+    idt = _torch_index(t.index_type)
+    crossings = torch.empty(n, dtype=idt, device="cuda")
+    winding = torch.empty(n, dtype=idt, device="cuda")
+    if n == 0:
+        return PointCrossings(crossings, winding)
+    flag = torch.zeros(1, dtype=torch.int32, device="cuda")
+    lib.call("ibvh_point_crossings", C.byref(bvh.struct()), _ptr(tris), tris.shape[0], _ptr(p), n, axis, _ptr(crossings),
+             _ptr(winding), _ptr(flag), _stream())
+    if int(flag.item()) & 2:
+        raise ValueError(f"point_crossings: a leaf's index lies outside 1..{tris.shape[0]} (the number of triangles given)")
+    return PointCrossings(*_unpermute(order, (crossings, winding)))
+
+
+def _inside(pc, rule):
+    return (pc.crossings & 1) == 1 if rule == "parity" else pc.winding != 0
+
+
+def points_inside(bvh, triangles, points, axis=0, rule="parity"):
+    """Which query points lie inside the closed mesh `bvh` was built over -> (N,) bool tensor, from point_crossings:
+    rule="parity": the axis ray crosses an odd number of triangles (independent of the triangles' orientation);
+    rule="winding": the winding number is not zero (needs a consistent orientation; right for unions of overlapping closed
+    bodies).  Arguments and ValueErrors as for point_crossings; also an unknown rule."""
+    _check_rule(rule, "points_inside")
+    return _inside(point_crossings(bvh, triangles, points, axis=axis), rule)
+
+
+def signed_distance(bvh, triangles, points, axis=0, rule="parity", max_distance=None):
+    """The signed distance of every query point to the closed mesh `bvh` was built over -> (distance, ClosestPoints):
+    distance (N,) = sqrt(closest_points().distance2), negated where points_inside(rule) says inside, +Inf where no triangle
+    lies within max_distance.  The batch is ordered along the Morton curve once and both queries walk it in that order: two
+    launches; torch computes the sign and the square root only.  Arguments and ValueErrors as for closest_points and
+    points_inside."""
+    torch = _require_gpu()
+    _check_rule(rule, "signed_distance")
+    axis = _check_axis(axis, "signed_distance")
+    if not (isinstance(points, torch.Tensor) and points.dim() == 2 and points.shape[0] == 3):
+        raise ValueError("signed_distance: size(points, 1) == 3 must hold")
+    order = None
+    if points.shape[1] > 0 and points.is_cuda:
+        order = _morton_order(points.t())
+        points = points[:, order]
+    cp = closest_points(bvh, triangles, points, max_distance=max_distance, presorted=True)
+    inside = _inside(point_crossings(bvh, triangles, points, axis=axis, presorted=True), rule)
+    distance = torch.sqrt(cp.distance2)
+    distance = torch.where(inside & (cp.index != 0), -distance, distance)
+    distance, index, d2, q = _unpermute(order, (distance, cp.index, cp.distance2, cp.point))
+    return distance, ClosestPoints(index, d2, q)
 
 
 def lvt_work_counters(bvh, bvh2=None, points=None, directions=None):

@@ -103,9 +103,10 @@ __global__ __launch_bounds__(kBlock) void closest_walk_kernel(TreeDev tree, int 
                 bad = true;
             }
         };
+        auto box = [&](const T *lo, const T *up) { return pointwalk::box_bound(lo, up, p); }; // lb(B) of include/ibvh.h
         // a NaN coordinate makes every d2 NaN and a NaN radius admits nothing: a miss either way, and no bound could prune
         const bool hopeless = !((p[0] == p[0]) & (p[1] == p[1]) & (p[2] == p[2]) & (max_d2 == max_d2));
-        if (!hopeless) pointwalk::walk<BBox<T>, TN>(tree, built_level, leaves, lay, nodes, p, [&]() { return best; }, visit);
+        if (!hopeless) pointwalk::walk<BBox<T>, TN>(tree, built_level, leaves, lay, nodes, box, [&]() { return best; }, visit);
         const bool hit = best_index != 0;
         if (out_index) out_index[item] = best_index;
         if (out_d2) out_d2[item] = hit ? best : std::numeric_limits<T>::infinity();

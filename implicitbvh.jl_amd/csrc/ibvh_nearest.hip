@@ -66,9 +66,10 @@ __global__ __launch_bounds__(kBlock) void nearest_walk_kernel(TreeDev tree, int 
                 cnt += full ? 0 : 1;
             }
         };
+        auto box = [&](const T *lo, const T *up) { return pointwalk::box_bound(lo, up, p); }; // lb(B) of include/ibvh.h
         // a NaN coordinate makes every d2 NaN and a NaN radius admits nothing: no answer either way, and no bound could prune
         const bool hopeless = !((p[0] == p[0]) & (p[1] == p[1]) & (p[2] == p[2]) & (max_d2 == max_d2));
-        if (!hopeless) pointwalk::walk<VL, TN>(tree, built_level, leaves, lay, nodes, p, [&]() { return d[K - 1]; }, visit);
+        if (!hopeless) pointwalk::walk<VL, TN>(tree, built_level, leaves, lay, nodes, box, [&]() { return d[K - 1]; }, visit);
 #pragma unroll
         for (int j = 0; j < K; ++j) {
             if (j >= base) {

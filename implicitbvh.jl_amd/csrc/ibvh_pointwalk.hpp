@@ -1,12 +1,15 @@
-// ibvh_pointwalk.hpp — the bounded walk of one query point through a BVH, shared by the point queries that prune on a bound
-// which shrinks while they walk: ibvh_closest.hip (the closest triangle) and ibvh_nearest.hip (the k nearest leaf centres),
+// ibvh_pointwalk.hpp — the bounded walk of one query point through a BVH, shared by the point queries: the two that prune
+// on a bound which shrinks while they walk, ibvh_closest.hip (the closest triangle) and ibvh_nearest.hip (the k nearest
+// leaf centres), and ibvh_crossings.hip (the triangles an axis ray from the point crosses), whose bound is a fixed yes / no;
 // and the argument checks their entry points have in common.  No reference counterpart: every traversal of ImplicitBVH.jl
 // is a fixed-volume overlap test (traverse/, raytrace/).
 //
-// A query hands the walk two things: limit(), the squared distance beyond which nothing can enter its answer any more, and
-// visit(rec), what to do with a leaf record that is still within it.  The walk is lossless if the COMPUTED bound of a box
-// never exceeds the COMPUTED distance of anything the query could find under it; each query argues that for its own
-// distance.  A box is skipped iff bound > limit(): strictly, because an equal distance under it may carry a smaller index.
+// A query hands the walk three things: bound(lo, up), its lower bound for a box (box_bound below for the distance queries;
+// 0 / 1 = "the ray can / cannot meet the box" for the crossings), limit(), the value beyond which nothing can enter its
+// answer any more, and visit(rec), what to do with a leaf record that is still within it.  The walk is lossless if the
+// COMPUTED bound of a box never exceeds the COMPUTED bound or distance of anything the query could find under it; each query
+// argues that for its own bound.  A box is skipped iff bound > limit(): strictly, because an equal distance under it may
+// carry a smaller index.
 //
 // Work mapping: one lane per query, everything in registers.  The lane descends to the child with the smaller bound
 // first and keeps ONE bit per level — "the other child is still owed" — in a 64-bit trail word (levels <= 62): no
@@ -34,12 +37,13 @@ template <class T> IBVH_D T box_bound(const T *lo, const T *up, const T *p) {
     return (f[0] * f[0] + f[1] * f[1]) + f[2] * f[2];
 }
 
-// The walk of query point p from every root of the built part of the tree.  VL: the leaves' volume type, T its float
+// The walk of one query from every root of the built part of the tree.  VL: the leaves' volume type, T its float
 // type; TN: the nodes' (the same or wider — a node box then holds values of T, widened exactly, and narrows back exactly).
-// limit() -> T is read afresh at every test; visit(const char *rec) may lower it.
-template <class VL, class TN, class Limit, class Visit>
+// bound(const T *lo, const T *up) -> T is the query's bound of a box (it knows the query point); limit() -> T is read
+// afresh at every test; visit(const char *rec) may lower it.
+template <class VL, class TN, class Bound, class Limit, class Visit>
 IBVH_D void walk(const TreeDev &tree, int built_level, const char *__restrict__ leaves, const LeafLayout &lay,
-                 const BBox<TN> *__restrict__ nodes, const typename VL::elt *p, const Limit &limit, const Visit &visit) {
+                 const BBox<TN> *__restrict__ nodes, const Bound &bound, const Limit &limit, const Visit &visit) {
     using T = typename VL::elt;
     const int levels = (int)tree.levels;
     const int64_t vl = tree.virtual_leaves;
@@ -50,11 +54,11 @@ IBVH_D void walk(const TreeDev &tree, int built_level, const char *__restrict__ 
     auto bound_of = [&](uint64_t i, int level) -> T {
         if (level == levels) {
             const BBox<T> b = convert_to(load_vol<VL>(leaves + (int64_t)(i - leaf_first) * lay.stride), (BBox<T> *)nullptr);
-            return box_bound(b.lo, b.up, p);
+            return bound(b.lo, b.up);
         }
         const BBox<TN> n = load_vol<BBox<TN>>(nodes + ((int64_t)i - level_skips(levels, vl, level) - 1));
         const T lo[3] = {T(n.lo[0]), T(n.lo[1]), T(n.lo[2])}, up[3] = {T(n.up[0]), T(n.up[1]), T(n.up[2])};
-        return box_bound(lo, up, p);
+        return bound(lo, up);
     };
 
     for (int64_t r = 0; r < roots; ++r) {

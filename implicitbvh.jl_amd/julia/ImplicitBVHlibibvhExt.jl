@@ -290,6 +290,10 @@ c_nearest_leaves(bvh, points, num_points, k, max_distance2, nearest_index, neare
     ccall((:ibvh_nearest_leaves, libibvh), Cint,
           (Ref{IbvhBvh}, Ptr{Cvoid}, Int64, Int32, Ptr{Cvoid}, Ptr{Cvoid}, Ptr{Cvoid}, Ptr{Cvoid}),
           bvh, points, num_points, k, max_distance2, nearest_index, nearest_d2, stream)
+c_point_crossings(bvh, triangles, num_triangles, points, num_points, axis, crossings, winding, flag, stream) =
+    ccall((:ibvh_point_crossings, libibvh), Cint,
+          (Ref{IbvhBvh}, Ptr{Cvoid}, Int64, Ptr{Cvoid}, Int64, Int32, Ptr{Cvoid}, Ptr{Cvoid}, Ptr{Cvoid}, Ptr{Cvoid}),
+          bvh, triangles, num_triangles, points, num_points, axis, crossings, winding, flag, stream)
 c_lvt_scratch_bytes(types, n_items, cache_slots, out) =
     ccall((:ibvh_lvt_scratch_bytes, libibvh), Cint,
           (Ref{IbvhTypes}, Int64, Int32, Ref{Csize_t}),
@@ -674,6 +678,60 @@ function closest_points(bvh::RocBVH{I}, triangles::ROCMatrix{T}, points::ROCMatr
     isnothing(order) && return (; index, distance2, point)
     inv = ROCVector{Int64}(invperm(order))
     (; index=index[inv], distance2=distance2[inv], point=point[:, inv])
+end
+
+# ---- inside / outside of a closed mesh for a batch of query points (include/ibvh.h, ibvh_point_crossings) ------------
+"""
+    point_crossings(bvh::BVH, triangles::ROCMatrix{T}, points::ROCMatrix{T}; axis=1, presorted=false)
+        -> (; crossings, winding)
+
+For every query point P (column of the 3 x N `points`) the triangles of the mesh `bvh` was built over that the ray from P
+along the positive coordinate `axis` (1, 2 or 3) crosses: `crossings[i]` how many, `winding[i]` the counter-clockwise ones
+minus the clockwise ones (+1 inside an outward-oriented closed mesh, -1 inside an inward-oriented one, 0 outside).  Both are
+counts over ALL triangles — equal to a brute force; the guard, the canonical edge order that makes a ray through a shared edge
+or vertex cross the surface once, the depth test and why pruning loses nothing are spelled out in include/ibvh.h.
+`triangles` is 9 x n (column k = p1 p2 p3 of the triangle with user index k).  The BVH must have `BBox{T}` leaves made from
+the triangles (a skin margin and `refit!` are fine) under `BBox` nodes of `T` or wider; anything else raises ArgumentError.
+Points on the surface are ambiguous; shared vertices must be bit-identical.  The device walks the batch along a Morton curve
+through the points and the outputs come back in the caller's order; `presorted=true` walks it as given.  Not a method of
+ImplicitBVH: the reference has no such query.
+"""
+function point_crossings(bvh::RocBVH{I}, triangles::ROCMatrix{T}, points::ROCMatrix{T}; axis::Integer=1,
+                         presorted::Bool=false) where {I, T}
+    d = bvh_desc(bvh)
+    isnothing(d) && throw(ArgumentError("point_crossings: no libibvh instantiation for this BVH's types"))
+    leaf_volume_type(bvh.leaves) === BBox{T} && eltype(bvh.nodes) <: BBox && sizeof(eltype(bvh.nodes)) >= sizeof(BBox{T}) ||
+        throw(ArgumentError("point_crossings: the BVH must have BBox{$T} leaves under BBox nodes of $T or wider"))
+    1 <= axis <= 3 || throw(ArgumentError("point_crossings: axis must be 1, 2 or 3"))
+    size(triangles, 1) == 9 || throw(ArgumentError("point_crossings: triangles must be 9 x n (p1 p2 p3 per column)"))
+    size(points, 1) == 3 || throw(ArgumentError("size(points, 1) == 3 must hold"))
+    n = size(points, 2)
+    crossings = similar(points, I, n)
+    winding = similar(points, I, n)
+    n == 0 && return (; crossings, winding)
+    order = presorted ? nothing : point_morton_order(points)
+    p = isnothing(order) ? points : points[:, ROCVector{Int64}(order)]
+    flag = scratch!(:crossings_flag, 4)
+    fill!(flag, 0x00)
+    check(c_point_crossings(d, devptr(triangles), Int64(size(triangles, 2)), devptr(p), Int64(n), Int32(axis - 1),
+                            devptr(crossings), devptr(winding), devptr(flag), stream_ptr()), "ibvh_point_crossings")
+    Array(flag)[1] & 0x02 != 0 && throw(ArgumentError("point_crossings: a leaf's index lies outside 1:$(size(triangles, 2))"))
+    isnothing(order) && return (; crossings, winding)
+    inv = ROCVector{Int64}(invperm(order))
+    (; crossings=crossings[inv], winding=winding[inv])
+end
+
+"""
+    points_inside(bvh::BVH, triangles::ROCMatrix{T}, points::ROCMatrix{T}; axis=1, rule=:parity) -> ROCVector{Bool}
+
+Which query points lie inside the closed mesh `bvh` was built over, from `point_crossings`: `rule=:parity` — the axis ray
+crosses an odd number of triangles (independent of the triangles' orientation); `rule=:winding` — the winding number is not
+zero (needs a consistent orientation; right for unions of overlapping closed bodies).
+"""
+function points_inside(bvh::RocBVH, triangles::ROCMatrix{T}, points::ROCMatrix{T}; axis::Integer=1, rule::Symbol=:parity) where {T}
+    rule in (:parity, :winding) || throw(ArgumentError("points_inside: rule must be :parity or :winding"))
+    c = point_crossings(bvh, triangles, points; axis)
+    rule === :parity ? isodd.(c.crossings) : c.winding .!= 0
 end
 
 # ---- k nearest leaves for a batch of query points (include/ibvh.h, ibvh_nearest_leaves) ------------------------------

@@ -44,6 +44,7 @@ extern "C" {
  *   7: ibvh_refit; ibvh_rays_resolve_triangles (additive under 7: a new entry point, no struct layout or existing
  *      argument list moves, so a binding written against the earlier 7 keeps working); ibvh_closest_triangles (additive
  *      under 7 in the same way); ibvh_nearest_leaves and IBVH_NEAREST_MAX_K (additive under 7 in the same way);
+ *      ibvh_point_crossings (additive under 7 in the same way);
  *      argument checks only, no layout or argument list moves: ibvh_key_histogram takes
  *      what fits its LDS staging (10 rows at 12-bit digits) and refuses shift > 63 and a negative prefix_shift,
  *      ibvh_pack_records / ibvh_dist_plan answer IBVH_ERR_OVERFLOW for an index past IBVH_I32 */
@@ -544,6 +545,71 @@ ibvh_status ibvh_closest_triangles(const ibvh_bvh *bvh, const void *triangles, i
 #define IBVH_NEAREST_MAX_K 16
 ibvh_status ibvh_nearest_leaves(const ibvh_bvh *bvh, const void *points, int64_t num_points, int32_t k,
                                 const void *max_distance2, void *nearest_index, void *nearest_d2, void *stream);
+
+/* ----------------------------------------------------------------------------------- */
+/* inside / outside: the triangles an axis ray from a query point crosses               */
+/* ----------------------------------------------------------------------------------- */
+/* For every query point P: the triangles of the mesh the BVH was built over (ibvh_volumes_from_triangles with IBVH_BBOX)
+ * that the ray P + t*e_axis, t > 0, crosses — how many, and the signed sum of their orientations.  On a closed mesh that is
+ * the side of the surface P lies on.  No reference counterpart (every traversal of the reference is a fixed-volume overlap
+ * test, and its ray test has no rule for a ray through a shared edge or vertex); ONE launch, NO host synchronisation, no
+ * atomics, no scratch buffer.
+ *   triangles  : num_triangles x 9 values (p1 p2 p3) of bvh->types.leaf_float, `flt` below; user index k is row k - 1
+ *   points     : num_points x 3 row-major values of `flt`, processed in the order given (neighbours in memory that are
+ *                neighbours in space walk the same nodes: sort a scattered batch along a Morton curve first)
+ *   axis       : 0, 1 or 2: the ray runs along +x, +y or +z
+ * Outputs — each optional, at least one non-NULL; what was not asked for is not written:
+ *   crossings  : num_points x I, the number of crossing triangles
+ *   winding    : num_points x I, the number of ccw crossings minus the number of cw ones: +1 inside an outward-oriented
+ *                closed mesh, -1 inside an inward-oriented one, 0 outside
+ * All arguments are validated before any launch: NULL required pointers, negative sizes, no output at all, an axis outside
+ * 0..2, a tree shape that is not an ImplicitTree's: IBVH_ERR_INVALID_ARG.  num_points == 0: IBVH_OK, nothing is touched.
+ * The result is defined independently of how it is found: both counts run over ALL triangles.  With the CYCLIC coordinates
+ *     u = (axis + 1) % 3;  v = (axis + 2) % 3;  w = axis        (cyclic: orientation is preserved)
+ * a triangle (A, B, C) = (p1, p2, p3) is a crossing iff rules 1 to 4 hold, in `flt`, every operation rounded once (nothing
+ * fused), so that it can be pinned bit for bit:
+ *   1. Guard:  P.u >= min3(A.u, B.u, C.u) && P.u <= max3(A.u, B.u, C.u), the same for v, and max3(A.w, B.w, C.w) >= P.w
+ *      (min3 / max3: the `x < y ? x : y` ternaries of BBox{T}(p1, p2, p3)).  Comparisons only, false on NaN.
+ *   2. Edges:  for each directed edge (X, Y) in (A, B), (B, C), (C, A): put the endpoints in CANONICAL order —
+ *        flipped = Y is lexicographically smaller than X on (u, v, w);  swap X and Y if so —
+ *        e = (Y.u - X.u)*(P.v - X.v) - (Y.v - X.v)*(P.u - X.u)      on the canonical pair
+ *        left = (e >= 0)      a tie goes LEFT of the canonical edge
+ *        side = left XOR flipped
+ *   3. Orientation:  ccw = all three sides true;  cw = all three false;  anything else is no crossing.
+ *   4. Depth:  ab = B - A;  ac = C - A;  d = P - A, each in (u, v, w);
+ *        N = (ab.v*ac.w - ab.w*ac.v,  ab.w*ac.u - ab.u*ac.w,  ab.u*ac.v - ab.v*ac.u);   s = (N0*d.u + N1*d.v) + N2*d.w
+ *      a crossing iff (ccw && s < 0) || (cw && s > 0);  s == 0 (P on the plane) and NaN are no crossing.
+ * Why the canonical edge: it makes the count WATERTIGHT without exact arithmetic.  Two triangles that share an edge — its
+ *   endpoints bit-identical in both — compute the same bits for e and put P on the same side of that edge's line, ties
+ *   included, so a ray through a shared edge or a shared vertex crosses the surface once, not zero or two times.
+ * Why pruning is lossless WITHOUT an epsilon: a box B (a node, or a leaf's stored volume) is entered iff the guard's five
+ *   comparisons hold on the box,
+ *       P.u >= B.lo.u && P.u <= B.up.u && P.v >= B.lo.v && P.v <= B.up.v && B.up.w >= P.w
+ *   and every box of the tree contains the boxes below it exactly (min / max, widening conversions), so a triangle whose
+ *   own box passes the guard has every box above it pass.  Nothing is computed, so nothing is rounded.  Traversal order and
+ *   work mapping therefore cannot change the result.
+ * Limits.  A point ON the surface is ambiguous (s == 0 is no crossing; which side a point within rounding of the surface is
+ *   given follows the sign of the computed s).  Watertightness holds on shared edges and vertices of a mesh whose shared
+ *   vertices are bit-identical; it does not hold for T-junctions or cracks.  The parity of `crossings` is
+ *   orientation-independent; `winding` needs a consistent orientation but is right for unions of overlapping closed bodies
+ *   (2 inside two of them).  Zero-area triangles never count (s == 0).
+ * Accepted BVHs — the guard needs boxes that contain their triangles' boxes exactly:
+ *   leaf_kind == node_kind == IBVH_BBOX, triangles and points of leaf_float, node_float the same as or wider than
+ *   leaf_float; any index and Morton type.  Anything else — sphere leaves (a sphere does not contain its triangle exactly),
+ *   sphere nodes, F64 leaves under F32 nodes — is IBVH_ERR_UNSUPPORTED, never an answer.
+ *   Exact PROVIDED every leaf's box contains its triangle's box: a skin margin on the leaves is allowed, and so is a BVH
+ *   after ibvh_refit.  Levels above bvh->built_level are not read.
+ * NaN: a triangle with a NaN vertex in u or v fails the guard or an edge test and never counts; a NaN or +Inf query
+ *   coordinate crosses nothing (-Inf along the axis is a ray from infinitely far away: finite where no 0 * Inf arises).  But, as for ibvh_closest_triangles, a NaN leaf box can make merge.jl's `a < b ? a : b` produce
+ *   a node box that does NOT contain the NaN-free leaves below it: on a mesh with NaN vertices the other triangles' counts are
+ *   only guaranteed in trees of at most two leaves.
+ * Guards: the triangle is read through the leaf record's .index, not its position.  A leaf whose index lies outside
+ * 1..num_triangles is skipped, nothing outside the array is read, and bit 1 of `flag` is set — the flag contract of
+ * ibvh_rays_resolve_triangles: optional, 4 bytes the GPU can write, a plain load and store, never cleared by the library
+ * (zero it before the call). */
+ibvh_status ibvh_point_crossings(const ibvh_bvh *bvh, const void *triangles, int64_t num_triangles,
+                                 const void *points, int64_t num_points, int32_t axis,
+                                 void *crossings, void *winding, void *flag, void *stream);
 
 /* ----------------------------------------------------------------------------------- */
 /* breadth-first traversal (BFSTraversal): level-synchronous pair queues                 */
