@@ -1,5 +1,6 @@
 // ibvh_build.hip — BVH construction on gfx950: extrema -> Morton keys -> stable sort of the records -> bottom-up merge.
-// Replaces src/build.jl:198-271 and src/morton/*.jl of the reference.
+// Replaces src/build.jl:198-271 and src/morton/*.jl of the reference.  Here: the extrema and the keys, the scratch carve, the
+// choice of the sort and the build driver; the sorts are ibvh_msd.hip / ibvh_sort.hip, the merge is ibvh_aggregate.hip.
 //
 // Data flow (BSphere{F32} leaves, n of them; bytes per leaf in brackets):
 //   extrema_partial   read volumes [16]                         -> per-workgroup min/max
@@ -9,8 +10,9 @@
 //   sort              n >= 4,096: ibvh_msd.hip — ONE partition of the finished records by the top bits of their key
 //                     (read key [4] + volume [16 random], write record [24]), every cell finished in LDS [24 + 24]
 //                     n <  4,096: ibvh_sort.hip — (key, position) pairs; the last pass writes the records
-//   aggregate         read records [24 stride, 16 used], write nodes [24 * ~1]
+//   aggregate         ibvh_aggregate.hip
 #include "ibvh_common.hpp"
+#include "ibvh_aggregate.hpp"
 #include "ibvh_radix.hpp"
 #include "ibvh_msd.hpp"
 #include "ibvh_sort.hpp"
@@ -42,6 +44,40 @@ template <class T> IBVH_D T wave_max(T v) {
     return v;
 }
 
+// Six running extrema (three minima, three maxima) through a workgroup of `waves` waves: every wave reduces its lanes, lane 0
+// hands the six results over in row `w` of `s`, and behind the one barrier thread k < 6 folds value k of all rows into `v`
+// (minimum k on thread k, maximum k on thread 3 + k).  True on those six threads.
+template <class T> IBVH_D bool fold_extrema(const T mn[3], const T mx[3], T (*s)[6], int waves, T &v) {
+    const int lane = threadIdx.x & 63, w = threadIdx.x >> 6;
+#pragma unroll
+    for (int k = 0; k < 3; ++k) {
+        T a = wave_min(mn[k]), b = wave_max(mx[k]);
+        if (lane == 0) {
+            s[w][k] = a;
+            s[w][3 + k] = b;
+        }
+    }
+    __syncthreads();
+    if (threadIdx.x >= 6) return false;
+    v = s[0][threadIdx.x];
+    for (int i = 1; i < waves; ++i) {
+        T t = s[i][threadIdx.x];
+        v = threadIdx.x < 3 ? (v < t ? v : t) : (v > t ? v : t);
+    }
+    return true;
+}
+// A thread's share of the per-workgroup partial extrema (extrema_partial_kernel): every `step`-th of `nparts`
+template <class T> IBVH_D void take_partials(const T *__restrict__ partials, int nparts, int step, T mn[3], T mx[3]) {
+    for (int i = threadIdx.x; i < nparts; i += step) {
+#pragma unroll
+        for (int k = 0; k < 3; ++k) {
+            const T a = partials[i * 6 + k], b = partials[i * 6 + 3 + k];
+            mn[k] = mn[k] < a ? mn[k] : a;
+            mx[k] = mx[k] > b ? mx[k] : b;
+        }
+    }
+}
+
 // min/max are exact and order-free (no NaNs), so any reduction tree reproduces the reference's
 // mapreduce bit for bit.  Inits: min <- floatmax(T); max <- floatmin(T) (sic, utils.jl:39-40).
 template <class V>
@@ -61,24 +97,8 @@ __global__ __launch_bounds__(EXT_TPB) void extrema_partial_kernel(const char *__
         }
     }
     __shared__ T s[EXT_TPB / 64][6];
-    const int lane = threadIdx.x & 63, w = threadIdx.x >> 6;
-#pragma unroll
-    for (int k = 0; k < 3; ++k) {
-        T a = wave_min(mn[k]), b = wave_max(mx[k]);
-        if (lane == 0) {
-            s[w][k] = a;
-            s[w][3 + k] = b;
-        }
-    }
-    __syncthreads();
-    if (threadIdx.x < 6) {
-        T v = s[0][threadIdx.x];
-        for (int i = 1; i < EXT_TPB / 64; ++i) {
-            T t = s[i][threadIdx.x];
-            v = threadIdx.x < 3 ? (v < t ? v : t) : (v > t ? v : t);
-        }
-        partials[(int64_t)blockIdx.x * 6 + threadIdx.x] = v;
-    }
+    T v;
+    if (fold_extrema(mn, mx, s, EXT_TPB / 64, v)) partials[(int64_t)blockIdx.x * 6 + threadIdx.x] = v;
 }
 
 // compute_skips! on device memory (build.jl:232-239), folded into whichever single-workgroup kernel the build launches
@@ -96,44 +116,18 @@ IBVH_D void write_skips(const SkipsOut &so) {
     else ((int64_t *)so.skips)[level - 1] = v;
 }
 
-// One workgroup folds the partials and applies the epsilon expansion of
-// bounding_volumes_extrema (utils.jl:63-69): x -/+ rp*abs(x) -/+ floatmin, two roundings a side.
+// One workgroup folds the partials and applies the epsilon expansion of bounding_volumes_extrema (expand_bound).
 template <class T>
 __global__ __launch_bounds__(EXT_TPB) void extrema_final_kernel(const T *__restrict__ partials, int nparts, int expand,
                                                                 T *__restrict__ out, T *__restrict__ out2, SkipsOut so) {
     write_skips(so);
     T mn[3] = {float_max<T>(), float_max<T>(), float_max<T>()};
     T mx[3] = {float_min_normal<T>(), float_min_normal<T>(), float_min_normal<T>()};
-    for (int i = threadIdx.x; i < nparts; i += EXT_TPB) {
-#pragma unroll
-        for (int k = 0; k < 3; ++k) {
-            T a = partials[i * 6 + k], b = partials[i * 6 + 3 + k];
-            mn[k] = mn[k] < a ? mn[k] : a;
-            mx[k] = mx[k] > b ? mx[k] : b;
-        }
-    }
+    take_partials(partials, nparts, EXT_TPB, mn, mx);
     __shared__ T s[EXT_TPB / 64][6];
-    const int lane = threadIdx.x & 63, w = threadIdx.x >> 6;
-#pragma unroll
-    for (int k = 0; k < 3; ++k) {
-        T a = wave_min(mn[k]), b = wave_max(mx[k]);
-        if (lane == 0) {
-            s[w][k] = a;
-            s[w][3 + k] = b;
-        }
-    }
-    __syncthreads();
-    if (threadIdx.x < 6) {
-        T v = s[0][threadIdx.x];
-        for (int i = 1; i < EXT_TPB / 64; ++i) {
-            T t = s[i][threadIdx.x];
-            v = threadIdx.x < 3 ? (v < t ? v : t) : (v > t ? v : t);
-        }
-        if (expand) {
-            const T rp = relative_precision<T>(), fm = float_min_normal<T>();
-            T a = rp * ibvh_abs(v);
-            v = threadIdx.x < 3 ? (v - a) - fm : (v + a) + fm;
-        }
+    T v;
+    if (fold_extrema(mn, mx, s, EXT_TPB / 64, v)) {
+        if (expand) v = expand_bound(v, threadIdx.x < 3);
         out[threadIdx.x] = v;
         if (out2) out2[threadIdx.x] = v; // the caller's copy (ibvh_build's extrema_out): no separate 24-byte memcpy
     }
@@ -199,34 +193,10 @@ __global__ __launch_bounds__(1024) void encode_hist_kernel(const char *__restric
         if (blockIdx.x == 0) write_skips(fold.so);
         T mn[3] = {float_max<T>(), float_max<T>(), float_max<T>()};
         T mx[3] = {float_min_normal<T>(), float_min_normal<T>(), float_min_normal<T>()};
-        for (int i = threadIdx.x; i < fold.nparts; i += blockDim.x) {
-#pragma unroll
-            for (int k = 0; k < 3; ++k) {
-                const T a = fold.partials[i * 6 + k], b = fold.partials[i * 6 + 3 + k];
-                mn[k] = mn[k] < a ? mn[k] : a;
-                mx[k] = mx[k] > b ? mx[k] : b;
-            }
-        }
-        const int lane = threadIdx.x & 63, w = threadIdx.x >> 6;
-#pragma unroll
-        for (int k = 0; k < 3; ++k) {
-            const T a = wave_min(mn[k]), b = wave_max(mx[k]);
-            if (lane == 0) {
-                s_fold[w][k] = a;
-                s_fold[w][3 + k] = b;
-            }
-        }
-        __syncthreads();
-        if (threadIdx.x < 6) {
-            T v = s_fold[0][threadIdx.x];
-            for (int i = 1; i < (int)(blockDim.x >> 6); ++i) {
-                const T t = s_fold[i][threadIdx.x];
-                v = threadIdx.x < 3 ? (v < t ? v : t) : (v > t ? v : t);
-            }
-            // bounding_volumes_extrema (utils.jl:63-69): x -/+ rp*abs(x) -/+ floatmin, two roundings a side
-            const T rp = relative_precision<T>(), fm = float_min_normal<T>();
-            const T a = rp * ibvh_abs(v);
-            v = threadIdx.x < 3 ? (v - a) - fm : (v + a) + fm;
+        take_partials(fold.partials, fold.nparts, (int)blockDim.x, mn, mx);
+        T v;
+        if (fold_extrema(mn, mx, s_fold, (int)(blockDim.x >> 6), v)) {
+            v = expand_bound(v, threadIdx.x < 3);
             s_ext[threadIdx.x] = v;
             if (blockIdx.x == 0) {
                 fold.out[threadIdx.x] = v;
@@ -258,239 +228,6 @@ __global__ __launch_bounds__(1024) void encode_hist_kernel(const char *__restric
         for (int d = threadIdx.x; d <= (int)mask; d += blockDim.x) tile_hist[(int64_t)d * num_tiles + blockIdx.x] = h[d];
 }
 
-// ------------------------------------------------------------------------------------------
-// A1 + A2: bottom-up merge — build.jl:366-523.  One launch builds up to CH_LEVELS tree levels:
-// a workgroup owns 2*TPB consecutive inputs (leaves, or nodes of the level the previous launch
-// ended on), merges them pairwise, and keeps folding through LDS, writing every level it makes.
-// The reference launches once per level (build.jl:371-375: ~levels launches); this needs
-// ceil((levels-1)/CH_LEVELS).
-// ------------------------------------------------------------------------------------------
-constexpr int AGG_TPB = 256;
-constexpr int CH_LEVELS = 9; // 2*256 inputs -> 256,128,...,1 nodes
-
-// The rest of a launch: fold the workgroup's nodes of `level` (`mine`; `nreal` of them on that level) upwards through LDS,
-// up to CH_LEVELS - 1 more levels and not above built_level, writing every node made.
-template <class N>
-IBVH_D void fold_up(N *s_nodes, N mine, int64_t level, int64_t nreal, const TreeDev &tree, int64_t built_level, N *__restrict__ nodes) {
-    const int t = threadIdx.x;
-    int count = AGG_TPB;
-#pragma unroll 1
-    for (int s = 1; s < CH_LEVELS; ++s) {
-        if (level - 1 < built_level) break; // uniform
-        __syncthreads();
-        if (t < count) s_nodes[t] = mine;
-        __syncthreads();
-        count >>= 1;
-        level -= 1;
-        const int64_t child_real = nreal;
-        nreal = level_num_real(tree.levels, tree.virtual_leaves, level);
-        const int64_t i = (int64_t)blockIdx.x * count + t;
-        if ((t < count) && (i < nreal)) {
-            N a = s_nodes[2 * t];
-            if (2 * i + 1 < child_real) mine = merge_to(a, s_nodes[2 * t + 1], (N *)nullptr);
-            else mine = a;
-            nodes[level_start(tree.levels, tree.virtual_leaves, level) - 1 + i] = mine;
-        }
-    }
-}
-
-template <class L, class N, bool FROM_LEAVES>
-__global__ __launch_bounds__(AGG_TPB) void aggregate_kernel(const char *__restrict__ in, int64_t in_stride, int64_t in_level,
-                                                            TreeDev tree, int64_t built_level, N *__restrict__ nodes) {
-    __shared__ N s_nodes[AGG_TPB];
-    const int t = threadIdx.x;
-    // level being produced first: in_level - 1
-    int64_t level = in_level - 1;
-    const int64_t in_real = FROM_LEAVES ? tree.real_leaves : level_num_real(tree.levels, tree.virtual_leaves, in_level);
-    const int64_t i = (int64_t)blockIdx.x * AGG_TPB + t; // 0-based node index within `level`
-    const int64_t nreal = level_num_real(tree.levels, tree.virtual_leaves, level);
-    N mine;
-    if (i < nreal) {
-        int64_t l = 2 * i, r = 2 * i + 1; // 0-based children within in_level
-        if constexpr (FROM_LEAVES) {
-            L a = load_vol<L>(in + l * in_stride);
-            if (r < in_real) {
-                L b = load_vol<L>(in + r * in_stride);
-                mine = merge_to(a, b, (N *)nullptr);
-            } else {
-                mine = convert_to(a, (N *)nullptr);
-            }
-        } else {
-            N a = load_vol<N>(in + l * in_stride);
-            if (r < in_real) {
-                N b = load_vol<N>(in + r * in_stride);
-                mine = merge_to(a, b, (N *)nullptr);
-            } else {
-                mine = a;
-            }
-        }
-        nodes[level_start(tree.levels, tree.virtual_leaves, level) - 1 + i] = mine;
-    }
-    fold_up<N>(s_nodes, mine, level, nreal, tree, built_level, nodes);
-}
-
-// Refit from new volumes in the user's order (ibvh_refit): the first launch of aggregate<L, N>, with the gather fused in.
-// Each leaf takes volumes[.index - 1], stores it into its record (volume bytes only) and is merged exactly as in
-// aggregate_kernel<L, N, true>.  The index is checked BEFORE the load: a leaf whose index lies outside 1..m keeps its old
-// volume and stores 1 to *flag.  A 1-leaf tree has no nodes: its leaf is only gathered.
-template <class L, class N, class I>
-__global__ __launch_bounds__(AGG_TPB) void refit_kernel(char *__restrict__ leaves, LeafLayout lay, const char *__restrict__ volumes,
-                                                        int64_t m, uint32_t *flag, TreeDev tree, int64_t built_level,
-                                                        N *__restrict__ nodes) {
-    __shared__ N s_nodes[AGG_TPB];
-    const int64_t i = (int64_t)blockIdx.x * AGG_TPB + threadIdx.x;
-    const bool one_leaf = tree.levels == 1;
-    const int64_t level = tree.levels - 1;
-    const int64_t nreal = one_leaf ? 1 : level_num_real(tree.levels, tree.virtual_leaves, level);
-    N mine;
-    if (i < nreal) {
-        const bool has_b = !one_leaf && 2 * i + 1 < tree.real_leaves;
-        char *ra = leaves + 2 * i * lay.stride, *rb = ra + lay.stride;
-        // both indices, then both gathers, then both stores: two dependent round trips per item, not four
-        const I ia = load_index<I>(ra, lay), ib = has_b ? load_index<I>(rb, lay) : I(1);
-        const bool oka = ia >= 1 && (int64_t)ia <= m, okb = ib >= 1 && (int64_t)ib <= m;
-        const char *sa = oka ? volumes + ((int64_t)ia - 1) * (int64_t)sizeof(L) : ra;
-        const char *sb = okb ? volumes + ((int64_t)ib - 1) * (int64_t)sizeof(L) : rb;
-        L a, b;
-        if constexpr (sizeof(L) % 16 == 0) { // raw BSphere{F32}/{F64}, BBox{F64}: one 16-byte request per 16 bytes
-            a = oka && ((uintptr_t)volumes & 15) == 0 ? load_vol16<L>(sa) : load_vol<L>(sa);
-            if (has_b) b = okb && ((uintptr_t)volumes & 15) == 0 ? load_vol16<L>(sb) : load_vol<L>(sb);
-        } else {
-            a = load_vol<L>(sa);
-            if (has_b) b = load_vol<L>(sb);
-        }
-        if (oka) store_vol(ra, a);
-        if (has_b && okb) store_vol(rb, b);
-        if (flag && !(oka && okb)) *flag = 1u;
-        if (one_leaf) return; // (uniform: a one-block launch)
-        mine = has_b ? merge_to(a, b, (N *)nullptr) : convert_to(a, (N *)nullptr);
-        nodes[level_start(tree.levels, tree.virtual_leaves, level) - 1 + i] = mine;
-    }
-    if (one_leaf) return;
-    fold_up<N>(s_nodes, mine, level, nreal, tree, built_level, nodes);
-}
-
-// The top of the tree: one workgroup folds all levels above `in_level` (<= AGG_TOP_MAX inputs), a barrier per level; same
-// merge_to as below, so the nodes are bit-identical.  IN_LDS (round 3; the inputs fit 128 KB): the level being folded
-// lives in LDS — inputs read from memory once, every level's nodes stored as they are made, and the next level folds the
-// LDS copy — instead of each level re-reading through L2 what the level before has just stored (eleven dependent
-// store -> load round trips at 1e6 leaves: 8.3 us for a kernel whose work is 4 k merges).
-constexpr int AGG_TOP_TPB = 1024, AGG_TOP_MAX = 4096, AGG_TOP_LDS_BYTES = 128 * 1024;
-template <class N, bool IN_LDS>
-__global__ __launch_bounds__(AGG_TOP_TPB) void aggregate_top_kernel(TreeDev tree, int64_t in_level, int64_t built_level, N *nodes) {
-    if constexpr (IN_LDS) {
-        extern __shared__ __attribute__((aligned(16))) unsigned char top_smem[];
-        N *s = (N *)top_smem;
-        int64_t have = level_num_real(tree.levels, tree.virtual_leaves, in_level); // nodes of the level held in LDS
-        {
-            const N *in = nodes + (level_start(tree.levels, tree.virtual_leaves, in_level) - 1);
-            for (int64_t i = threadIdx.x; i < have; i += AGG_TOP_TPB) s[i] = load_vol<N>(in + i);
-        }
-        __syncthreads();
-        for (int64_t level = in_level - 1; level >= built_level && level >= 1; --level) {
-            const int64_t nreal = level_num_real(tree.levels, tree.virtual_leaves, level);
-            N *out = nodes + (level_start(tree.levels, tree.virtual_leaves, level) - 1);
-            // (nreal <= AGG_TOP_MAX / 2 <= 2 * AGG_TOP_TPB: at most two nodes per thread, read before anything is overwritten)
-            N mine[2];
-#pragma unroll
-            for (int k = 0; k < 2; ++k) {
-                const int64_t i = threadIdx.x + (int64_t)k * AGG_TOP_TPB;
-                if (i < nreal) mine[k] = (2 * i + 1 < have) ? merge_to(s[2 * i], s[2 * i + 1], (N *)nullptr) : s[2 * i];
-            }
-            __syncthreads();
-#pragma unroll
-            for (int k = 0; k < 2; ++k) {
-                const int64_t i = threadIdx.x + (int64_t)k * AGG_TOP_TPB;
-                if (i < nreal) {
-                    s[i] = mine[k];
-                    store_vol(out + i, mine[k]);
-                }
-            }
-            __syncthreads();
-            have = nreal;
-        }
-        return;
-    }
-    for (int64_t level = in_level - 1; level >= built_level && level >= 1; --level) {
-        const int64_t nreal = level_num_real(tree.levels, tree.virtual_leaves, level);
-        const int64_t child_real = level_num_real(tree.levels, tree.virtual_leaves, level + 1);
-        const N *in = nodes + (level_start(tree.levels, tree.virtual_leaves, level + 1) - 1);
-        N *out = nodes + (level_start(tree.levels, tree.virtual_leaves, level) - 1);
-        for (int64_t i = threadIdx.x; i < nreal; i += AGG_TOP_TPB) {
-            const N a = load_vol<N>(in + 2 * i);
-            if (2 * i + 1 < child_real) store_vol(out + i, merge_to(a, load_vol<N>(in + 2 * i + 1), (N *)nullptr));
-            else store_vol(out + i, a);
-        }
-        __threadfence_block();
-        __syncthreads();
-    }
-}
-
-// ibvh_refit from volumes in the user's order: what the first launch of aggregate() gathers into the leaf records
-struct RefitGather {
-    LeafLayout lay;
-    int index_type;
-    const void *volumes; // m raw volumes of the leaf type
-    int64_t m;
-    uint32_t *flag;      // optional
-};
-
-template <class L, class N>
-int aggregate(const char *leaves, int64_t leaf_stride, const ibvh_tree &tree, int64_t built_level, N *nodes, hipStream_t st,
-              const RefitGather *gather = nullptr) {
-    if (tree.real_nodes < 2 && !gather) return IBVH_OK; // build.jl:266
-    TreeDev td{tree.levels, tree.real_leaves, tree.virtual_leaves};
-    // launch 1: leaves (level `levels`) -> levels-1 .. levels-CH_LEVELS.  The last-level merge always
-    // runs (aggregate_last_level!, build.jl:369), even when built_level == levels.
-    int64_t in_level = tree.levels;
-    {
-        int64_t nreal = tree.levels > 1 ? level_num_real(tree.levels, tree.virtual_leaves, in_level - 1) : 1;
-        int64_t eff_built = built_level > tree.levels - 1 ? tree.levels - 1 : built_level;
-        if (gather) {
-            int e = dispatch_index(gather->index_type, [&](auto it) -> int {
-                using I = typename decltype(it)::type;
-                IBVH_LAUNCH((refit_kernel<L, N, I>), dim3((unsigned)ceil_div(nreal, AGG_TPB)), dim3(AGG_TPB), 0, st,
-                            (char *)leaves, gather->lay, (const char *)gather->volumes, gather->m, gather->flag, td, eff_built, nodes);
-                return IBVH_OK;
-            });
-            if (e) return e;
-        } else {
-            IBVH_LAUNCH((aggregate_kernel<L, N, true>), dim3((unsigned)ceil_div(nreal, AGG_TPB)), dim3(AGG_TPB), 0, st,
-                               leaves, leaf_stride, in_level, td, eff_built, nodes);
-        }
-        IBVH_LAUNCH_CHECK();
-        if (tree.real_nodes < 2) return IBVH_OK; // (a refit of one leaf: gathered, no nodes)
-        in_level = in_level - CH_LEVELS;
-    }
-    while (in_level - 1 >= built_level && in_level - 1 >= 1) {
-        if (level_num_real(tree.levels, tree.virtual_leaves, in_level) <= AGG_TOP_MAX) {
-            // few nodes left: ONE workgroup folds every remaining level (a launch costs more than these levels)
-            const size_t top_bytes = (size_t)level_num_real(tree.levels, tree.virtual_leaves, in_level) * sizeof(N);
-            if (top_bytes <= (size_t)AGG_TOP_LDS_BYTES) {
-                IBVH_HIP_CHECK(hipFuncSetAttribute((const void *)aggregate_top_kernel<N, true>, hipFuncAttributeMaxDynamicSharedMemorySize, AGG_TOP_LDS_BYTES));
-                IBVH_LAUNCH((aggregate_top_kernel<N, true>), dim3(1), dim3(AGG_TOP_TPB), top_bytes, st, td, in_level, built_level, nodes);
-            } else {
-                IBVH_LAUNCH((aggregate_top_kernel<N, false>), dim3(1), dim3(AGG_TOP_TPB), 0, st, td, in_level, built_level, nodes);
-            }
-            IBVH_LAUNCH_CHECK();
-            break;
-        }
-        int64_t nreal = level_num_real(tree.levels, tree.virtual_leaves, in_level - 1);
-        const char *in = (const char *)(nodes + (level_start(tree.levels, tree.virtual_leaves, in_level) - 1));
-        IBVH_LAUNCH((aggregate_kernel<L, N, false>), dim3((unsigned)ceil_div(nreal, AGG_TPB)), dim3(AGG_TPB), 0, st,
-                           in, (int64_t)sizeof(N), in_level, td, built_level, nodes);
-        IBVH_LAUNCH_CHECK();
-        in_level -= CH_LEVELS;
-    }
-    return IBVH_OK;
-}
-
-// compute_skips! on device memory in the index type I (build.jl:232-239)
-template <class I> __global__ void skips_kernel(TreeDev tree, I *skips) {
-    int64_t level = threadIdx.x + 1;
-    if (level <= tree.levels) skips[level - 1] = (I)level_skips(tree.levels, tree.virtual_leaves, level);
-}
-
 inline int grid_for(int64_t n, int tpb, int max_blocks) {
     int64_t b = ceil_div(n, tpb);
     return (int)(b < 1 ? 1 : (b > max_blocks ? max_blocks : b));
@@ -507,7 +244,6 @@ struct Scratch {
     char *sort;      // rsort::scratch_bytes(n)
     size_t total;
 };
-inline int morton_key_bits(int morton_type);
 inline Scratch carve(char *base, int64_t n, int key_bytes, int64_t leaf_bytes, int morton_type) {
     Scratch s;
     size_t off = 0;
@@ -524,7 +260,7 @@ inline Scratch carve(char *base, int64_t n, int key_bytes, int64_t leaf_bytes, i
     s.vals_alt = take((size_t)n * 4);
     s.records = take((size_t)n * leaf_bytes);
     s.records2 = take((size_t)n * leaf_bytes);
-    const size_t a = rsort::scratch_bytes(n), b = msd::scratch_bytes(n, morton_key_bits(morton_type), key_bytes, (int)leaf_bytes);
+    const size_t a = rsort::scratch_bytes(n), b = msd::scratch_bytes(n, key_bits(morton_type), key_bytes, (int)leaf_bytes);
     s.sort = take(a > b ? a : b);
     s.total = off;
     return s;
@@ -552,15 +288,13 @@ int extrema(const char *recs, int64_t stride, int64_t n, int expand, typename V:
 template <class V>
 int encode(const char *recs, int64_t stride, int64_t n, const typename V::elt *ext, int morton_type, void *keys, hipStream_t st) {
     int blocks = grid_for(n, 256, 256 * 16);
-    return dispatch_key(morton_type == IBVH_U64 ? 8 : 4, [&](auto kt) -> int {
+    return dispatch_key(key_bytes(morton_type), [&](auto kt) -> int {
         using K = typename decltype(kt)::type;
         IBVH_LAUNCH((encode_kernel<V, K>), dim3(blocks), dim3(256), 0, st, recs, stride, n, ext, morton_type, (K *)keys);
         IBVH_LAUNCH_CHECK();
         return IBVH_OK;
     });
 }
-
-inline int morton_key_bits(int morton_type) { return morton_type == IBVH_U16 ? 15 : (morton_type == IBVH_U32 ? 30 : 63); }
 
 // ------------------------------------------------------------------------------------------
 // ibvh_build: extrema -> keys + the sort's first tile histogram -> sort -> merge
@@ -612,8 +346,7 @@ inline SortRoute choose_route(int64_t n, int key_bits, int key_bytes, int leaf_b
 template <class L> int launch_extrema(const BuildCall &b, ExtremaFold<typename L::elt> &fold) {
     using T = typename L::elt;
     T *ext = (T *)b.sc.extrema;
-    const TreeDev td{b.tree.levels, b.tree.real_leaves, b.tree.virtual_leaves};
-    const SkipsOut so{td, b.skips, b.desc->types.index_type == IBVH_I32 ? 4 : 8};
+    const SkipsOut so{tree_dev(b.tree), b.skips, index_bytes(b.desc->types.index_type)};
     fold = ExtremaFold<T>{nullptr, 0, ext, (T *)b.extrema_out, so};
     // Small builds are launch-latency bound: the encode kernel's workgroups fold the partial extrema themselves (one
     // launch less on the critical path: -6 us at 1e6 leaves).  With thousands of encode workgroups the redundant folds
@@ -648,17 +381,17 @@ template <class L> int launch_keys(const BuildCall &b, const SortRoute &h, const
 }
 
 // The records in Morton order into `leaves` (index = position + 1 for fresh volumes, build.jl:345-349, or the source
-// record's own index, :220-222), then the merge.
+// record's own index, :220-222).
 //   record sort: ONE partition of the finished records into scratch by the top bits of their key, cells finished in LDS
 //                into `leaves` (an in-place build reads `leaves`, stages in scratch and writes `leaves`: no extra copy)
 //   pair sort:   stable sort of (key, position); the last pass writes the records — into scratch for an in-place build,
 //                which then copies them back
-template <class L, class N> int sort_and_aggregate(const BuildCall &b, const SortRoute &route) {
+inline int sort_records(const BuildCall &b, const SortRoute &route) {
     const ibvh_build_desc &d = *b.desc;
     const Scratch &sc = b.sc;
     char *dst = (route.by_records() || b.in_place) ? sc.records : (char *)b.leaves;
     const rsort::RecordArgs ra{b.src, dst, b.src_stride, b.wrapped ? 1 : 0, (int32_t)(b.lay.volume_bytes / 8),
-                               d.types.index_type == IBVH_I32 ? 4 : 8, b.dlay};
+                               index_bytes(d.types.index_type), b.dlay};
     if (route.by_records()) {
         if (int e = msd::sort_records(route.records, b.key_bytes, b.key_bits, sc.keys, b.n, ra, sc.records2, (char *)b.leaves,
                                       sc.keys_alt, (uint32_t *)sc.vals_alt, sc.keys, (uint32_t *)sc.vals, d.sort_levels,
@@ -673,7 +406,7 @@ template <class L, class N> int sort_and_aggregate(const BuildCall &b, const Sor
         if (b.in_place)
             IBVH_HIP_CHECK(hipMemcpyAsync(b.leaves, sc.records, (size_t)b.n * b.lay.leaf_bytes, hipMemcpyDeviceToDevice, b.st));
     }
-    return aggregate<L, N>((const char *)b.leaves, b.lay.leaf_bytes, b.tree, d.built_level, (N *)b.nodes, b.st);
+    return IBVH_OK;
 }
 
 } // namespace build
@@ -689,8 +422,7 @@ ibvh_status ibvh_build_scratch_bytes(const ibvh_types *types, int64_t n, size_t 
     ibvh_layout lay;
     if (!layout_of(*types, lay)) return IBVH_ERR_UNSUPPORTED;
     if (n < 1) return IBVH_ERR_DOMAIN;
-    int kb = types->morton_type == IBVH_U64 ? 8 : 4;
-    *bytes_out = carve(nullptr, n, kb, lay.leaf_bytes, types->morton_type).total;
+    *bytes_out = carve(nullptr, n, key_bytes(types->morton_type), lay.leaf_bytes, types->morton_type).total;
     return IBVH_OK;
 }
 
@@ -723,40 +455,6 @@ ibvh_status ibvh_morton_keys(const ibvh_types *types, const void *records, int32
     });
 }
 
-ibvh_status ibvh_aggregate(const ibvh_types *types, const ibvh_tree *tree, int64_t built_level, const void *leaves,
-                           void *nodes, void *stream) {
-    if (!types || !tree || !leaves) return IBVH_ERR_INVALID_ARG;
-    if (built_level < 1 || built_level > tree->levels) return IBVH_ERR_INVALID_ARG;
-    ibvh_layout lay;
-    if (!layout_of(*types, lay)) return IBVH_ERR_UNSUPPORTED;
-    if (tree->real_nodes >= 2 && !nodes) return IBVH_ERR_INVALID_ARG;
-    return (ibvh_status)dispatch_leaf_node(*types, [&](auto lt, auto nt) -> int {
-        using L = typename decltype(lt)::type;
-        using N = typename decltype(nt)::type;
-        return aggregate<L, N>((const char *)leaves, lay.leaf_bytes, *tree, built_level, (N *)nodes, (hipStream_t)stream);
-    });
-}
-
-ibvh_status ibvh_refit(const ibvh_bvh *bvh, const void *volumes, int64_t num_volumes, void *flag, void *stream) {
-    if (!bvh || !bvh->leaves) return IBVH_ERR_INVALID_ARG;
-    const ibvh_tree &tree = bvh->tree;
-    if (tree.real_leaves < 1 || tree.levels < 1) return IBVH_ERR_INVALID_ARG;
-    if (bvh->built_level < 1 || bvh->built_level > tree.levels) return IBVH_ERR_INVALID_ARG;
-    if (tree.real_nodes >= 2 && !bvh->nodes) return IBVH_ERR_INVALID_ARG;
-    if (volumes && (num_volumes < 0 || ((uintptr_t)volumes & 7) != 0)) return IBVH_ERR_INVALID_ARG;
-    ibvh_layout lay;
-    LeafLayout dlay;
-    if (!layout_of(bvh->types, lay, &dlay)) return IBVH_ERR_UNSUPPORTED;
-    const RefitGather g{dlay, bvh->types.index_type, volumes, num_volumes, (uint32_t *)flag};
-    return (ibvh_status)dispatch_leaf_node(bvh->types, [&](auto lt, auto nt) -> int {
-        using L = typename decltype(lt)::type;
-        using N = typename decltype(nt)::type;
-        // the in-place form is exactly aggregate_oibvh! over the records as they stand
-        return aggregate<L, N>((const char *)bvh->leaves, lay.leaf_bytes, tree, bvh->built_level, (N *)bvh->nodes,
-                               (hipStream_t)stream, volumes ? &g : nullptr);
-    });
-}
-
 ibvh_status ibvh_build(const ibvh_build_desc *desc, const void *volumes, void *leaves, void *nodes, void *skips,
                        void *extrema_out, void *scratch, size_t scratch_bytes, void *stream) {
     if (!desc || !leaves || !skips || !scratch) return IBVH_ERR_INVALID_ARG;
@@ -773,8 +471,8 @@ ibvh_status ibvh_build(const ibvh_build_desc *desc, const void *volumes, void *l
     if (tree.real_nodes >= 2 && !nodes) return IBVH_ERR_INVALID_ARG;
     BuildCall b{};
     b.desc = desc, b.lay = lay, b.dlay = dlay, b.tree = tree, b.n = desc->n;
-    b.key_bytes = ty.morton_type == IBVH_U64 ? 8 : 4;
-    b.key_bits = morton_key_bits(ty.morton_type);
+    b.key_bytes = key_bytes(ty.morton_type);
+    b.key_bits = key_bits(ty.morton_type);
     b.sc = carve((char *)scratch, b.n, b.key_bytes, lay.leaf_bytes, ty.morton_type);
     if (scratch_bytes < b.sc.total) return IBVH_ERR_SCRATCH;
     // already_wrapped with a non-NULL `volumes`: `volumes` holds the source RECORDS and `leaves` receives the sorted
@@ -786,15 +484,16 @@ ibvh_status ibvh_build(const ibvh_build_desc *desc, const void *volumes, void *l
     b.leaves = leaves, b.nodes = nodes, b.skips = skips, b.extrema_out = extrema_out;
     b.st = (hipStream_t)stream;
 
-    return (ibvh_status)dispatch_leaf_node(ty, [&](auto lt, auto nt) -> int {
+    const SortRoute route = choose_route(b.n, b.key_bits, b.key_bytes, (int)lay.leaf_bytes, b.sc.sort);
+    int e = dispatch_volume(ty.leaf_kind, ty.leaf_float, [&](auto lt) -> int {
         using L = typename decltype(lt)::type;
-        using N = typename decltype(nt)::type;
-        const SortRoute route = choose_route(b.n, b.key_bits, b.key_bytes, (int)lay.leaf_bytes, b.sc.sort);
         ExtremaFold<typename L::elt> fold;
         if (int e = launch_extrema<L>(b, fold)) return e;
-        if (int e = launch_keys<L>(b, route, fold)) return e;
-        return sort_and_aggregate<L, N>(b, route);
+        return launch_keys<L>(b, route, fold);
     });
+    if (!e) e = sort_records(b, route);
+    if (!e) e = aggregate_tree(ty, leaves, tree, desc->built_level, nodes, b.st);
+    return (ibvh_status)e;
 }
 
 } // extern "C"

@@ -142,7 +142,7 @@ ibvh_status ibvh_closest_triangles(const ibvh_bvh *bvh, const void *triangles, i
     ibvh_layout layout;
     LeafLayout lay;
     if (!layout_of(t, layout, &lay)) return IBVH_ERR_UNSUPPORTED;
-    const TreeDev tree{tr.levels, tr.real_leaves, tr.virtual_leaves};
+    const TreeDev tree = tree_dev(tr);
     const unsigned blocks = pointwalk::grid_blocks(num_points);
     auto launch = [&](auto ft, auto nt, auto it) -> int {
         using T = typename decltype(ft)::type;

@@ -393,6 +393,12 @@ template <> IBVH_HD double float_min_normal<double>() { return 2.225073858507201
 template <class T> IBVH_HD T relative_precision(); // default.jl:179-181
 template <> IBVH_HD float relative_precision<float>() { return 1e-5f; }
 template <> IBVH_HD double relative_precision<double>() { return 1e-14; }
+// The epsilon expansion of bounding_volumes_extrema (morton/utils.jl:63-69) of one bound: x -/+ rp*abs(x) -/+ floatmin, two
+// roundings a side
+template <class T> IBVH_HD T expand_bound(T v, bool is_min) {
+    const T a = relative_precision<T>() * ibvh_abs(v), fm = float_min_normal<T>();
+    return is_min ? (v - a) - fm : (v + a) + fm;
+}
 
 // ------------------------------------------------------------------------------------------
 // implicit tree index math — implicit_tree.jl (levels <= 62 here; Julia's >> saturates to 0)
@@ -451,12 +457,17 @@ inline bool same_types(const ibvh_types &x, const ibvh_types &y) {
            x.node_float == y.node_float && x.index_type == y.index_type && x.morton_type == y.morton_type;
 }
 inline int64_t align_up(int64_t v, int64_t a) { return (v + a - 1) / a * a; }
+// Morton keys as the sorts see them: 15, 30 or 63 significant bits in 4 or 8 bytes (a UInt16 code travels as a 4-byte key)
+inline int key_bits(int morton_type) { return morton_type == IBVH_U16 ? 15 : (morton_type == IBVH_U32 ? 30 : 63); }
+inline int key_bytes(int morton_type) { return morton_type == IBVH_U64 ? 8 : 4; }
+inline int index_bytes(int index_type) { return index_type == IBVH_I32 ? 4 : 8; }
+inline TreeDev tree_dev(const ibvh_tree &t) { return TreeDev{t.levels, t.real_leaves, t.virtual_leaves}; }
 inline bool layout_of(const ibvh_types &t, ibvh_layout &out, LeafLayout *dev = nullptr) {
     if (!combo_ok(t)) return false;
     int64_t fl = t.leaf_float == IBVH_F32 ? 4 : 8, fn = t.node_float == IBVH_F32 ? 4 : 8;
     int64_t vb = (t.leaf_kind == IBVH_BSPHERE ? 4 : 6) * fl;
     int64_t nb = (t.node_kind == IBVH_BSPHERE ? 4 : 6) * fn;
-    int64_t ib = t.index_type == IBVH_I32 ? 4 : 8;
+    int64_t ib = index_bytes(t.index_type);
     int64_t mb = t.morton_type == IBVH_U16 ? 2 : (t.morton_type == IBVH_U32 ? 4 : 8);
     int64_t io = align_up(vb, ib);
     int64_t mo = align_up(io + ib, mb);

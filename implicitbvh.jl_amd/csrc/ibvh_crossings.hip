@@ -117,7 +117,7 @@ ibvh_status ibvh_point_crossings(const ibvh_bvh *bvh, const void *triangles, int
     ibvh_layout layout;
     LeafLayout lay;
     if (!layout_of(t, layout, &lay)) return IBVH_ERR_UNSUPPORTED;
-    const TreeDev tree{tr.levels, tr.real_leaves, tr.virtual_leaves};
+    const TreeDev tree = tree_dev(tr);
     const unsigned blocks = pointwalk::grid_blocks(num_points);
     const int u = (axis + 1) % 3, v = (axis + 2) % 3, w = axis; // cyclic: orientation is preserved
     auto launch = [&](auto ft, auto nt, auto it) -> int {

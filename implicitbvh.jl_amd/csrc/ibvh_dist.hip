@@ -43,16 +43,10 @@ __global__ __launch_bounds__(256) void dest_kernel(const K *__restrict__ keys, i
     }
 }
 
-// epsilon expansion of bounding_volumes_extrema (morton/utils.jl:63-69) applied to already reduced
-// extrema: mins - rp*|mins| - floatmin, maxs + rp*|maxs| + floatmin, two roundings per side
+// epsilon expansion of bounding_volumes_extrema (expand_bound) applied to already reduced extrema
 template <class T> __global__ void expand_kernel(T *ext) {
     const int k = threadIdx.x;
-    if (k < 6) {
-        const T rp = relative_precision<T>(), fm = float_min_normal<T>();
-        T v = ext[k];
-        T a = rp * ibvh_abs(v);
-        ext[k] = k < 3 ? (v - a) - fm : (v + a) + fm;
-    }
+    if (k < 6) ext[k] = expand_bound(ext[k], k < 3);
 }
 
 // The all-reduce(MAX) vector of the distributed build, assembled on device in one launch:
@@ -69,12 +63,7 @@ template <class T> __global__ void pack_extrema_kernel(const T *ext, int has_dat
 // (double -> float of values that came from floats is exact).
 template <class T> __global__ void unpack_extrema_kernel(const double *vec, T *ext) {
     const int k = threadIdx.x;
-    if (k < 6) {
-        const T rp = relative_precision<T>(), fm = float_min_normal<T>();
-        const T v = k < 3 ? (T)(-vec[k]) : (T)vec[k];
-        const T a = rp * ibvh_abs(v);
-        ext[k] = k < 3 ? (v - a) - fm : (v + a) + fm;
-    }
+    if (k < 6) ext[k] = expand_bound(k < 3 ? (T)(-vec[k]) : (T)vec[k], k < 3);
 }
 
 // Digit histograms for the splitter search: out[j][d] = #keys with (key >> prefix_shift) == prefix[j]
@@ -258,7 +247,7 @@ ibvh_status ibvh_pack_records(const ibvh_types *types, const void *volumes, cons
         using V = typename decltype(vt)::type;
         return dispatch_index(types->index_type, [&](auto it) -> int {
             using I = typename decltype(it)::type;
-            return dispatch_key(types->morton_type == IBVH_U64 ? 8 : 4, [&](auto kt) -> int {
+            return dispatch_key(key_bytes(types->morton_type), [&](auto kt) -> int {
                 using K = typename decltype(kt)::type;
                 IBVH_LAUNCH((distk::pack_kernel<V, I, K>), dim3(blocks), dim3(256), 0, st, (const V *)volumes, (const K *)keys,
                             (const uint32_t *)perm, index_base, n, dl, (char *)records_out);

@@ -39,8 +39,6 @@ namespace {
 constexpr int DIGIT_BITS = 12;
 constexpr int MAX_RANKS = IBVH_DIST_MAX_RANKS;
 
-int key_bits_of(const ibvh_types &t) { return t.morton_type == IBVH_U16 ? 15 : (t.morton_type == IBVH_U32 ? 30 : 63); }
-int key_bytes_of(const ibvh_types &t) { return t.morton_type == IBVH_U64 ? 8 : 4; }
 int float_bytes(int flt) { return flt == IBVH_F64 ? 8 : 4; }
 // counters of the largest histogram one ibvh_key_histogram call of the splitter search fills (any digit width it uses)
 size_t hist_table_counters() {
@@ -81,7 +79,7 @@ Layout make_layout(const ibvh_types &t, int64_t n, int size) {
     L.allh = take((size_t)size * (1 << DIGIT_BITS) * 4);
     L.cnt = take((size_t)4 * size * 8);
     L.ext_scratch = take((size_t)1 << 17);
-    L.keys = take((size_t)n * key_bytes_of(t));
+    L.keys = take((size_t)n * key_bytes(t.morton_type));
     L.perm = take((size_t)n * 4);
     ibvh_dist_partition_scratch_bytes(n, &L.part_bytes);
     L.part = take(L.part_bytes);
@@ -325,7 +323,7 @@ ibvh_status ibvh_dist_plan(const ibvh_types *types, const ibvh_comm *comm, const
     const Layout L = make_layout(*types, n_local, P);
     char *base = (char *)scratch;
     const int flt = types->leaf_float, fb = float_bytes(flt);
-    const int kb = key_bytes_of(*types), key_bits = key_bits_of(*types);
+    const int kb = key_bytes(types->morton_type), key_bits = ibvh::key_bits(types->morton_type);
     std::memset(plan, 0, sizeof(*plan));
     plan->size = P;
     plan->n_local = n_local;
@@ -760,7 +758,7 @@ ibvh_status ibvh_dist_cross_plan(const ibvh_comm *comm, const ibvh_bvh *bvh, int
     // 1. this rank's record, on the device
     if (status == IBVH_OK) {
         const bool from_leaf = bvh->tree.real_nodes <= bvh->tree.real_leaves;
-        const TreeDev td{bvh->tree.levels, bvh->tree.real_leaves, bvh->tree.virtual_leaves};
+        const TreeDev td = tree_dev(bvh->tree);
         const int e = dispatch_volume(bvh->types.node_kind, bvh->types.node_float, [&](auto nt) -> int {
             using NV = typename decltype(nt)::type;
             return dispatch_volume(bvh->types.leaf_kind, bvh->types.leaf_float, [&](auto lt) -> int {

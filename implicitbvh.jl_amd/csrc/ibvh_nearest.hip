@@ -102,7 +102,7 @@ ibvh_status ibvh_nearest_leaves(const ibvh_bvh *bvh, const void *points, int64_t
     ibvh_layout layout;
     LeafLayout lay;
     if (!layout_of(t, layout, &lay)) return IBVH_ERR_UNSUPPORTED;
-    const TreeDev tree{tr.levels, tr.real_leaves, tr.virtual_leaves};
+    const TreeDev tree = tree_dev(tr);
     const unsigned blocks = pointwalk::grid_blocks(num_points);
     return (ibvh_status)dispatch_volume(t.leaf_kind, t.leaf_float, [&](auto lt) -> int {
         using VL = typename decltype(lt)::type;

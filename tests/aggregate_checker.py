@@ -1,4 +1,4 @@
-"""The checker of the bottom-up merge (aggregate<L, N>() in csrc/ibvh_build.hip, behind ibvh_aggregate, ibvh_refit and
+"""The checker of the bottom-up merge (aggregate<L, N>() in csrc/ibvh_aggregate.hip, behind ibvh_aggregate, ibvh_refit and
 ibvh_build): inputs that are NOT in Morton order, two references that do not use the library, and the table of launches.
 
 A plain module, not a conftest: tests/test_gpu_aggregate_routes.py and tests/test_host_aggregate.py import it.
@@ -24,7 +24,7 @@ import mixed_pair_checker as mpc
 import oracle_lib as orc
 from implicitbvh_amd import abi
 
-# csrc/ibvh_build.hip as it stands (tests/test_host_aggregate.py reads the source and fails when one of them moves)
+# csrc/ibvh_aggregate.hip as it stands (tests/test_host_aggregate.py reads the source and fails when one of them moves)
 AGG_TPB, CH_LEVELS, AGG_TOP_TPB, AGG_TOP_MAX, AGG_TOP_LDS_BYTES = 256, 9, 1024, 4096, 128 * 1024
 CONSTANTS = {"AGG_TPB": AGG_TPB, "CH_LEVELS": CH_LEVELS, "AGG_TOP_TPB": AGG_TOP_TPB, "AGG_TOP_MAX": AGG_TOP_MAX,
              "AGG_TOP_LDS_BYTES": AGG_TOP_LDS_BYTES}

@@ -1,4 +1,4 @@
-"""The bottom-up merge (aggregate<L, N>() in csrc/ibvh_build.hip) on every launch route, node type and built level, called
+"""The bottom-up merge (aggregate<L, N>() in csrc/ibvh_aggregate.hip) on every launch route, node type and built level, called
 directly through ibvh_aggregate and once each behind ibvh_refit and ibvh_build.
 
 The route depends on the tree size, the node size and built_level alone (aggregate_checker.expected_launches; L = levels,

@@ -1,7 +1,7 @@
 """The bottom-up merge on the host side: ibvh_aggregate's refusals (each returns before any HIP call), the checker of
 tests/aggregate_checker.py against itself (the oracle at every built_level is a slice of its built_level = 1 run; the flat
 min / max reduction accepts the oracle's BBox nodes and rejects two swapped neighbours), and the table of launches against
-the constants as they stand in csrc/ibvh_build.hip.  No GPU."""
+the constants as they stand in csrc/ibvh_aggregate.hip.  No GPU."""
 import ctypes as C
 import os
 import re
@@ -173,7 +173,7 @@ def test_inputs_are_unsorted_and_take_the_containment_branches():
 # 3. the table of launches
 # ---------------------------------------------------------------------------------------------
 def test_constants_are_those_of_the_source():
-    src = open(os.path.join(ROOT, "implicitbvh.jl_amd", "csrc", "ibvh_build.hip")).read()
+    src = open(os.path.join(ROOT, "implicitbvh.jl_amd", "csrc", "ibvh_aggregate.hip")).read()
     found = {}
     for name in chk.CONSTANTS:
         m = re.findall(r"\b%s\s*=\s*([0-9][0-9 *]*)[,;]" % name, src)

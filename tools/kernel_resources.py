@@ -13,7 +13,7 @@ for b in blocks:
     if not m:
         continue
     d = {}
-    for k, pat in (("vgpr", r"\bVGPRs"), ("agpr", r"AGPRs"), ("sgpr", r"\bSGPRs"), ("scratch", r"ScratchSize \[bytes/lane\]"),
+    for k, pat in (("vgpr", r"\bVGPRs"), ("agpr", r"AGPRs"), ("sgpr", r"\b(?:Total)?SGPRs"), ("scratch", r"ScratchSize \[bytes/lane\]"),
                    ("occ", r"Occupancy \[waves/SIMD\]"), ("sgpr_spill", r"SGPRs Spill"), ("vgpr_spill", r"VGPRs Spill"),
                    ("lds", r"LDS Size \[bytes/block\]")):
         mm = re.search(pat + r": (\d+)", b)
