@@ -625,6 +625,8 @@ inline int level_grid() {
     // (default 4 a CU: one resident round at the self / pair kernels' occupancy; every workgroup costs a serialised tail
     // atomic per flush)
     const int per = g_tuning.bfs_wg_per_cu < 1 ? 1 : (g_tuning.bfs_wg_per_cu > 16 ? 16 : g_tuning.bfs_wg_per_cu);
+    // (development knob bfs_grid: exactly that many workgroups, so that a small tree gives one workgroup many chunks)
+    if (g_tuning.bfs_grid > 0) return g_tuning.bfs_grid < cus * 16 ? g_tuning.bfs_grid : cus * 16;
     return cus * per;
 }
 

@@ -554,6 +554,7 @@ struct Tuning {
     int lvt_scan_fused = 1; // the scan behind walker 2's counting pass in one kernel (scan_fused_kernel / scan_fused_grouped_kernel); 0 = reduce + apply; N > 1 = at most N workgroups (development: the default is half of what the device holds at once)
     int msd_equalize = 0;   // equalised cells (ibvh_msd.hip): 0 = when the build asks (ibvh_build_desc.sort_equalize), 1 = always, -1 = never
     int bfs_wg_per_cu = 4;  // workgroups per CU of the BFS level kernels' fixed grid (ibvh_bfs.hip, level_grid)
+    int bfs_grid = 0;       // development: exactly this many workgroups for every BFS level kernel (0 = CUs x bfs_wg_per_cu; at most CUs x 16) — a small grid puts many chunks and several flushes on one workgroup at test sizes
     int rays_binned = 1;    // ray traversals (F32 trees) cut the walk at a level and finish it subtree by subtree out of LDS:
                             // 1 = where it pays (rays_bin_plan: >= 17 levels, or >= 13 under <= 8,192 rays; not a small tree under many
                             // rays), 2 = wherever the tree allows it, 0 = never

@@ -65,7 +65,7 @@ struct Knob {
 const Knob kKnobs[] = {
     {"ray_block", &Tuning::ray_block},   {"lvt_wide", &Tuning::lvt_wide},     {"lvt_xcd", &Tuning::lvt_xcd},
     {"sort_lsd", &Tuning::sort_lsd},     {"sort_msd_avg", &Tuning::sort_msd_avg},
-    {"msd_avg", &Tuning::msd_avg},       {"msd_equalize", &Tuning::msd_equalize}, {"msd_rescue", &Tuning::msd_rescue}, {"lvt_scan_fused", &Tuning::lvt_scan_fused}, {"bfs_wg_per_cu", &Tuning::bfs_wg_per_cu},
+    {"msd_avg", &Tuning::msd_avg},       {"msd_equalize", &Tuning::msd_equalize}, {"msd_rescue", &Tuning::msd_rescue}, {"lvt_scan_fused", &Tuning::lvt_scan_fused}, {"bfs_wg_per_cu", &Tuning::bfs_wg_per_cu}, {"bfs_grid", &Tuning::bfs_grid},
     {"lvt_blocks", &Tuning::lvt_blocks}, {"lvt_block_shift", &Tuning::lvt_block_shift}, {"lvt_blocks_min_items", &Tuning::lvt_blocks_min_items}, {"lvt_blocks_paired_below", &Tuning::lvt_blocks_paired_below},
     {"rays_binned", &Tuning::rays_binned}, {"rays_subtree_depth", &Tuning::rays_subtree_depth},
     {"rays_items_per_ray", &Tuning::rays_items_per_ray}, {"rays_tail", &Tuning::rays_tail},

@@ -101,6 +101,14 @@ def load():
         raise ImportError(
             f"{LIB_PATH} not found: the HIP extension is not built (no CPU fallback exists). "
             "Run `python -c 'import __graft_entry__ as g; g.build()'`.")
+    # One HIP runtime per process, and it has to be torch's: a PyTorch-ROCm wheel brings its own libamdhip64, every tensor
+    # the mirror hands to the library lives in it, and libibvh.so binds to whichever libamdhip64 is loaded when it comes in.
+    # Loaded before torch, it pulled in the system's runtime instead and its first launch on a torch tensor returned a HIP
+    # error (build() followed by smoke() in a fresh process did exactly that).
+    try:
+        import torch  # noqa: F401
+    except ImportError:
+        pass
     lib = C.CDLL(LIB_PATH)
     for name, argtypes in SIGNATURES.items():
         fn = getattr(lib, name)  # AttributeError here = header / library mismatch

@@ -886,8 +886,8 @@ ibvh_status ibvh_lvt_work_counters(const ibvh_bvh *bvh, const ibvh_bvh *bvh2, co
  * on them, only speed and which code path is taken).  One process-wide table: set a knob BEFORE the calls it should
  * affect and not concurrently with them.  The library never reads the environment.  Names (exactly the table in
  * csrc/ibvh_core.hip; meanings: csrc/ibvh_common.hpp, struct Tuning): "ray_block", "lvt_wide", "lvt_xcd", "sort_lsd",
- * "sort_msd_avg", "msd_avg", "msd_equalize", "msd_rescue", "lvt_scan_fused", "bfs_wg_per_cu", "lvt_blocks",
- * "lvt_block_shift", "lvt_blocks_min_items", "lvt_blocks_paired_below", "rays_binned" (1 = the binned ray path where it
+ * "sort_msd_avg", "msd_avg", "msd_equalize", "msd_rescue", "lvt_scan_fused", "bfs_wg_per_cu", "bfs_grid" (k > 0 = exactly k
+ * workgroups for every BFS level kernel, at most CUs x 16; 0 = CUs x bfs_wg_per_cu), "lvt_blocks", "lvt_block_shift", "lvt_blocks_min_items", "lvt_blocks_paired_below", "rays_binned" (1 = the binned ray path where it
  * pays, 2 = wherever the tree allows it, 0 = never), "rays_subtree_depth", "rays_items_per_ray", "rays_tail".  Unknown
  * name: IBVH_ERR_INVALID_ARG — that includes the knobs of removed experiments (lvt_dual, rays_shadow, msd_range and
  * rays_fast_slab; the last commit with them is f9264f8) and the knobs that forced sort geometries no shipped plan picks
