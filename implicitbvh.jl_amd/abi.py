@@ -76,6 +76,10 @@ NEAREST_LEAVES_ARGTYPES = [C.POINTER(Bvh), C.c_void_p, C.c_int64, C.c_int32, C.c
 # ibvh_point_crossings(bvh, triangles, num_triangles, points, num_points, axis, crossings, winding, flag, stream)
 POINT_CROSSINGS_ARGTYPES = [C.POINTER(Bvh), C.c_void_p, C.c_int64, C.c_void_p, C.c_int64, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p,
                             C.c_void_p]
+# ibvh_cast_rays(bvh, triangles, num_triangles, points, directions, num_rays, t_max, mode, hit_index, hit_t, hit_uv, occluded,
+#                flag, stream)
+CAST_CLOSEST, CAST_ANY = 0, 1
+CAST_RAYS_ARGTYPES = [C.POINTER(Bvh), C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p, C.c_int32] + [C.c_void_p] * 6
 
 
 class BuildDesc(C.Structure):

@@ -32,6 +32,7 @@ __all__ = [
     "NARROW_MORTON_LT", "NARROW_INDEX_LT", "NARROW_RAY_ORIGIN_OUTSIDE", "LeafBatch", "lvt_work_counters", "refit",
     "resolve_triangles", "raycast", "RayHits", "closest_points", "ClosestPoints",
     "nearest_leaves", "NearestLeaves", "point_crossings", "PointCrossings", "points_inside", "signed_distance",
+    "cast_rays", "RayCast",
 ]
 
 NARROW_MORTON_LT = abi.NARROW_MORTON_LT
@@ -1477,6 +1478,88 @@ def nearest_leaves(bvh, points, k=1, max_distance=None, presorted=False):
         return NearestLeaves(index, d2)
     lib.call("ibvh_nearest_leaves", C.byref(bvh.struct()), _ptr(p), n, int(k), radius2, _ptr(index), _ptr(d2), _stream())
     return NearestLeaves(*_unpermute(order, (index, d2)))
+
+
+# ---------------------------------------------------------------------------------------------
+# ray cast: the closest hit or any hit of a batch of rays against the mesh (ibvh_cast_rays; no reference counterpart)
+# ---------------------------------------------------------------------------------------------
+class RayCast:
+    """Per ray: .index (N,) the closest exactly hit triangle's user index (0 = miss), .t (N,) the hit parameter t* (+Inf =
+    miss), .uv (N, 2) the barycentric weights of p2, p3 (0, 0 on a miss), .hit (N,) bool = index != 0."""
+
+    def __init__(self, index, t, uv):
+        self.index, self.t, self.uv = index, t, uv
+
+    @property
+    def hit(self):
+        return self.index != 0
+
+
+def cast_rays(bvh, triangles, points, directions, t_max=None, any_hit=False, presorted=False):
+    """For every ray points[:, i] + t * directions[:, i] the closest exactly hit triangle of the mesh `bvh` was built over
+    -> RayCast; with any_hit=True only whether the ray hits anything within its limit -> (N,) bool tensor (a visibility ray:
+    the walk ends at its first hit).  One launch (include/ibvh.h, ibvh_cast_rays: the slab test, the exact test — that of
+    resolve_triangles —, the clamp t* = max(t, entry of the leaf's box), the tie rule — smallest t*, then the smaller index —
+    and why pruning on the best hit so far loses nothing are spelled out there); exact: bit-equal to a brute force over all
+    triangles.
+
+    bvh: BBox leaves made from `triangles` (bounding_volumes_from_triangles(triangles, BBox(dtype)); a skin margin and
+    refit are fine) under BBox nodes of the same or a wider float type.  triangles: (n, 9) / (n, 3, 3) CUDA tensor of the
+    leaves' dtype, user index k = row k - 1.  points, directions: (3, N) CUDA tensors of that dtype, as for traverse_rays.
+    t_max: None (unbounded), a number, or an (N,) tensor of per-ray limits; a hit needs t* <= t_max (inclusive), a NaN or
+    negative limit gives a miss.  The device walks the batch in Morton order of the origins (lanes of a wave then share
+    nodes) and the outputs are put back in the caller's order; presorted=True walks it as given.
+
+    Not watertight along shared edges, like resolve_triangles; a ray cast from a surface hits it at t ~ 0.
+
+    ValueError: sphere leaves or nodes, nodes narrower than the leaves, a wrong dtype, device or shape, and a leaf whose
+    index lies outside 1..n (flag bit 1; such leaves are skipped)."""
+    torch = _require_gpu()
+    t = bvh.types
+    if t.leaf_kind != abi.BBOX or t.node_kind != abi.BBOX:
+        raise ValueError("cast_rays: the BVH must have BBox leaves under BBox nodes (the exact bound needs boxes that contain "
+                         "their triangles' boxes; sphere leaves are not supported)")
+    if t.leaf_float == abi.F64 and t.node_float == abi.F32:
+        raise ValueError("cast_rays: Float32 nodes over Float64 leaves do not contain them exactly")
+    tris = _check_triangles(triangles, "cast_rays")
+    ft = _torch_float(t.leaf_float)
+    if tris.dtype != ft:
+        raise ValueError(f"cast_rays: triangles must be {ft}, the BVH's leaf float type")
+    p, n, _, order = _query_points(points, ft, None, presorted, "cast_rays")
+    if not (isinstance(directions, torch.Tensor) and directions.dim() == 2 and tuple(directions.shape) == (3, n)):
+        raise ValueError("cast_rays: size(directions) == size(points) == (3, N) must hold")
+    if directions.dtype != ft or not directions.is_cuda:
+        raise ValueError(f"cast_rays: directions must be a {ft} tensor on the GPU (device='cuda')")
+    d = directions.t().contiguous()
+    lim = None
+    if t_max is not None:
+        if isinstance(t_max, torch.Tensor):
+            if tuple(t_max.shape) != (n,) or t_max.dtype != ft or not t_max.is_cuda:
+                raise ValueError(f"cast_rays: t_max must be a number or an (N,) {ft} tensor on the GPU")
+            lim = t_max.contiguous()
+        elif isinstance(t_max, (int, float, np.integer, np.floating)) and not isinstance(t_max, bool):
+            lim = torch.full((n,), float(t_max), dtype=ft, device="cuda")
+        else:
+            raise ValueError(f"cast_rays: t_max must be a number or an (N,) {ft} tensor on the GPU")
+    if order is not None:
+        d = d[order]
+        lim = None if lim is None else lim[order]
+    idt = _torch_index(t.index_type)
+    if any_hit:
+        occluded = torch.empty(n, dtype=torch.uint8, device="cuda")
+        outs = (None, None, None, occluded)
+    else:
+        outs = (torch.empty(n, dtype=idt, device="cuda"), torch.empty(n, dtype=ft, device="cuda"),
+                torch.empty((n, 2), dtype=ft, device="cuda"), None)
+    if n > 0:
+        flag = torch.zeros(1, dtype=torch.int32, device="cuda")
+        lib.call("ibvh_cast_rays", C.byref(bvh.struct()), _ptr(tris), tris.shape[0], _ptr(p), _ptr(d), n, _ptr(lim),
+                 abi.CAST_ANY if any_hit else abi.CAST_CLOSEST, *[_ptr(o) for o in outs], _ptr(flag), _stream())
+        if int(flag.item()) & 2:
+            raise ValueError(f"cast_rays: a leaf's index lies outside 1..{tris.shape[0]} (the number of triangles given)")
+    if any_hit:
+        return _unpermute(order, (outs[3],))[0] != 0
+    return RayCast(*_unpermute(order, outs[:3]))
 
 
 # ---------------------------------------------------------------------------------------------

@@ -1,0 +1,164 @@
+// ibvh_cast.hip — cast a batch of rays against the mesh a BVH was built over, in one launch: per ray the closest exactly
+// hit triangle (index, t, u, v), or only whether anything lies in the way (include/ibvh.h, ibvh_cast_rays).  No reference
+// counterpart: ImplicitBVH.jl's ray traversal stops at the (leaf, ray) candidate list of the whole infinite line
+// (raytrace/leaf_vs_tree/leaf_vs_tree.jl:170-228); nothing there prunes on the best hit so far, limits a ray to a segment
+// or stops at the first hit.
+//
+// The result is defined over ALL triangles — the lexicographic minimum of (t*, index) over the hits, t* = max(t, entry of
+// the triangle's leaf box) — so the walk only has to be lossless.  It is, without an epsilon: the slab entry distance of a
+// box is computed from (corner - p) * inv, round-to-nearest subtraction and multiplication by a fixed inv are monotone, and
+// every box of the tree contains the boxes below it exactly (min / max, widening conversions, a skin margin, ibvh_refit).  So
+// the COMPUTED entry of a node is <= that of every box below it, an admitted box has admitted ancestors, and
+// t* >= entry(leaf) >= entry(every ancestor): a box whose entry exceeds the limit holds nothing that could still win.
+//
+// The walk itself — work mapping, the trail word, the pop, the strict skip — is ibvh_pointwalk.hpp's, here with the slab
+// entry as the bound.  The limit starts at the ray's own t_max; the closest hit lowers it to the best t* so far, the any-hit
+// query drops it to -Inf at its first hit, which ends the walk.  The exact test is ibvh_raytest.hpp's, the one copy
+// ibvh_raytri.hip resolves candidate lists with.  Ray, inverse direction and best hit live in registers.
+#include "ibvh_pointwalk.hpp"
+#include "ibvh_raytest.hpp"
+
+#include <limits>
+#include <type_traits>
+
+namespace ibvh {
+namespace cast {
+
+// entry(box) of include/ibvh.h: the slab test's tmin where the ray meets the box, +Inf where it does not.  An axis the ray
+// does not move along admits or refuses by comparing the origin; the selects keep a NaN where the header says they do.
+template <class T> IBVH_D T slab_entry(const T *lo, const T *up, const T *p, const T *d, const T *inv) {
+    const T inf = std::numeric_limits<T>::infinity();
+    T tmin = -inf, tmax = inf;
+    bool ok = true;
+#pragma unroll
+    for (int k = 0; k < 3; ++k) {
+        const bool still = d[k] == T(0);
+        const T t1 = (lo[k] - p[k]) * inv[k], t2 = (up[k] - p[k]) * inv[k];
+        const T tnear = t2 < t1 ? t2 : t1, tfar = t2 > t1 ? t2 : t1;
+        const T nmin = tnear > tmin ? tnear : tmin, nmax = tfar < tmax ? tfar : tmax;
+        ok &= !still | ((lo[k] <= p[k]) & (p[k] <= up[k]));
+        tmin = still ? tmin : nmin;
+        tmax = still ? tmax : nmax;
+    }
+    return (ok & (tmin <= tmax) & (tmax >= T(0))) ? tmin : inf;
+}
+
+// T: the leaves', triangles' and rays' float type; TN: the nodes' (the same or wider — a node box then holds values of T,
+// widened exactly, and narrows back exactly); ANY: only "is there a hit", the walk ends at the first one
+template <class T, class TN, class I, bool ANY>
+__global__ __launch_bounds__(pointwalk::kBlock) void cast_walk_kernel(
+    TreeDev tree, int built_level, const char *__restrict__ leaves, LeafLayout lay, const BBox<TN> *__restrict__ nodes,
+    const T *__restrict__ tris, int64_t num_triangles, const T *__restrict__ points, const T *__restrict__ dirs, int64_t num_rays,
+    const T *__restrict__ t_max, I *__restrict__ out_index, T *__restrict__ out_t, T *__restrict__ out_uv,
+    uint8_t *__restrict__ out_occluded, uint32_t *flag) {
+    constexpr int kBlock = pointwalk::kBlock;
+    const T inf = std::numeric_limits<T>::infinity();
+    bool bad = false;
+    for (int64_t item = (int64_t)blockIdx.x * kBlock + threadIdx.x; item < num_rays; item += (int64_t)gridDim.x * kBlock) {
+        const T p[3] = {points[3 * item], points[3 * item + 1], points[3 * item + 2]};
+        const T d[3] = {dirs[3 * item], dirs[3 * item + 1], dirs[3 * item + 2]};
+        const T inv[3] = {T(1) / d[0], T(1) / d[1], T(1) / d[2]};
+        // L of include/ibvh.h: a hit is finite (a NaN limit stays NaN and admits nothing)
+        const T given = t_max ? t_max[item] : inf;
+        const T L = given > std::numeric_limits<T>::max() ? std::numeric_limits<T>::max() : given;
+        T best = L, best_u = T(0), best_v = T(0);
+        I best_index = 0;
+        bool occluded = false;
+        auto box = [&](const T *lo, const T *up) { return slab_entry(lo, up, p, d, inv); };
+        // only a leaf that passes gathers its triangle (36 / 72 bytes)
+        auto visit = [&](const char *rec) {
+            const I index = load_index<I>(rec, lay);
+            if (index >= 1 && (int64_t)index <= num_triangles) {
+                const BBox<T> b = load_vol<BBox<T>>(rec);
+                const T entry = slab_entry(b.lo, b.up, p, d, inv);
+                raytri::Tri<T> tr;
+                __builtin_memcpy(&tr, __builtin_assume_aligned(tris + 9 * ((int64_t)index - 1), sizeof(T)), sizeof(tr));
+                T t, u, v;
+                if (raytri::ray_triangle(tr, p, d, t, u, v)) {
+                    const T ts = entry > t ? entry : t; // t*: the clamp
+                    if constexpr (ANY) {
+                        occluded |= ts <= L;
+                    } else if ((ts < best) | ((ts == best) & ((best_index == 0) | (index < best_index)))) {
+                        // (t*, index) lexicographically; the first one only has to be within the limit (best == L)
+                        best = ts;
+                        best_index = index;
+                        best_u = u;
+                        best_v = v;
+                    }
+                }
+            } else {
+                bad = true;
+            }
+        };
+        // t* >= t >= 0: a negative or NaN limit admits nothing, and a NaN could not prune
+        if (L >= T(0)) {
+            if constexpr (ANY)
+                pointwalk::walk<BBox<T>, TN>(tree, built_level, leaves, lay, nodes, box, [&]() { return occluded ? -inf : L; }, visit);
+            else
+                pointwalk::walk<BBox<T>, TN>(tree, built_level, leaves, lay, nodes, box, [&]() { return best; }, visit);
+        }
+        if constexpr (ANY) {
+            out_occluded[item] = occluded ? 1 : 0;
+        } else {
+            const bool hit = best_index != 0;
+            if (out_index) out_index[item] = best_index;
+            if (out_t) out_t[item] = hit ? best : inf;
+            if (out_uv) {
+                out_uv[2 * item] = best_u;
+                out_uv[2 * item + 1] = best_v;
+            }
+        }
+    }
+    if (bad && flag) raise_flag(flag, 2u);
+}
+
+} // namespace cast
+} // namespace ibvh
+
+using namespace ibvh;
+
+extern "C" {
+
+ibvh_status ibvh_cast_rays(const ibvh_bvh *bvh, const void *triangles, int64_t num_triangles, const void *points,
+                           const void *directions, int64_t num_rays, const void *t_max, int32_t mode, void *hit_index,
+                           void *hit_t, void *hit_uv, void *occluded, void *flag, void *stream) {
+    if (!bvh || num_triangles < 0 || num_rays < 0) return IBVH_ERR_INVALID_ARG;
+    if (mode != IBVH_CAST_CLOSEST && mode != IBVH_CAST_ANY) return IBVH_ERR_INVALID_ARG;
+    const bool any = mode == IBVH_CAST_ANY;
+    if (any ? (!occluded || hit_index || hit_t || hit_uv) : (occluded || (!hit_index && !hit_t && !hit_uv))) return IBVH_ERR_INVALID_ARG;
+    const ibvh_types &t = bvh->types;
+    if (!combo_ok(t)) return IBVH_ERR_UNSUPPORTED;
+    // the lossless bound needs boxes that contain their triangles' boxes exactly, all the way up
+    if (t.leaf_kind != IBVH_BBOX || !pointwalk::box_nodes_hold_leaves(t)) return IBVH_ERR_UNSUPPORTED;
+    const ibvh_tree &tr = bvh->tree;
+    if (!pointwalk::tree_ok(bvh)) return IBVH_ERR_INVALID_ARG;
+    if ((num_triangles > 0 && !triangles) || (num_rays > 0 && (!points || !directions))) return IBVH_ERR_INVALID_ARG;
+    if (num_rays == 0) return IBVH_OK;
+    ibvh_layout layout;
+    LeafLayout lay;
+    if (!layout_of(t, layout, &lay)) return IBVH_ERR_UNSUPPORTED;
+    const TreeDev tree = tree_dev(tr);
+    const unsigned blocks = pointwalk::grid_blocks(num_rays);
+    auto launch = [&](auto ft, auto nt, auto it, auto mt) -> int {
+        using T = typename decltype(ft)::type;
+        using TN = typename decltype(nt)::type;
+        using I = typename decltype(it)::type;
+        constexpr bool ANY = decltype(mt)::value;
+        IBVH_LAUNCH((cast::cast_walk_kernel<T, TN, I, ANY>), dim3(blocks), dim3(pointwalk::kBlock), 0, (hipStream_t)stream, tree,
+                    (int)bvh->built_level, (const char *)bvh->leaves, lay, (const BBox<TN> *)bvh->nodes, (const T *)triangles,
+                    num_triangles, (const T *)points, (const T *)directions, num_rays, (const T *)t_max, (I *)hit_index, (T *)hit_t,
+                    (T *)hit_uv, (uint8_t *)occluded, (uint32_t *)flag);
+        IBVH_LAUNCH_CHECK();
+        return IBVH_OK;
+    };
+    // the mode is a template parameter: the any-hit kernel carries no best hit
+    auto modes = [&](auto ft, auto nt, auto it) -> int {
+        return any ? launch(ft, nt, it, std::true_type{}) : launch(ft, nt, it, std::false_type{});
+    };
+    return (ibvh_status)dispatch_index(t.index_type, [&](auto it) -> int {
+        if (t.leaf_float == IBVH_F64) return modes(Tag<double>{}, Tag<double>{}, it);
+        return t.node_float == IBVH_F64 ? modes(Tag<float>{}, Tag<double>{}, it) : modes(Tag<float>{}, Tag<float>{}, it);
+    });
+}
+
+} // extern "C"

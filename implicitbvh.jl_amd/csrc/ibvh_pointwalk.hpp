@@ -1,12 +1,14 @@
 // ibvh_pointwalk.hpp — the bounded walk of one query point through a BVH, shared by the point queries: the two that prune
 // on a bound which shrinks while they walk, ibvh_closest.hip (the closest triangle) and ibvh_nearest.hip (the k nearest
-// leaf centres), and ibvh_crossings.hip (the triangles an axis ray from the point crosses), whose bound is a fixed yes / no;
-// and the argument checks their entry points have in common.  No reference counterpart: every traversal of ImplicitBVH.jl
+// leaf centres), ibvh_crossings.hip (the triangles an axis ray from the point crosses), whose bound is a fixed yes / no, and
+// ibvh_cast.hip (the closest or any hit of a ray from the point), whose bound is the ray's entry distance into a box; and the
+// argument checks their entry points have in common.  No reference counterpart: every traversal of ImplicitBVH.jl
 // is a fixed-volume overlap test (traverse/, raytrace/).
 //
 // A query hands the walk three things: bound(lo, up), its lower bound for a box (box_bound below for the distance queries;
-// 0 / 1 = "the ray can / cannot meet the box" for the crossings), limit(), the value beyond which nothing can enter its
-// answer any more, and visit(rec), what to do with a leaf record that is still within it.  The walk is lossless if the
+// 0 / 1 = "the ray can / cannot meet the box" for the crossings; the slab test's entry distance for the ray cast), limit(),
+// the value beyond which nothing can enter its answer any more, and visit(rec), what to do with a leaf record that is still
+// within it.  The walk is lossless if the
 // COMPUTED bound of a box never exceeds the COMPUTED bound or distance of anything the query could find under it; each query
 // argues that for its own bound.  A box is skipped iff bound > limit(): strictly, because an equal distance under it may
 // carry a smaller index.

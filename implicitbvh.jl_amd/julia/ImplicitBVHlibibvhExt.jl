@@ -294,6 +294,10 @@ c_point_crossings(bvh, triangles, num_triangles, points, num_points, axis, cross
     ccall((:ibvh_point_crossings, libibvh), Cint,
           (Ref{IbvhBvh}, Ptr{Cvoid}, Int64, Ptr{Cvoid}, Int64, Int32, Ptr{Cvoid}, Ptr{Cvoid}, Ptr{Cvoid}, Ptr{Cvoid}),
           bvh, triangles, num_triangles, points, num_points, axis, crossings, winding, flag, stream)
+c_cast_rays(bvh, triangles, num_triangles, points, directions, num_rays, t_max, mode, hit_index, hit_t, hit_uv, occluded, flag, stream) =
+    ccall((:ibvh_cast_rays, libibvh), Cint,
+          (Ref{IbvhBvh}, Ptr{Cvoid}, Int64, Ptr{Cvoid}, Ptr{Cvoid}, Int64, Ptr{Cvoid}, Int32, Ptr{Cvoid}, Ptr{Cvoid}, Ptr{Cvoid}, Ptr{Cvoid}, Ptr{Cvoid}, Ptr{Cvoid}),
+          bvh, triangles, num_triangles, points, directions, num_rays, t_max, mode, hit_index, hit_t, hit_uv, occluded, flag, stream)
 c_lvt_scratch_bytes(types, n_items, cache_slots, out) =
     ccall((:ibvh_lvt_scratch_bytes, libibvh), Cint,
           (Ref{IbvhTypes}, Int64, Int32, Ref{Csize_t}),
@@ -732,6 +736,58 @@ function points_inside(bvh::RocBVH, triangles::ROCMatrix{T}, points::ROCMatrix{T
     rule in (:parity, :winding) || throw(ArgumentError("points_inside: rule must be :parity or :winding"))
     c = point_crossings(bvh, triangles, points; axis)
     rule === :parity ? isodd.(c.crossings) : c.winding .!= 0
+end
+
+# ---- ray cast: closest hit or any hit of a batch of rays against the mesh (include/ibvh.h, ibvh_cast_rays) -----------
+const IBVH_CAST_CLOSEST = Int32(0)
+const IBVH_CAST_ANY = Int32(1)
+"""
+    cast_rays(bvh::BVH, triangles::ROCMatrix{T}, points::ROCMatrix{T}, directions::ROCMatrix{T};
+              t_max=nothing, any_hit=false, presorted=false) -> (; index, t, uv, hit)  |  ROCVector{Bool}
+
+For every ray `points[:, i] + t * directions[:, i]` the closest exactly hit triangle of the mesh `bvh` was built over, in one
+launch: `index[i]` its user index (0 = miss), `t[i]` the hit parameter (`Inf` = miss), `uv[:, i]` the barycentric weights of
+p2 and p3 (zeros = miss), `hit[i] = index[i] != 0`.  With `any_hit=true` only whether the ray hits anything within its limit
+(a visibility ray: the walk ends at the first hit).  `t_max`: `nothing` (unbounded) or a `ROCVector{T}` of per-ray limits,
+inclusive.  The result is the lexicographic minimum of (t*, index) over ALL triangles' hits — bit-equal to a brute force; the
+slab test, the clamp t* = max(t, entry of the leaf box), the limit and why pruning loses nothing are spelled out in
+include/ibvh.h.  `triangles` is 9 x n (column k = p1 p2 p3 of the triangle with user index k).  The BVH must have `BBox{T}`
+leaves made from the triangles (a skin margin and `refit!` are fine) under `BBox` nodes of `T` or wider; anything else raises
+ArgumentError.  The device walks the batch along a Morton curve through the origins and the outputs come back in the
+caller's order; `presorted=true` walks it as given.  Not a method of ImplicitBVH: the reference has no such query.
+"""
+function cast_rays(bvh::RocBVH{I}, triangles::ROCMatrix{T}, points::ROCMatrix{T}, directions::ROCMatrix{T};
+                   t_max::Union{Nothing, ROCVector{T}}=nothing, any_hit::Bool=false, presorted::Bool=false) where {I, T}
+    d = bvh_desc(bvh)
+    isnothing(d) && throw(ArgumentError("cast_rays: no libibvh instantiation for this BVH's types"))
+    leaf_volume_type(bvh.leaves) === BBox{T} && eltype(bvh.nodes) <: BBox && sizeof(eltype(bvh.nodes)) >= sizeof(BBox{T}) ||
+        throw(ArgumentError("cast_rays: the BVH must have BBox{$T} leaves under BBox nodes of $T or wider"))
+    size(triangles, 1) == 9 || throw(ArgumentError("cast_rays: triangles must be 9 x n (p1 p2 p3 per column)"))
+    size(points, 1) == size(directions, 1) == 3 || throw(ArgumentError("size(points, 1) == size(directions, 1) == 3 must hold"))
+    size(points, 2) == size(directions, 2) || throw(ArgumentError("size(points, 2) == size(directions, 2) must hold"))
+    n = size(points, 2)
+    isnothing(t_max) || length(t_max) == n || throw(ArgumentError("cast_rays: length(t_max) == size(points, 2) must hold"))
+    index = any_hit ? nothing : similar(points, I, n)
+    t = any_hit ? nothing : similar(points, T, n)
+    uv = any_hit ? nothing : similar(points, T, 2, n)
+    occluded = any_hit ? similar(points, UInt8, n) : nothing
+    n == 0 && return any_hit ? (occluded .!= 0x00) : (; index, t, uv, hit=index .!= 0)
+    order = presorted ? nothing : point_morton_order(points)
+    perm = isnothing(order) ? nothing : ROCVector{Int64}(order)
+    p = isnothing(perm) ? points : points[:, perm]
+    dir = isnothing(perm) ? directions : directions[:, perm]
+    lim = isnothing(t_max) || isnothing(perm) ? t_max : t_max[perm]
+    flag = scratch!(:cast_flag, 4)
+    fill!(flag, 0x00)
+    check(c_cast_rays(d, devptr(triangles), Int64(size(triangles, 2)), devptr(p), devptr(dir), Int64(n), devptr(lim),
+                      any_hit ? IBVH_CAST_ANY : IBVH_CAST_CLOSEST, devptr(index), devptr(t), devptr(uv), devptr(occluded),
+                      devptr(flag), stream_ptr()), "ibvh_cast_rays")
+    Array(flag)[1] & 0x02 != 0 && throw(ArgumentError("cast_rays: a leaf's index lies outside 1:$(size(triangles, 2))"))
+    if !isnothing(order)
+        inv = ROCVector{Int64}(invperm(order))
+        any_hit ? (occluded = occluded[inv]) : ((index, t, uv) = (index[inv], t[inv], uv[:, inv]))
+    end
+    any_hit ? (occluded .!= 0x00) : (; index, t, uv, hit=index .!= 0)
 end
 
 # ---- k nearest leaves for a batch of query points (include/ibvh.h, ibvh_nearest_leaves) ------------------------------

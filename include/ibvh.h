@@ -44,7 +44,8 @@ extern "C" {
  *   7: ibvh_refit; ibvh_rays_resolve_triangles (additive under 7: a new entry point, no struct layout or existing
  *      argument list moves, so a binding written against the earlier 7 keeps working); ibvh_closest_triangles (additive
  *      under 7 in the same way); ibvh_nearest_leaves and IBVH_NEAREST_MAX_K (additive under 7 in the same way);
- *      ibvh_point_crossings (additive under 7 in the same way);
+ *      ibvh_point_crossings (additive under 7 in the same way); ibvh_cast_rays and IBVH_CAST_CLOSEST / IBVH_CAST_ANY
+ *      (additive under 7 in the same way);
  *      argument checks only, no layout or argument list moves: ibvh_key_histogram takes
  *      what fits its LDS staging (10 rows at 12-bit digits) and refuses shift > 63 and a negative prefix_shift,
  *      ibvh_pack_records / ibvh_dist_plan answer IBVH_ERR_OVERFLOW for an index past IBVH_I32 */
@@ -610,6 +611,80 @@ ibvh_status ibvh_nearest_leaves(const ibvh_bvh *bvh, const void *points, int64_t
 ibvh_status ibvh_point_crossings(const ibvh_bvh *bvh, const void *triangles, int64_t num_triangles,
                                  const void *points, int64_t num_points, int32_t axis,
                                  void *crossings, void *winding, void *flag, void *stream);
+
+/* ----------------------------------------------------------------------------------- */
+/* ray cast: the closest hit, or any hit, of a batch of rays against the mesh           */
+/* ----------------------------------------------------------------------------------- */
+/* For every ray p + t d: the closest exactly hit triangle of the mesh the BVH was built over (ibvh_volumes_from_triangles
+ * with IBVH_BBOX) with its t, u, v — or, for a visibility ray, only whether anything lies in the way.
+ * No reference counterpart (the reference's ray traversal stops at the candidate list of the whole infinite line and never
+ * prunes on a hit); ONE launch, NO host synchronisation, no atomics, no LDS, no scratch buffer.
+ *   triangles  : num_triangles x 9 values (p1 p2 p3) of bvh->types.leaf_float, `flt` below; user index k is row k - 1
+ *   points, directions : num_rays x 3 row-major values of `flt`, processed in the order given (neighbours in memory that
+ *                are neighbours in space walk the same nodes: sort a scattered batch along a Morton curve of the origins first)
+ *   t_max      : optional DEVICE array of num_rays values of `flt`, the far end of each ray's segment; NULL = unbounded
+ *   mode       : IBVH_CAST_CLOSEST or IBVH_CAST_ANY
+ * IBVH_CAST_CLOSEST outputs — each optional, at least one non-NULL; what was not asked for is not written; `occluded`
+ * must be NULL:
+ *   hit_index  : num_rays x I, the winning triangle's user index; 0 = miss
+ *   hit_t      : num_rays x flt; +Inf = miss
+ *   hit_uv     : num_rays x 2 x flt, the hit's barycentric (u, v) (weights of p2, p3); 0, 0 on a miss
+ * IBVH_CAST_ANY output:
+ *   occluded   : num_rays x uint8, 1 = the ray hits something within its limit, 0 = it does not; required, and the other
+ *                three outputs must be NULL: WHICH triangle stopped the ray depends on the walk order, so it is not reported.
+ * All arguments are validated before any launch: a wrong combination of outputs, an unknown mode, NULL required pointers,
+ * negative sizes, a tree shape that is not an ImplicitTree's: IBVH_ERR_INVALID_ARG.  num_rays == 0: IBVH_OK, nothing is
+ * touched.
+ * The result is defined independently of how it is found, in `flt`, every operation rounded once (nothing fused; correctly
+ * rounded divide), so that it can be pinned bit for bit.
+ * Slab test of a box [lo, up]:  inv_k = 1 / d_k, computed once per ray;  tmin = -Inf;  tmax = +Inf;  per axis k
+ *     d_k == 0 :  the axis admits iff lo_k <= p_k && p_k <= up_k, and contributes nothing to tmin / tmax (the query's own
+ *                 rule, not the reference's isintersection, whose 0 * Inf is NaN on a box face)
+ *     otherwise:  t1 = (lo_k - p_k) * inv_k;  t2 = (up_k - p_k) * inv_k
+ *                 tnear = t2 < t1 ? t2 : t1;  tfar = t2 > t1 ? t2 : t1
+ *                 tmin = tnear > tmin ? tnear : tmin;  tmax = tfar < tmax ? tfar : tmax
+ *   The box is admitted iff every zero-direction axis admits and tmin <= tmax && tmax >= 0.  Every comparison is false on
+ *   NaN.   entry(box) = tmin if admitted, +Inf otherwise.
+ * Triangle k: exactly the arithmetic and hit condition of ibvh_rays_resolve_triangles above:
+ *     det != 0 && u >= 0 && v >= 0 && u + v <= 1 && t >= 0
+ * Clamped hit parameter:  t*_k = max(t_k, entry(leaf box of k)) = entry > t_k ? entry : t_k, where the leaf box is the stored
+ *   leaf volume, skin included.
+ * Ray limit:  L = min(t_max[i], largest finite flt) = t_max[i] > largest ? largest : t_max[i].  A hit must be finite, so L is
+ *   never +Inf and an un-admitted box (entry +Inf) is always skipped.  A NaN or negative t_max gives no hit.
+ * Hit condition: triangle k is a hit of ray i iff the exact test passes, its leaf box is admitted, and t*_k <= L (the
+ *   limit is inclusive).
+ * IBVH_CAST_CLOSEST is the LEXICOGRAPHIC MINIMUM of (t*_k, k) over all hits: the smallest t*, and among equal t* the
+ *   SMALLER INDEX.  The outputs carry t* and the u, v of the exact test unchanged.  IBVH_CAST_ANY is 1 iff a hit exists.
+ * Why pruning is lossless WITHOUT an epsilon: round-to-nearest subtraction and multiplication by a fixed inv_k are
+ *   monotone, and box merges are min / max plus exact widening, so the COMPUTED entry of a node is <= that of every box
+ *   below it and an admitted box has admitted ancestors:  t*_k >= entry(leaf_k) >= entry(every ancestor).  A node or leaf
+ *   is skipped iff entry > limit() — strictly: an equal t* under it may carry a smaller index.  limit() starts at L; the
+ *   closest hit lowers it to the best t* found so far, any hit drops it to -Inf on the first hit.  Traversal order and work
+ *   mapping therefore cannot change the result.
+ * Limits.  On ordinary meshes the clamp changes nothing (it is a guard for the proof; a hit within rounding of a face of its
+ *   leaf's box is the exception: 1 of 606,903 hitting rays on a 7.2 M-triangle torus).  It matters for a triangle that lies
+ *   flat in a face of its own box, such as an axis-aligned floor: there t* may exceed ibvh_rays_resolve_triangles's t by
+ *   rounding.  The test is not watertight along shared edges (a ray through an edge can miss both triangles or hit both),
+ *   as with the resolve.  Rays cast from a surface hit it at t ~ 0: there is no t_min.
+ * Accepted BVHs — exactly those of ibvh_closest_triangles: leaf_kind == node_kind == IBVH_BBOX, triangles and rays of
+ *   leaf_float, node_float the same as or wider than leaf_float; any index and Morton type.  Anything else — sphere leaves,
+ *   sphere nodes, F64 leaves under F32 nodes — is IBVH_ERR_UNSUPPORTED, never an answer.  Exact PROVIDED every leaf's box
+ *   contains its triangle's box: a skin margin on the leaves is allowed, and so is a BVH after ibvh_refit.  Levels above
+ *   bvh->built_level are not read.
+ * NaN: a triangle with a NaN vertex fails the exact test and is never a hit; a NaN origin or direction hits nothing.  But, as
+ *   for ibvh_closest_triangles, a NaN leaf box can make merge.jl's `a < b ? a : b` produce a node box that does NOT contain
+ *   the NaN-free leaves below it: on a mesh with NaN vertices the other triangles' hits are only guaranteed in trees of at
+ *   most two leaves.
+ * Guards: the triangle is read through the leaf record's .index, not its position.  A leaf whose index lies outside
+ * 1..num_triangles is skipped, nothing outside the array is read, and bit 1 of `flag` is set — the flag contract of
+ * ibvh_rays_resolve_triangles: optional, 4 bytes the GPU can write, a plain load and store, never cleared by the library
+ * (zero it before the call). */
+enum { IBVH_CAST_CLOSEST = 0, IBVH_CAST_ANY = 1 };
+ibvh_status ibvh_cast_rays(const ibvh_bvh *bvh, const void *triangles, int64_t num_triangles,
+                           const void *points, const void *directions, int64_t num_rays,
+                           const void *t_max, int32_t mode,
+                           void *hit_index, void *hit_t, void *hit_uv, void *occluded,
+                           void *flag, void *stream);
 
 /* ----------------------------------------------------------------------------------- */
 /* breadth-first traversal (BFSTraversal): level-synchronous pair queues                 */
