@@ -1369,13 +1369,18 @@ def _morton_order(p):
     return torch.argsort((cell[:, 0] << 2) | (cell[:, 1] << 1) | cell[:, 2])
 
 
+def _check_points_shape(points, what):
+    torch = _torch()
+    if not (isinstance(points, torch.Tensor) and points.dim() == 2 and points.shape[0] == 3):
+        raise ValueError(f"{what}: size(points, 1) == 3 must hold")
+
+
 def _query_points(points, ft, max_distance, presorted, what):
     """The point queries' common input: the (3, N) CUDA tensor `points` of dtype ft, checked -> the (N, 3) contiguous tensor
     the device walks (in Morton order unless presorted), N, max_distance squared in ft as a byref host scalar (None =
     unbounded) and the permutation applied (None = none)."""
     torch = _torch()
-    if not (isinstance(points, torch.Tensor) and points.dim() == 2 and points.shape[0] == 3):
-        raise ValueError(f"{what}: size(points, 1) == 3 must hold")
+    _check_points_shape(points, what)
     if points.dtype != ft or not points.is_cuda:
         raise ValueError(f"{what}: points must be a {ft} tensor on the GPU (device='cuda')")
     n = int(points.shape[1])
@@ -1398,6 +1403,38 @@ def _unpermute(order, outputs):
     return tuple(torch.empty_like(x).index_copy_(0, order, x) for x in outputs)
 
 
+def _check_box_nodes(bvh, what, leaves="leaves"):
+    """What every bounded walk needs above the leaves: BBox nodes that hold the leaves' values exactly."""
+    t = bvh.types
+    if t.node_kind != abi.BBOX:
+        raise ValueError(f"{what}: the BVH must have BBox nodes (the exact bound needs boxes that contain the {leaves})")
+    if t.leaf_float == abi.F64 and t.node_float == abi.F32:
+        raise ValueError(f"{what}: Float32 nodes over Float64 leaves do not contain them exactly")
+
+
+def _mesh_query_setup(bvh, triangles, what):
+    """The mesh queries' common checks: BBox leaves under such nodes, `triangles` of the leaves' float type -> the (n, 9)
+    contiguous triangles, the float dtype, the index dtype."""
+    if bvh.types.leaf_kind != abi.BBOX:
+        raise ValueError(f"{what}: the BVH must have BBox leaves under BBox nodes (the exact bound needs boxes that contain "
+                         "their triangles; sphere leaves are not supported)")
+    _check_box_nodes(bvh, what, "triangles' boxes")
+    tris = _check_triangles(triangles, what)
+    ft = _torch_float(bvh.types.leaf_float)
+    if tris.dtype != ft:
+        raise ValueError(f"{what}: triangles must be {ft}, the BVH's leaf float type")
+    return tris, ft, _torch_index(bvh.types.index_type)
+
+
+def _mesh_query_call(entry, what, bvh, tris, *args):
+    """One mesh query on the current stream: entry(bvh, triangles, n, *args, flag, stream) with a fresh flag word, which is
+    read back afterwards (a synchronisation).  Bit 1 of it: a leaf named no row of `tris`."""
+    flag = _torch().zeros(1, dtype=_torch().int32, device="cuda")
+    lib.call(entry, C.byref(bvh.struct()), _ptr(tris), tris.shape[0], *args, _ptr(flag), _stream())
+    if int(flag.item()) & 2:
+        raise ValueError(f"{what}: a leaf's index lies outside 1..{tris.shape[0]} (the number of triangles given)")
+
+
 def closest_points(bvh, triangles, points, max_distance=None, presorted=False):
     """For every query point the closest triangle of the mesh `bvh` was built over, the closest point on it and the squared
     distance -> ClosestPoints (include/ibvh.h, ibvh_closest_triangles: the arithmetic, the tie rule — smallest distance, then
@@ -1414,28 +1451,14 @@ def closest_points(bvh, triangles, points, max_distance=None, presorted=False):
     ValueError: sphere leaves or nodes, nodes narrower than the leaves, a wrong dtype, device or shape, and a leaf whose
     index lies outside 1..n (flag bit 1; such leaves are skipped)."""
     torch = _require_gpu()
-    t = bvh.types
-    if t.leaf_kind != abi.BBOX or t.node_kind != abi.BBOX:
-        raise ValueError("closest_points: the BVH must have BBox leaves under BBox nodes (the exact bound needs boxes that contain "
-                         "their triangles' boxes; sphere leaves are not supported)")
-    if t.leaf_float == abi.F64 and t.node_float == abi.F32:
-        raise ValueError("closest_points: Float32 nodes over Float64 leaves do not contain them exactly")
-    tris = _check_triangles(triangles, "closest_points")
-    ft = _torch_float(t.leaf_float)
-    if tris.dtype != ft:
-        raise ValueError(f"closest_points: triangles must be {ft}, the BVH's leaf float type")
+    tris, ft, idt = _mesh_query_setup(bvh, triangles, "closest_points")
     p, n, radius2, order = _query_points(points, ft, max_distance, presorted, "closest_points")
-    idt = _torch_index(t.index_type)
     index = torch.empty(n, dtype=idt, device="cuda")
     d2 = torch.empty(n, dtype=ft, device="cuda")
     q = torch.empty((n, 3), dtype=ft, device="cuda")
     if n == 0:
         return ClosestPoints(index, d2, q)
-    flag = torch.zeros(1, dtype=torch.int32, device="cuda")
-    lib.call("ibvh_closest_triangles", C.byref(bvh.struct()), _ptr(tris), tris.shape[0], _ptr(p), n, radius2, _ptr(index), _ptr(d2),
-             _ptr(q), _ptr(flag), _stream())
-    if int(flag.item()) & 2:
-        raise ValueError(f"closest_points: a leaf's index lies outside 1..{tris.shape[0]} (the number of triangles given)")
+    _mesh_query_call("ibvh_closest_triangles", "closest_points", bvh, tris, _ptr(p), n, radius2, _ptr(index), _ptr(d2), _ptr(q))
     return ClosestPoints(*_unpermute(order, (index, d2, q)))
 
 
@@ -1464,10 +1487,7 @@ def nearest_leaves(bvh, points, k=1, max_distance=None, presorted=False):
     ValueError: sphere nodes, nodes narrower than the leaves, k out of range, a wrong dtype, device or shape."""
     torch = _require_gpu()
     t = bvh.types
-    if t.node_kind != abi.BBOX:
-        raise ValueError("nearest_leaves: the BVH must have BBox nodes (the exact bound needs boxes that contain the leaves' centres)")
-    if t.leaf_float == abi.F64 and t.node_float == abi.F32:
-        raise ValueError("nearest_leaves: Float32 nodes over Float64 leaves do not contain them exactly")
+    _check_box_nodes(bvh, "nearest_leaves", "leaves' centres")
     if not (isinstance(k, (int, np.integer)) and not isinstance(k, bool) and 1 <= k <= abi.NEAREST_MAX_K):
         raise ValueError(f"nearest_leaves: k must be an integer in 1..{abi.NEAREST_MAX_K}")
     ft = _torch_float(t.leaf_float)
@@ -1515,16 +1535,7 @@ def cast_rays(bvh, triangles, points, directions, t_max=None, any_hit=False, pre
     ValueError: sphere leaves or nodes, nodes narrower than the leaves, a wrong dtype, device or shape, and a leaf whose
     index lies outside 1..n (flag bit 1; such leaves are skipped)."""
     torch = _require_gpu()
-    t = bvh.types
-    if t.leaf_kind != abi.BBOX or t.node_kind != abi.BBOX:
-        raise ValueError("cast_rays: the BVH must have BBox leaves under BBox nodes (the exact bound needs boxes that contain "
-                         "their triangles' boxes; sphere leaves are not supported)")
-    if t.leaf_float == abi.F64 and t.node_float == abi.F32:
-        raise ValueError("cast_rays: Float32 nodes over Float64 leaves do not contain them exactly")
-    tris = _check_triangles(triangles, "cast_rays")
-    ft = _torch_float(t.leaf_float)
-    if tris.dtype != ft:
-        raise ValueError(f"cast_rays: triangles must be {ft}, the BVH's leaf float type")
+    tris, ft, idt = _mesh_query_setup(bvh, triangles, "cast_rays")
     p, n, _, order = _query_points(points, ft, None, presorted, "cast_rays")
     if not (isinstance(directions, torch.Tensor) and directions.dim() == 2 and tuple(directions.shape) == (3, n)):
         raise ValueError("cast_rays: size(directions) == size(points) == (3, N) must hold")
@@ -1544,7 +1555,6 @@ def cast_rays(bvh, triangles, points, directions, t_max=None, any_hit=False, pre
     if order is not None:
         d = d[order]
         lim = None if lim is None else lim[order]
-    idt = _torch_index(t.index_type)
     if any_hit:
         occluded = torch.empty(n, dtype=torch.uint8, device="cuda")
         outs = (None, None, None, occluded)
@@ -1552,11 +1562,8 @@ def cast_rays(bvh, triangles, points, directions, t_max=None, any_hit=False, pre
         outs = (torch.empty(n, dtype=idt, device="cuda"), torch.empty(n, dtype=ft, device="cuda"),
                 torch.empty((n, 2), dtype=ft, device="cuda"), None)
     if n > 0:
-        flag = torch.zeros(1, dtype=torch.int32, device="cuda")
-        lib.call("ibvh_cast_rays", C.byref(bvh.struct()), _ptr(tris), tris.shape[0], _ptr(p), _ptr(d), n, _ptr(lim),
-                 abi.CAST_ANY if any_hit else abi.CAST_CLOSEST, *[_ptr(o) for o in outs], _ptr(flag), _stream())
-        if int(flag.item()) & 2:
-            raise ValueError(f"cast_rays: a leaf's index lies outside 1..{tris.shape[0]} (the number of triangles given)")
+        _mesh_query_call("ibvh_cast_rays", "cast_rays", bvh, tris, _ptr(p), _ptr(d), n, _ptr(lim),
+                         abi.CAST_ANY if any_hit else abi.CAST_CLOSEST, *[_ptr(o) for o in outs])
     if any_hit:
         return _unpermute(order, (outs[3],))[0] != 0
     return RayCast(*_unpermute(order, outs[:3]))
@@ -1601,28 +1608,14 @@ def point_crossings(bvh, triangles, points, axis=0, presorted=False):
     ValueError: sphere leaves or nodes, nodes narrower than the leaves, a wrong dtype, device or shape, an axis outside
     0..2, and a leaf whose index lies outside 1..n (flag bit 1; such leaves are skipped)."""
     torch = _require_gpu()
-    t = bvh.types
-    if t.leaf_kind != abi.BBOX or t.node_kind != abi.BBOX:
-        raise ValueError("point_crossings: the BVH must have BBox leaves under BBox nodes (the guard needs boxes that contain "
-                         "their triangles exactly; sphere leaves are not supported)")
-    if t.leaf_float == abi.F64 and t.node_float == abi.F32:
-        raise ValueError("point_crossings: Float32 nodes over Float64 leaves do not contain them exactly")
     axis = _check_axis(axis, "point_crossings")
-    tris = _check_triangles(triangles, "point_crossings")
-    ft = _torch_float(t.leaf_float)
-    if tris.dtype != ft:
-        raise ValueError(f"point_crossings: triangles must be {ft}, the BVH's leaf float type")
+    tris, ft, idt = _mesh_query_setup(bvh, triangles, "point_crossings")
     p, n, _, order = _query_points(points, ft, None, presorted, "point_crossings")
-    idt = _torch_index(t.index_type)
     crossings = torch.empty(n, dtype=idt, device="cuda")
     winding = torch.empty(n, dtype=idt, device="cuda")
     if n == 0:
         return PointCrossings(crossings, winding)
-    flag = torch.zeros(1, dtype=torch.int32, device="cuda")
-    lib.call("ibvh_point_crossings", C.byref(bvh.struct()), _ptr(tris), tris.shape[0], _ptr(p), n, axis, _ptr(crossings),
-             _ptr(winding), _ptr(flag), _stream())
-    if int(flag.item()) & 2:
-        raise ValueError(f"point_crossings: a leaf's index lies outside 1..{tris.shape[0]} (the number of triangles given)")
+    _mesh_query_call("ibvh_point_crossings", "point_crossings", bvh, tris, _ptr(p), n, axis, _ptr(crossings), _ptr(winding))
     return PointCrossings(*_unpermute(order, (crossings, winding)))
 
 
@@ -1648,8 +1641,7 @@ def signed_distance(bvh, triangles, points, axis=0, rule="parity", max_distance=
     torch = _require_gpu()
     _check_rule(rule, "signed_distance")
     axis = _check_axis(axis, "signed_distance")
-    if not (isinstance(points, torch.Tensor) and points.dim() == 2 and points.shape[0] == 3):
-        raise ValueError("signed_distance: size(points, 1) == 3 must hold")
+    _check_points_shape(points, "signed_distance")
     order = None
     if points.shape[1] > 0 and points.is_cuda:
         order = _morton_order(points.t())

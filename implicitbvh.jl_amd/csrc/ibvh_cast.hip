@@ -24,6 +24,8 @@
 namespace ibvh {
 namespace cast {
 
+using pointwalk::kBlock;
+
 // entry(box) of include/ibvh.h: the slab test's tmin where the ray meets the box, +Inf where it does not.  An axis the ray
 // does not move along admits or refuses by comparing the origin; the selects keep a NaN where the header says they do.
 template <class T> IBVH_D T slab_entry(const T *lo, const T *up, const T *p, const T *d, const T *inv) {
@@ -51,7 +53,6 @@ __global__ __launch_bounds__(pointwalk::kBlock) void cast_walk_kernel(
     const T *__restrict__ tris, int64_t num_triangles, const T *__restrict__ points, const T *__restrict__ dirs, int64_t num_rays,
     const T *__restrict__ t_max, I *__restrict__ out_index, T *__restrict__ out_t, T *__restrict__ out_uv,
     uint8_t *__restrict__ out_occluded, uint32_t *flag) {
-    constexpr int kBlock = pointwalk::kBlock;
     const T inf = std::numeric_limits<T>::infinity();
     bool bad = false;
     for (int64_t item = (int64_t)blockIdx.x * kBlock + threadIdx.x; item < num_rays; item += (int64_t)gridDim.x * kBlock) {
@@ -67,12 +68,11 @@ __global__ __launch_bounds__(pointwalk::kBlock) void cast_walk_kernel(
         auto box = [&](const T *lo, const T *up) { return slab_entry(lo, up, p, d, inv); };
         // only a leaf that passes gathers its triangle (36 / 72 bytes)
         auto visit = [&](const char *rec) {
-            const I index = load_index<I>(rec, lay);
-            if (index >= 1 && (int64_t)index <= num_triangles) {
+            I index;
+            raytri::Tri<T> tr;
+            if (pointwalk::leaf_triangle(rec, lay, tris, num_triangles, index, tr.v)) {
                 const BBox<T> b = load_vol<BBox<T>>(rec);
                 const T entry = slab_entry(b.lo, b.up, p, d, inv);
-                raytri::Tri<T> tr;
-                __builtin_memcpy(&tr, __builtin_assume_aligned(tris + 9 * ((int64_t)index - 1), sizeof(T)), sizeof(tr));
                 T t, u, v;
                 if (raytri::ray_triangle(tr, p, d, t, u, v)) {
                     const T ts = entry > t ? entry : t; // t*: the clamp
@@ -126,28 +126,20 @@ ibvh_status ibvh_cast_rays(const ibvh_bvh *bvh, const void *triangles, int64_t n
     if (mode != IBVH_CAST_CLOSEST && mode != IBVH_CAST_ANY) return IBVH_ERR_INVALID_ARG;
     const bool any = mode == IBVH_CAST_ANY;
     if (any ? (!occluded || hit_index || hit_t || hit_uv) : (occluded || (!hit_index && !hit_t && !hit_uv))) return IBVH_ERR_INVALID_ARG;
-    const ibvh_types &t = bvh->types;
-    if (!combo_ok(t)) return IBVH_ERR_UNSUPPORTED;
-    // the lossless bound needs boxes that contain their triangles' boxes exactly, all the way up
-    if (t.leaf_kind != IBVH_BBOX || !pointwalk::box_nodes_hold_leaves(t)) return IBVH_ERR_UNSUPPORTED;
-    const ibvh_tree &tr = bvh->tree;
-    if (!pointwalk::tree_ok(bvh)) return IBVH_ERR_INVALID_ARG;
-    if ((num_triangles > 0 && !triangles) || (num_rays > 0 && (!points || !directions))) return IBVH_ERR_INVALID_ARG;
-    if (num_rays == 0) return IBVH_OK;
-    ibvh_layout layout;
-    LeafLayout lay;
-    if (!layout_of(t, layout, &lay)) return IBVH_ERR_UNSUPPORTED;
-    const TreeDev tree = tree_dev(tr);
-    const unsigned blocks = pointwalk::grid_blocks(num_rays);
+    // box leaves: the lossless bound needs boxes that contain their triangles' boxes exactly, all the way up
+    pointwalk::Prepared pre;
+    const bool pointers_ok = (num_triangles == 0 || triangles) && (num_rays == 0 || (points && directions));
+    const ibvh_status st = pointwalk::prepare(bvh, true, num_rays, pointers_ok, pre);
+    if (st != IBVH_OK || pre.blocks == 0) return st;
     auto launch = [&](auto ft, auto nt, auto it, auto mt) -> int {
         using T = typename decltype(ft)::type;
         using TN = typename decltype(nt)::type;
         using I = typename decltype(it)::type;
         constexpr bool ANY = decltype(mt)::value;
-        IBVH_LAUNCH((cast::cast_walk_kernel<T, TN, I, ANY>), dim3(blocks), dim3(pointwalk::kBlock), 0, (hipStream_t)stream, tree,
-                    (int)bvh->built_level, (const char *)bvh->leaves, lay, (const BBox<TN> *)bvh->nodes, (const T *)triangles,
-                    num_triangles, (const T *)points, (const T *)directions, num_rays, (const T *)t_max, (I *)hit_index, (T *)hit_t,
-                    (T *)hit_uv, (uint8_t *)occluded, (uint32_t *)flag);
+        IBVH_LAUNCH((cast::cast_walk_kernel<T, TN, I, ANY>), dim3(pre.blocks), dim3(pointwalk::kBlock), 0, (hipStream_t)stream,
+                    pre.tree, (int)bvh->built_level, (const char *)bvh->leaves, pre.lay, (const BBox<TN> *)bvh->nodes,
+                    (const T *)triangles, num_triangles, (const T *)points, (const T *)directions, num_rays, (const T *)t_max,
+                    (I *)hit_index, (T *)hit_t, (T *)hit_uv, (uint8_t *)occluded, (uint32_t *)flag);
         IBVH_LAUNCH_CHECK();
         return IBVH_OK;
     };
@@ -155,10 +147,7 @@ ibvh_status ibvh_cast_rays(const ibvh_bvh *bvh, const void *triangles, int64_t n
     auto modes = [&](auto ft, auto nt, auto it) -> int {
         return any ? launch(ft, nt, it, std::true_type{}) : launch(ft, nt, it, std::false_type{});
     };
-    return (ibvh_status)dispatch_index(t.index_type, [&](auto it) -> int {
-        if (t.leaf_float == IBVH_F64) return modes(Tag<double>{}, Tag<double>{}, it);
-        return t.node_float == IBVH_F64 ? modes(Tag<float>{}, Tag<double>{}, it) : modes(Tag<float>{}, Tag<float>{}, it);
-    });
+    return (ibvh_status)pointwalk::dispatch_box_types(bvh->types, modes);
 }
 
 } // extern "C"

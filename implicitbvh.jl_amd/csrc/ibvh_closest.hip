@@ -86,10 +86,9 @@ __global__ __launch_bounds__(kBlock) void closest_walk_kernel(TreeDev tree, int 
         I best_index = 0;
         // only a leaf that passes gathers its triangle (36 / 72 bytes)
         auto visit = [&](const char *rec) {
-            const I index = load_index<I>(rec, lay);
-            if (index >= 1 && (int64_t)index <= num_triangles) {
-                T tr[9], q[3];
-                __builtin_memcpy(tr, __builtin_assume_aligned(tris + 9 * ((int64_t)index - 1), sizeof(T)), sizeof(tr));
+            I index;
+            T tr[9], q[3];
+            if (pointwalk::leaf_triangle(rec, lay, tris, num_triangles, index, tr)) {
                 const T d2 = closest_on_triangle(tr, p, q);
                 // (d2, index) lexicographically; the first one only has to be within the radius (best == max_d2)
                 if ((d2 < best) | ((d2 == best) & ((best_index == 0) | (index < best_index)))) {
@@ -104,9 +103,8 @@ __global__ __launch_bounds__(kBlock) void closest_walk_kernel(TreeDev tree, int 
             }
         };
         auto box = [&](const T *lo, const T *up) { return pointwalk::box_bound(lo, up, p); }; // lb(B) of include/ibvh.h
-        // a NaN coordinate makes every d2 NaN and a NaN radius admits nothing: a miss either way, and no bound could prune
-        const bool hopeless = !((p[0] == p[0]) & (p[1] == p[1]) & (p[2] == p[2]) & (max_d2 == max_d2));
-        if (!hopeless) pointwalk::walk<BBox<T>, TN>(tree, built_level, leaves, lay, nodes, box, [&]() { return best; }, visit);
+        if (!pointwalk::hopeless(p, max_d2)) // (a NaN point or radius: a miss)
+            pointwalk::walk<BBox<T>, TN>(tree, built_level, leaves, lay, nodes, box, [&]() { return best; }, visit);
         const bool hit = best_index != 0;
         if (out_index) out_index[item] = best_index;
         if (out_d2) out_d2[item] = hit ? best : std::numeric_limits<T>::infinity();
@@ -131,34 +129,21 @@ ibvh_status ibvh_closest_triangles(const ibvh_bvh *bvh, const void *triangles, i
                                    void *closest_point, void *flag, void *stream) {
     if (!bvh || num_triangles < 0 || num_points < 0) return IBVH_ERR_INVALID_ARG;
     if (!closest_index && !closest_d2 && !closest_point) return IBVH_ERR_INVALID_ARG;
-    const ibvh_types &t = bvh->types;
-    if (!combo_ok(t)) return IBVH_ERR_UNSUPPORTED;
-    // the lossless bound needs boxes all the way up
-    if (t.leaf_kind != IBVH_BBOX || !pointwalk::box_nodes_hold_leaves(t)) return IBVH_ERR_UNSUPPORTED;
-    const ibvh_tree &tr = bvh->tree;
-    if (!pointwalk::tree_ok(bvh)) return IBVH_ERR_INVALID_ARG;
-    if ((num_triangles > 0 && !triangles) || (num_points > 0 && !points)) return IBVH_ERR_INVALID_ARG;
-    if (num_points == 0) return IBVH_OK;
-    ibvh_layout layout;
-    LeafLayout lay;
-    if (!layout_of(t, layout, &lay)) return IBVH_ERR_UNSUPPORTED;
-    const TreeDev tree = tree_dev(tr);
-    const unsigned blocks = pointwalk::grid_blocks(num_points);
-    auto launch = [&](auto ft, auto nt, auto it) -> int {
+    // box leaves: the lossless bound needs boxes all the way up
+    pointwalk::Prepared pre;
+    const bool pointers_ok = (num_triangles == 0 || triangles) && (num_points == 0 || points);
+    const ibvh_status st = pointwalk::prepare(bvh, true, num_points, pointers_ok, pre);
+    if (st != IBVH_OK || pre.blocks == 0) return st;
+    return (ibvh_status)pointwalk::dispatch_box_types(bvh->types, [&](auto ft, auto nt, auto it) -> int {
         using T = typename decltype(ft)::type;
         using TN = typename decltype(nt)::type;
         using I = typename decltype(it)::type;
-        const T max_d2 = max_distance2 ? *(const T *)max_distance2 : std::numeric_limits<T>::infinity();
-        IBVH_LAUNCH((closest::closest_walk_kernel<T, TN, I>), dim3(blocks), dim3(pointwalk::kBlock), 0, (hipStream_t)stream, tree,
-                    (int)bvh->built_level, (const char *)bvh->leaves, lay, (const BBox<TN> *)bvh->nodes, (const T *)triangles,
-                    num_triangles, (const T *)points, num_points, max_d2, (I *)closest_index, (T *)closest_d2,
-                    (T *)closest_point, (uint32_t *)flag);
+        IBVH_LAUNCH((closest::closest_walk_kernel<T, TN, I>), dim3(pre.blocks), dim3(pointwalk::kBlock), 0, (hipStream_t)stream,
+                    pre.tree, (int)bvh->built_level, (const char *)bvh->leaves, pre.lay, (const BBox<TN> *)bvh->nodes,
+                    (const T *)triangles, num_triangles, (const T *)points, num_points, pointwalk::radius_or_inf<T>(max_distance2),
+                    (I *)closest_index, (T *)closest_d2, (T *)closest_point, (uint32_t *)flag);
         IBVH_LAUNCH_CHECK();
         return IBVH_OK;
-    };
-    return (ibvh_status)dispatch_index(t.index_type, [&](auto it) -> int {
-        if (t.leaf_float == IBVH_F64) return launch(Tag<double>{}, Tag<double>{}, it);
-        return t.node_float == IBVH_F64 ? launch(Tag<float>{}, Tag<double>{}, it) : launch(Tag<float>{}, Tag<float>{}, it);
     });
 }
 

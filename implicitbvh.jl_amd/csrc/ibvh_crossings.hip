@@ -72,7 +72,9 @@ __global__ __launch_bounds__(kBlock) void crossings_walk_kernel(TreeDev tree, in
             const T lo0 = pick(lo, u), up0 = pick(up, u), lo1 = pick(lo, v), up1 = pick(up, v), up2 = pick(up, w);
             return ((p[0] >= lo0) & (p[0] <= up0) & (p[1] >= lo1) & (p[1] <= up1) & (up2 >= p[2])) ? T(0) : T(1);
         };
-        // only a leaf that passes gathers its triangle (36 / 72 bytes)
+        // only a leaf that passes gathers its triangle (36 / 72 bytes).  The statements of pointwalk::leaf_triangle, spelled out:
+        // behind the helper's return value the compiler joins the two paths ahead of the axis selects below, the nine values
+        // cross the join, and the kernel comes out 1 % longer and waits on its loads one by one
         auto visit = [&](const char *rec) {
             const I index = load_index<I>(rec, lay);
             if (index >= 1 && (int64_t)index <= num_triangles) {
@@ -106,33 +108,22 @@ ibvh_status ibvh_point_crossings(const ibvh_bvh *bvh, const void *triangles, int
                                  int64_t num_points, int32_t axis, void *crossings, void *winding, void *flag, void *stream) {
     if (!bvh || num_triangles < 0 || num_points < 0 || axis < 0 || axis > 2) return IBVH_ERR_INVALID_ARG;
     if (!crossings && !winding) return IBVH_ERR_INVALID_ARG;
-    const ibvh_types &t = bvh->types;
-    if (!combo_ok(t)) return IBVH_ERR_UNSUPPORTED;
-    // the lossless guard needs boxes that contain their triangles exactly, all the way up
-    if (t.leaf_kind != IBVH_BBOX || !pointwalk::box_nodes_hold_leaves(t)) return IBVH_ERR_UNSUPPORTED;
-    const ibvh_tree &tr = bvh->tree;
-    if (!pointwalk::tree_ok(bvh)) return IBVH_ERR_INVALID_ARG;
-    if ((num_triangles > 0 && !triangles) || (num_points > 0 && !points)) return IBVH_ERR_INVALID_ARG;
-    if (num_points == 0) return IBVH_OK;
-    ibvh_layout layout;
-    LeafLayout lay;
-    if (!layout_of(t, layout, &lay)) return IBVH_ERR_UNSUPPORTED;
-    const TreeDev tree = tree_dev(tr);
-    const unsigned blocks = pointwalk::grid_blocks(num_points);
+    // box leaves: the lossless guard needs boxes that contain their triangles exactly, all the way up
+    pointwalk::Prepared pre;
+    const bool pointers_ok = (num_triangles == 0 || triangles) && (num_points == 0 || points);
+    const ibvh_status st = pointwalk::prepare(bvh, true, num_points, pointers_ok, pre);
+    if (st != IBVH_OK || pre.blocks == 0) return st;
     const int u = (axis + 1) % 3, v = (axis + 2) % 3, w = axis; // cyclic: orientation is preserved
-    auto launch = [&](auto ft, auto nt, auto it) -> int {
+    return (ibvh_status)pointwalk::dispatch_box_types(bvh->types, [&](auto ft, auto nt, auto it) -> int {
         using T = typename decltype(ft)::type;
         using TN = typename decltype(nt)::type;
         using I = typename decltype(it)::type;
-        IBVH_LAUNCH((crossings::crossings_walk_kernel<T, TN, I>), dim3(blocks), dim3(pointwalk::kBlock), 0, (hipStream_t)stream,
-                    tree, (int)bvh->built_level, (const char *)bvh->leaves, lay, (const BBox<TN> *)bvh->nodes, (const T *)triangles,
-                    num_triangles, (const T *)points, num_points, u, v, w, (I *)crossings, (I *)winding, (uint32_t *)flag);
+        IBVH_LAUNCH((crossings::crossings_walk_kernel<T, TN, I>), dim3(pre.blocks), dim3(pointwalk::kBlock), 0,
+                    (hipStream_t)stream, pre.tree, (int)bvh->built_level, (const char *)bvh->leaves, pre.lay,
+                    (const BBox<TN> *)bvh->nodes, (const T *)triangles, num_triangles, (const T *)points, num_points, u, v, w,
+                    (I *)crossings, (I *)winding, (uint32_t *)flag);
         IBVH_LAUNCH_CHECK();
         return IBVH_OK;
-    };
-    return (ibvh_status)dispatch_index(t.index_type, [&](auto it) -> int {
-        if (t.leaf_float == IBVH_F64) return launch(Tag<double>{}, Tag<double>{}, it);
-        return t.node_float == IBVH_F64 ? launch(Tag<float>{}, Tag<double>{}, it) : launch(Tag<float>{}, Tag<float>{}, it);
     });
 }
 

@@ -67,9 +67,8 @@ __global__ __launch_bounds__(kBlock) void nearest_walk_kernel(TreeDev tree, int 
             }
         };
         auto box = [&](const T *lo, const T *up) { return pointwalk::box_bound(lo, up, p); }; // lb(B) of include/ibvh.h
-        // a NaN coordinate makes every d2 NaN and a NaN radius admits nothing: no answer either way, and no bound could prune
-        const bool hopeless = !((p[0] == p[0]) & (p[1] == p[1]) & (p[2] == p[2]) & (max_d2 == max_d2));
-        if (!hopeless) pointwalk::walk<VL, TN>(tree, built_level, leaves, lay, nodes, box, [&]() { return d[K - 1]; }, visit);
+        if (!pointwalk::hopeless(p, max_d2)) // (a NaN point or radius: no answer)
+            pointwalk::walk<VL, TN>(tree, built_level, leaves, lay, nodes, box, [&]() { return d[K - 1]; }, visit);
 #pragma unroll
         for (int j = 0; j < K; ++j) {
             if (j >= base) {
@@ -92,29 +91,22 @@ ibvh_status ibvh_nearest_leaves(const ibvh_bvh *bvh, const void *points, int64_t
                                 const void *max_distance2, void *nearest_index, void *nearest_d2, void *stream) {
     if (!bvh || num_points < 0 || k < 1 || k > IBVH_NEAREST_MAX_K) return IBVH_ERR_INVALID_ARG;
     if (!nearest_index && !nearest_d2) return IBVH_ERR_INVALID_ARG;
+    // sphere leaves too: only their centres are asked for
+    pointwalk::Prepared pre;
+    const ibvh_status st = pointwalk::prepare(bvh, false, num_points, num_points == 0 || points, pre);
+    if (st != IBVH_OK || pre.blocks == 0) return st;
     const ibvh_types &t = bvh->types;
-    if (!combo_ok(t)) return IBVH_ERR_UNSUPPORTED;
-    if (!pointwalk::box_nodes_hold_leaves(t)) return IBVH_ERR_UNSUPPORTED;
-    const ibvh_tree &tr = bvh->tree;
-    if (!pointwalk::tree_ok(bvh)) return IBVH_ERR_INVALID_ARG;
-    if (num_points > 0 && !points) return IBVH_ERR_INVALID_ARG;
-    if (num_points == 0) return IBVH_OK;
-    ibvh_layout layout;
-    LeafLayout lay;
-    if (!layout_of(t, layout, &lay)) return IBVH_ERR_UNSUPPORTED;
-    const TreeDev tree = tree_dev(tr);
-    const unsigned blocks = pointwalk::grid_blocks(num_points);
     return (ibvh_status)dispatch_volume(t.leaf_kind, t.leaf_float, [&](auto lt) -> int {
         using VL = typename decltype(lt)::type;
         using T = typename VL::elt;
-        const T max_d2 = max_distance2 ? *(const T *)max_distance2 : std::numeric_limits<T>::infinity();
+        const T max_d2 = pointwalk::radius_or_inf<T>(max_distance2);
         return dispatch_index(t.index_type, [&](auto it) -> int {
             using I = typename decltype(it)::type;
             auto launch = [&](auto nt, auto kt) -> int {
                 using TN = typename decltype(nt)::type;
                 constexpr int K = decltype(kt)::value;
-                IBVH_LAUNCH((nearest::nearest_walk_kernel<VL, TN, I, K>), dim3(blocks), dim3(pointwalk::kBlock), 0,
-                            (hipStream_t)stream, tree, (int)bvh->built_level, (const char *)bvh->leaves, lay,
+                IBVH_LAUNCH((nearest::nearest_walk_kernel<VL, TN, I, K>), dim3(pre.blocks), dim3(pointwalk::kBlock), 0,
+                            (hipStream_t)stream, pre.tree, (int)bvh->built_level, (const char *)bvh->leaves, pre.lay,
                             (const BBox<TN> *)bvh->nodes, (const T *)points, num_points, (int)k, max_d2, (I *)nearest_index,
                             (T *)nearest_d2);
                 IBVH_LAUNCH_CHECK();

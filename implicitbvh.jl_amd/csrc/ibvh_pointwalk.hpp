@@ -1,9 +1,13 @@
-// ibvh_pointwalk.hpp — the bounded walk of one query point through a BVH, shared by the point queries: the two that prune
-// on a bound which shrinks while they walk, ibvh_closest.hip (the closest triangle) and ibvh_nearest.hip (the k nearest
-// leaf centres), ibvh_crossings.hip (the triangles an axis ray from the point crosses), whose bound is a fixed yes / no, and
-// ibvh_cast.hip (the closest or any hit of a ray from the point), whose bound is the ray's entry distance into a box; and the
-// argument checks their entry points have in common.  No reference counterpart: every traversal of ImplicitBVH.jl
-// is a fixed-volume overlap test (traverse/, raytrace/).
+// ibvh_pointwalk.hpp — what the four queries that walk one point (or ray origin) per lane through a BVH have in common:
+// ibvh_closest.hip (the closest triangle) and ibvh_nearest.hip (the k nearest leaf centres), which prune on a bound that
+// shrinks while they walk, ibvh_crossings.hip (the triangles an axis ray from the point crosses), whose bound is a fixed
+// yes / no, and ibvh_cast.hip (the closest or any hit of a ray from the point), whose bound is the ray's entry distance into a
+// box.  No reference counterpart: every traversal of ImplicitBVH.jl is a fixed-volume overlap test (traverse/, raytrace/).
+//
+// For the kernels: the workgroup size, the distance queries' point-box bound (box_bound) and NaN test (hopeless), the walk,
+// and the mesh queries' gather of a leaf's triangle (leaf_triangle).  For the entry points: the rules they share and prepare(),
+// the one place that applies them, in the one order a call with several faults is refused in; the (T, TN, I) dispatch of a tree
+// with box leaves; the optional radius.  An entry point keeps its own checks (counts, axis, mode, k, outputs) and its launch.
 //
 // A query hands the walk three things: bound(lo, up), its lower bound for a box (box_bound below for the distance queries;
 // 0 / 1 = "the ray can / cannot meet the box" for the crossings; the slab test's entry distance for the ray cast), limit(),
@@ -22,6 +26,8 @@
 // keep the order they are given, the host mirrors sort the batch along a Morton curve first.
 #pragma once
 #include "ibvh_common.hpp"
+
+#include <limits>
 
 namespace ibvh {
 namespace pointwalk {
@@ -104,7 +110,23 @@ IBVH_D void walk(const TreeDev &tree, int built_level, const char *__restrict__ 
     }
 }
 
-// ---- the entry points' common argument checks (host) ---------------------------------------------------------------
+// The mesh queries' visit of a leaf record that passed: the leaf's index -> `index`, and, if it names one of the
+// num_triangles rows of `tris` (1-based), that triangle's nine values (36 / 72 bytes) -> tr9 and true.  false: the index lies
+// outside the mesh, nothing was gathered; the caller skips the leaf and raises flag bit 1 when its lane is done.
+template <class T, class I>
+IBVH_D bool leaf_triangle(const char *rec, const LeafLayout &lay, const T *tris, int64_t num_triangles, I &index, T *tr9) {
+    index = load_index<I>(rec, lay);
+    if (!(index >= 1 && (int64_t)index <= num_triangles)) return false;
+    __builtin_memcpy(tr9, __builtin_assume_aligned(tris + 9 * ((int64_t)index - 1), sizeof(T)), 9 * sizeof(T));
+    return true;
+}
+
+// a NaN coordinate makes every d2 NaN and a NaN radius admits nothing: no answer either way, and no bound could prune
+template <class T> IBVH_D bool hopeless(const T *p, T max_d2) {
+    return !((p[0] == p[0]) & (p[1] == p[1]) & (p[2] == p[2]) & (max_d2 == max_d2));
+}
+
+// ---- the entry points' common front end (host) ---------------------------------------------------------------------
 
 // the lossless bound needs boxes above the leaves, holding the leaves' values exactly (else IBVH_ERR_UNSUPPORTED)
 inline bool box_nodes_hold_leaves(const ibvh_types &t) {
@@ -126,6 +148,42 @@ inline unsigned grid_blocks(int64_t num_points) {
     const int64_t b = ceil_div(num_points, kBlock);
     return (unsigned)(b > (int64_t(1) << 22) ? (int64_t(1) << 22) : b);
 }
+
+// what a launch needs besides the entry point's own arguments; blocks == 0: nothing to launch
+struct Prepared {
+    TreeDev tree;
+    LeafLayout lay;
+    unsigned blocks = 0;
+};
+
+// The checks every entry point makes once its own are done, in the order a call with several faults is refused in: the type
+// combination and — box_leaves: the query reads a triangle's box from its leaf — the leaf kind (IBVH_ERR_UNSUPPORTED), the
+// tree, then pointers_ok, the caller's "the arrays this many queries need are there" (IBVH_ERR_INVALID_ARG); num == 0 is
+// IBVH_OK with nothing to launch.  Otherwise fills `out` for a grid over num queries.
+inline ibvh_status prepare(const ibvh_bvh *bvh, bool box_leaves, int64_t num, bool pointers_ok, Prepared &out) {
+    const ibvh_types &t = bvh->types;
+    if (!combo_ok(t)) return IBVH_ERR_UNSUPPORTED;
+    if ((box_leaves && t.leaf_kind != IBVH_BBOX) || !box_nodes_hold_leaves(t)) return IBVH_ERR_UNSUPPORTED;
+    if (!tree_ok(bvh) || !pointers_ok) return IBVH_ERR_INVALID_ARG;
+    if (num == 0) return IBVH_OK;
+    ibvh_layout layout;
+    if (!layout_of(t, layout, &out.lay)) return IBVH_ERR_UNSUPPORTED;
+    out.tree = tree_dev(bvh->tree);
+    out.blocks = grid_blocks(num);
+    return IBVH_OK;
+}
+
+// (T, TN, I) of a tree with box leaves that prepare() admitted — the leaves' float type, the nodes' (the same or wider) and
+// the index type — as f(Tag<T>, Tag<TN>, Tag<I>)
+template <class F> int dispatch_box_types(const ibvh_types &t, F &&f) {
+    return dispatch_index(t.index_type, [&](auto it) -> int {
+        if (t.leaf_float == IBVH_F64) return f(Tag<double>{}, Tag<double>{}, it);
+        return t.node_float == IBVH_F64 ? f(Tag<float>{}, Tag<double>{}, it) : f(Tag<float>{}, Tag<float>{}, it);
+    });
+}
+
+// an optional squared radius: the host scalar of type T behind p, +Inf where there is none
+template <class T> T radius_or_inf(const void *p) { return p ? *(const T *)p : std::numeric_limits<T>::infinity(); }
 
 } // namespace pointwalk
 } // namespace ibvh

@@ -21,17 +21,9 @@ from implicitbvh_amd import abi, api, lib  # noqa: E402
 from implicitbvh_amd.synthetic import torus_mesh  # noqa: E402
 
 import closest_point_checker as cpc  # noqa: E402
-from test_gpu_parity import cuda, make_options  # noqa: E402
-from test_gpu_rays_binned import _kernels_of  # noqa: E402
+from mesh_query_kit import FLOATS, MESHES, NP_F, NP_I, assert_one_kernel, build as _build, tf as _tf  # noqa: E402
+from test_gpu_parity import cuda  # noqa: E402
 
-NP_F = {abi.F32: np.float32, abi.F64: np.float64}
-NP_I = {abi.I32: np.int32, abi.I64: np.int64}
-MESHES = {"torus40": (40, 40), "torus64x63": (64, 63)}
-FLOATS = {"f32": (abi.F32, abi.F32), "f64": (abi.F64, abi.F64), "f32_under_f64": (abi.F32, abi.F64)}
-
-
-def _tf(flt):
-    return torch.float32 if flt == abi.F32 else torch.float64
 
 
 @functools.lru_cache(maxsize=None)
@@ -43,19 +35,6 @@ def _reference(mesh, flt):
     for a in (tris, bf.index, bf.d2, bf.point):  # (p goes through torch.from_numpy, which wants a writable array)
         a.setflags(write=False)
     return tris, p, bf
-
-
-def _build(tris, leaf_flt=abi.F32, node_flt=None, idx=abi.I32, leaf_kind=abi.BBOX, node_kind=abi.BBOX, skin=None, built_level=1):
-    node_flt = leaf_flt if node_flt is None else node_flt
-    types = abi.make_types(leaf_kind, leaf_flt, node_kind, node_flt, index_type=idx)
-    tdev = cuda(tris.astype(NP_F[leaf_flt]))
-    token = ibvh.BBox if leaf_kind == abi.BBOX else ibvh.BSphere
-    vols = ibvh.bounding_volumes_from_triangles(tdev, token(_tf(leaf_flt)))
-    if skin is not None:
-        vols[:, :3] -= skin
-        vols[:, 3:] += skin
-    ntoken = ibvh.BBox if node_kind == abi.BBOX else ibvh.BSphere
-    return ibvh.BVH(vols, ntoken(_tf(node_flt)), built_level=built_level, options=make_options(types)), tdev
 
 
 def _bits(a):
@@ -307,12 +286,4 @@ def test_one_call_is_one_kernel_of_the_new_translation_unit():
     tris, p, bf = _reference("torus40", abi.F32)
     bvh, tdev = _build(tris)
     P = cuda(p).t()
-    torch.cuda.synchronize()
-    count = C.c_int64(-1)
-
-    def run():
-        ibvh.closest_points(bvh, tdev, P, presorted=True)
-        torch.cuda.synchronize()
-        lib.call("ibvh_profile_count", C.byref(count))
-    names = _kernels_of(run)
-    assert names == {"closest_walk_kernel"} and count.value == 1, (names, count.value)
+    assert_one_kernel(lambda: ibvh.closest_points(bvh, tdev, P, presorted=True), "closest_walk_kernel")

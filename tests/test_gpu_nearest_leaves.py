@@ -16,20 +16,14 @@ import implicitbvh_amd as ibvh  # noqa: E402
 from implicitbvh_amd import abi, api, lib  # noqa: E402
 
 import nearest_leaves_checker as nlc  # noqa: E402
+from mesh_query_kit import NP_F, NP_I, assert_one_kernel, tf as _tf  # noqa: E402
 from test_gpu_parity import cuda, make_options  # noqa: E402
-from test_gpu_rays_binned import _kernels_of  # noqa: E402
 
-NP_F = {abi.F32: np.float32, abi.F64: np.float64}
-NP_I = {abi.I32: np.int32, abi.I64: np.int64}
 # (leaf kind, leaf float, node float)
 COMBOS = {"sphere32_box32": (abi.BSPHERE, abi.F32, abi.F32), "sphere32_box64": (abi.BSPHERE, abi.F32, abi.F64),
           "sphere64_box64": (abi.BSPHERE, abi.F64, abi.F64), "box32_box32": (abi.BBOX, abi.F32, abi.F32),
           "box64_box64": (abi.BBOX, abi.F64, abi.F64)}
 KS = (1, 2, 3, 8, 16)
-
-
-def _tf(flt):
-    return torch.float32 if flt == abi.F32 else torch.float64
 
 
 @functools.lru_cache(maxsize=None)
@@ -334,12 +328,4 @@ def test_refusals_of_the_c_entry_and_the_python_mirror():
 def test_one_call_is_one_kernel_of_the_new_translation_unit():
     bvh = _build(_cloud(abi.BSPHERE, abi.F32, 1000))
     P = cuda(_points(abi.F32, 65)).t()
-    torch.cuda.synchronize()
-    count = C.c_int64(-1)
-
-    def run():
-        ibvh.nearest_leaves(bvh, P, k=8, presorted=True)
-        torch.cuda.synchronize()
-        lib.call("ibvh_profile_count", C.byref(count))
-    names = _kernels_of(run)
-    assert names == {"nearest_walk_kernel"} and count.value == 1, (names, count.value)
+    assert_one_kernel(lambda: ibvh.nearest_leaves(bvh, P, k=8, presorted=True), "nearest_walk_kernel")

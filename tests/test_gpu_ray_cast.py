@@ -18,19 +18,11 @@ from implicitbvh_amd import abi, api, lib  # noqa: E402
 from implicitbvh_amd.synthetic import torus_mesh  # noqa: E402
 
 import ray_cast_checker as rcc  # noqa: E402
-from test_gpu_parity import cuda, make_options  # noqa: E402
-from test_gpu_rays_binned import _kernels_of  # noqa: E402
+from mesh_query_kit import FLOATS, MESHES, NP_F, NP_I, assert_one_kernel, build as _build, tf as _tf  # noqa: E402
+from test_gpu_parity import cuda  # noqa: E402
 
-NP_F = {abi.F32: np.float32, abi.F64: np.float64}
-NP_I = {abi.I32: np.int32, abi.I64: np.int64}
 BITS = {np.dtype(np.float32): np.int32, np.dtype(np.float64): np.int64}
-MESHES = {"torus40": (40, 40), "torus64x63": (64, 63)}
-FLOATS = {"f32": (abi.F32, abi.F32), "f64": (abi.F64, abi.F64), "f32_under_f64": (abi.F32, abi.F64)}
 NAME = "ibvh_cast_rays"
-
-
-def _tf(flt):
-    return torch.float32 if flt == abi.F32 else torch.float64
 
 
 @functools.lru_cache(maxsize=None)
@@ -43,19 +35,6 @@ def _reference(mesh, flt):
     for a in (tris, bf.index, bf.t, bf.uv, bf.occluded, bf.clamped, bf.tied):  # (p, d go through torch.from_numpy: writable)
         a.setflags(write=False)
     return tris, p, d, bf
-
-
-def _build(tris, leaf_flt=abi.F32, node_flt=None, idx=abi.I32, leaf_kind=abi.BBOX, node_kind=abi.BBOX, skin=None, built_level=1):
-    node_flt = leaf_flt if node_flt is None else node_flt
-    types = abi.make_types(leaf_kind, leaf_flt, node_kind, node_flt, index_type=idx)
-    tdev = cuda(tris.astype(NP_F[leaf_flt]))
-    token = ibvh.BBox if leaf_kind == abi.BBOX else ibvh.BSphere
-    vols = ibvh.bounding_volumes_from_triangles(tdev, token(_tf(leaf_flt)))
-    if skin is not None:
-        vols[:, :3] -= skin
-        vols[:, 3:] += skin
-    ntoken = ibvh.BBox if node_kind == abi.BBOX else ibvh.BSphere
-    return ibvh.BVH(vols, ntoken(_tf(node_flt)), built_level=built_level, options=make_options(types)), tdev
 
 
 def _bits(a):
@@ -381,12 +360,5 @@ def test_one_call_is_one_kernel_of_the_new_translation_unit():
     bvh, tdev = _build(tris)
     P, D = cuda(p).t(), cuda(d).t()
     L = torch.ones(800, device="cuda")
-    torch.cuda.synchronize()
-    count = C.c_int64(-1)
     for kw in (dict(), dict(any_hit=True), dict(t_max=L)):
-        def run():
-            ibvh.cast_rays(bvh, tdev, P, D, presorted=True, **kw)
-            torch.cuda.synchronize()
-            lib.call("ibvh_profile_count", C.byref(count))
-        names = _kernels_of(run)
-        assert names == {"cast_walk_kernel"} and count.value == 1, (kw, names, count.value)
+        assert_one_kernel(lambda: ibvh.cast_rays(bvh, tdev, P, D, presorted=True, **kw), "cast_walk_kernel", kw)

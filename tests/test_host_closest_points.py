@@ -5,8 +5,7 @@ included — before any launch.  The numpy checker the GPU test pins the kernel 
 with its own float64 run, its point-box bound never exceeds a distance, and the GPU test's non-vacuity conditions hold for
 the brute force alone.  No GPU."""
 import ctypes as C
-import os
-import re
+import functools
 
 import numpy as np
 import pytest
@@ -16,28 +15,18 @@ from implicitbvh_amd import abi, lib
 from implicitbvh_amd.synthetic import torus_mesh
 
 import closest_point_checker as cpc
+import mesh_query_kit as kit
+from mesh_query_kit import MESHES
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 NAME = "ibvh_closest_triangles"
-MESHES = {"torus40": (40, 40), "torus64x63": (64, 63)}
-
-
-def _read(*parts):
-    return open(os.path.join(ROOT, *parts)).read()
+_fake_bvh = functools.partial(kit.fake_bvh, leaf_kind=abi.BBOX)
 
 
 def test_header_declares_the_entry_point_under_abi_version_7():
-    raw = _read("include", "ibvh.h")
-    hdr = re.sub(r"/\*.*?\*/", "", raw, flags=re.S)
-    m = re.search(r"ibvh_status\s+" + NAME + r"\s*\(([^)]*)\)\s*;", hdr)
-    assert m, "include/ibvh.h declares " + NAME
-    args = [" ".join(a.split()) for a in m.group(1).split(",")]
+    raw, hdr, args, note = kit.header_prototype(NAME)
     assert args == ["const ibvh_bvh *bvh", "const void *triangles", "int64_t num_triangles", "const void *points", "int64_t num_points",
                     "const void *max_distance2", "void *closest_index", "void *closest_d2", "void *closest_point", "void *flag",
                     "void *stream"]
-    assert int(re.search(r"#define IBVH_ABI_VERSION (\d+)", hdr).group(1)) == 7 == abi.ABI_VERSION
-    assert lib.load().ibvh_abi_version() == 7
-    note = raw[raw.index("Bumped whenever"):raw.index("#define IBVH_ABI_VERSION")]
     assert NAME in note and note.count("additive") >= 2
     # the doc comment carries the contract: arithmetic, tie rule, the clamp and why, accepted types, guards, miss values
     doc = raw[raw.index("closest point on the mesh for a batch of query points"):raw.index("ibvh_status " + NAME)]
@@ -54,42 +43,17 @@ def test_binding_table_makefile_launch_and_python_surface():
     assert hasattr(lib.load(), NAME), "libibvh.so exports " + NAME
     for name in ("closest_points", "ClosestPoints"):
         assert name in ibvh.__all__ and callable(getattr(ibvh, name))
-    mk = _read("implicitbvh.jl_amd", "csrc", "Makefile")
-    assert "ibvh_closest.hip" in mk[mk.index("SRCS"):mk.index("OBJS")]
-    src = _read("implicitbvh.jl_amd", "csrc", "ibvh_closest.hip")
-    launches = re.findall(r"IBVH_LAUNCH\(\((closest::\w+)<", src)
-    assert launches == ["closest::closest_walk_kernel"], "ONE launch, through the profiling wrapper"
-    # (the walk the kernel calls lives in ibvh_pointwalk.hpp: the same holds for it)
-    for text in (src, _read("implicitbvh.jl_amd", "csrc", "ibvh_pointwalk.hpp")):
-        assert "hipLaunchKernelGGL" not in text and "<<<" not in text
-        assert "atomicAdd" not in text and "hipStreamSynchronize" not in text and "hipDeviceSynchronize" not in text and "hipMemcpy" not in text
+    src = kit.query_unit("ibvh_closest.hip", "closest::closest_walk_kernel")
+    assert "pointwalk::hopeless(p, max_d2)" in src and "pointwalk::radius_or_inf<T>(max_distance2)" in src
     # raise_flag is shared with the ray resolve, defined once
-    assert "void raise_flag(" in _read("implicitbvh.jl_amd", "csrc", "ibvh_common.hpp")
-    assert "void raise_flag(" not in src and "void raise_flag(" not in _read("implicitbvh.jl_amd", "csrc", "ibvh_raytri.hip")
+    assert "void raise_flag(" in kit.read("implicitbvh.jl_amd", "csrc", "ibvh_common.hpp")
+    assert "void raise_flag(" not in kit.read("implicitbvh.jl_amd", "csrc", "ibvh_raytri.hip")
 
 
 def test_julia_wrapper_binds_it_with_the_ctypes_signature():
-    src = _read("implicitbvh.jl_amd", "julia", "ImplicitBVHlibibvhExt.jl")
-    m = re.search(r"\n(c_\w+)\([^)]*\) =\n\s*ccall\(\(:" + NAME + r", libibvh\), Cint,\s*\(([^)]*)\)", src)
-    assert m, "one ccall wrapper binds " + NAME
-    jl = {"Ptr{Cvoid}": C.c_void_p, "Int64": C.c_int64, "Int32": C.c_int32, "Ref{IbvhBvh}": C.POINTER(abi.Bvh)}
-    assert [jl[a.strip()] for a in m.group(2).split(",")] == lib.SIGNATURES[NAME]
-    assert m.group(1) + "(" in src[src.index("function closest_points("):]
-    assert "function ImplicitBVH.closest_points" not in src
-    for doc in ("INTEGRATION.md", "README.md", "DESIGN.md"):
-        assert NAME in _read(doc), doc
-    design = _read("DESIGN.md")
+    kit.julia_ccall(NAME, "closest_points")
+    design = kit.read("DESIGN.md")
     assert "no reference counterpart" in design[design.index("Closest point on the mesh"):][:3000]
-
-
-def _fake_bvh(leaf_kind=abi.BBOX, leaf_float=abi.F32, node_kind=abi.BBOX, node_float=abi.F32, idx=abi.I32, n=5, built_level=1,
-              leaves=64, nodes=64):
-    """a hand-filled ibvh_bvh over fake non-NULL pointers: never dereferenced"""
-    b = abi.Bvh()
-    b.types = abi.make_types(leaf_kind, leaf_float, node_kind, node_float, idx)
-    lib.call("ibvh_tree_shape", n, C.byref(b.tree))
-    b.built_level, b.leaves, b.nodes, b.skips = built_level, leaves, nodes, 64
-    return b
 
 
 def test_entry_point_validates_its_arguments_before_any_launch():

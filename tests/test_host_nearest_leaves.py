@@ -5,7 +5,7 @@ refused type combinations included — before any launch.  The numpy checker the
 (tests/nearest_leaves_checker.py) agrees with a naive per-point loop, and its point-box bound never exceeds the distance of
 a centre inside the box.  No GPU."""
 import ctypes as C
-import os
+import functools
 import re
 
 import numpy as np
@@ -14,27 +14,17 @@ import pytest
 import implicitbvh_amd as ibvh
 from implicitbvh_amd import abi, lib
 
+import mesh_query_kit as kit
 import nearest_leaves_checker as nlc
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 NAME = "ibvh_nearest_leaves"
-
-
-def _read(*parts):
-    return open(os.path.join(ROOT, *parts)).read()
+_fake_bvh = functools.partial(kit.fake_bvh, leaf_kind=abi.BSPHERE)
 
 
 def test_header_declares_the_entry_point_under_abi_version_7():
-    raw = _read("include", "ibvh.h")
-    hdr = re.sub(r"/\*.*?\*/", "", raw, flags=re.S)
-    m = re.search(r"ibvh_status\s+" + NAME + r"\s*\(([^)]*)\)\s*;", hdr)
-    assert m, "include/ibvh.h declares " + NAME
-    args = [" ".join(a.split()) for a in m.group(1).split(",")]
+    raw, hdr, args, note = kit.header_prototype(NAME)
     assert args == ["const ibvh_bvh *bvh", "const void *points", "int64_t num_points", "int32_t k", "const void *max_distance2",
                     "void *nearest_index", "void *nearest_d2", "void *stream"]
-    assert int(re.search(r"#define IBVH_ABI_VERSION (\d+)", hdr).group(1)) == 7 == abi.ABI_VERSION
-    assert lib.load().ibvh_abi_version() == 7
-    note = raw[raw.index("Bumped whenever"):raw.index("#define IBVH_ABI_VERSION")]
     assert NAME in note and "IBVH_NEAREST_MAX_K" in note and note.count("additive") >= 3
     # the doc comment carries the contract: arithmetic, tie rule, the bound and why, what makes it exact, accepted types
     doc = raw[raw.index("k nearest leaves for a batch of query points"):raw.index("ibvh_status " + NAME)]
@@ -45,47 +35,25 @@ def test_header_declares_the_entry_point_under_abi_version_7():
 
 
 def test_header_mirror_and_julia_agree_on_the_prototype_and_the_largest_k():
-    hdr = _read("include", "ibvh.h")
+    hdr = kit.read("include", "ibvh.h")
     max_k = int(re.search(r"#define IBVH_NEAREST_MAX_K (\d+)", hdr).group(1))
     assert max_k == abi.NEAREST_MAX_K == 16
     want = [C.POINTER(abi.Bvh), C.c_void_p, C.c_int64, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
     assert abi.NEAREST_LEAVES_ARGTYPES == want and lib.SIGNATURES[NAME] == want
     assert hasattr(lib.load(), NAME), "libibvh.so exports " + NAME
-    src = _read("implicitbvh.jl_amd", "julia", "ImplicitBVHlibibvhExt.jl")
+    src = kit.julia_ccall(NAME, "nearest_leaves")
     assert int(re.search(r"const IBVH_NEAREST_MAX_K = (\d+)", src).group(1)) == max_k
-    m = re.search(r"\n(c_\w+)\([^)]*\) =\n\s*ccall\(\(:" + NAME + r", libibvh\), Cint,\s*\(([^)]*)\)", src)
-    assert m, "one ccall wrapper binds " + NAME
-    jl = {"Ptr{Cvoid}": C.c_void_p, "Int64": C.c_int64, "Int32": C.c_int32, "Ref{IbvhBvh}": C.POINTER(abi.Bvh)}
-    assert [jl[a.strip()] for a in m.group(2).split(",")] == want
-    assert m.group(1) + "(" in src[src.index("function nearest_leaves("):]
-    assert "function ImplicitBVH.nearest_leaves" not in src
-    for doc in ("INTEGRATION.md", "README.md", "DESIGN.md"):
-        assert NAME in _read(doc), doc
 
 
 def test_makefile_launch_and_python_surface():
     for name in ("nearest_leaves", "NearestLeaves"):
         assert name in ibvh.__all__ and callable(getattr(ibvh, name))
-    mk = _read("implicitbvh.jl_amd", "csrc", "Makefile")
-    assert "ibvh_nearest.hip" in mk[mk.index("SRCS"):mk.index("OBJS")] and "-ffp-contract=off" in mk
-    src = _read("implicitbvh.jl_amd", "csrc", "ibvh_nearest.hip")
-    launches = re.findall(r"IBVH_LAUNCH\(\((nearest::\w+)<", src)
-    assert launches == ["nearest::nearest_walk_kernel"], "ONE launch, through the profiling wrapper"
-    # (the walk the kernel calls lives in ibvh_pointwalk.hpp: the same holds for it)
-    for text in (src, _read("implicitbvh.jl_amd", "csrc", "ibvh_pointwalk.hpp")):
-        assert "hipLaunchKernelGGL" not in text and "<<<" not in text
-        assert "atomic" not in text and "hipStreamSynchronize" not in text and "hipDeviceSynchronize" not in text and "hipMemcpy" not in text
+    # the walk, its block size and grid and the prologue are the shared ones; no mesh: no gather, no flag, its own dispatch
+    src = kit.query_unit("ibvh_nearest.hip", "nearest::nearest_walk_kernel", mesh=False)
+    assert "pointwalk::hopeless(p, max_d2)" in src and "pointwalk::radius_or_inf<T>(max_distance2)" in src
+    assert "-ffp-contract=off" in kit.read("implicitbvh.jl_amd", "csrc", "Makefile")
+    for text in (src, kit.read("implicitbvh.jl_amd", "csrc", "ibvh_pointwalk.hpp")):
         assert "fp-contract" not in text and "fma(" not in text   # the Makefile's -ffp-contract=off holds for this file
-
-
-def _fake_bvh(leaf_kind=abi.BSPHERE, leaf_float=abi.F32, node_kind=abi.BBOX, node_float=abi.F32, idx=abi.I32, morton=abi.U32, n=5,
-              built_level=1, leaves=64, nodes=64):
-    """a hand-filled ibvh_bvh over fake non-NULL pointers: never dereferenced"""
-    b = abi.Bvh()
-    b.types = abi.make_types(leaf_kind, leaf_float, node_kind, node_float, idx, morton)
-    lib.call("ibvh_tree_shape", n, C.byref(b.tree))
-    b.built_level, b.leaves, b.nodes, b.skips = built_level, leaves, nodes, 64
-    return b
 
 
 def test_entry_point_validates_its_arguments_before_any_launch():

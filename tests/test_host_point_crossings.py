@@ -7,8 +7,6 @@ guard on a triangle's box implies the guard on every enclosing box, and the GPU 
 brute force alone.  No GPU."""
 import ctypes as C
 import functools
-import os
-import re
 
 import numpy as np
 import pytest
@@ -17,28 +15,18 @@ import implicitbvh_amd as ibvh
 from implicitbvh_amd import abi, lib
 from implicitbvh_amd.synthetic import torus_mesh
 
+import mesh_query_kit as kit
 import point_crossings_checker as pcc
+from mesh_query_kit import MESHES
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 NAME = "ibvh_point_crossings"
-MESHES = {"torus40": (40, 40), "torus64x63": (64, 63)}
-
-
-def _read(*parts):
-    return open(os.path.join(ROOT, *parts)).read()
+_fake_bvh = functools.partial(kit.fake_bvh, leaf_kind=abi.BBOX)
 
 
 def test_header_declares_the_entry_point_under_abi_version_7():
-    raw = _read("include", "ibvh.h")
-    hdr = re.sub(r"/\*.*?\*/", "", raw, flags=re.S)
-    m = re.search(r"ibvh_status\s+" + NAME + r"\s*\(([^)]*)\)\s*;", hdr)
-    assert m, "include/ibvh.h declares " + NAME
-    args = [" ".join(a.split()) for a in m.group(1).split(",")]
+    raw, hdr, args, note = kit.header_prototype(NAME)
     assert args == ["const ibvh_bvh *bvh", "const void *triangles", "int64_t num_triangles", "const void *points", "int64_t num_points",
                     "int32_t axis", "void *crossings", "void *winding", "void *flag", "void *stream"]
-    assert int(re.search(r"#define IBVH_ABI_VERSION (\d+)", hdr).group(1)) == 7 == abi.ABI_VERSION
-    assert lib.load().ibvh_abi_version() == 7
-    note = raw[raw.index("Bumped whenever"):raw.index("#define IBVH_ABI_VERSION")]
     assert NAME in note and note.count("additive") >= 4
     # the doc comment carries the contract: the cyclic coordinates, the four rules, why it is watertight and lossless, the limits
     doc = raw[raw.index("inside / outside: the triangles an axis ray from a query point crosses"):raw.index("ibvh_status " + NAME)]
@@ -60,52 +48,22 @@ def test_binding_table_makefile_launch_and_python_surface():
     assert hasattr(lib.load(), NAME), "libibvh.so exports " + NAME
     for name in ("point_crossings", "PointCrossings", "points_inside", "signed_distance"):
         assert name in ibvh.__all__ and callable(getattr(ibvh, name))
-    mk = _read("implicitbvh.jl_amd", "csrc", "Makefile")
-    assert "ibvh_crossings.hip" in mk[mk.index("SRCS"):mk.index("OBJS")]
-    src = _read("implicitbvh.jl_amd", "csrc", "ibvh_crossings.hip")
-    launches = re.findall(r"IBVH_LAUNCH\(\((crossings::\w+)<", src)
-    assert launches == ["crossings::crossings_walk_kernel"] and src.count("IBVH_LAUNCH(") == 1, "ONE launch, through the profiling wrapper"
-    assert src.count("IBVH_LAUNCH_CHECK()") == 1
-    assert "hipLaunchKernelGGL" not in src and "<<<" not in src
-    for banned in ("atomic", "hipMemcpy", "hipStreamSynchronize", "hipDeviceSynchronize", "hipEventSynchronize", "__shared__", "hipMalloc"):
-        assert banned not in src, banned
-    # the walk is the shared one, with the shared block size and grid; the flag goes through the shared raise_flag
-    assert re.search(r'^#include "ibvh_pointwalk.hpp"$', src, flags=re.M) and "pointwalk::walk<" in src
-    assert "pointwalk::kBlock" in src and "pointwalk::grid_blocks" in src and not re.search(r"\bkBlock\s*=", src)
-    assert "__builtin_clzll" not in src and "box_bound" not in src
-    assert "pointwalk::tree_ok" in src and "pointwalk::box_nodes_hold_leaves" in src
-    assert "raise_flag(flag, 2u)" in src and "void raise_flag(" not in src
-    # three (T, TN) instantiations times two index types, not times three axes
-    assert len(re.findall(r"\blaunch\(Tag<", src)) == 3 and "dispatch_index" in src and "template <class T, class TN, class I>" in src
+    # the walk, its block size and grid, the prologue, the dispatch and the flag are the shared ones
+    src = kit.query_unit("ibvh_crossings.hip", "crossings::crossings_walk_kernel", own_gather=True)
+    assert "box_bound" not in src
+    # three (T, TN) instantiations times two index types — the shared dispatch —, not times three axes
+    assert "template <class T, class TN, class I>" in src and "int u, int v" in src
 
 
 def test_julia_wrapper_binds_it_with_the_ctypes_signature_and_the_docs_name_it():
-    src = _read("implicitbvh.jl_amd", "julia", "ImplicitBVHlibibvhExt.jl")
-    m = re.search(r"\n(c_\w+)\([^)]*\) =\n\s*ccall\(\(:" + NAME + r", libibvh\), Cint,\s*\(([^)]*)\)", src)
-    assert m, "one ccall wrapper binds " + NAME
-    assert src.count(":" + NAME + ",") == 1
-    jl = {"Ptr{Cvoid}": C.c_void_p, "Int64": C.c_int64, "Int32": C.c_int32, "Ref{IbvhBvh}": C.POINTER(abi.Bvh)}
-    assert [jl[a.strip()] for a in m.group(2).split(",")] == lib.SIGNATURES[NAME]
-    assert m.group(1) + "(" in src[src.index("function point_crossings("):]
+    src = kit.julia_ccall(NAME, "point_crossings")
     assert "point_crossings(" in src[src.index("function points_inside("):]
-    assert "function ImplicitBVH.point_crossings" not in src and "function ImplicitBVH.points_inside" not in src
-    for doc in ("INTEGRATION.md", "README.md", "DESIGN.md"):
-        assert NAME in _read(doc), doc
-    design = _read("DESIGN.md")
+    assert "function ImplicitBVH.points_inside" not in src
+    design = kit.read("DESIGN.md")
     section = design[design.index("Inside / outside of a closed mesh"):][:6000]
     for phrase in ("no reference counterpart", "lossless", "canonical", "watertight", "ambiguous", "T-junctions", "VGPRs", "scratch"):
         assert phrase in section, phrase
-    assert os.path.exists(os.path.join(ROOT, "tools", "bench_inside.py"))
-
-
-def _fake_bvh(leaf_kind=abi.BBOX, leaf_float=abi.F32, node_kind=abi.BBOX, node_float=abi.F32, idx=abi.I32, n=5, built_level=1,
-              leaves=64, nodes=64):
-    """a hand-filled ibvh_bvh over fake non-NULL pointers: never dereferenced"""
-    b = abi.Bvh()
-    b.types = abi.make_types(leaf_kind, leaf_float, node_kind, node_float, idx)
-    lib.call("ibvh_tree_shape", n, C.byref(b.tree))
-    b.built_level, b.leaves, b.nodes, b.skips = built_level, leaves, nodes, 64
-    return b
+    assert kit.read("tools", "bench_inside.py")
 
 
 def test_entry_point_validates_its_arguments_before_any_launch():

@@ -7,7 +7,6 @@ and an admitted box has admitted enclosing boxes (what makes pruning lossless), 
 active on an axis-aligned floor, and the GPU test's non-vacuity conditions hold for the brute force alone.  No GPU."""
 import ctypes as C
 import functools
-import os
 import re
 
 import numpy as np
@@ -17,31 +16,21 @@ import implicitbvh_amd as ibvh
 from implicitbvh_amd import abi, lib
 from implicitbvh_amd.synthetic import torus_mesh
 
+import mesh_query_kit as kit
 import ray_cast_checker as rcc
+from mesh_query_kit import MESHES
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 NAME = "ibvh_cast_rays"
-MESHES = {"torus40": (40, 40), "torus64x63": (64, 63)}
-
-
-def _read(*parts):
-    return open(os.path.join(ROOT, *parts)).read()
+_fake_bvh = functools.partial(kit.fake_bvh, leaf_kind=abi.BBOX)
 
 
 def test_header_declares_the_entry_point_under_abi_version_7():
-    raw = _read("include", "ibvh.h")
-    hdr = re.sub(r"/\*.*?\*/", "", raw, flags=re.S)
-    m = re.search(r"ibvh_status\s+" + NAME + r"\s*\(([^)]*)\)\s*;", hdr)
-    assert m, "include/ibvh.h declares " + NAME
-    args = [" ".join(a.split()) for a in m.group(1).split(",")]
+    raw, hdr, args, note = kit.header_prototype(NAME)
     assert args == ["const ibvh_bvh *bvh", "const void *triangles", "int64_t num_triangles", "const void *points", "const void *directions",
                     "int64_t num_rays", "const void *t_max", "int32_t mode", "void *hit_index", "void *hit_t", "void *hit_uv",
                     "void *occluded", "void *flag", "void *stream"]
     assert re.search(r"enum\s*\{\s*IBVH_CAST_CLOSEST = 0,\s*IBVH_CAST_ANY = 1\s*\};", hdr)
     assert (abi.CAST_CLOSEST, abi.CAST_ANY) == (0, 1)
-    assert int(re.search(r"#define IBVH_ABI_VERSION (\d+)", hdr).group(1)) == 7 == abi.ABI_VERSION
-    assert lib.load().ibvh_abi_version() == 7
-    note = raw[raw.index("Bumped whenever"):raw.index("#define IBVH_ABI_VERSION")]
     flat = " ".join(note.replace("*", " ").split())
     assert NAME + " and IBVH_CAST_CLOSEST / IBVH_CAST_ANY (additive under 7 in the same way)" in flat
     assert flat.count("additive under 7 in the same way") == 4 and note.count("additive") >= 5
@@ -67,59 +56,29 @@ def test_binding_table_makefile_launch_and_python_surface():
     assert hasattr(lib.load(), NAME), "libibvh.so exports " + NAME
     for name in ("cast_rays", "RayCast"):
         assert name in ibvh.__all__ and callable(getattr(ibvh, name))
-    mk = _read("implicitbvh.jl_amd", "csrc", "Makefile")
-    assert "ibvh_cast.hip" in mk[mk.index("SRCS"):mk.index("OBJS")]
-    src = _read("implicitbvh.jl_amd", "csrc", "ibvh_cast.hip")
-    launches = re.findall(r"IBVH_LAUNCH\(\((cast::\w+)<", src)
-    assert launches == ["cast::cast_walk_kernel"] and src.count("IBVH_LAUNCH(") == 1, "ONE launch, through the profiling wrapper"
-    assert src.count("IBVH_LAUNCH_CHECK()") == 1
-    assert "hipLaunchKernelGGL" not in src and "<<<" not in src
-    for banned in ("atomic", "hipMemcpy", "hipStreamSynchronize", "hipDeviceSynchronize", "hipEventSynchronize", "__shared__", "hipMalloc"):
-        assert banned not in src, banned
-    # the walk is the shared one, with the shared block size and grid; the flag goes through the shared raise_flag
-    assert re.search(r'^#include "ibvh_pointwalk.hpp"$', src, flags=re.M) and src.count("pointwalk::walk<") == 2  # (one per mode)
-    assert "pointwalk::kBlock" in src and "pointwalk::grid_blocks" in src and not re.search(r"\bkBlock\s*=\s*\d", src)
-    assert "__builtin_clzll" not in src and "box_bound" not in src
-    assert "pointwalk::tree_ok" in src and "pointwalk::box_nodes_hold_leaves" in src
-    assert "raise_flag(flag, 2u)" in src and "void raise_flag(" not in src
+    # the walk (one call per mode), its block size and grid, the prologue, the gather and the flag are the shared ones
+    src = kit.query_unit("ibvh_cast.hip", "cast::cast_walk_kernel", walks=2)
+    assert "box_bound" not in src
     # the exact test is the shared one: defined once, in the header both translation units include
-    shared = _read("implicitbvh.jl_amd", "csrc", "ibvh_raytest.hpp")
-    resolve = _read("implicitbvh.jl_amd", "csrc", "ibvh_raytri.hip")
+    shared = kit.read("implicitbvh.jl_amd", "csrc", "ibvh_raytest.hpp")
+    resolve = kit.read("implicitbvh.jl_amd", "csrc", "ibvh_raytri.hip")
     define = r"\bbool ray_triangle\s*\("
     assert len(re.findall(define, shared)) == 1 and not re.search(define, src) and not re.search(define, resolve)
     for unit in (src, resolve):
         assert re.search(r'^#include "ibvh_raytest.hpp"$', unit, flags=re.M) and "ray_triangle(tr, p, d, t, u, v)" in unit
         assert "void cross3(" not in unit and "1) / det" not in unit
-    # three (T, TN) instantiations times two index types times the two modes
-    assert len(re.findall(r"\bmodes\(Tag<", src)) == 3 and "dispatch_index" in src and "template <class T, class TN, class I, bool ANY>" in src
+    # three (T, TN) instantiations times two index types — the shared dispatch — times the two modes
+    assert "pointwalk::dispatch_box_types(bvh->types, modes)" in src and "template <class T, class TN, class I, bool ANY>" in src
+    assert "any ? launch(ft, nt, it, std::true_type{}) : launch(ft, nt, it, std::false_type{})" in src
 
 
 def test_julia_wrapper_binds_it_with_the_ctypes_signature_and_the_docs_name_it():
-    src = _read("implicitbvh.jl_amd", "julia", "ImplicitBVHlibibvhExt.jl")
-    m = re.search(r"\n(c_\w+)\([^)]*\) =\n\s*ccall\(\(:" + NAME + r", libibvh\), Cint,\s*\(([^)]*)\)", src)
-    assert m, "one ccall wrapper binds " + NAME
-    assert src.count(":" + NAME + ",") == 1
-    jl = {"Ptr{Cvoid}": C.c_void_p, "Int64": C.c_int64, "Int32": C.c_int32, "Ref{IbvhBvh}": C.POINTER(abi.Bvh)}
-    assert [jl[a.strip()] for a in m.group(2).split(",")] == lib.SIGNATURES[NAME]
-    assert m.group(1) + "(" in src[src.index("function cast_rays("):]
-    assert "function ImplicitBVH.cast_rays" not in src
-    for doc in ("INTEGRATION.md", "README.md", "DESIGN.md"):
-        assert NAME in _read(doc), doc
-    design = _read("DESIGN.md")
+    kit.julia_ccall(NAME, "cast_rays")
+    design = kit.read("DESIGN.md")
     section = design[design.index("Ray cast"):][:8000]
     for phrase in ("no reference counterpart", "lossless", "clamp", "shared edge", "VGPRs", "scratch"):
         assert phrase in section, phrase
-    assert os.path.exists(os.path.join(ROOT, "tools", "bench_cast.py"))
-
-
-def _fake_bvh(leaf_kind=abi.BBOX, leaf_float=abi.F32, node_kind=abi.BBOX, node_float=abi.F32, idx=abi.I32, n=5, built_level=1,
-              leaves=64, nodes=64):
-    """a hand-filled ibvh_bvh over fake non-NULL pointers: never dereferenced"""
-    b = abi.Bvh()
-    b.types = abi.make_types(leaf_kind, leaf_float, node_kind, node_float, idx)
-    lib.call("ibvh_tree_shape", n, C.byref(b.tree))
-    b.built_level, b.leaves, b.nodes, b.skips = built_level, leaves, nodes, 64
-    return b
+    assert kit.read("tools", "bench_cast.py")
 
 
 def test_entry_point_validates_its_arguments_before_any_launch():
