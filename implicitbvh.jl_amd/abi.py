@@ -80,6 +80,11 @@ POINT_CROSSINGS_ARGTYPES = [C.POINTER(Bvh), C.c_void_p, C.c_int64, C.c_void_p, C
 #                flag, stream)
 CAST_CLOSEST, CAST_ANY = 0, 1
 CAST_RAYS_ARGTYPES = [C.POINTER(Bvh), C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p, C.c_int32] + [C.c_void_p] * 6
+# ibvh_sphere_contacts(bvh, triangles, num_triangles, centers, radii, num_spheres, mode, counts, offsets, capacity,
+#                      contact_index, contact_d2, contact_point, contact_region, flag, stream)
+SPHERES_COUNT, SPHERES_WRITE = 0, 1
+SPHERE_CONTACTS_ARGTYPES = ([C.POINTER(Bvh), C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p, C.c_int64, C.c_int32, C.c_void_p, C.c_void_p,
+                             C.c_int64] + [C.c_void_p] * 6)
 
 
 class BuildDesc(C.Structure):

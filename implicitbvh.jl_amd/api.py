@@ -32,7 +32,7 @@ __all__ = [
     "NARROW_MORTON_LT", "NARROW_INDEX_LT", "NARROW_RAY_ORIGIN_OUTSIDE", "LeafBatch", "lvt_work_counters", "refit",
     "resolve_triangles", "raycast", "RayHits", "closest_points", "ClosestPoints",
     "nearest_leaves", "NearestLeaves", "point_crossings", "PointCrossings", "points_inside", "signed_distance",
-    "cast_rays", "RayCast",
+    "cast_rays", "RayCast", "sphere_contacts", "SphereContacts",
 ]
 
 NARROW_MORTON_LT = abi.NARROW_MORTON_LT
@@ -1428,11 +1428,13 @@ def _mesh_query_setup(bvh, triangles, what):
 
 def _mesh_query_call(entry, what, bvh, tris, *args):
     """One mesh query on the current stream: entry(bvh, triangles, n, *args, flag, stream) with a fresh flag word, which is
-    read back afterwards (a synchronisation).  Bit 1 of it: a leaf named no row of `tris`."""
+    read back afterwards (a synchronisation) -> the flag word.  Bit 1 of it: a leaf named no row of `tris`."""
     flag = _torch().zeros(1, dtype=_torch().int32, device="cuda")
     lib.call(entry, C.byref(bvh.struct()), _ptr(tris), tris.shape[0], *args, _ptr(flag), _stream())
-    if int(flag.item()) & 2:
+    word = int(flag.item())
+    if word & 2:
         raise ValueError(f"{what}: a leaf's index lies outside 1..{tris.shape[0]} (the number of triangles given)")
+    return word
 
 
 def closest_points(bvh, triangles, points, max_distance=None, presorted=False):
@@ -1567,6 +1569,86 @@ def cast_rays(bvh, triangles, points, directions, t_max=None, any_hit=False, pre
     if any_hit:
         return _unpermute(order, (outs[3],))[0] != 0
     return RayCast(*_unpermute(order, outs[:3]))
+
+
+# ---------------------------------------------------------------------------------------------
+# sphere-vs-mesh contacts: every triangle within each sphere's radius (ibvh_sphere_contacts; no reference counterpart)
+# ---------------------------------------------------------------------------------------------
+class SphereContacts:
+    """The contacts of N spheres with a mesh, M in all, grouped by sphere in the caller's order and, within a sphere, in the
+    order of the triangles' leaves in the BVH: sphere s (0-based) owns rows offsets[s] : offsets[s + 1].
+    .offsets (N + 1,) int64, .counts (N,) int64; per contact .index (M,) the triangle's user index, .distance2 (M,) the
+    SQUARED distance, .point (M, 3) the closest point on the triangle, .region (M,) uint8 the feature that point lies on
+    (0 vertex p1, 1 vertex p2, 2 edge p1p2, 3 vertex p3, 4 edge p1p3, 5 edge p2p3, 6 face) and .sphere (M,) the 1-based
+    number of the sphere the row belongs to (computed when first asked for).  After count_only=True the per-contact
+    fields are None."""
+
+    def __init__(self, offsets, index=None, distance2=None, point=None, region=None):
+        self.offsets, self.index, self.distance2, self.point, self.region = offsets, index, distance2, point, region
+        self.counts = offsets[1:] - offsets[:-1]
+        self._sphere = None
+
+    @property
+    def sphere(self):
+        if self._sphere is None and self.index is not None:
+            torch = _torch()
+            ids = torch.arange(1, self.counts.shape[0] + 1, dtype=torch.int64, device=self.counts.device)
+            self._sphere = torch.repeat_interleave(ids, self.counts, output_size=int(self.index.shape[0]))
+        return self._sphere
+
+
+def sphere_contacts(bvh, triangles, centers, radii, count_only=False, presorted=False):
+    """For every sphere ALL triangles of the mesh `bvh` was built over that lie within its radius of its centre, with the
+    squared distance, the closest point and the feature touched -> SphereContacts (include/ibvh.h, ibvh_sphere_contacts: the
+    arithmetic — that of closest_points —, the order and why pruning loses nothing are spelled out there).  Two launches, a
+    count and a write, around a scan of the counts here; exact: bit-equal to a brute force over all triangles.
+
+    bvh: BBox leaves made from `triangles` (bounding_volumes_from_triangles(triangles, BBox(dtype)); a skin margin and
+    refit are fine) under BBox nodes of the same or a wider float type.  triangles: (n, 9) / (n, 3, 3) CUDA tensor of the
+    leaves' dtype, user index k = row k - 1.  centers: (3, N) CUDA tensor of that dtype, as for traverse_rays.  radii: an
+    (N,) CUDA tensor of that dtype, or one number for all (a radius search around points).  A triangle is a contact iff its
+    squared distance <= r * r, squared in that dtype; a negative or NaN radius and a NaN centre touch nothing.
+    count_only=True stops after the first pass.  The device walks the batch in Morton order of the centres (lanes of a wave
+    then share nodes) and writes each sphere's rows where the caller's order wants them; presorted=True walks it as given.
+    The total is read on the host between the passes, as in traverse.
+
+    ValueError: sphere leaves or nodes, nodes narrower than the leaves, a wrong dtype, device or shape of triangles, centers
+    or radii, and a leaf whose index lies outside 1..n (flag bit 1; such leaves are skipped)."""
+    torch = _require_gpu()
+    what = "sphere_contacts"
+    tris, ft, idt = _mesh_query_setup(bvh, triangles, what)
+    p, n, _, order = _query_points(centers, ft, None, presorted, what)
+    if isinstance(radii, torch.Tensor):
+        if tuple(radii.shape) != (n,) or radii.dtype != ft or not radii.is_cuda:
+            raise ValueError(f"{what}: radii must be a number or an (N,) {ft} tensor on the GPU")
+        r = radii.contiguous()
+    elif isinstance(radii, (int, float, np.integer, np.floating)) and not isinstance(radii, bool):
+        r = torch.full((n,), float(radii), dtype=ft, device="cuda")
+    else:
+        raise ValueError(f"{what}: radii must be a number or an (N,) {ft} tensor on the GPU")
+    offsets = torch.zeros(n + 1, dtype=torch.int64, device="cuda")
+    empty = lambda m: (torch.empty(m, dtype=idt, device="cuda"), torch.empty(m, dtype=ft, device="cuda"),
+                       torch.empty((m, 3), dtype=ft, device="cuda"), torch.empty(m, dtype=torch.uint8, device="cuda"))
+    if n == 0:
+        return SphereContacts(offsets, *(() if count_only else empty(0)))
+    if order is not None:
+        r = r[order]
+    walked = torch.empty(n, dtype=torch.int64, device="cuda")
+    _mesh_query_call("ibvh_sphere_contacts", what, bvh, tris, _ptr(p), _ptr(r), n, abi.SPHERES_COUNT, _ptr(walked), None, 0,
+                     None, None, None, None)
+    # the counts back in the caller's order, scanned there: a sphere's rows then follow its predecessor's in that order
+    torch.cumsum(_unpermute(order, (walked,))[0], dim=0, out=offsets[1:])
+    if count_only:
+        return SphereContacts(offsets)
+    total = int(offsets[-1].item())  # the one read between the passes
+    outs = empty(total)
+    if total > 0:
+        first = offsets[:-1] if order is None else offsets[:-1][order]  # ... gathered back into walk order
+        word = _mesh_query_call("ibvh_sphere_contacts", what, bvh, tris, _ptr(p), _ptr(r), n, abi.SPHERES_WRITE, None,
+                                _ptr(first), total, *[_ptr(o) for o in outs])
+        if word & 4:
+            raise RuntimeError(f"{what}: the write pass found more contacts than the count pass (inputs changed between them?)")
+    return SphereContacts(offsets, *outs)
 
 
 # ---------------------------------------------------------------------------------------------

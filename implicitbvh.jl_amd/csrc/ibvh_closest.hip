@@ -10,6 +10,7 @@
 //
 // The walk itself — work mapping, near child first, the trail word, the pop, the strict skip — is ibvh_pointwalk.hpp's.
 #include "ibvh_pointwalk.hpp"
+#include "ibvh_pointtri.hpp"
 
 #include <limits>
 
@@ -18,57 +19,7 @@ namespace closest {
 
 using pointwalk::kBlock;
 
-template <class T> IBVH_D T dot3(const T *x, const T *y) { return (x[0] * y[0] + x[1] * y[1]) + x[2] * y[2]; }
-
-// Ericson's region walk (Real-Time Collision Detection 5.1.5), the first matching case decides; then q is clamped into the
-// triangle's exact box.  -ffp-contract=off: every operation is rounded once.
-template <class T> IBVH_D T closest_on_triangle(const T *tr, const T *p, T *q) {
-    const T *a = tr, *b = tr + 3, *c = tr + 6;
-    const T ab[3] = {b[0] - a[0], b[1] - a[1], b[2] - a[2]};
-    const T ac[3] = {c[0] - a[0], c[1] - a[1], c[2] - a[2]};
-    const T ap[3] = {p[0] - a[0], p[1] - a[1], p[2] - a[2]};
-    const T d1 = dot3(ab, ap), d2 = dot3(ac, ap);
-    const T bp[3] = {p[0] - b[0], p[1] - b[1], p[2] - b[2]};
-    const T d3 = dot3(ab, bp), d4 = dot3(ac, bp);
-    const T cp[3] = {p[0] - c[0], p[1] - c[1], p[2] - c[2]};
-    const T d5 = dot3(ab, cp), d6 = dot3(ac, cp);
-    const T vc = d1 * d4 - d3 * d2, vb = d5 * d2 - d1 * d6, va = d3 * d6 - d5 * d4;
-    if ((d1 <= T(0)) & (d2 <= T(0))) {
-#pragma unroll
-        for (int k = 0; k < 3; ++k) q[k] = a[k];
-    } else if ((d3 >= T(0)) & (d4 <= d3)) {
-#pragma unroll
-        for (int k = 0; k < 3; ++k) q[k] = b[k];
-    } else if ((vc <= T(0)) & (d1 >= T(0)) & (d3 <= T(0))) {
-        const T v = d1 / (d1 - d3);
-#pragma unroll
-        for (int k = 0; k < 3; ++k) q[k] = a[k] + v * ab[k];
-    } else if ((d6 >= T(0)) & (d5 <= d6)) {
-#pragma unroll
-        for (int k = 0; k < 3; ++k) q[k] = c[k];
-    } else if ((vb <= T(0)) & (d2 >= T(0)) & (d6 <= T(0))) {
-        const T w = d2 / (d2 - d6);
-#pragma unroll
-        for (int k = 0; k < 3; ++k) q[k] = a[k] + w * ac[k];
-    } else if ((va <= T(0)) & ((d4 - d3) >= T(0)) & ((d5 - d6) >= T(0))) {
-        const T w = (d4 - d3) / ((d4 - d3) + (d5 - d6));
-#pragma unroll
-        for (int k = 0; k < 3; ++k) q[k] = b[k] + w * (c[k] - b[k]);
-    } else {
-        const T den = T(1) / ((va + vb) + vc);
-        const T v = vb * den, w = vc * den;
-#pragma unroll
-        for (int k = 0; k < 3; ++k) q[k] = (a[k] + v * ab[k]) + w * ac[k];
-    }
-    T e[3];
-#pragma unroll
-    for (int k = 0; k < 3; ++k) {
-        const T lo = minimum3(a[k], b[k], c[k]), up = maximum3(a[k], b[k], c[k]); // bbox_from_triangle
-        q[k] = q[k] < lo ? lo : (q[k] > up ? up : q[k]);                            // (NaN stays NaN)
-        e[k] = p[k] - q[k];
-    }
-    return (e[0] * e[0] + e[1] * e[1]) + e[2] * e[2];
-}
+using pointtri::closest_on_triangle; // the evaluation of include/ibvh.h: ibvh_pointtri.hpp, shared with ibvh_spheres.hip
 
 // T: the leaves' and triangles' float type; TN: the nodes' (the same or wider — a node box then holds values of T, widened
 // exactly, and narrows back exactly)
@@ -88,8 +39,9 @@ __global__ __launch_bounds__(kBlock) void closest_walk_kernel(TreeDev tree, int 
         auto visit = [&](const char *rec) {
             I index;
             T tr[9], q[3];
+            int region; // (not part of this query's answer)
             if (pointwalk::leaf_triangle(rec, lay, tris, num_triangles, index, tr)) {
-                const T d2 = closest_on_triangle(tr, p, q);
+                const T d2 = closest_on_triangle(tr, p, q, region);
                 // (d2, index) lexicographically; the first one only has to be within the radius (best == max_d2)
                 if ((d2 < best) | ((d2 == best) & ((best_index == 0) | (index < best_index)))) {
                     best = d2;

@@ -612,7 +612,9 @@ IBVH_D int lane_id() { return (int)__builtin_amdgcn_mbcnt_hi(~0u, __builtin_amdg
 
 // A caller's flag word (ibvh_rays_resolve_triangles, ibvh_closest_triangles) may be device memory or mapped pinned host
 // memory: a plain read and a plain store of one word, no read-modify-write instruction.  Correct as long as one launch
-// raises only ONE bit: racing raisers then store the same word.
+// raises only ONE bit: racing raisers then store the same word.  The one launch that can raise two — the write pass of
+// ibvh_sphere_contacts, bits 1 and 2 — may lose one of them to that race and promises only that at least one is set
+// (include/ibvh.h); its bit 1 is already known from the count pass, which raises nothing else.
 IBVH_D void raise_flag(uint32_t *flag, uint32_t bit) {
     const uint32_t old = __hip_atomic_load(flag, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);
     if (!(old & bit)) __hip_atomic_store(flag, old | bit, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);

@@ -298,6 +298,10 @@ c_cast_rays(bvh, triangles, num_triangles, points, directions, num_rays, t_max, 
     ccall((:ibvh_cast_rays, libibvh), Cint,
           (Ref{IbvhBvh}, Ptr{Cvoid}, Int64, Ptr{Cvoid}, Ptr{Cvoid}, Int64, Ptr{Cvoid}, Int32, Ptr{Cvoid}, Ptr{Cvoid}, Ptr{Cvoid}, Ptr{Cvoid}, Ptr{Cvoid}, Ptr{Cvoid}),
           bvh, triangles, num_triangles, points, directions, num_rays, t_max, mode, hit_index, hit_t, hit_uv, occluded, flag, stream)
+c_sphere_contacts(bvh, triangles, num_triangles, centers, radii, num_spheres, mode, counts, offsets, capacity, contact_index, contact_d2, contact_point, contact_region, flag, stream) =
+    ccall((:ibvh_sphere_contacts, libibvh), Cint,
+          (Ref{IbvhBvh}, Ptr{Cvoid}, Int64, Ptr{Cvoid}, Ptr{Cvoid}, Int64, Int32, Ptr{Cvoid}, Ptr{Cvoid}, Int64, Ptr{Cvoid}, Ptr{Cvoid}, Ptr{Cvoid}, Ptr{Cvoid}, Ptr{Cvoid}, Ptr{Cvoid}),
+          bvh, triangles, num_triangles, centers, radii, num_spheres, mode, counts, offsets, capacity, contact_index, contact_d2, contact_point, contact_region, flag, stream)
 c_lvt_scratch_bytes(types, n_items, cache_slots, out) =
     ccall((:ibvh_lvt_scratch_bytes, libibvh), Cint,
           (Ref{IbvhTypes}, Int64, Int32, Ref{Csize_t}),
@@ -788,6 +792,71 @@ function cast_rays(bvh::RocBVH{I}, triangles::ROCMatrix{T}, points::ROCMatrix{T}
         any_hit ? (occluded = occluded[inv]) : ((index, t, uv) = (index[inv], t[inv], uv[:, inv]))
     end
     any_hit ? (occluded .!= 0x00) : (; index, t, uv, hit=index .!= 0)
+end
+
+# ---- sphere-vs-mesh contacts: every triangle within each sphere's radius (include/ibvh.h, ibvh_sphere_contacts) ------
+const IBVH_SPHERES_COUNT = Int32(0)
+const IBVH_SPHERES_WRITE = Int32(1)
+"""
+    sphere_contacts(bvh::BVH, triangles::ROCMatrix{T}, centers::ROCMatrix{T}, radii; count_only=false, presorted=false)
+        -> (; offsets, counts, index, distance2, point, region)
+
+For every sphere (column of the 3 x N `centers`, `radii[i]`; or one number for all: a radius search around points) ALL
+triangles of the mesh `bvh` was built over that lie within the radius of the centre.  Sphere `i` owns rows
+`offsets[i] + 1 : offsets[i + 1]` of the per-contact outputs: `index` the triangle's user index, `distance2` the squared
+distance, `point[:, j]` the closest point on it, `region[j]` the feature that point lies on (0 vertex p1, 1 vertex p2,
+2 edge p1p2, 3 vertex p3, 4 edge p1p3, 5 edge p2p3, 6 face).  Within a sphere the rows follow the order of the triangles' leaves
+in `bvh.leaves`.  A triangle is a contact iff its squared distance <= r * r (squared in `T`); a negative or NaN radius and a
+NaN centre touch nothing.  Bit-equal to a brute force over all triangles; the arithmetic — that of `closest_points` —, the
+order and why pruning loses nothing are spelled out in include/ibvh.h.  Two launches, a count and a write, around a `cumsum`
+of the counts on the device array; the total is read on the host between them.  `count_only=true` stops after the first
+(the per-contact outputs are `nothing`).  `triangles` is 9 x n (column k = p1 p2 p3 of the triangle with user index k).  The
+BVH must have `BBox{T}` leaves made from the triangles (a skin margin and `refit!` are fine) under `BBox` nodes of `T` or
+wider; anything else raises ArgumentError.  The device walks the batch along a Morton curve through the centres and writes
+each sphere's rows where the caller's order wants them; `presorted=true` walks it as given.  Not a method of ImplicitBVH:
+the reference has no such query.
+"""
+function sphere_contacts(bvh::RocBVH{I}, triangles::ROCMatrix{T}, centers::ROCMatrix{T}, radii::Union{Real, ROCVector{T}};
+                         count_only::Bool=false, presorted::Bool=false) where {I, T}
+    d = bvh_desc(bvh)
+    isnothing(d) && throw(ArgumentError("sphere_contacts: no libibvh instantiation for this BVH's types"))
+    leaf_volume_type(bvh.leaves) === BBox{T} && eltype(bvh.nodes) <: BBox && sizeof(eltype(bvh.nodes)) >= sizeof(BBox{T}) ||
+        throw(ArgumentError("sphere_contacts: the BVH must have BBox{$T} leaves under BBox nodes of $T or wider"))
+    size(triangles, 1) == 9 || throw(ArgumentError("sphere_contacts: triangles must be 9 x n (p1 p2 p3 per column)"))
+    size(centers, 1) == 3 || throw(ArgumentError("size(centers, 1) == 3 must hold"))
+    n = size(centers, 2)
+    radii isa Real || length(radii) == n || throw(ArgumentError("sphere_contacts: length(radii) == size(centers, 2) must hold"))
+    r = radii isa Real ? fill!(similar(centers, T, n), T(radii)) : radii
+    offsets = fill!(similar(centers, Int64, n + 1), 0)
+    none(m) = (similar(centers, I, m), similar(centers, T, m), similar(centers, T, 3, m), similar(centers, UInt8, m))
+    if n == 0
+        index, distance2, point, region = count_only ? (nothing, nothing, nothing, nothing) : none(0)
+        return (; offsets, counts=similar(centers, Int64, 0), index, distance2, point, region)
+    end
+    order = presorted ? nothing : point_morton_order(centers)
+    perm = isnothing(order) ? nothing : ROCVector{Int64}(order)
+    c = isnothing(perm) ? centers : centers[:, perm]
+    rw = isnothing(perm) ? r : r[perm]
+    flag = scratch!(:spheres_flag, 4)
+    fill!(flag, 0x00)
+    walked = similar(centers, Int64, n)
+    nt = Int64(size(triangles, 2))
+    check(c_sphere_contacts(d, devptr(triangles), nt, devptr(c), devptr(rw), Int64(n), IBVH_SPHERES_COUNT, devptr(walked), C_NULL,
+                            Int64(0), C_NULL, C_NULL, C_NULL, C_NULL, devptr(flag), stream_ptr()), "ibvh_sphere_contacts")
+    Array(flag)[1] & 0x02 != 0 && throw(ArgumentError("sphere_contacts: a leaf's index lies outside 1:$nt"))
+    # the counts back in the caller's order, scanned there: a sphere's rows then follow its predecessor's in that order
+    counts = isnothing(perm) ? walked : walked[ROCVector{Int64}(invperm(order))]
+    offsets[2:end] .= cumsum(counts)
+    count_only && return (; offsets, counts, index=nothing, distance2=nothing, point=nothing, region=nothing)
+    total = Array(offsets[end:end])[1]                           # the one read between the passes
+    index, distance2, point, region = none(total)
+    total == 0 && return (; offsets, counts, index, distance2, point, region)
+    first_row = isnothing(perm) ? offsets[1:n] : offsets[1:n][perm]   # ... gathered back into walk order
+    check(c_sphere_contacts(d, devptr(triangles), nt, devptr(c), devptr(rw), Int64(n), IBVH_SPHERES_WRITE, C_NULL, devptr(first_row),
+                            Int64(total), devptr(index), devptr(distance2), devptr(point), devptr(region), devptr(flag), stream_ptr()),
+          "ibvh_sphere_contacts")
+    Array(flag)[1] & 0x04 != 0 && error("sphere_contacts: the write pass found more contacts than the count pass")
+    (; offsets, counts, index, distance2, point, region)
 end
 
 # ---- k nearest leaves for a batch of query points (include/ibvh.h, ibvh_nearest_leaves) ------------------------------

@@ -45,7 +45,8 @@ extern "C" {
  *      argument list moves, so a binding written against the earlier 7 keeps working); ibvh_closest_triangles (additive
  *      under 7 in the same way); ibvh_nearest_leaves and IBVH_NEAREST_MAX_K (additive under 7 in the same way);
  *      ibvh_point_crossings (additive under 7 in the same way); ibvh_cast_rays and IBVH_CAST_CLOSEST / IBVH_CAST_ANY
- *      (additive under 7 in the same way);
+ *      (additive under 7 in the same way); ibvh_sphere_contacts and IBVH_SPHERES_COUNT / IBVH_SPHERES_WRITE (additive
+ *      under 7 likewise: one more entry point);
  *      argument checks only, no layout or argument list moves: ibvh_key_histogram takes
  *      what fits its LDS staging (10 rows at 12-bit digits) and refuses shift > 63 and a negative prefix_shift,
  *      ibvh_pack_records / ibvh_dist_plan answer IBVH_ERR_OVERFLOW for an index past IBVH_I32 */
@@ -685,6 +686,78 @@ ibvh_status ibvh_cast_rays(const ibvh_bvh *bvh, const void *triangles, int64_t n
                            const void *t_max, int32_t mode,
                            void *hit_index, void *hit_t, void *hit_uv, void *occluded,
                            void *flag, void *stream);
+
+/* ----------------------------------------------------------------------------------- */
+/* sphere-vs-mesh contacts: every triangle within each sphere's radius                  */
+/* ----------------------------------------------------------------------------------- */
+/* For every sphere (centre c, radius r): ALL triangles of the mesh the BVH was built over (ibvh_volumes_from_triangles with
+ * IBVH_BBOX) that lie within r of c — which ones, the squared distance, the closest point on each and the FEATURE of the
+ * triangle that point lies on.  The narrow phase of sphere-vs-mesh contact (a particle in a corner touches several
+ * triangles; the feature lets the caller count a shared edge or vertex once), and with one radius for all a radius search
+ * around points.  No reference counterpart (the reference's traversal of spheres against a mesh ends at pairs of a sphere
+ * and a triangle's BOX); a variable-length answer in TWO calls of ONE launch each — count, the caller's scan, write — with
+ * NO host synchronisation inside either, no LDS, no scratch buffer, no read-modify-write of memory.
+ *   triangles  : num_triangles x 9 values (p1 p2 p3) of bvh->types.leaf_float, `flt` below; user index k is row k - 1
+ *   centers    : num_spheres x 3 row-major values of `flt`, processed in the order given (neighbours in memory that are
+ *                neighbours in space walk the same nodes: sort a scattered batch along a Morton curve first)
+ *   radii      : num_spheres values of `flt`, one per sphere
+ *   mode       : IBVH_SPHERES_COUNT or IBVH_SPHERES_WRITE
+ * IBVH_SPHERES_COUNT, the first pass:
+ *   counts     : num_spheres x int64 (whatever the index type), required; counts[s] = the number of contacts of sphere s.
+ *                Nothing of `offsets` or the contact_* arrays is read or written: they may be NULL.
+ * Between the passes the caller scans: offsets = ANY exclusive prefix sum of counts (its last element plus the last count
+ *   is the number of rows the outputs need).  The scan is the caller's — hipCUB, torch.cumsum, Julia's accumulate — the
+ *   library's own scan is private to the leaf-vs-tree scratch protocol.
+ * IBVH_SPHERES_WRITE, the second pass, with the SAME bvh, triangles, centers and radii:
+ *   offsets    : num_spheres x int64, required; contact j of sphere s goes to row offsets[s] + j.  They need NOT be monotone
+ *                (a batch walked in Morton order may write its lists in the caller's order); `counts` is not read.
+ *   capacity   : the number of rows every non-NULL contact_* array holds.  A row >= capacity or < 0 is never written and
+ *                sets bit 2 of `flag` (value 4) instead: a wrong `offsets` array cannot write outside the caller's buffers.
+ *                The guard is per ROW, not per sphere: with offsets[s] = -1 contact 0 of sphere s is refused and its
+ *                contacts 1, 2, ... are written to rows 0, 1, ...
+ *   contact_index  : capacity x I, the triangle's user index
+ *   contact_d2     : capacity x flt, its squared distance d2
+ *   contact_point  : capacity x 3 x flt, the closest point q on it
+ *   contact_region : capacity x uint8, the feature q lies on: the case of the region walk that decided —
+ *                    0 vertex a, 1 vertex b, 2 edge ab, 3 vertex c, 4 edge ac, 5 edge bc, 6 face  (a = p1, b = p2, c = p3)
+ *   each optional, at least one non-NULL; what was not asked for is not written.
+ * All arguments are validated before any launch: NULL bvh or required pointers, negative sizes or capacity, an unknown mode,
+ * no `counts` in the count pass, no `offsets` or no output at all in the write pass, a tree shape that is not an
+ * ImplicitTree's: IBVH_ERR_INVALID_ARG.  num_spheres == 0: IBVH_OK, nothing is touched.
+ * The result is defined independently of how it is found.  r2 = r * r, rounded once in `flt`.  The contacts of sphere s are
+ *   ALL triangles k with d2(k, c) <= r2, where d2, q and the deciding case are exactly the evaluation ibvh_closest_triangles
+ *   documents above: the same operations in the same order, the same clamp of q into the triangle's box, every operation
+ *   rounded once (nothing fused; correctly rounded divide).  The comparison is false on NaN: a triangle whose d2 is NaN is
+ *   never a contact.  The outputs carry d2 and q bits unchanged.
+ *   A sphere has NO contacts if a coordinate of its centre is NaN, or if !(r >= 0): a negative or NaN radius.  r = 0 keeps
+ *   the triangles the centre lies ON (d2 == 0); r = +Inf admits every triangle with a non-NaN d2 (+Inf included).
+ * Order: the contacts of one sphere come in LEAF ORDER — ascending position of the triangle's leaf in bvh->leaves — in both
+ *   passes, which is what lets them agree.  A triangle that two leaves name appears twice, once per leaf.
+ * Why pruning is lossless WITHOUT an epsilon: lb(B) of ibvh_closest_triangles — the point-box bound in d2's operation order
+ *   — never exceeds, as COMPUTED, the COMPUTED d2 of a triangle under B.  A node or a leaf is skipped iff lb(B) > r2, so a
+ *   skipped box holds no contact.  Why the order holds: both children that pass are equals to the walk, which then takes the
+ *   first child first; nothing a visit does changes where the walk goes next.  Work mapping therefore cannot change the
+ *   result: one lane per sphere, a register counter in the first pass, a running row in the second.
+ * Accepted BVHs — exactly those of ibvh_closest_triangles: leaf_kind == node_kind == IBVH_BBOX, triangles and spheres of
+ *   leaf_float, node_float the same as or wider than leaf_float; any index and Morton type.  Anything else — sphere leaves,
+ *   sphere nodes, F64 leaves under F32 nodes — is IBVH_ERR_UNSUPPORTED, never an answer.  Exact PROVIDED every leaf's box
+ *   contains its triangle's box: a skin margin on the leaves is allowed, and so is a BVH after ibvh_refit.  Levels above
+ *   bvh->built_level are not read.
+ * NaN: a triangle with a NaN vertex has a NaN d2 and is never a contact.  But, as for ibvh_closest_triangles, a NaN leaf box
+ *   can make merge.jl's `a < b ? a : b` produce a node box that does NOT contain the NaN-free leaves below it: on a mesh with
+ *   NaN vertices the other triangles' contacts are only guaranteed in trees of at most two leaves.
+ * Guards: the triangle is read through the leaf record's .index, not its position.  A leaf whose index lies outside
+ * 1..num_triangles is skipped — in BOTH passes alike, so their rows still agree — nothing outside the array is read, and
+ * bit 1 of `flag` (value 2) is set.  The flag contract of ibvh_rays_resolve_triangles: optional, 4 bytes the GPU can
+ * write, a plain load and store, never cleared by the library (zero it before the call).  The count pass can only raise
+ * bit 1.  A write pass in which BOTH faults occur raises at least one of the two bits (two plain stores may race): read
+ * bit 1 after the count pass. */
+enum { IBVH_SPHERES_COUNT = 0, IBVH_SPHERES_WRITE = 1 };
+ibvh_status ibvh_sphere_contacts(const ibvh_bvh *bvh, const void *triangles, int64_t num_triangles,
+                                 const void *centers, const void *radii, int64_t num_spheres, int32_t mode,
+                                 void *counts, const void *offsets, int64_t capacity,
+                                 void *contact_index, void *contact_d2, void *contact_point, void *contact_region,
+                                 void *flag, void *stream);
 
 /* ----------------------------------------------------------------------------------- */
 /* breadth-first traversal (BFSTraversal): level-synchronous pair queues                 */

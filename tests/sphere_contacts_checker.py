@@ -1,0 +1,124 @@
+"""Checker of ibvh_sphere_contacts (include/ibvh.h): the brute force over all triangles — the definition of the result — built
+on closest_point_checker's evaluation (the input dtype throughout, every operation rounded once), and the sphere sets the
+tests share.  Per sphere: every triangle k with d2(k, c) <= r * r, in a caller-supplied leaf order.  Host only."""
+import numpy as np
+
+import closest_point_checker as cpc
+
+REGION_NAMES = ("vertex a", "vertex b", "edge ab", "vertex c", "edge ac", "edge bc", "face")
+
+
+class Contacts:
+    """counts (m,) int64, offsets (m + 1,) int64, and per contact, grouped by sphere and within a sphere in leaf order:
+    index (M,) of `idt`, d2 (M,), point (M, 3), region (M,) uint8, sphere (M,) 0-based; r2 (m,) the squared radii."""
+
+
+def brute_force(tris, centers, radii, leaf_order=None, idt=np.int32, chunk=128):
+    """The definition of the result.  tris (n, 9), centers (m, 3), radii (m,) of ONE float dtype.  leaf_order: the user
+    indices (1-based) of the leaves in the order they lie in bvh.leaves, None = 1..n; an entry outside 1..n names no triangle
+    and is skipped (the entry point's guard).  r2 = r * r in the dtype; a contact iff d2 <= r2 (false on NaN), none for a
+    sphere with a NaN centre coordinate or !(r >= 0)."""
+    dt = tris.dtype
+    assert centers.dtype == dt and radii.dtype == dt and radii.shape == (len(centers),), (dt, centers.dtype, radii.dtype, radii.shape)
+    n, m = len(tris), len(centers)
+    order = np.arange(1, n + 1, dtype=np.int64) if leaf_order is None else np.asarray(leaf_order).astype(np.int64)
+    order = order[(order >= 1) & (order <= n)]
+    cols = order - 1
+    with np.errstate(all="ignore"):
+        r2 = radii * radii
+        alive = (radii >= 0) & ~np.isnan(centers).any(axis=1)
+    assert r2.dtype == dt
+    parts = {k: [] for k in ("sphere", "index", "d2", "point", "region")}
+    for s in range(0, m, chunk):
+        sl = slice(s, min(s + chunk, m))
+        if n == 0:
+            break
+        q, d2, region = cpc._evaluate(tris[None], centers[sl, None, :])
+        with np.errstate(invalid="ignore"):
+            hit = (d2 <= r2[sl, None]) & alive[sl, None]
+        rows, js = np.nonzero(hit[:, cols])   # row-major: by sphere, then by leaf position
+        k = cols[js]
+        parts["sphere"].append(rows + s)
+        parts["index"].append(order[js])
+        parts["d2"].append(d2[rows, k])
+        parts["point"].append(q[rows, k])
+        parts["region"].append(region[rows, k])
+    out = Contacts()
+    cat = lambda key, shape, t: np.concatenate(parts[key]).astype(t) if parts[key] else np.empty(shape, t)
+    out.sphere = cat("sphere", (0,), np.int64)
+    out.index = cat("index", (0,), idt)
+    out.d2 = cat("d2", (0,), dt)
+    out.point = cat("point", (0, 3), dt)
+    out.region = cat("region", (0,), np.uint8)
+    out.counts = np.bincount(out.sphere, minlength=m).astype(np.int64)
+    out.offsets = np.concatenate([[0], np.cumsum(out.counts)]).astype(np.int64)
+    out.r2 = r2
+    return out
+
+
+def in_leaf_order(bf, leaf_order):
+    """`bf` with every sphere's list put in another leaf order, for a leaf_order that names every triangle at most once: the
+    same contacts, re-sorted (what brute_force(..., leaf_order) gives, without evaluating again)"""
+    order = np.asarray(leaf_order).astype(np.int64)
+    assert len(np.unique(order)) == len(order)
+    rank = np.full(max(int(order.max(initial=0)), int(bf.index.max(initial=0))) + 1, -1, np.int64)
+    rank[order[order >= 0]] = np.flatnonzero(order >= 0)
+    assert (rank[bf.index] >= 0).all()
+    perm = np.lexsort((rank[bf.index], bf.sphere))
+    out = Contacts()
+    out.counts, out.offsets, out.r2 = bf.counts, bf.offsets, bf.r2
+    out.sphere, out.index, out.d2, out.point, out.region = (a[perm] for a in (bf.sphere, bf.index, bf.d2, bf.point, bf.region))
+    return out
+
+
+def mean_edge(tris):
+    """the mean length of edge ab, in float64"""
+    t = tris.astype(np.float64)
+    return float(np.linalg.norm(t[:, 3:6] - t[:, 0:3], axis=1).mean())
+
+
+def radius_whose_square_is_a_distance(d2_row, start=4):
+    """r with r * r — squared in the dtype — EQUAL to one of d2_row: from its (start + 1)-th smallest on, the first that is
+    the square of a float (the square root, nudged by one unit in the last place either way); None if there is none"""
+    dt = d2_row.dtype.type
+    ordered = np.sort(d2_row[~np.isnan(d2_row)])
+    for target in ordered[start:]:
+        root = np.sqrt(target)
+        for r in (root, np.nextafter(root, dt(0)), np.nextafter(root, dt(np.inf))):
+            if r * r == target:
+                return r
+    return None
+
+
+def pipeline_spheres(tris, dt):
+    """The whole-pipeline test's spheres: the 800 query points of closest_point_checker as centres; radii
+    rng(21).random(800) * 4 * e, e the mean length of edge ab; radius 0 on rows 600::2 (surface points); on rows 0:600:16 a
+    radius whose square in the dtype EQUALS one of that sphere's own brute-force d2 -> (centres (800, 3), radii (800,))"""
+    tris = tris.astype(dt)
+    c = cpc.query_points(tris, dt)
+    radii = (np.random.default_rng(21).random(len(c)) * 4 * mean_edge(tris)).astype(dt)
+    radii[600::2] = 0
+    rows = np.arange(0, 600, 16)
+    _, d2, _ = cpc.evaluate(tris, c[rows])
+    for row, d2_row in zip(rows, d2):
+        r = radius_whose_square_is_a_distance(d2_row)
+        assert r is not None, row
+        radii[row] = r
+    return c, radii
+
+
+def non_vacuity(bf, radii):
+    """what makes a comparison against `bf` mean something -> dict of the quantities the tests assert on"""
+    per_region = np.bincount(bf.region, minlength=7)
+    r_of = radii[bf.sphere]
+    return dict(none=int((bf.counts == 0).sum()), one=int((bf.counts == 1).sum()), several=int((bf.counts >= 2).sum()),
+                per_region=per_region.tolist(), at_zero=int((r_of == 0).sum()),
+                on_the_rim=int(((bf.d2 == bf.r2[bf.sphere]) & (r_of > 0)).sum()), largest=int(bf.counts.max(initial=0)),
+                total=int(len(bf.index)))
+
+
+def assert_non_vacuous(nv):
+    """the thresholds of the whole-pipeline test (set from the four CPU runs: both meshes, both dtypes)"""
+    assert nv["none"] >= 300 and nv["one"] >= 20 and nv["several"] >= 250, nv
+    assert len(nv["per_region"]) == 7 and min(nv["per_region"]) >= 300, nv
+    assert nv["at_zero"] >= 20 and nv["on_the_rim"] >= 30 and nv["largest"] >= 64, nv
