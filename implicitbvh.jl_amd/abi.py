@@ -85,6 +85,12 @@ CAST_RAYS_ARGTYPES = [C.POINTER(Bvh), C.c_void_p, C.c_int64, C.c_void_p, C.c_voi
 SPHERES_COUNT, SPHERES_WRITE = 0, 1
 SPHERE_CONTACTS_ARGTYPES = ([C.POINTER(Bvh), C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p, C.c_int64, C.c_int32, C.c_void_p, C.c_void_p,
                              C.c_int64] + [C.c_void_p] * 6)
+# ibvh_triangle_contacts(bvh, triangles, num_triangles, queries, query_ids, num_queries, mode, skip, counts, offsets, capacity,
+#                        contact_index, contact_mask, contact_points, flag, stream)
+TRIS_COUNT, TRIS_WRITE = 0, 1
+TRIS_SKIP_SHARED_VERTEX = 1
+TRIANGLE_CONTACTS_ARGTYPES = ([C.POINTER(Bvh), C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p, C.c_int64, C.c_int32, C.c_int32, C.c_void_p,
+                               C.c_void_p, C.c_int64] + [C.c_void_p] * 5)
 
 
 class BuildDesc(C.Structure):

@@ -33,6 +33,7 @@ __all__ = [
     "resolve_triangles", "raycast", "RayHits", "closest_points", "ClosestPoints",
     "nearest_leaves", "NearestLeaves", "point_crossings", "PointCrossings", "points_inside", "signed_distance",
     "cast_rays", "RayCast", "sphere_contacts", "SphereContacts",
+    "triangle_contacts", "TriangleContacts", "self_intersections",
 ]
 
 NARROW_MORTON_LT = abi.NARROW_MORTON_LT
@@ -1649,6 +1650,105 @@ def sphere_contacts(bvh, triangles, centers, radii, count_only=False, presorted=
         if word & 4:
             raise RuntimeError(f"{what}: the write pass found more contacts than the count pass (inputs changed between them?)")
     return SphereContacts(offsets, *outs)
+
+
+# ---------------------------------------------------------------------------------------------
+# triangle-vs-mesh contacts: every mesh triangle each query triangle cuts (ibvh_triangle_contacts; no reference counterpart)
+# ---------------------------------------------------------------------------------------------
+class TriangleContacts:
+    """The contacts of N query triangles with a mesh, M in all, grouped by query in the caller's order and, within a query,
+    in the order of the triangles' leaves in the BVH: query i (0-based) owns rows offsets[i] : offsets[i + 1].
+    .offsets (N + 1,) int64, .counts (N,) int64; per contact .index (M,) the mesh triangle's user index, .mask (M,) uint8 the
+    edge tests that found it (bits 0-2: the query's edges ab, bc, ca against the mesh triangle; bits 3-5: the mesh triangle's
+    edges p1p2, p2p3, p3p1 against the query), .points (M, 2, 3) the two ends of the cut (the points of the lowest and the
+    highest set bit) and .query (M,) the 1-based number of the query the row belongs to (computed when first asked for).
+    After count_only=True the per-contact fields are None."""
+
+    def __init__(self, offsets, index=None, mask=None, points=None):
+        self.offsets, self.index, self.mask, self.points = offsets, index, mask, points
+        self.counts = offsets[1:] - offsets[:-1]
+        self._query = None
+
+    @property
+    def query(self):
+        if self._query is None and self.index is not None:
+            torch = _torch()
+            ids = torch.arange(1, self.counts.shape[0] + 1, dtype=torch.int64, device=self.counts.device)
+            self._query = torch.repeat_interleave(ids, self.counts, output_size=int(self.index.shape[0]))
+        return self._query
+
+
+def triangle_contacts(bvh, triangles, queries, query_ids=None, skip_shared_vertices=False, count_only=False, presorted=False):
+    """For every query triangle ALL triangles of the mesh `bvh` was built over that it cuts, with the edge tests that found
+    each and the two ends of the cut -> TriangleContacts (include/ibvh.h, ibvh_triangle_contacts: the six edge-against-triangle
+    tests — the exact test of resolve_triangles on each edge, t <= 1 —, the box clause, the order and why pruning loses
+    nothing are spelled out there).  Two launches, a count and a write, around a scan of the counts here; exact: bit-equal
+    to a brute force over all triangles.  Coplanar and touching pairs are decided by rounding (exactly coplanar arithmetic
+    finds no contact).
+
+    bvh: BBox leaves made from `triangles` (bounding_volumes_from_triangles(triangles, BBox(dtype)); a skin margin and
+    refit are fine) under BBox nodes of the same or a wider float type.  triangles: (n, 9) / (n, 3, 3) CUDA tensor of the
+    leaves' dtype, user index k = row k - 1.  queries: (N, 9) / (N, 3, 3) CUDA tensor of that dtype.  query_ids: None, or an
+    (N,) CUDA tensor of the BVH's index dtype: query i then only meets triangles whose index > query_ids[i].
+    skip_shared_vertices=True drops every pair with an equal vertex.  A query with a NaN coordinate touches nothing.
+    count_only=True stops after the first pass.  The device walks the batch in Morton order of the queries' first vertices
+    (lanes of a wave then share nodes) and writes each query's rows where the caller's order wants them; presorted=True
+    walks it as given.  The total is read on the host between the passes, as in traverse.
+
+    ValueError: sphere leaves or nodes, nodes narrower than the leaves, a wrong dtype, device or shape of triangles, queries
+    or query_ids, and a leaf whose index lies outside 1..n (flag bit 1; such leaves are skipped)."""
+    torch = _require_gpu()
+    what = "triangle_contacts"
+    tris, ft, idt = _mesh_query_setup(bvh, triangles, what)
+    if not isinstance(queries, torch.Tensor) or not (
+            (queries.dim() == 2 and queries.shape[1] == 9) or (queries.dim() == 3 and tuple(queries.shape[1:]) == (3, 3))):
+        raise ValueError(f"{what}: queries must be an (N, 9) or (N, 3, 3) tensor (a b c per triangle)")
+    if queries.dtype != ft or not queries.is_cuda:
+        raise ValueError(f"{what}: queries must be a {ft} tensor on the GPU (device='cuda')")
+    q = queries.reshape(queries.shape[0], 9).contiguous()
+    n = int(q.shape[0])
+    ids = None
+    if query_ids is not None:
+        if not isinstance(query_ids, torch.Tensor) or tuple(query_ids.shape) != (n,) or query_ids.dtype != idt or not query_ids.is_cuda:
+            raise ValueError(f"{what}: query_ids must be None or an (N,) {idt} tensor on the GPU")
+        ids = query_ids.contiguous()
+    skip = abi.TRIS_SKIP_SHARED_VERTEX if skip_shared_vertices else 0
+    offsets = torch.zeros(n + 1, dtype=torch.int64, device="cuda")
+    empty = lambda m: (torch.empty(m, dtype=idt, device="cuda"), torch.empty(m, dtype=torch.uint8, device="cuda"),
+                       torch.empty((m, 2, 3), dtype=ft, device="cuda"))
+    if n == 0:
+        return TriangleContacts(offsets, *(() if count_only else empty(0)))
+    order = None if presorted else _morton_order(q[:, :3])
+    if order is not None:
+        q = q[order]
+        ids = None if ids is None else ids[order]
+    walked = torch.empty(n, dtype=torch.int64, device="cuda")
+    _mesh_query_call("ibvh_triangle_contacts", what, bvh, tris, _ptr(q), _ptr(ids), n, abi.TRIS_COUNT, skip, _ptr(walked), None, 0,
+                     None, None, None)
+    # the counts back in the caller's order, scanned there: a query's rows then follow its predecessor's in that order
+    torch.cumsum(_unpermute(order, (walked,))[0], dim=0, out=offsets[1:])
+    if count_only:
+        return TriangleContacts(offsets)
+    total = int(offsets[-1].item())  # the one read between the passes
+    outs = empty(total)
+    if total > 0:
+        first = offsets[:-1] if order is None else offsets[:-1][order]  # ... gathered back into walk order
+        word = _mesh_query_call("ibvh_triangle_contacts", what, bvh, tris, _ptr(q), _ptr(ids), n, abi.TRIS_WRITE, skip, None,
+                                _ptr(first), total, *[_ptr(o) for o in outs])
+        if word & 4:
+            raise RuntimeError(f"{what}: the write pass found more contacts than the count pass (inputs changed between them?)")
+    return TriangleContacts(offsets, *outs)
+
+
+def self_intersections(bvh, triangles, count_only=False):
+    """The pairs of triangles of ONE mesh that cut each other -> TriangleContacts with the mesh's triangles as the queries:
+    triangle_contacts(bvh, triangles, triangles, query_ids=1..n, skip_shared_vertices=True).  Each unordered pair appears
+    once, under its lower index (.query) with the higher one as .index; never a triangle with itself or with a neighbour
+    that shares a vertex with it."""
+    torch = _require_gpu()
+    tris, _, idt = _mesh_query_setup(bvh, triangles, "self_intersections")
+    ids = torch.arange(1, tris.shape[0] + 1, dtype=idt, device="cuda")
+    return triangle_contacts(bvh, tris, tris, query_ids=ids, skip_shared_vertices=True, count_only=count_only)
 
 
 # ---------------------------------------------------------------------------------------------

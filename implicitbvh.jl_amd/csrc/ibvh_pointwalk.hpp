@@ -1,7 +1,8 @@
-// ibvh_pointwalk.hpp — what the five queries that walk one point (or ray origin) per lane through a BVH have in common:
-// ibvh_closest.hip (the closest triangle) and ibvh_nearest.hip (the k nearest leaf centres), which prune on a bound that
-// shrinks while they walk, ibvh_crossings.hip (the triangles an axis ray from the point crosses) and ibvh_spheres.hip (every
-// triangle within a sphere's radius of the point), whose bound is a fixed yes / no, and ibvh_cast.hip (the closest or any hit
+// ibvh_pointwalk.hpp — what the six queries that walk one point (ray origin, query triangle) per lane through a BVH have in
+// common: ibvh_closest.hip (the closest triangle) and ibvh_nearest.hip (the k nearest leaf centres), which prune on a bound that
+// shrinks while they walk, ibvh_crossings.hip (the triangles an axis ray from the point crosses), ibvh_spheres.hip (every
+// triangle within a sphere's radius of the point) and ibvh_tritri.hip (every triangle a query triangle cuts), whose bound is
+// a fixed yes / no, and ibvh_cast.hip (the closest or any hit
 // of a ray from the point), whose bound is the ray's entry distance into a box.  No reference counterpart: every traversal of
 // ImplicitBVH.jl is a fixed-volume overlap test (traverse/, raytrace/).
 //

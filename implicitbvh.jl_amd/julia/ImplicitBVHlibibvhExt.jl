@@ -302,6 +302,10 @@ c_sphere_contacts(bvh, triangles, num_triangles, centers, radii, num_spheres, mo
     ccall((:ibvh_sphere_contacts, libibvh), Cint,
           (Ref{IbvhBvh}, Ptr{Cvoid}, Int64, Ptr{Cvoid}, Ptr{Cvoid}, Int64, Int32, Ptr{Cvoid}, Ptr{Cvoid}, Int64, Ptr{Cvoid}, Ptr{Cvoid}, Ptr{Cvoid}, Ptr{Cvoid}, Ptr{Cvoid}, Ptr{Cvoid}),
           bvh, triangles, num_triangles, centers, radii, num_spheres, mode, counts, offsets, capacity, contact_index, contact_d2, contact_point, contact_region, flag, stream)
+c_triangle_contacts(bvh, triangles, num_triangles, queries, query_ids, num_queries, mode, skip, counts, offsets, capacity, contact_index, contact_mask, contact_points, flag, stream) =
+    ccall((:ibvh_triangle_contacts, libibvh), Cint,
+          (Ref{IbvhBvh}, Ptr{Cvoid}, Int64, Ptr{Cvoid}, Ptr{Cvoid}, Int64, Int32, Int32, Ptr{Cvoid}, Ptr{Cvoid}, Int64, Ptr{Cvoid}, Ptr{Cvoid}, Ptr{Cvoid}, Ptr{Cvoid}, Ptr{Cvoid}),
+          bvh, triangles, num_triangles, queries, query_ids, num_queries, mode, skip, counts, offsets, capacity, contact_index, contact_mask, contact_points, flag, stream)
 c_lvt_scratch_bytes(types, n_items, cache_slots, out) =
     ccall((:ibvh_lvt_scratch_bytes, libibvh), Cint,
           (Ref{IbvhTypes}, Int64, Int32, Ref{Csize_t}),
@@ -857,6 +861,89 @@ function sphere_contacts(bvh::RocBVH{I}, triangles::ROCMatrix{T}, centers::ROCMa
           "ibvh_sphere_contacts")
     Array(flag)[1] & 0x04 != 0 && error("sphere_contacts: the write pass found more contacts than the count pass")
     (; offsets, counts, index, distance2, point, region)
+end
+
+# ---- triangle-vs-mesh contacts: every mesh triangle each query triangle cuts (include/ibvh.h, ibvh_triangle_contacts) --
+const IBVH_TRIS_COUNT = Int32(0)
+const IBVH_TRIS_WRITE = Int32(1)
+const IBVH_TRIS_SKIP_SHARED_VERTEX = Int32(1)
+"""
+    triangle_contacts(bvh::BVH, triangles::ROCMatrix{T}, queries::ROCMatrix{T}; query_ids=nothing,
+                      skip_shared_vertices=false, count_only=false, presorted=false)
+        -> (; offsets, counts, index, mask, points)
+
+For every query triangle (column of the 9 x N `queries`: a b c) ALL triangles of the mesh `bvh` was built over that it cuts.
+Query `i` owns rows `offsets[i] + 1 : offsets[i + 1]` of the per-contact outputs: `index` the mesh triangle's user index,
+`mask` the edge tests that found it (bits 0-2: the query's edges ab, bc, ca against the mesh triangle; bits 3-5: the mesh
+triangle's edges p1p2, p2p3, p3p1 against the query) and `points[:, 1, j]`, `points[:, 2, j]` the two ends of the cut (the
+points of the lowest and the highest set bit).  Within a query the rows follow the order of the triangles' leaves in
+`bvh.leaves`.  An edge test is the exact ray-triangle test of `resolve_triangles` along the edge with `t <= 1`; coplanar and
+touching pairs are decided by rounding; a query with a NaN coordinate touches nothing.  With `query_ids` (length N, of the BVH's index type)
+query `i` only meets triangles whose index exceeds `query_ids[i]`; `skip_shared_vertices=true` drops pairs with an equal
+vertex.  Bit-equal to a brute force over all triangles; the definition, the order and why pruning loses nothing are spelled
+out in include/ibvh.h.  Two launches, a count and a write, around a `cumsum` of the counts on the device array; the total is
+read on the host between them.  `count_only=true` stops after the first (the per-contact outputs are `nothing`).  The BVH
+must have `BBox{T}` leaves made from the triangles (a skin margin and `refit!` are fine) under `BBox` nodes of `T` or wider;
+anything else raises ArgumentError.  The device walks the batch along a Morton curve through the queries' first vertices and
+writes each query's rows where the caller's order wants them; `presorted=true` walks it as given.  Not a method of
+ImplicitBVH: the reference has no such query.
+"""
+function triangle_contacts(bvh::RocBVH{I}, triangles::ROCMatrix{T}, queries::ROCMatrix{T};
+                           query_ids::Union{Nothing, ROCVector{I}}=nothing, skip_shared_vertices::Bool=false,
+                           count_only::Bool=false, presorted::Bool=false) where {I, T}
+    d = bvh_desc(bvh)
+    isnothing(d) && throw(ArgumentError("triangle_contacts: no libibvh instantiation for this BVH's types"))
+    leaf_volume_type(bvh.leaves) === BBox{T} && eltype(bvh.nodes) <: BBox && sizeof(eltype(bvh.nodes)) >= sizeof(BBox{T}) ||
+        throw(ArgumentError("triangle_contacts: the BVH must have BBox{$T} leaves under BBox nodes of $T or wider"))
+    size(triangles, 1) == 9 || throw(ArgumentError("triangle_contacts: triangles must be 9 x n (p1 p2 p3 per column)"))
+    size(queries, 1) == 9 || throw(ArgumentError("triangle_contacts: queries must be 9 x N (a b c per column)"))
+    n = size(queries, 2)
+    isnothing(query_ids) || length(query_ids) == n ||
+        throw(ArgumentError("triangle_contacts: length(query_ids) == size(queries, 2) must hold"))
+    skip = skip_shared_vertices ? IBVH_TRIS_SKIP_SHARED_VERTEX : Int32(0)
+    offsets = fill!(similar(queries, Int64, n + 1), 0)
+    none(m) = (similar(queries, I, m), similar(queries, UInt8, m), similar(queries, T, 3, 2, m))
+    if n == 0
+        index, mask, points = count_only ? (nothing, nothing, nothing) : none(0)
+        return (; offsets, counts=similar(queries, Int64, 0), index, mask, points)
+    end
+    order = presorted ? nothing : point_morton_order(queries[1:3, :])
+    perm = isnothing(order) ? nothing : ROCVector{Int64}(order)
+    q = isnothing(perm) ? queries : queries[:, perm]
+    ids = isnothing(query_ids) ? nothing : (isnothing(perm) ? query_ids : query_ids[perm])
+    idp = isnothing(ids) ? C_NULL : devptr(ids)
+    flag = scratch!(:tris_flag, 4)
+    fill!(flag, 0x00)
+    walked = similar(queries, Int64, n)
+    nt = Int64(size(triangles, 2))
+    check(c_triangle_contacts(d, devptr(triangles), nt, devptr(q), idp, Int64(n), IBVH_TRIS_COUNT, skip, devptr(walked), C_NULL,
+                              Int64(0), C_NULL, C_NULL, C_NULL, devptr(flag), stream_ptr()), "ibvh_triangle_contacts")
+    Array(flag)[1] & 0x02 != 0 && throw(ArgumentError("triangle_contacts: a leaf's index lies outside 1:$nt"))
+    # the counts back in the caller's order, scanned there: a query's rows then follow its predecessor's in that order
+    counts = isnothing(perm) ? walked : walked[ROCVector{Int64}(invperm(order))]
+    offsets[2:end] .= cumsum(counts)
+    count_only && return (; offsets, counts, index=nothing, mask=nothing, points=nothing)
+    total = Array(offsets[end:end])[1]                           # the one read between the passes
+    index, mask, points = none(total)
+    total == 0 && return (; offsets, counts, index, mask, points)
+    first_row = isnothing(perm) ? offsets[1:n] : offsets[1:n][perm]   # ... gathered back into walk order
+    check(c_triangle_contacts(d, devptr(triangles), nt, devptr(q), idp, Int64(n), IBVH_TRIS_WRITE, skip, C_NULL, devptr(first_row),
+                              Int64(total), devptr(index), devptr(mask), devptr(points), devptr(flag), stream_ptr()),
+          "ibvh_triangle_contacts")
+    Array(flag)[1] & 0x04 != 0 && error("triangle_contacts: the write pass found more contacts than the count pass")
+    (; offsets, counts, index, mask, points)
+end
+
+"""
+    self_intersections(bvh::BVH, triangles::ROCMatrix{T}; count_only=false) -> (; offsets, counts, index, mask, points)
+
+The pairs of triangles of ONE mesh that cut each other: `triangle_contacts` with the mesh's own triangles as the queries,
+`query_ids = 1:n` and `skip_shared_vertices=true`.  Each unordered pair appears once, in the rows of its lower index with
+the higher one as `index`; never a triangle with itself or with a neighbour that shares a vertex with it.
+"""
+function self_intersections(bvh::RocBVH{I}, triangles::ROCMatrix{T}; count_only::Bool=false) where {I, T}
+    ids = ROCVector{I}(collect(I(1):I(size(triangles, 2))))
+    triangle_contacts(bvh, triangles, triangles; query_ids=ids, skip_shared_vertices=true, count_only)
 end
 
 # ---- k nearest leaves for a batch of query points (include/ibvh.h, ibvh_nearest_leaves) ------------------------------

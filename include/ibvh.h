@@ -47,6 +47,7 @@ extern "C" {
  *      ibvh_point_crossings (additive under 7 in the same way); ibvh_cast_rays and IBVH_CAST_CLOSEST / IBVH_CAST_ANY
  *      (additive under 7 in the same way); ibvh_sphere_contacts and IBVH_SPHERES_COUNT / IBVH_SPHERES_WRITE (additive
  *      under 7 likewise: one more entry point);
+ *      ibvh_triangle_contacts and IBVH_TRIS_COUNT / IBVH_TRIS_WRITE (additive under 7 likewise: one more entry point);
  *      argument checks only, no layout or argument list moves: ibvh_key_histogram takes
  *      what fits its LDS staging (10 rows at 12-bit digits) and refuses shift > 63 and a negative prefix_shift,
  *      ibvh_pack_records / ibvh_dist_plan answer IBVH_ERR_OVERFLOW for an index past IBVH_I32 */
@@ -758,6 +759,91 @@ ibvh_status ibvh_sphere_contacts(const ibvh_bvh *bvh, const void *triangles, int
                                  void *counts, const void *offsets, int64_t capacity,
                                  void *contact_index, void *contact_d2, void *contact_point, void *contact_region,
                                  void *flag, void *stream);
+
+/* ----------------------------------------------------------------------------------- */
+/* triangle-vs-mesh contacts: every mesh triangle each query triangle cuts               */
+/* ----------------------------------------------------------------------------------- */
+/* For every query triangle Q = (a, b, c): ALL triangles K = (p1, p2, p3) of the mesh the BVH was built over
+ * (ibvh_volumes_from_triangles with IBVH_BBOX) that Q cuts — which ones, which edge of which triangle pierces the other, and
+ * the two ends of the cut.  The narrow phase of mesh-vs-mesh contact (the queries are the other mesh's triangles) and of
+ * self-intersection (the queries are the mesh's own).  No reference counterpart (the reference's traversal of two meshes ends
+ * at pairs of triangle BOXES); a variable-length answer in TWO calls of ONE launch each — count, the caller's scan, write —
+ * with NO host synchronisation inside either, no LDS, no scratch buffer, no read-modify-write of memory.
+ *   triangles  : num_triangles x 9 values (p1 p2 p3) of bvh->types.leaf_float, `flt` below; user index k is row k - 1
+ *   queries    : num_queries x 9 values (a b c) of `flt`, processed in the order given (neighbours in memory that are
+ *                neighbours in space walk the same nodes: sort a scattered batch along a Morton curve first)
+ *   query_ids  : optional, num_queries values of the BVH's index type I; with it K is a contact of query i only if K's
+ *                index > query_ids[i].  With queries = triangles and query_ids = 1..n each unordered pair of one mesh is
+ *                found once and no triangle meets itself.
+ *   mode       : IBVH_TRIS_COUNT or IBVH_TRIS_WRITE
+ *   skip       : 0 or IBVH_TRIS_SKIP_SHARED_VERTEX (bit 0): a K that shares a vertex with Q is no contact.  Equal means ==
+ *                on all three coordinates, over the nine vertex pairs.  Neighbours in one mesh always touch; this drops them.
+ * IBVH_TRIS_COUNT, the first pass:
+ *   counts     : num_queries x int64 (whatever the index type), required; counts[i] = the number of contacts of query i.
+ *                Nothing of `offsets` or the contact_* arrays is read or written: they may be NULL.
+ * Between the passes the caller scans: offsets = ANY exclusive prefix sum of counts.  The scan is the caller's.
+ * IBVH_TRIS_WRITE, the second pass, with the SAME bvh, triangles, queries, query_ids and skip:
+ *   offsets    : num_queries x int64, required; contact j of query i goes to row offsets[i] + j.  They need NOT be monotone;
+ *                `counts` is not read.
+ *   capacity   : the number of rows every non-NULL contact_* array holds.  A row >= capacity or < 0 is never written and
+ *                sets bit 2 of `flag` (value 4) instead.  The guard is per ROW, as in ibvh_sphere_contacts.
+ *   contact_index  : capacity x I, K's user index
+ *   contact_mask   : capacity x uint8, the tests that found the contact (bits 0..5 below)
+ *   contact_points : capacity x 2 x 3 x flt, the two ends of the cut (below)
+ *   each optional, at least one non-NULL; what was not asked for is not written.
+ * All arguments are validated before any launch, in this order.  The entry's own checks: NULL bvh, negative sizes or
+ * capacity, an unknown mode, any bit of `skip` other than bit 0, no `counts` in the count pass, no `offsets` or no output at
+ * all in the write pass: IBVH_ERR_INVALID_ARG.  Then the type combination (below): IBVH_ERR_UNSUPPORTED.  Then a tree shape
+ * that is not an ImplicitTree's or a missing array: IBVH_ERR_INVALID_ARG.  num_queries == 0: IBVH_OK, nothing is touched.
+ * The result is defined independently of how it is found, in `flt` throughout, every operation rounded once (nothing fused;
+ * correctly rounded divide):
+ *   Q's box: qlo_k / qup_k = the minimum / maximum of the three vertices' k-th coordinates, folded from a with
+ *     `x < m ? x : m` / `x > m ? x : m`.  This is exact.
+ *   The box clause: apart(box [lo, up]) = qup_k < lo_k || qlo_k > up_k for some k: six strict comparisons, each false on NaN.
+ *   The edge tests: seg(P0, P1, Tri) = the ray-triangle test of ibvh_rays_resolve_triangles above with p = P0,
+ *     d = P1 - P0 against Tri is true, AND t <= 1.  Six of them, in this order, each setting one bit of `mask`:
+ *       bit 0  a -> b against K      bit 3  p1 -> p2 against Q
+ *       bit 1  b -> c against K      bit 4  p2 -> p3 against Q
+ *       bit 2  c -> a against K      bit 5  p3 -> p1 against Q
+ *   K is a contact of query i iff  !apart(K's stored leaf box)  and  mask != 0  and  (query_ids is NULL or
+ *     index > query_ids[i])  and  (bit 0 of skip is clear or no vertex of Q equals a vertex of K).
+ *   The contact points: points[2 * row] = P0 + t * d of the LOWEST set bit, points[2 * row + 1] that of the HIGHEST set bit;
+ *     each coordinate is one rounded product and one rounded sum.  In general position exactly two bits are set and the two
+ *     points are the ends of the intersection segment; with one bit set both rows hold the same point.
+ *   A query with a NaN coordinate has NO contacts (it is not walked).
+ * Order: the contacts of one query come in LEAF ORDER — ascending position of K's leaf in bvh->leaves — in both passes, which
+ *   is what lets them agree.  A triangle that two leaves name appears twice, once per leaf.
+ * Why pruning is lossless WITHOUT an epsilon: the box clause is part of the definition, and every box of the tree contains
+ *   the boxes below it exactly — through min / max, widening conversions, a skin margin and ibvh_refit.  A node that is apart
+ *   from Q therefore has only leaves that are apart from Q, and a node or a leaf is skipped iff it is apart.  A NaN box is
+ *   entered.  For leaves that contain their triangles the box clause only removes ghosts of rounding: a pair whose boxes are
+ *   apart does not meet.  Why the order holds: as for ibvh_sphere_contacts, the walk is handed 0 / 1 under a constant limit.
+ * What follows from the definition:
+ *   Coplanar pairs have det == 0 in all six tests wherever the products are exact (axis-aligned planes, small integers):
+ *     they are then never contacts, however much they overlap.  In general the COMPUTED det of a coplanar pair is rounding
+ *     noise, not 0, and such a pair — a triangle against itself included — is decided by rounding, like a touching one:
+ *     query_ids and the shared-vertex rule, not the arithmetic, keep a triangle from meeting itself and its neighbours.
+ *   Touching configurations (a vertex on a face, an edge through an edge) depend on rounding.
+ *   The decision is symmetric: (Q, K) and (K, Q) run the same six computations, and the masks have bits 0-2 and 3-5
+ *     exchanged (given that neither stored box is apart from the other triangle's box).
+ *   A test that reads a NaN coordinate is false.  A triangle with a NaN vertex can therefore be found only through the one
+ *     edge between its two other vertices, and it hides no other triangle in trees of at most two leaves; above that, as for
+ *     ibvh_closest_triangles, a NaN leaf box can make merge.jl's `a < b ? a : b` produce a node box that does not contain
+ *     the NaN-free leaves below it.
+ * Accepted BVHs — exactly those of ibvh_closest_triangles: leaf_kind == node_kind == IBVH_BBOX, triangles and queries of
+ *   leaf_float, node_float the same as or wider than leaf_float; any index and Morton type.  Anything else — sphere leaves,
+ *   sphere nodes, F64 leaves under F32 nodes — is IBVH_ERR_UNSUPPORTED, never an answer.  Levels above bvh->built_level are
+ *   not read.
+ * Guards: the triangle is read through the leaf record's .index, not its position.  A leaf whose index lies outside
+ * 1..num_triangles is skipped — in BOTH passes alike, so their rows still agree — nothing outside the array is read, and
+ * bit 1 of `flag` (value 2) is set.  The flag contract of ibvh_sphere_contacts: optional, never cleared by the library, the
+ * count pass can only raise bit 1. */
+enum { IBVH_TRIS_COUNT = 0, IBVH_TRIS_WRITE = 1 };
+enum { IBVH_TRIS_SKIP_SHARED_VERTEX = 1 };
+ibvh_status ibvh_triangle_contacts(const ibvh_bvh *bvh, const void *triangles, int64_t num_triangles,
+                                   const void *queries, const void *query_ids, int64_t num_queries, int32_t mode, int32_t skip,
+                                   void *counts, const void *offsets, int64_t capacity,
+                                   void *contact_index, void *contact_mask, void *contact_points, void *flag, void *stream);
 
 /* ----------------------------------------------------------------------------------- */
 /* breadth-first traversal (BFSTraversal): level-synchronous pair queues                 */

@@ -1,0 +1,440 @@
+"""ibvh_triangle_contacts / triangle_contacts / self_intersections on the GPU: counts, offsets, index, mask, the two contact
+points and the ORDER of every query's list are BIT-EQUAL to the brute force over all triangles of
+tests/triangle_contacts_checker.py — the definition of the result — through the whole pipeline (volumes from triangles, build,
+count, scan, write) for every accepted float / index combination, in the given order, through the Morton-sorted default path
+and counting only; the self-intersection of two tori; hand-made meshes straight through the C entry point (tiny trees,
+piercing, touching, coplanar and degenerate triangles, NaN and Inf vertices, output subsets, the index guard), offsets in a
+permuted order and the capacity guard, skin margins and refit against the stored leaf boxes, the refusals, and one kernel per
+pass."""
+import ctypes as C
+import functools
+import itertools
+
+import numpy as np
+import pytest
+
+pytestmark = pytest.mark.gpu
+torch = pytest.importorskip("torch")
+import implicitbvh_amd as ibvh  # noqa: E402
+from implicitbvh_amd import abi, api, lib  # noqa: E402
+from implicitbvh_amd.synthetic import torus_mesh  # noqa: E402
+
+import triangle_contacts_checker as tcc  # noqa: E402
+from mesh_query_kit import FLOATS, MESHES, NP_F, NP_I, assert_one_kernel, build as _build, tf as _tf  # noqa: E402
+from test_gpu_parity import cuda  # noqa: E402
+
+NAME = "ibvh_triangle_contacts"
+
+
+@functools.lru_cache(maxsize=None)
+def _reference(mesh, flt):
+    """(triangles, queries, brute force in the order 1..n over tight boxes) of a mesh in a dtype: computed once, shared,
+    never modified"""
+    tris = torus_mesh(*MESHES[mesh]).astype(NP_F[flt])
+    q = tcc.pipeline_queries(tris)
+    bf = tcc.brute_force(tris, q, idt=np.int64)
+    for a in (tris, bf.counts, bf.offsets, bf.query, bf.index, bf.mask, bf.points):
+        a.setflags(write=False)   # (q goes through torch.from_numpy, which wants a writable array)
+    return tris, q, bf
+
+
+@functools.lru_cache(maxsize=None)
+def _two_tori():
+    """torus40 and its rigid transform as ONE mesh of 6,400 triangles, and its self-test in the order 1..n: all pairs with
+    shared vertices skipped, and those with ids as well"""
+    tris = torus_mesh(*MESHES["torus40"])
+    both = np.concatenate([tris, tcc.other(tris)])
+    twice = tcc.brute_force(both, both, skip_shared=True, idt=np.int64)
+    once = tcc.brute_force(both, both, skip_shared=True, query_ids=np.arange(1, len(both) + 1), idt=np.int64)
+    for a in (both, once.index, once.mask, once.points, once.query, twice.index, twice.mask, twice.points, twice.query):
+        a.setflags(write=False)
+    return both, once, twice
+
+
+def _bits(a):
+    return np.ascontiguousarray(a).tobytes()
+
+
+def _leaf_order(bvh):
+    return bvh.leaves.index.cpu().numpy().astype(np.int64)
+
+
+def _stored_boxes(bvh, n):
+    """the boxes stored in the leaves, by triangle (n, 6)"""
+    vol = bvh.leaves.volume.cpu().numpy()
+    boxes = np.zeros((n, 6), vol.dtype)
+    order = _leaf_order(bvh)
+    ok = (order >= 1) & (order <= n)
+    boxes[order[ok] - 1] = vol[ok]
+    return boxes
+
+
+def _assert_equal(got, exp, what, count_only=False):
+    assert got.offsets.dtype == got.counts.dtype == torch.int64, what
+    assert (got.counts.cpu().numpy() == exp.counts).all() and (got.offsets.cpu().numpy() == exp.offsets).all(), what
+    if count_only:
+        assert got.index is None and got.mask is None and got.points is None and got.query is None, what
+        return
+    m = len(exp.index)
+    assert got.index.shape == (m,) and got.points.shape == (m, 2, 3) and got.mask.dtype == torch.uint8 and got.mask.shape == (m,), what
+    assert (got.index.cpu().numpy() == exp.index).all(), what
+    assert (got.mask.cpu().numpy() == exp.mask).all(), what
+    assert _bits(got.points.cpu().numpy()) == _bits(exp.points), what
+    assert (got.query.cpu().numpy() == exp.query + 1).all(), what
+
+
+# ---- 1. brute force, whole pipeline ------------------------------------------------------------------------------------
+@pytest.mark.parametrize("idx", [abi.I32, abi.I64], ids=["i32", "i64"])
+@pytest.mark.parametrize("floats", sorted(FLOATS))
+@pytest.mark.parametrize("mesh", sorted(MESHES))
+def test_whole_pipeline_is_bit_equal_to_the_brute_force(mesh, floats, idx):
+    leaf_flt, node_flt = FLOATS[floats]
+    tris, q, bf = _reference(mesh, leaf_flt)
+    # the conditions that make the comparison mean something (tests/test_host_triangle_contacts.py pins them on the host too)
+    nv = tcc.non_vacuity(bf)
+    print(f"{mesh} {floats}: {nv}")
+    tcc.assert_non_vacuous(nv)
+    bvh, tdev = _build(tris, leaf_flt, node_flt, idx)
+    assert bvh.tree.virtual_leaves > 0
+    order = _leaf_order(bvh)
+    assert sorted(order.tolist()) == list(range(1, len(tris) + 1)) and (np.diff(order) < 0).any()
+    exp = tcc.in_leaf_order(bf, order)
+    assert (exp.index != bf.index).any()   # the leaf order is not the triangles' own: the order is being tested
+    Q = cuda(q)
+    got = ibvh.triangle_contacts(bvh, tdev, Q, presorted=True)
+    assert got.index.dtype == (torch.int32 if idx == abi.I32 else torch.int64) and got.points.dtype == _tf(leaf_flt)
+    _assert_equal(got, exp, (mesh, floats, idx, "given order"))
+    _assert_equal(ibvh.triangle_contacts(bvh, tdev, Q.reshape(-1, 3, 3)), exp, (mesh, floats, idx, "sorted"))
+    _assert_equal(ibvh.triangle_contacts(bvh, tdev.reshape(-1, 3, 3), Q, count_only=True), exp, (mesh, floats, idx, "count"), count_only=True)
+    _assert_equal(ibvh.triangle_contacts(bvh, tdev, Q, count_only=True, presorted=True), exp, (mesh, floats, idx, "count, given"), count_only=True)
+
+
+# ---- 2. one mesh against itself ----------------------------------------------------------------------------------------
+@pytest.mark.parametrize("idx", [abi.I32, abi.I64], ids=["i32", "i64"])
+def test_self_intersections_of_two_tori_in_one_mesh(idx):
+    both, once, twice = _two_tori()
+    n = len(both)
+    assert len(once.index) == 384 and len(twice.index) == 768
+    assert ((once.query < n // 2) & (once.index > n // 2)).all()   # every one across the two tori, under its lower index
+    bvh, tdev = _build(both, idx=idx)
+    order = _leaf_order(bvh)
+    got = ibvh.self_intersections(bvh, tdev)
+    _assert_equal(got, tcc.in_leaf_order(once, order), "self")
+    assert (got.index > got.query.to(got.index.dtype)).all()
+    _assert_equal(ibvh.self_intersections(bvh, tdev, count_only=True), once, "self, count", count_only=True)
+    # without ids every pair appears in both directions, with bits 0-2 and 3-5 of the masks exchanged
+    sym = ibvh.triangle_contacts(bvh, tdev, tdev, skip_shared_vertices=True)
+    _assert_equal(sym, tcc.in_leaf_order(twice, order), "both directions")
+    a, b, mask = sym.query.cpu().numpy(), sym.index.cpu().numpy().astype(np.int64), sym.mask.cpu().numpy()
+    there = {(int(x), int(y)): int(m) for x, y, m in zip(a, b, mask)}
+    assert len(there) == 768 and all(there[(y, x)] == int(tcc.swap_mask(m)) for (x, y), m in there.items())
+    assert sorted((x, y) for (x, y) in there if x < y) == sorted(zip((once.query + 1).tolist(), once.index.tolist()))
+
+
+# ---- 3. hand-made, straight through the C entry ------------------------------------------------------------------------
+SENTINEL = {"i": -7, "m": 249, "p": -7.0}
+
+
+def _call(bvh, tris, q, ids=None, skip=0, num_triangles=None, flag=0, outs="imp", num_queries=None, offsets=None, capacity=None, rows=None):
+    """count, scan on the host, write -> dict: counts, the outputs (prefilled with a sentinel so that 'not written' is
+    visible; `rows` of them, default the total), both flag words and both statuses"""
+    n = len(q) if num_queries is None else num_queries
+    nt = len(tris) if num_triangles is None else num_triangles
+    T, Qd = cuda(np.array(tris)), cuda(np.array(q))   # (copies: the shared reference arrays are read-only)
+    idt = api._torch_index(bvh.types.index_type)
+    Id = None if ids is None else torch.as_tensor(np.asarray(ids), device="cuda").to(idt)
+    f = getattr(lib.load(), NAME)
+    counts = torch.full((max(len(q), 1),), -7, dtype=torch.int64, device="cuda")
+    fl = torch.full((2,), flag, dtype=torch.int32, device="cuda")
+    out = {}
+    out["status_count"] = f(C.byref(bvh.struct()), api._ptr(T), nt, api._ptr(Qd), api._ptr(Id), n, abi.TRIS_COUNT, skip, api._ptr(counts),
+                            None, 0, None, None, None, C.c_void_p(fl.data_ptr()), api._stream())
+    torch.cuda.synchronize()
+    out["counts"] = counts.cpu().numpy()
+    cn = out["counts"][:n] if out["status_count"] == 0 else np.zeros(0, np.int64)
+    total = int(cn.sum())
+    scan = (np.cumsum(cn) - cn).astype(np.int64) if offsets is None else np.asarray(offsets, np.int64)
+    out["offsets"], out["total"] = scan, total
+    m = total if rows is None else rows
+    o = {"i": torch.full((max(m, 1),), SENTINEL["i"], dtype=idt, device="cuda"),
+         "m": torch.full((max(m, 1),), SENTINEL["m"], dtype=torch.uint8, device="cuda"),
+         "p": torch.full((max(m, 1), 2, 3), SENTINEL["p"], dtype=T.dtype, device="cuda")}
+    ptr = lambda k: C.c_void_p(o[k].data_ptr()) if k in outs else None
+    Od = cuda(scan if len(scan) else np.zeros(1, np.int64))
+    out["status"] = f(C.byref(bvh.struct()), api._ptr(T), nt, api._ptr(Qd), api._ptr(Id), n, abi.TRIS_WRITE, skip, None, C.c_void_p(Od.data_ptr()),
+                      m if capacity is None else capacity, ptr("i"), ptr("m"), ptr("p"), C.c_void_p(fl.data_ptr() + 4), api._stream())
+    torch.cuda.synchronize()
+    out.update({k: v.cpu().numpy() for k, v in o.items()})
+    out["flag_count"], out["flag"] = (int(x) for x in fl.cpu().numpy())
+    return out
+
+
+def _same(got, exp, what=None, outs="imp"):
+    assert got["status_count"] == 0 and got["status"] == 0, what
+    n, m = len(exp.counts), len(exp.index)
+    assert (got["counts"][:n] == exp.counts).all() and got["total"] == m, what
+    for k, e in (("i", exp.index), ("m", exp.mask), ("p", exp.points)):
+        if k in outs:
+            assert _bits(got[k][:m]) == _bits(e.astype(got[k].dtype)), (what, k)
+        else:
+            assert (got[k] == SENTINEL[k]).all(), (what, k)
+
+
+UNIT = [0, 0, 0, 1, 0, 0, 0, 1, 0]
+HAND = [UNIT,
+        [5, 5, 5, 6, 6, 6, 7, 7, 7],             # zero area: collinear
+        [9, 9, 9, 9, 9, 9, 9, 9, 9],             # zero area: one point
+        [3, 0, 0, 4, 0, 0, 3, 1, 0],
+        [0, 0, 3, 1, 0, 3, 0, 1, 3]]
+PIERCING = [0.25, 0.25, -1, 0.25, 0.25, 1, 2, 2, 1]          # its edge ab goes through UNIT, UNIT's edge p2p3 through it
+TOUCHING = [0.25, 0.25, 0, 0.25, 0.25, 1, 1, 1, 1]           # its vertex a lies on UNIT's face
+COPLANAR = [0.125, 0.125, 0, 0.75, 0.125, 0, 0.125, 0.75, 0]  # overlaps UNIT in its plane
+COLLINEAR = [0.25, 0.25, -1, 0.25, 0.25, 0.5, 0.25, 0.25, 1]  # zero area, through UNIT: its edges ab and ca pierce it
+A_POINT = [0.25, 0.25, 0] * 3                                 # zero area, on UNIT
+SLAB = [-10, 0.25, -10, 20, 0.25, -10, 0, 0.25, 30]           # the plane y = 0.25 through triangles 1, 4 and 5
+HAND_QUERIES = [PIERCING, TOUCHING, COPLANAR, COLLINEAR, A_POINT, SLAB,
+                [np.nan, 0.25, -1, 0.25, 0.25, 1, 2, 2, 1], [0.25, 0.25, -1, 0.25, np.nan, 1, 2, 2, 1], [0.25, 0.25, -1, 0.25, 0.25, 1, 2, 2, np.nan],
+                [0.25, 0.25, -1, 0.25, 0.25, np.inf, 2, 2, 1], [-np.inf, 0.25, -1, 0.25, 0.25, 1, 2, 2, 1],
+                [3.25, 0.25, -1, 3.25, 0.25, 1, 9, 9, 9],      # through triangle 4, a vertex on triangle 3
+                [0.25, 0.25, 2, 0.25, 0.25, 4, 5, 5, 5],       # through triangle 5, a vertex on triangle 2
+                [50, 50, 50, 51, 50, 50, 50, 51, 50],           # far from everything
+                UNIT]                                            # a mesh triangle itself: coplanar, every vertex shared
+
+
+def _hand(n, dt):
+    rng = np.random.default_rng(17)
+    extra = (rng.random((40, 9)) * 6 - 1).astype(dt)
+    return np.array(HAND[:n], dt), np.concatenate([np.array(HAND_QUERIES, dt), extra])
+
+
+@pytest.mark.parametrize("idx", [abi.I32, abi.I64], ids=["i32", "i64"])
+@pytest.mark.parametrize("flt", [abi.F32, abi.F64], ids=["f32", "f64"])
+@pytest.mark.parametrize("n,built_level", [(1, 1), (2, 1), (3, 1), (5, 1), (5, 2), (5, 4)])
+def test_hand_made_meshes_through_the_c_entry(n, built_level, flt, idx):
+    dt = NP_F[flt]
+    tris, q = _hand(n, dt)
+    bvh, _ = _build(tris, flt, idx=idx, built_level=built_level)
+    assert bvh.tree.levels == {1: 1, 2: 2, 3: 3, 5: 4}[n] and bvh.built_level == built_level
+    order = _leaf_order(bvh)
+    boxes = _stored_boxes(bvh, n)
+    assert _bits(boxes) == _bits(tcc.tight_boxes(tris))
+    exp = tcc.brute_force(tris, q, leaf_order=order, leaf_boxes=boxes, idt=NP_I[idx])
+    got = _call(bvh, tris, q)
+    _same(got, exp, (n, built_level))
+    assert got["flag_count"] == 0 and got["flag"] == 0
+    # what the checker itself says about these inputs
+    of = lambda i: list(zip(exp.index[exp.query == i].tolist(), exp.mask[exp.query == i].tolist()))
+    assert of(0) == [(1, 17)] and exp.points[exp.query == 0].tolist() == [[[0.25, 0.25, 0], [0.5, 0.5, 0]]]
+    assert of(1) == [(1, 5)] and exp.points[exp.query == 1].tolist() == [[[0.25, 0.25, 0]] * 2]
+    assert of(2) == [] and of(4) == [] and of(3) == [(1, 5)]
+    assert exp.counts[6:9].tolist() == [0, 0, 0] and exp.counts[13] == 0 and exp.counts[14] == 0
+    if n == 5:
+        assert sorted(i for i, _ in of(5)) == [1, 4, 5] and [i for i, _ in of(5)] == [i for i in order if i in (1, 4, 5)]
+        assert (np.diff(order) < 0).any() and 4 in [i for i, _ in of(11)] and 5 in [i for i, _ in of(12)]
+        assert {0, 1, 3} <= set(exp.counts.tolist()) and exp.counts[9] == 0 and exp.counts[10] == 0
+    # ids and the shared-vertex rule straight through the entry
+    ids = np.arange(len(q)) % (n + 1)
+    for skip in (0, abi.TRIS_SKIP_SHARED_VERTEX):
+        e = tcc.brute_force(tris, q, leaf_order=order, leaf_boxes=boxes, query_ids=ids, skip_shared=bool(skip), idt=NP_I[idx])
+        _same(_call(bvh, tris, q, ids=ids, skip=skip), e, ("ids", skip))
+    # any subset of the outputs; what was not asked for is not written
+    subsets = ["".join(x) for k in range(1, 4) for x in itertools.combinations("imp", k)]
+    assert len(subsets) == 7
+    for outs in subsets:
+        _same(_call(bvh, tris, q, outs=outs), exp, outs, outs=outs)
+    # num_queries = 0 with a pre-set flag: nothing is touched
+    none = _call(bvh, tris, q, num_queries=0, flag=4, rows=3)
+    assert none["status_count"] == 0 and none["status"] == 0 and none["flag_count"] == 4 and none["flag"] == 4
+    assert (none["counts"] == -7).all() and all((none[k] == SENTINEL[k]).all() for k in "imp")
+    # num_triangles below the largest leaf index: those leaves are skipped in both passes, bit 1 is raised (never cleared: 4 stays)
+    if n >= 3:
+        cut = _call(bvh, tris, q, num_triangles=n - 2, flag=4)
+        assert cut["flag_count"] == 6 and cut["flag"] == 6
+        cut_exp = tcc.brute_force(tris[:n - 2], q, leaf_order=order, leaf_boxes=boxes[:n - 2], idt=NP_I[idx])
+        assert n < 5 or len(cut_exp.index) < len(exp.index)
+        _same(cut, cut_exp, "guard")
+
+
+def test_two_roots_one_over_a_virtual_sibling_and_a_batch_of_a_wave_and_one():
+    """built_level = 2 over 3 leaves: the walk starts from two roots, and the second root's other child is virtual; 65
+    queries are a full wave and one lane of a second workgroup"""
+    tris = np.array([UNIT, HAND[3], HAND[4]], np.float32)
+    rng = np.random.default_rng(65)
+    q = np.concatenate([np.array(HAND_QUERIES[:6], np.float32), (rng.random((59, 9)) * 5 - 1).astype(np.float32)])
+    q[64] = SLAB
+    bvh, _ = _build(tris, built_level=2)
+    assert len(q) == 65 and (bvh.tree.levels, bvh.built_level, bvh.tree.real_leaves, bvh.tree.virtual_leaves) == (3, 2, 3, 1)
+    exp = tcc.brute_force(tris, q, leaf_order=_leaf_order(bvh), leaf_boxes=_stored_boxes(bvh, 3), idt=np.int32)
+    assert set(exp.index.tolist()) == {1, 2, 3} and exp.counts[64] == 3 and {0, 1, 3} <= set(exp.counts.tolist())
+    _same(_call(bvh, tris, q), exp)
+
+
+@pytest.mark.parametrize("flt", [abi.F32, abi.F64], ids=["f32", "f64"])
+@pytest.mark.parametrize("order", [(0, 1), (1, 0)], ids=["nan_second", "nan_first"])
+def test_a_triangle_with_a_nan_vertex_hides_none_and_reads_as_the_definition_says(order, flt):
+    dt = NP_F[flt]
+    both = np.array([UNIT, [np.nan, 0, 0.5, 1, 0, 0.5, 0, 1, 0.5]], dt)[list(order)]
+    q = np.array([PIERCING, TOUCHING, COLLINEAR, SLAB, [0.5, 0.5, 0.25, 0.5, 0.5, 0.75, 2, 2, 2]], dt)
+    bvh, _ = _build(both, flt)
+    exp = tcc.brute_force(both, q, leaf_order=_leaf_order(bvh), leaf_boxes=_stored_boxes(bvh, 2), idt=np.int32)
+    good = order.index(0) + 1
+    assert all(good in exp.index[exp.query == i].tolist() for i in range(4))
+    got = _call(bvh, both, q)
+    _same(got, exp, order)
+    assert not np.isnan(got["p"][:got["total"]]).any()
+
+
+# ---- 4. offsets and capacity -------------------------------------------------------------------------------------------
+def test_offsets_in_a_permuted_order_and_the_capacity_guard():
+    tris, q, bf = _reference("torus40", abi.F32)
+    nq = len(q)
+    bvh, _ = _build(tris)
+    exp = tcc.in_leaf_order(bf, _leaf_order(bvh))
+    total = len(exp.index)
+    assert total > 800 and (exp.counts > 0).sum() > 150
+    # the lists laid out in another order of the queries: each query's rows land where its offset says
+    perm = np.random.default_rng(9).permutation(nq)
+    offs = np.empty(nq, np.int64)
+    offs[perm] = np.cumsum(exp.counts[perm]) - exp.counts[perm]
+    assert (np.diff(offs) < 0).any()
+    row = np.repeat(offs, exp.counts) + (np.arange(total) - np.repeat(exp.offsets[:-1], exp.counts))
+    assert sorted(row.tolist()) == list(range(total))
+    got = _call(bvh, tris, q, offsets=offs)
+    assert got["status"] == 0 and got["flag"] == 0 and got["total"] == total
+    assert (got["i"][row] == exp.index).all() and (got["m"][row] == exp.mask).all() and _bits(got["p"][row]) == _bits(exp.points)
+    # capacity one short of the total (the buffers hold the total): exactly the last row keeps its sentinel, bit 2 is raised
+    short = _call(bvh, tris, q, capacity=total - 1, rows=total)
+    assert short["status"] == 0 and short["flag"] == 4 and short["flag_count"] == 0
+    for k, e in (("i", exp.index), ("m", exp.mask), ("p", exp.points)):
+        assert _bits(short[k][:total - 1]) == _bits(e[:total - 1].astype(short[k].dtype)) and (short[k][total - 1] == SENTINEL[k]).all(), k
+    # ... the same through permuted offsets: the rows >= capacity, wherever their queries are
+    cap = total - 37
+    short = _call(bvh, tris, q, offsets=offs, capacity=cap, rows=total)
+    keep = row < cap
+    assert short["flag"] == 4 and (~keep).sum() == 37
+    assert (short["i"][row[keep]] == exp.index[keep]).all() and _bits(short["p"][row[keep]]) == _bits(exp.points[keep])
+    assert all((short[k][cap:] == SENTINEL[k]).all() for k in "imp")
+    # negative rows and rows far beyond are refused alike, never written
+    busy = np.flatnonzero(exp.counts > 0)[:2]
+    wild = offs.copy()
+    wild[busy[0]], wild[busy[1]] = -10 ** 6, 2 ** 62
+    bad = _call(bvh, tris, q, offsets=wild, rows=total)
+    ok = ~np.isin(exp.query, busy)
+    assert bad["status"] == 0 and bad["flag"] == 4 and (~ok).sum() >= 2
+    assert (bad["i"][row[ok]] == exp.index[ok]).all() and (bad["i"][row[~ok]] == SENTINEL["i"]).all()
+    # the guard is per ROW, not per query: with an offset of -1 a query's first contact (row -1) is refused and its later
+    # ones land in rows 0, 1, ...; the other queries are laid out behind them, so no row is written twice
+    b = int(np.flatnonzero(exp.counts >= 3)[0])
+    cb = int(exp.counts[b])
+    edge = np.empty(nq, np.int64)
+    others = np.delete(np.arange(nq), b)
+    edge[others] = (cb - 1) + np.cumsum(exp.counts[others]) - exp.counts[others]
+    edge[b] = -1
+    erow = np.repeat(edge, exp.counts) + (np.arange(total) - np.repeat(exp.offsets[:-1], exp.counts))
+    lost = erow < 0
+    assert lost.sum() == 1 and exp.query[lost] == b and sorted(erow[~lost].tolist()) == list(range(total - 1))
+    got = _call(bvh, tris, q, offsets=edge, capacity=total - 1, rows=total)
+    assert got["status"] == 0 and got["flag"] == 4
+    for k, e in (("i", exp.index), ("m", exp.mask), ("p", exp.points)):
+        assert _bits(got[k][erow[~lost]]) == _bits(e[~lost].astype(got[k].dtype)) and (got[k][total - 1] == SENTINEL[k]).all(), k
+    # capacity 0: nothing is written
+    zero = _call(bvh, tris, q, capacity=0, rows=total)
+    assert zero["status"] == 0 and zero["flag"] == 4 and all((zero[k] == SENTINEL[k]).all() for k in "imp")
+
+
+# ---- 5. skin and refit -------------------------------------------------------------------------------------------------
+@pytest.mark.parametrize("floats", sorted(FLOATS))
+def test_skin_margins_and_refit_follow_the_stored_leaf_boxes(floats):
+    leaf_flt, node_flt = FLOATS[floats]
+    dt = NP_F[leaf_flt]
+    tris, q, bf = _reference("torus40", leaf_flt)
+    n = len(tris)
+    Q = cuda(q)
+    bvh, tdev = _build(tris, leaf_flt, node_flt, skin=0.02)
+    boxes = _stored_boxes(bvh, n)
+    assert (boxes[:, :3] < tcc.tight_boxes(tris)[:, :3]).all()
+    exp = tcc.brute_force(tris, q, leaf_order=_leaf_order(bvh), leaf_boxes=boxes, idt=np.int64)
+    assert len(exp.index) >= len(bf.index)
+    _assert_equal(ibvh.triangle_contacts(bvh, tdev, Q), exp, (floats, "skin"))
+    # refit the tight build to moved vertices: the moved triangles' brute force over the refitted boxes
+    bvh, tdev = _build(tris, leaf_flt, node_flt)
+    rng = np.random.default_rng(11)
+    moved = (tris + 0.01 * (rng.random(tris.shape) - 0.5)).astype(dt)
+    mdev = cuda(moved)
+    ibvh.refit(bvh, ibvh.bounding_volumes_from_triangles(mdev, ibvh.BBox(_tf(leaf_flt))))
+    boxes = _stored_boxes(bvh, n)
+    assert _bits(boxes) == _bits(tcc.tight_boxes(moved))
+    exp = tcc.brute_force(moved, q, leaf_order=_leaf_order(bvh), leaf_boxes=boxes, idt=np.int64)
+    assert (exp.counts != bf.counts).any() and len(exp.index) > 500
+    for presorted in (True, False):
+        _assert_equal(ibvh.triangle_contacts(bvh, mdev, Q, presorted=presorted), exp, (floats, "refit", presorted))
+
+
+# ---- 6. refusals -------------------------------------------------------------------------------------------------------
+def test_refusals_of_the_c_entry_and_the_python_mirror():
+    tris, q, bf = _reference("torus40", abi.F32)
+    nq = len(q)
+    Q = cuda(q)
+    f = getattr(lib.load(), NAME)
+    out = torch.full((nq,), -7, dtype=torch.int64, device="cuda")
+    for what, kw in (("sphere leaves", dict(leaf_kind=abi.BSPHERE)), ("sphere nodes", dict(leaf_kind=abi.BSPHERE, node_kind=abi.BSPHERE)),
+                     ("f64 leaves under f32 nodes", dict(leaf_flt=abi.F64, node_flt=abi.F32))):
+        bvh, tdev = _build(tris, **kw)
+        qd = cuda(q.astype(NP_F[bvh.types.leaf_float]))
+        for mode, counts, offsets, index in ((abi.TRIS_COUNT, api._ptr(out), None, None), (abi.TRIS_WRITE, None, api._ptr(out), api._ptr(out))):
+            st = f(C.byref(bvh.struct()), api._ptr(tdev), len(tris), api._ptr(qd), None, nq, mode, 0, counts, offsets, nq, index,
+                   None, None, None, api._stream())
+            torch.cuda.synchronize()
+            assert st == abi.ERR_UNSUPPORTED and (out == -7).all(), (what, mode)
+        with pytest.raises(ValueError):
+            ibvh.triangle_contacts(bvh, tdev, qd)
+        with pytest.raises(ValueError):
+            ibvh.self_intersections(bvh, tdev)
+    bvh, tdev = _build(tris)
+    for mode in (abi.TRIS_COUNT, abi.TRIS_WRITE):   # a bit of `skip` other than bit 0: refused before anything is read
+        st = f(C.byref(bvh.struct()), api._ptr(tdev), len(tris), api._ptr(Q), None, nq, mode, 2, api._ptr(out), api._ptr(out), nq, api._ptr(out),
+               None, None, None, api._stream())
+        torch.cuda.synchronize()
+        assert st == abi.ERR_INVALID_ARG and (out == -7).all()
+    with pytest.raises(ValueError):
+        ibvh.triangle_contacts(bvh, tdev.double(), Q)          # triangles of the other dtype
+    with pytest.raises(ValueError):
+        ibvh.triangle_contacts(bvh, tdev, Q.double())          # queries of the other dtype
+    for bad in (tdev.cpu(), tdev.to(torch.int32), tdev[:, :8], tdev.reshape(-1), tris):
+        with pytest.raises(ValueError):
+            ibvh.triangle_contacts(bvh, bad, Q)
+    for bad in (Q.cpu(), Q.t(), Q[:, :8], Q.reshape(-1), Q.reshape(-1, 3), q, None):
+        with pytest.raises(ValueError):
+            ibvh.triangle_contacts(bvh, tdev, bad)
+    ids = torch.arange(1, nq + 1, dtype=torch.int32, device="cuda")
+    for bad in (ids.cpu(), ids.long(), ids[:nq - 1], ids.reshape(-1, 1), ids.float(), list(range(nq)), 1):
+        with pytest.raises(ValueError):
+            ibvh.triangle_contacts(bvh, tdev, Q, query_ids=bad)
+    with pytest.raises(ValueError, match="outside 1"):
+        ibvh.triangle_contacts(bvh, tdev[:10], Q)              # flag bit 1
+    with pytest.raises(ValueError, match="outside 1"):
+        ibvh.triangle_contacts(bvh, tdev[:10], Q, count_only=True)
+    e = ibvh.triangle_contacts(bvh, tdev, Q[:0])
+    assert e.offsets.tolist() == [0] and e.counts.shape == (0,) and e.index.shape == (0,) and e.index.dtype == torch.int32
+    assert e.mask.shape == (0,) and e.mask.dtype == torch.uint8 and e.points.shape == (0, 2, 3) and e.query.shape == (0,)
+    away = Q + 100
+    far = ibvh.triangle_contacts(bvh, tdev, away)              # no contact at all: no write pass, empty outputs
+    assert far.offsets.tolist() == [0] * (nq + 1) and far.index.shape == (0,) and far.points.shape == (0, 2, 3) and far.query.shape == (0,)
+    assert_one_kernel(lambda: ibvh.triangle_contacts(bvh, tdev, away, presorted=True), "tritri_walk_kernel", "no write pass")
+
+
+# ---- 7. one kernel per pass --------------------------------------------------------------------------------------------
+def test_each_pass_is_one_kernel_of_the_new_translation_unit():
+    tris, q, bf = _reference("torus40", abi.F32)
+    bvh, tdev = _build(tris)
+    Q = cuda(q)
+    assert_one_kernel(lambda: ibvh.triangle_contacts(bvh, tdev, Q, count_only=True, presorted=True), "tritri_walk_kernel")
+    # the write pass straight through the C entry: one launch too
+    got = ibvh.triangle_contacts(bvh, tdev, Q, presorted=True)
+    first = got.offsets[:-1].contiguous()
+    index = torch.zeros_like(got.index)
+    mask = torch.zeros_like(got.mask)
+    call = lambda: lib.call(NAME, C.byref(bvh.struct()), api._ptr(tdev), len(tris), api._ptr(Q), None, len(q), abi.TRIS_WRITE, 0, None,
+                            api._ptr(first), index.shape[0], api._ptr(index), api._ptr(mask), None, None, api._stream())
+    assert_one_kernel(call, "tritri_walk_kernel", "write")
+    assert (index == got.index).all() and (mask == got.mask).all()
