@@ -1572,10 +1572,59 @@ def cast_rays(bvh, triangles, points, directions, t_max=None, any_hit=False, pre
     return RayCast(*_unpermute(order, outs[:3]))
 
 
+# ---- the list queries, sphere_contacts and triangle_contacts: one shape of result, one count / scan / write sequence ----
+class _ContactLists:
+    """Lists of contacts grouped by the item (sphere, query triangle) that owns them, in the caller's order: item i (0-based)
+    owns rows offsets[i] : offsets[i + 1] of every per-contact field; .index is the first of those."""
+
+    def __init__(self, offsets, index):
+        self.offsets, self.index = offsets, index
+        self.counts = offsets[1:] - offsets[:-1]
+        self._owner = None
+
+    def _owner_column(self):
+        """(M,) the 1-based number of the item each row belongs to, computed when first asked for; None after count_only"""
+        if self._owner is None and self.index is not None:
+            torch = _torch()
+            ids = torch.arange(1, self.counts.shape[0] + 1, dtype=torch.int64, device=self.counts.device)
+            self._owner = torch.repeat_interleave(ids, self.counts, output_size=int(self.index.shape[0]))
+        return self._owner
+
+
+def _contact_lists(result, what, bvh, tris, n, walk, tail, outs, count_only):
+    """A list query's two launches, a count and a write, around the scan of the counts -> result(offsets, *output columns),
+    result(offsets) after count_only.  result.ENTRY: (entry, count mode, write mode); a launch is entry(bvh, triangles, *head,
+    n, mode, *tail, counts, offsets, capacity, *outputs, flag, stream).  walk() -> (order, the query's own input tensors in
+    walk order — `head` their pointers; order: that permutation, None = none), called once there is something to walk.
+    outs: (dtype, trailing shape) per output column.  The total is read on the host; if it is 0 there is no write pass."""
+    torch = _torch()
+    entry, count_mode, write_mode = result.ENTRY
+    empty = lambda m: [torch.empty((m,) + shape, dtype=dt, device="cuda") for dt, shape in outs]
+    offsets = torch.zeros(n + 1, dtype=torch.int64, device="cuda")
+    if n == 0:
+        return result(offsets, *([] if count_only else empty(0)))
+    order, inputs = walk()  # (held to the end: the launches read them)
+    head = [_ptr(t) for t in inputs]
+    walked = torch.empty(n, dtype=torch.int64, device="cuda")
+    _mesh_query_call(entry, what, bvh, tris, *head, n, count_mode, *tail, _ptr(walked), None, 0, *[None] * len(outs))
+    # the counts back in the caller's order, scanned there: an item's rows then follow its predecessor's in that order
+    torch.cumsum(_unpermute(order, (walked,))[0], dim=0, out=offsets[1:])
+    if count_only:
+        return result(offsets)
+    total = int(offsets[-1].item())  # the one read between the passes
+    columns = empty(total)
+    if total > 0:
+        first = offsets[:-1] if order is None else offsets[:-1][order]  # ... gathered back into walk order
+        word = _mesh_query_call(entry, what, bvh, tris, *head, n, write_mode, *tail, None, _ptr(first), total, *map(_ptr, columns))
+        if word & 4:
+            raise RuntimeError(f"{what}: the write pass found more contacts than the count pass (inputs changed between them?)")
+    return result(offsets, *columns)
+
+
 # ---------------------------------------------------------------------------------------------
 # sphere-vs-mesh contacts: every triangle within each sphere's radius (ibvh_sphere_contacts; no reference counterpart)
 # ---------------------------------------------------------------------------------------------
-class SphereContacts:
+class SphereContacts(_ContactLists):
     """The contacts of N spheres with a mesh, M in all, grouped by sphere in the caller's order and, within a sphere, in the
     order of the triangles' leaves in the BVH: sphere s (0-based) owns rows offsets[s] : offsets[s + 1].
     .offsets (N + 1,) int64, .counts (N,) int64; per contact .index (M,) the triangle's user index, .distance2 (M,) the
@@ -1585,17 +1634,11 @@ class SphereContacts:
     fields are None."""
 
     def __init__(self, offsets, index=None, distance2=None, point=None, region=None):
-        self.offsets, self.index, self.distance2, self.point, self.region = offsets, index, distance2, point, region
-        self.counts = offsets[1:] - offsets[:-1]
-        self._sphere = None
+        super().__init__(offsets, index)
+        self.distance2, self.point, self.region = distance2, point, region
 
-    @property
-    def sphere(self):
-        if self._sphere is None and self.index is not None:
-            torch = _torch()
-            ids = torch.arange(1, self.counts.shape[0] + 1, dtype=torch.int64, device=self.counts.device)
-            self._sphere = torch.repeat_interleave(ids, self.counts, output_size=int(self.index.shape[0]))
-        return self._sphere
+    sphere = property(_ContactLists._owner_column)
+    ENTRY = ("ibvh_sphere_contacts", abi.SPHERES_COUNT, abi.SPHERES_WRITE)
 
 
 def sphere_contacts(bvh, triangles, centers, radii, count_only=False, presorted=False):
@@ -1627,35 +1670,15 @@ def sphere_contacts(bvh, triangles, centers, radii, count_only=False, presorted=
         r = torch.full((n,), float(radii), dtype=ft, device="cuda")
     else:
         raise ValueError(f"{what}: radii must be a number or an (N,) {ft} tensor on the GPU")
-    offsets = torch.zeros(n + 1, dtype=torch.int64, device="cuda")
-    empty = lambda m: (torch.empty(m, dtype=idt, device="cuda"), torch.empty(m, dtype=ft, device="cuda"),
-                       torch.empty((m, 3), dtype=ft, device="cuda"), torch.empty(m, dtype=torch.uint8, device="cuda"))
-    if n == 0:
-        return SphereContacts(offsets, *(() if count_only else empty(0)))
-    if order is not None:
-        r = r[order]
-    walked = torch.empty(n, dtype=torch.int64, device="cuda")
-    _mesh_query_call("ibvh_sphere_contacts", what, bvh, tris, _ptr(p), _ptr(r), n, abi.SPHERES_COUNT, _ptr(walked), None, 0,
-                     None, None, None, None)
-    # the counts back in the caller's order, scanned there: a sphere's rows then follow its predecessor's in that order
-    torch.cumsum(_unpermute(order, (walked,))[0], dim=0, out=offsets[1:])
-    if count_only:
-        return SphereContacts(offsets)
-    total = int(offsets[-1].item())  # the one read between the passes
-    outs = empty(total)
-    if total > 0:
-        first = offsets[:-1] if order is None else offsets[:-1][order]  # ... gathered back into walk order
-        word = _mesh_query_call("ibvh_sphere_contacts", what, bvh, tris, _ptr(p), _ptr(r), n, abi.SPHERES_WRITE, None,
-                                _ptr(first), total, *[_ptr(o) for o in outs])
-        if word & 4:
-            raise RuntimeError(f"{what}: the write pass found more contacts than the count pass (inputs changed between them?)")
-    return SphereContacts(offsets, *outs)
+    walk = lambda: (order, (p, r if order is None else r[order]))
+    return _contact_lists(SphereContacts, what, bvh, tris, n, walk, tail=(),
+                          outs=((idt, ()), (ft, ()), (ft, (3,)), (torch.uint8, ())), count_only=count_only)
 
 
 # ---------------------------------------------------------------------------------------------
 # triangle-vs-mesh contacts: every mesh triangle each query triangle cuts (ibvh_triangle_contacts; no reference counterpart)
 # ---------------------------------------------------------------------------------------------
-class TriangleContacts:
+class TriangleContacts(_ContactLists):
     """The contacts of N query triangles with a mesh, M in all, grouped by query in the caller's order and, within a query,
     in the order of the triangles' leaves in the BVH: query i (0-based) owns rows offsets[i] : offsets[i + 1].
     .offsets (N + 1,) int64, .counts (N,) int64; per contact .index (M,) the mesh triangle's user index, .mask (M,) uint8 the
@@ -1665,17 +1688,11 @@ class TriangleContacts:
     After count_only=True the per-contact fields are None."""
 
     def __init__(self, offsets, index=None, mask=None, points=None):
-        self.offsets, self.index, self.mask, self.points = offsets, index, mask, points
-        self.counts = offsets[1:] - offsets[:-1]
-        self._query = None
+        super().__init__(offsets, index)
+        self.mask, self.points = mask, points
 
-    @property
-    def query(self):
-        if self._query is None and self.index is not None:
-            torch = _torch()
-            ids = torch.arange(1, self.counts.shape[0] + 1, dtype=torch.int64, device=self.counts.device)
-            self._query = torch.repeat_interleave(ids, self.counts, output_size=int(self.index.shape[0]))
-        return self._query
+    query = property(_ContactLists._owner_column)
+    ENTRY = ("ibvh_triangle_contacts", abi.TRIS_COUNT, abi.TRIS_WRITE)
 
 
 def triangle_contacts(bvh, triangles, queries, query_ids=None, skip_shared_vertices=False, count_only=False, presorted=False):
@@ -1713,31 +1730,13 @@ def triangle_contacts(bvh, triangles, queries, query_ids=None, skip_shared_verti
             raise ValueError(f"{what}: query_ids must be None or an (N,) {idt} tensor on the GPU")
         ids = query_ids.contiguous()
     skip = abi.TRIS_SKIP_SHARED_VERTEX if skip_shared_vertices else 0
-    offsets = torch.zeros(n + 1, dtype=torch.int64, device="cuda")
-    empty = lambda m: (torch.empty(m, dtype=idt, device="cuda"), torch.empty(m, dtype=torch.uint8, device="cuda"),
-                       torch.empty((m, 2, 3), dtype=ft, device="cuda"))
-    if n == 0:
-        return TriangleContacts(offsets, *(() if count_only else empty(0)))
-    order = None if presorted else _morton_order(q[:, :3])
-    if order is not None:
-        q = q[order]
-        ids = None if ids is None else ids[order]
-    walked = torch.empty(n, dtype=torch.int64, device="cuda")
-    _mesh_query_call("ibvh_triangle_contacts", what, bvh, tris, _ptr(q), _ptr(ids), n, abi.TRIS_COUNT, skip, _ptr(walked), None, 0,
-                     None, None, None)
-    # the counts back in the caller's order, scanned there: a query's rows then follow its predecessor's in that order
-    torch.cumsum(_unpermute(order, (walked,))[0], dim=0, out=offsets[1:])
-    if count_only:
-        return TriangleContacts(offsets)
-    total = int(offsets[-1].item())  # the one read between the passes
-    outs = empty(total)
-    if total > 0:
-        first = offsets[:-1] if order is None else offsets[:-1][order]  # ... gathered back into walk order
-        word = _mesh_query_call("ibvh_triangle_contacts", what, bvh, tris, _ptr(q), _ptr(ids), n, abi.TRIS_WRITE, skip, None,
-                                _ptr(first), total, *[_ptr(o) for o in outs])
-        if word & 4:
-            raise RuntimeError(f"{what}: the write pass found more contacts than the count pass (inputs changed between them?)")
-    return TriangleContacts(offsets, *outs)
+    def walk():
+        order = None if presorted else _morton_order(q[:, :3])
+        if order is None:
+            return None, (q, ids)
+        return order, (q[order], None if ids is None else ids[order])
+    return _contact_lists(TriangleContacts, what, bvh, tris, n, walk, tail=(skip,),
+                          outs=((idt, ()), (torch.uint8, ()), (ft, (2, 3))), count_only=count_only)
 
 
 def self_intersections(bvh, triangles, count_only=False):

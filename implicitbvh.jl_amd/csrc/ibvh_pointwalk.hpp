@@ -7,9 +7,11 @@
 // ImplicitBVH.jl is a fixed-volume overlap test (traverse/, raytrace/).
 //
 // For the kernels: the workgroup size, the distance queries' point-box bound (box_bound) and NaN test (hopeless), the walk,
-// and the mesh queries' gather of a leaf's triangle (leaf_triangle).  For the entry points: the rules they share and prepare(),
+// the mesh queries' gather of a leaf's triangle (leaf_triangle), and the list queries' rows (first_row, contact, store_count:
+// the count / write protocol of ibvh_spheres.hip and ibvh_tritri.hip).  For the entry points: the rules they share and prepare(),
 // the one place that applies them, in the one order a call with several faults is refused in; the (T, TN, I) dispatch of a tree
-// with box leaves; the optional radius.  An entry point keeps its own checks (counts, axis, mode, k, outputs) and its launch.
+// with box leaves, and the list queries' (T, TN, I, pass); their two-pass argument rule (passes_ok); the optional radius.  An
+// entry point keeps its own checks (counts, axis, k, skip, which outputs it has) and its launch.
 //
 // A query hands the walk three things: bound(lo, up), its lower bound for a box (box_bound below for the distance queries;
 // 0 / 1 = "the ray can / cannot meet the box" for the crossings; the slab test's entry distance for the ray cast), limit(),
@@ -30,6 +32,7 @@
 #include "ibvh_common.hpp"
 
 #include <limits>
+#include <type_traits>
 
 namespace ibvh {
 namespace pointwalk {
@@ -123,6 +126,29 @@ IBVH_D bool leaf_triangle(const char *rec, const LeafLayout &lay, const T *tris,
     return true;
 }
 
+// The list queries' rows.  Both passes walk alike and meet an item's contacts in the same order; WRITE is the second, which
+// puts contact j of item i in row offsets[i] + j, otherwise the first, which only counts them.  One uint64 serves both: the
+// count pass's one counter, the write pass's running row (wraps, never overflows: a wild offset is only refused).
+template <bool WRITE> IBVH_D uint64_t first_row(const int64_t *offsets, int64_t item) {
+    if constexpr (WRITE) return (uint64_t)offsets[item];
+    else return 0;
+}
+
+// a contact was found: the write pass hands its row to put(row) if it lies below capacity (a negative row is a huge one),
+// else notes `over`, for flag bit 2 when the lane is done; both passes move on to the next row
+template <bool WRITE, class Put> IBVH_D void contact(uint64_t &row, int64_t capacity, bool &over, const Put &put) {
+    if constexpr (WRITE) {
+        if (row < (uint64_t)capacity) put(row);
+        else over = true;
+    }
+    ++row;
+}
+
+// the item's walk is done: the count pass stores how many it met
+template <bool WRITE> IBVH_D void store_count(int64_t *counts, int64_t item, uint64_t row) {
+    if constexpr (!WRITE) counts[item] = (int64_t)row;
+}
+
 // a NaN coordinate makes every d2 NaN and a NaN radius admits nothing: no answer either way, and no bound could prune
 template <class T> IBVH_D bool hopeless(const T *p, T max_d2) {
     return !((p[0] == p[0]) & (p[1] == p[1]) & (p[2] == p[2]) & (max_d2 == max_d2));
@@ -181,6 +207,22 @@ template <class F> int dispatch_box_types(const ibvh_types &t, F &&f) {
     return dispatch_index(t.index_type, [&](auto it) -> int {
         if (t.leaf_float == IBVH_F64) return f(Tag<double>{}, Tag<double>{}, it);
         return t.node_float == IBVH_F64 ? f(Tag<float>{}, Tag<double>{}, it) : f(Tag<float>{}, Tag<float>{}, it);
+    });
+}
+
+// The list queries' two passes.  Their public mode enums are one pair of values, which the rule below relies on.
+static_assert(IBVH_SPHERES_COUNT == 0 && IBVH_SPHERES_WRITE == 1 && IBVH_TRIS_COUNT == 0 && IBVH_TRIS_WRITE == 1, "one pair");
+
+// a valid mode; the count pass needs counts, the write pass offsets and at least one output (else IBVH_ERR_INVALID_ARG)
+inline bool passes_ok(int32_t mode, const void *counts, const void *offsets, bool any_output) {
+    return mode == IBVH_SPHERES_WRITE ? offsets && any_output : mode == IBVH_SPHERES_COUNT && counts;
+}
+
+// dispatch_box_types with the pass as a fourth tag, std::bool_constant<write>: the pass is a template parameter of the
+// kernel, so the counting kernel carries no outputs and reads no offsets
+template <class F> int dispatch_box_types_and_pass(const ibvh_types &t, bool write, F &&f) {
+    return dispatch_box_types(t, [&](auto ft, auto nt, auto it) -> int {
+        return write ? f(ft, nt, it, std::true_type{}) : f(ft, nt, it, std::false_type{});
     });
 }
 

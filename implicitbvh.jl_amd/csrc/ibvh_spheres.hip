@@ -14,12 +14,11 @@
 // writing pass see the same contacts in the same order, and contact j of the one is row j of the other.
 //
 // The walk itself — work mapping, the trail word, the pop, the strict skip — is ibvh_pointwalk.hpp's; the evaluation is
-// ibvh_pointtri.hpp's, the copy ibvh_closest.hip answers with.  Centre, squared radius and the running count live in
+// ibvh_pointtri.hpp's, the copy ibvh_closest.hip answers with; the rows of the two passes and the entry point's two-pass rule
+// are ibvh_pointwalk.hpp's too, shared with ibvh_tritri.hip.  Centre, squared radius and the running count live in
 // registers; a contact goes straight from registers to its row.
 #include "ibvh_pointwalk.hpp"
 #include "ibvh_pointtri.hpp"
-
-#include <type_traits>
 
 namespace ibvh {
 namespace spheres {
@@ -40,9 +39,7 @@ __global__ __launch_bounds__(pointwalk::kBlock) void spheres_walk_kernel(
         const T p[3] = {centers[3 * item], centers[3 * item + 1], centers[3 * item + 2]};
         const T r = radii[item];
         const T r2 = r * r;
-        // the count pass's one counter; the write pass's running row (wraps, never overflows: a wild offset is only refused)
-        uint64_t next = 0;
-        if constexpr (WRITE) next = (uint64_t)offsets[item];
+        uint64_t next = pointwalk::first_row<WRITE>(offsets, item);
         // 0 = the box may hold a contact, 1 = it cannot (false on NaN: such a box is entered)
         auto box = [&](const T *lo, const T *up) -> T { return pointwalk::box_bound(lo, up, p) > r2 ? T(1) : T(0); };
         // only a leaf that passes gathers its triangle (36 / 72 bytes)
@@ -53,21 +50,16 @@ __global__ __launch_bounds__(pointwalk::kBlock) void spheres_walk_kernel(
             if (pointwalk::leaf_triangle(rec, lay, tris, num_triangles, index, tr)) {
                 const T d2 = pointtri::closest_on_triangle(tr, p, q, region);
                 if (d2 <= r2) { // (false on NaN)
-                    if constexpr (WRITE) {
-                        if (next < (uint64_t)capacity) { // (a negative row is a huge one)
-                            if (out_index) out_index[next] = index;
-                            if (out_d2) out_d2[next] = d2;
-                            if (out_q) {
-                                out_q[3 * next] = q[0];
-                                out_q[3 * next + 1] = q[1];
-                                out_q[3 * next + 2] = q[2];
-                            }
-                            if (out_region) out_region[next] = (uint8_t)region;
-                        } else {
-                            over = true;
+                    pointwalk::contact<WRITE>(next, capacity, over, [&](uint64_t row) {
+                        if (out_index) out_index[row] = index;
+                        if (out_d2) out_d2[row] = d2;
+                        if (out_q) {
+                            out_q[3 * row] = q[0];
+                            out_q[3 * row + 1] = q[1];
+                            out_q[3 * row + 2] = q[2];
                         }
-                    }
-                    ++next;
+                        if (out_region) out_region[row] = (uint8_t)region;
+                    });
                 }
             } else {
                 bad = true;
@@ -76,7 +68,7 @@ __global__ __launch_bounds__(pointwalk::kBlock) void spheres_walk_kernel(
         // a negative or NaN radius and a NaN centre touch nothing, and a NaN could not prune
         if ((r >= T(0)) && !pointwalk::hopeless(p, r2))
             pointwalk::walk<BBox<T>, TN>(tree, built_level, leaves, lay, nodes, box, []() { return T(0); }, visit);
-        if constexpr (!WRITE) counts[item] = (int64_t)next;
+        pointwalk::store_count<WRITE>(counts, item, next);
     }
     if (bad && flag) raise_flag(flag, 2u);
     if (over && flag) raise_flag(flag, 4u);
@@ -94,9 +86,7 @@ ibvh_status ibvh_sphere_contacts(const ibvh_bvh *bvh, const void *triangles, int
                                  int64_t capacity, void *contact_index, void *contact_d2, void *contact_point,
                                  void *contact_region, void *flag, void *stream) {
     if (!bvh || num_triangles < 0 || num_spheres < 0 || capacity < 0) return IBVH_ERR_INVALID_ARG;
-    if (mode != IBVH_SPHERES_COUNT && mode != IBVH_SPHERES_WRITE) return IBVH_ERR_INVALID_ARG;
-    const bool write = mode == IBVH_SPHERES_WRITE;
-    if (write ? (!offsets || (!contact_index && !contact_d2 && !contact_point && !contact_region)) : !counts) return IBVH_ERR_INVALID_ARG;
+    if (!pointwalk::passes_ok(mode, counts, offsets, contact_index || contact_d2 || contact_point || contact_region)) return IBVH_ERR_INVALID_ARG;
     // box leaves: the lossless bound needs boxes that contain their triangles' boxes exactly, all the way up
     pointwalk::Prepared pre;
     const bool pointers_ok = (num_triangles == 0 || triangles) && (num_spheres == 0 || (centers && radii));
@@ -115,11 +105,7 @@ ibvh_status ibvh_sphere_contacts(const ibvh_bvh *bvh, const void *triangles, int
         IBVH_LAUNCH_CHECK();
         return IBVH_OK;
     };
-    // the pass is a template parameter: the counting kernel carries no outputs and reads no offsets
-    auto passes = [&](auto ft, auto nt, auto it) -> int {
-        return write ? launch(ft, nt, it, std::true_type{}) : launch(ft, nt, it, std::false_type{});
-    };
-    return (ibvh_status)pointwalk::dispatch_box_types(bvh->types, passes);
+    return (ibvh_status)pointwalk::dispatch_box_types_and_pass(bvh->types, mode == IBVH_SPHERES_WRITE, launch);
 }
 
 } // extern "C"

@@ -13,12 +13,11 @@
 // counting pass and the writing pass see the same contacts in the same order.
 //
 // The walk itself is ibvh_pointwalk.hpp's, the gather its leaf_triangle, the edge test ibvh_raytest.hpp's ray_triangle — the
-// copy ibvh_raytri.hip and ibvh_cast.hip answer with.  Q, its box and the running row live in registers, the six tests name
-// their vertices statically; a contact goes straight from registers to its row.
+// copy ibvh_raytri.hip and ibvh_cast.hip answer with; the rows of the two passes and the entry point's two-pass rule are
+// ibvh_pointwalk.hpp's too, shared with ibvh_spheres.hip.  Q, its box and the running row live in registers, the six tests
+// name their vertices statically; a contact goes straight from registers to its row.
 #include "ibvh_pointwalk.hpp"
 #include "ibvh_raytest.hpp"
-
-#include <type_traits>
 
 namespace ibvh {
 namespace tritri {
@@ -58,9 +57,7 @@ __global__ __launch_bounds__(pointwalk::kBlock) void tritri_walk_kernel(
         }
         I qid = 0;
         if (query_ids) qid = query_ids[item];
-        // the count pass's one counter; the write pass's running row (wraps, never overflows: a wild offset is only refused)
-        uint64_t next = 0;
-        if constexpr (WRITE) next = (uint64_t)offsets[item];
+        uint64_t next = pointwalk::first_row<WRITE>(offsets, item);
         // 0 = the box may hold a contact, 1 = it is apart from Q's (six strict comparisons, false on NaN: such a box is entered)
         auto box = [&](const T *lo, const T *up) -> T {
             const bool apart = (qup[0] < lo[0]) | (qlo[0] > up[0]) | (qup[1] < lo[1]) | (qlo[1] > up[1]) | (qup[2] < lo[2]) | (qlo[2] > up[2]);
@@ -104,28 +101,23 @@ __global__ __launch_bounds__(pointwalk::kBlock) void tritri_walk_kernel(
             seg(K.v + 3, K.v + 6, Q, 16u); // p2 -> p3
             seg(K.v + 6, K.v, Q, 32u);     // p3 -> p1
             if (mask != 0) {
-                if constexpr (WRITE) {
-                    if (next < (uint64_t)capacity) { // (a negative row is a huge one)
-                        if (out_index) out_index[next] = index;
-                        if (out_mask) out_mask[next] = (uint8_t)mask;
-                        if (out_points) {
-                            out_points[6 * next] = first[0];
-                            out_points[6 * next + 1] = first[1];
-                            out_points[6 * next + 2] = first[2];
-                            out_points[6 * next + 3] = last[0];
-                            out_points[6 * next + 4] = last[1];
-                            out_points[6 * next + 5] = last[2];
-                        }
-                    } else {
-                        over = true;
+                pointwalk::contact<WRITE>(next, capacity, over, [&](uint64_t row) {
+                    if (out_index) out_index[row] = index;
+                    if (out_mask) out_mask[row] = (uint8_t)mask;
+                    if (out_points) {
+                        out_points[6 * row] = first[0];
+                        out_points[6 * row + 1] = first[1];
+                        out_points[6 * row + 2] = first[2];
+                        out_points[6 * row + 3] = last[0];
+                        out_points[6 * row + 4] = last[1];
+                        out_points[6 * row + 5] = last[2];
                     }
-                }
-                ++next;
+                });
             }
         };
         // a query with a NaN coordinate touches nothing, and a NaN could not prune
         if (!nan) pointwalk::walk<BBox<T>, TN>(tree, built_level, leaves, lay, nodes, box, []() { return T(0); }, visit);
-        if constexpr (!WRITE) counts[item] = (int64_t)next;
+        pointwalk::store_count<WRITE>(counts, item, next);
     }
     if (bad && flag) raise_flag(flag, 2u);
     if (over && flag) raise_flag(flag, 4u);
@@ -143,10 +135,8 @@ ibvh_status ibvh_triangle_contacts(const ibvh_bvh *bvh, const void *triangles, i
                                    const void *offsets, int64_t capacity, void *contact_index, void *contact_mask,
                                    void *contact_points, void *flag, void *stream) {
     if (!bvh || num_triangles < 0 || num_queries < 0 || capacity < 0) return IBVH_ERR_INVALID_ARG;
-    if (mode != IBVH_TRIS_COUNT && mode != IBVH_TRIS_WRITE) return IBVH_ERR_INVALID_ARG;
     if (skip & ~IBVH_TRIS_SKIP_SHARED_VERTEX) return IBVH_ERR_INVALID_ARG;
-    const bool write = mode == IBVH_TRIS_WRITE;
-    if (write ? (!offsets || (!contact_index && !contact_mask && !contact_points)) : !counts) return IBVH_ERR_INVALID_ARG;
+    if (!pointwalk::passes_ok(mode, counts, offsets, contact_index || contact_mask || contact_points)) return IBVH_ERR_INVALID_ARG;
     // box leaves: the lossless walk needs boxes that contain the boxes below them exactly, all the way up
     pointwalk::Prepared pre;
     const bool pointers_ok = (num_triangles == 0 || triangles) && (num_queries == 0 || queries);
@@ -165,11 +155,7 @@ ibvh_status ibvh_triangle_contacts(const ibvh_bvh *bvh, const void *triangles, i
         IBVH_LAUNCH_CHECK();
         return IBVH_OK;
     };
-    // the pass is a template parameter: the counting kernel carries no outputs and reads no offsets
-    auto passes = [&](auto ft, auto nt, auto it) -> int {
-        return write ? launch(ft, nt, it, std::true_type{}) : launch(ft, nt, it, std::false_type{});
-    };
-    return (ibvh_status)pointwalk::dispatch_box_types(bvh->types, passes);
+    return (ibvh_status)pointwalk::dispatch_box_types_and_pass(bvh->types, mode == IBVH_TRIS_WRITE, launch);
 }
 
 } // extern "C"

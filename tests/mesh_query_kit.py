@@ -1,7 +1,12 @@
-"""What the tests of the four point-walk queries — closest_points, point_crossings, cast_rays, nearest_leaves — share: the type
-tables and meshes, the mesh-BVH builder and the one-kernel check of the GPU tests; the fake ibvh_bvh, the header / Julia
-matchers and the source-text facts about the shared front end (csrc/ibvh_pointwalk.hpp) of the host tests.  Each query's
-checker, hand-made meshes and reference builders stay with its own tests.  Importing this needs no GPU."""
+"""What the tests of the six point-walk queries — closest_points, point_crossings, cast_rays, nearest_leaves, sphere_contacts,
+triangle_contacts — share: the type tables and meshes, the mesh-BVH builder and the one-kernel check of the GPU tests; the fake
+ibvh_bvh, the header / Julia matchers and the source-text facts about the shared front end (csrc/ibvh_pointwalk.hpp) of the
+host tests.  For the two list queries, sphere_contacts and triangle_contacts, also everything about their count / write
+protocol, which is one protocol: the description of a list query (ListQuery), the checkers' re-sorting into a leaf order, the
+two passes through the C entry point, the two comparators, the offsets-and-capacity scenario, the one-kernel-per-pass check
+and the entry points' common argument matrix.  Each query's checker, hand-made meshes and reference builders stay with its
+own tests.  Importing this needs no GPU."""
+import collections
 import ctypes as C
 import os
 import re
@@ -58,6 +63,193 @@ def assert_one_kernel(call, kernel, what=None):
     assert names == {kernel} and count.value == 1, (what, names, count.value)
 
 
+# ---- the list queries: numpy only -----------------------------------------------------------------------------------------------
+# An output column: the checker's field, the Python result's, "index" / "float" (the BVH's types) or "uint8", the shape of a row,
+# and what the tests prefill it with so that 'not written' is visible.  A list query: its C entry point, its one kernel, the
+# name — in the checker (0-based) and the Python result (1-based) — of the column that says whose list a row is in, its two
+# modes, and letter -> Column in the entry point's order of outputs (the index first).
+Column = collections.namedtuple("Column", "checker result dtype shape sentinel")
+ListQuery = collections.namedtuple("ListQuery", "entry kernel owner count write columns")
+
+
+def bits(a):
+    return np.ascontiguousarray(a).tobytes()
+
+
+def in_leaf_order(bf, leaf_order, owner, fields):
+    """`bf` with every owner's list put in another leaf order, for a leaf_order that names every triangle at most once: the
+    same contacts, re-sorted (what brute_force(..., leaf_order) gives, without evaluating again).  fields: the per-contact
+    fields besides `owner` and index; whatever else `bf` holds is per item and stays."""
+    order = np.asarray(leaf_order).astype(np.int64)
+    assert len(np.unique(order)) == len(order)
+    rank = np.full(max(int(order.max(initial=0)), int(bf.index.max(initial=0))) + 1, -1, np.int64)
+    rank[order[order >= 0]] = np.flatnonzero(order >= 0)
+    assert (rank[bf.index] >= 0).all()
+    perm = np.lexsort((rank[bf.index], getattr(bf, owner)))
+    out = type(bf)()
+    vars(out).update(vars(bf))
+    for name in (owner, "index") + tuple(fields):
+        setattr(out, name, getattr(bf, name)[perm])
+    return out
+
+
+def same(query, got, exp, what=None, outs=None):
+    """what two_passes() returned is the checker's `exp`: both statuses, the counts, the total, every column asked for bit
+    for bit, and every other column untouched"""
+    outs = "".join(query.columns) if outs is None else outs
+    assert got["status_count"] == 0 and got["status"] == 0, what
+    n, m = len(exp.counts), len(exp.index)
+    assert (got["counts"][:n] == exp.counts).all() and got["total"] == m, what
+    for k, col in query.columns.items():
+        if k in outs:
+            assert bits(got[k][:m]) == bits(getattr(exp, col.checker).astype(got[k].dtype)), (what, k)
+        else:
+            assert (got[k] == col.sentinel).all(), (what, k)
+
+
+def _host(x):
+    return x.cpu().numpy() if hasattr(x, "cpu") else np.asarray(x)
+
+
+def assert_equal(query, got, exp, what, count_only=False):
+    """a Python result `got` is the checker's `exp`: int64 offsets and counts; after count_only no column at all; otherwise
+    every column's shape, the index by value, the other columns by dtype and bit for bit, and the 1-based owner column"""
+    offsets, counts = _host(got.offsets), _host(got.counts)
+    assert offsets.dtype == counts.dtype == np.int64, what
+    assert (counts == exp.counts).all() and (offsets == exp.offsets).all(), what
+    if count_only:
+        assert all(getattr(got, col.result) is None for col in query.columns.values()) and getattr(got, query.owner) is None, what
+        return
+    m = len(exp.index)
+    for k, col in query.columns.items():
+        g, e = _host(getattr(got, col.result)), getattr(exp, col.checker)
+        assert g.shape == (m,) + col.shape, (what, k)
+        if col.dtype == "index":
+            assert (g == e).all(), (what, k)
+        else:
+            assert g.dtype == e.dtype and bits(g) == bits(e), (what, k)
+    assert (_host(getattr(got, query.owner)) == getattr(exp, query.owner) + 1).all(), what
+
+
+# ---- the list queries: GPU tests ----------------------------------------------------------------------------------------------
+def leaf_order(bvh):
+    return bvh.leaves.index.cpu().numpy().astype(np.int64)
+
+
+def two_passes(query, bvh, tris, head, tail=(), num=None, num_triangles=None, flag=0, outs=None, offsets=None, capacity=None, rows=None):
+    """count, scan on the host, write, straight through the C entry point -> dict: counts, the outputs (prefilled with their
+    sentinel; `rows` of them, default the total), both flag words and both statuses.  head: the item arrays between
+    num_triangles and the number of items (None = a NULL pointer), tail: the arguments between mode and counts."""
+    import torch
+    from implicitbvh_amd import api
+    from test_gpu_parity import cuda
+    outs = "".join(query.columns) if outs is None else outs
+    items = len(head[0])
+    n = items if num is None else num
+    nt = len(tris) if num_triangles is None else num_triangles
+    T = cuda(np.array(tris))   # (copies: the shared reference arrays are read-only)
+    H = [None if h is None else cuda(np.array(h)) for h in head]
+    f = getattr(lib.load(), query.entry)
+    front = [C.byref(bvh.struct()), api._ptr(T), nt] + [api._ptr(h) for h in H] + [n]
+    counts = torch.full((max(items, 1),), -7, dtype=torch.int64, device="cuda")
+    fl = torch.full((2,), flag, dtype=torch.int32, device="cuda")
+    out = {}
+    out["status_count"] = f(*front, query.count, *tail, api._ptr(counts), None, 0, *[None] * len(query.columns),
+                            C.c_void_p(fl.data_ptr()), api._stream())
+    torch.cuda.synchronize()
+    out["counts"] = counts.cpu().numpy()
+    cn = out["counts"][:n] if out["status_count"] == 0 else np.zeros(0, np.int64)
+    total = int(cn.sum())
+    scan = (np.cumsum(cn) - cn).astype(np.int64) if offsets is None else np.asarray(offsets, np.int64)
+    out["offsets"], out["total"] = scan, total
+    m = total if rows is None else rows
+    dtypes = {"index": api._torch_index(bvh.types.index_type), "float": T.dtype, "uint8": torch.uint8}
+    o = {k: torch.full((max(m, 1),) + col.shape, col.sentinel, dtype=dtypes[col.dtype], device="cuda") for k, col in query.columns.items()}
+    Od = cuda(scan if len(scan) else np.zeros(1, np.int64))
+    out["status"] = f(*front, query.write, *tail, None, C.c_void_p(Od.data_ptr()), m if capacity is None else capacity,
+                      *[C.c_void_p(o[k].data_ptr()) if k in outs else None for k in query.columns], C.c_void_p(fl.data_ptr() + 4), api._stream())
+    torch.cuda.synchronize()
+    out.update({k: v.cpu().numpy() for k, v in o.items()})
+    out["flag_count"], out["flag"] = (int(x) for x in fl.cpu().numpy())
+    return out
+
+
+def check_offsets_and_capacity(query, call, exp):
+    """Offsets in a permuted order and the capacity guard.  call(**kw): two_passes() on the inputs `exp` is the checker's
+    result of, in the BVH's leaf order; the caller has made sure that there are contacts enough."""
+    n, total = len(exp.counts), len(exp.index)
+    owner = getattr(exp, query.owner)
+    cols = [(k, getattr(exp, col.checker), col.sentinel) for k, col in query.columns.items()]
+    untouched = lambda got, where=slice(None): all((got[k][where] == sentinel).all() for k, _, sentinel in cols)
+    # the lists laid out in another order of the items: each item's rows land where its offset says
+    perm = np.random.default_rng(9).permutation(n)
+    offs = np.empty(n, np.int64)
+    offs[perm] = np.cumsum(exp.counts[perm]) - exp.counts[perm]
+    assert (np.diff(offs) < 0).any()
+    row = np.repeat(offs, exp.counts) + (np.arange(total) - np.repeat(exp.offsets[:-1], exp.counts))
+    assert sorted(row.tolist()) == list(range(total))
+    got = call(offsets=offs)
+    assert got["status"] == 0 and got["flag"] == 0 and got["total"] == total
+    for k, e, _ in cols:
+        assert bits(got[k][row]) == bits(e.astype(got[k].dtype)), k
+    # capacity one short of the total (the buffers hold the total): exactly the last row keeps its sentinel, bit 2 is raised
+    short = call(capacity=total - 1, rows=total)
+    assert short["status"] == 0 and short["flag"] == 4 and short["flag_count"] == 0
+    for k, e, sentinel in cols:
+        assert bits(short[k][:total - 1]) == bits(e[:total - 1].astype(short[k].dtype)) and (short[k][total - 1] == sentinel).all(), k
+    # ... the same through permuted offsets: the rows >= capacity, wherever their items are
+    cap = total - 37
+    short = call(offsets=offs, capacity=cap, rows=total)
+    keep = row < cap
+    assert short["flag"] == 4 and (~keep).sum() == 37
+    for k, e, _ in cols:
+        assert bits(short[k][row[keep]]) == bits(e[keep].astype(short[k].dtype)), k
+    assert untouched(short, slice(cap, None))
+    # negative rows and rows far beyond are refused alike, never written
+    busy = np.flatnonzero(exp.counts > 0)[:2]
+    wild = offs.copy()
+    wild[busy[0]], wild[busy[1]] = -10 ** 6, 2 ** 62
+    bad = call(offsets=wild, rows=total)
+    ok = ~np.isin(owner, busy)
+    assert bad["status"] == 0 and bad["flag"] == 4 and (~ok).sum() >= 2
+    assert (bad["i"][row[ok]] == exp.index[ok]).all() and (bad["i"][row[~ok]] == query.columns["i"].sentinel).all()
+    # the guard is per ROW, not per item: with an offset of -1 an item's first contact (row -1) is refused and its later
+    # ones land in rows 0, 1, ...; the other items are laid out behind them, so no row is written twice
+    b = int(np.flatnonzero(exp.counts >= 3)[0])
+    cb = int(exp.counts[b])
+    edge = np.empty(n, np.int64)
+    others = np.delete(np.arange(n), b)
+    edge[others] = (cb - 1) + np.cumsum(exp.counts[others]) - exp.counts[others]
+    edge[b] = -1
+    erow = np.repeat(edge, exp.counts) + (np.arange(total) - np.repeat(exp.offsets[:-1], exp.counts))
+    lost = erow < 0
+    assert lost.sum() == 1 and owner[lost] == b and sorted(erow[~lost].tolist()) == list(range(total - 1))
+    got = call(offsets=edge, capacity=total - 1, rows=total)
+    assert got["status"] == 0 and got["flag"] == 4
+    for k, e, sentinel in cols:
+        assert bits(got[k][erow[~lost]]) == bits(e[~lost].astype(got[k].dtype)) and (got[k][total - 1] == sentinel).all(), k
+    # capacity 0: nothing is written
+    zero = call(capacity=0, rows=total)
+    assert zero["status"] == 0 and zero["flag"] == 4 and untouched(zero)
+
+
+def check_each_pass_is_one_kernel(query, bvh, tdev, python_call, head, tail, written):
+    """python_call(count_only=...): the Python query in the given order; its count pass is ONE launch of the query's kernel, and
+    so is the write pass straight through the C entry point — head, tail as for two_passes(), but device tensors —, which
+    writes the `written` columns (letters) as the Python query did"""
+    import torch
+    from implicitbvh_amd import api
+    assert_one_kernel(lambda: python_call(count_only=True), query.kernel)
+    got = python_call(count_only=False)
+    first = got.offsets[:-1].contiguous()
+    mine = {k: torch.zeros_like(getattr(got, query.columns[k].result)) for k in written}
+    call = lambda: lib.call(query.entry, C.byref(bvh.struct()), api._ptr(tdev), tdev.shape[0], *[api._ptr(h) for h in head],
+                            got.counts.shape[0], query.write, *tail, None, api._ptr(first), got.index.shape[0],
+                            *[api._ptr(mine.get(k)) for k in query.columns], None, api._stream())
+    assert_one_kernel(call, query.kernel, "write")
+    assert len(mine) >= 2 and all((mine[k] == getattr(got, query.columns[k].result)).all() for k in mine)
+
+
 # ---- host tests -------------------------------------------------------------------------------------------------------------
 def fake_bvh(leaf_kind=abi.BSPHERE, leaf_float=abi.F32, node_kind=abi.BBOX, node_float=abi.F32, idx=abi.I32, morton=abi.U32, n=5,
              built_level=1, leaves=64, nodes=64):
@@ -109,12 +301,23 @@ def _body(text, start):
     return text[:text.index("\n}\n")]
 
 
-def query_unit(unit, kernel, walks=1, mesh=True, own_gather=False):
-    """The source-text facts about a query's translation unit and the header it shares with the other three -> the unit's
+# the list queries' protocol, which only the shared header spells: the pass as a type, the row's capacity guard and why it
+# is safe, the two-pass argument rule
+PROTOCOL = ("std::true_type{}", "std::false_type{}", "row < (uint64_t)capacity", "a negative row is a huge one",
+            "wraps, never overflows", "mode == IBVH_SPHERES_WRITE ? offsets && any_output : mode == IBVH_SPHERES_COUNT && counts")
+# ... and the unit's use of it, once each
+PROTOCOL_USES = ("pointwalk::first_row<WRITE>(offsets, item)", "pointwalk::contact<WRITE>(next, capacity, over, [&](uint64_t row) {",
+                 "pointwalk::store_count<WRITE>(counts, item, next)", "pointwalk::passes_ok(mode, counts, offsets, ",
+                 "pointwalk::dispatch_box_types_and_pass(bvh->types, mode == ", "raise_flag(flag, 4u)")
+
+
+def query_unit(unit, kernel, walks=1, mesh=True, own_gather=False, lists=False):
+    """The source-text facts about a query's translation unit and the header it shares with the other five -> the unit's
     text.  The Makefile builds it; its ONE launch — of `kernel`, on the shared grid and block size — goes through the profiling
     wrapper and is checked; it calls the shared walk (`walks` times), the shared prologue once and, a mesh query, the shared
     gather (own_gather: spells its statements out once, with the reason), dispatch and raise_flag; it spells none of BANNED and
-    none of FRONT_END itself.  The header defines each shared piece once, refuses in the documented order and dispatches three
+    none of FRONT_END itself.  A list query (lists) dispatches on the pass too and uses each piece of the shared count / write
+    protocol once, which the header defines once and the unit does not spell.  The header defines each shared piece once, refuses in the documented order and dispatches three
     (T, TN) pairs per index type."""
     mk = read("implicitbvh.jl_amd", "csrc", "Makefile")
     assert unit in mk[mk.index("SRCS"):mk.index("OBJS")]
@@ -136,12 +339,22 @@ def query_unit(unit, kernel, walks=1, mesh=True, own_gather=False):
         why = src[src.index("only a leaf that passes gathers its triangle"):src.index("__builtin_memcpy")]
         assert "statements of pointwalk::leaf_triangle" in why and "(DESIGN.md)" in why
         assert "index >= 1 && (int64_t)index <= num_triangles" in why and "index >= 1 && (int64_t)index <= num_triangles" in header
-    assert src.count("pointwalk::dispatch_box_types(") == src.count("raise_flag(flag, 2u)") == int(mesh)
+    assert src.count("pointwalk::dispatch_box_types(") + src.count("pointwalk::dispatch_box_types_and_pass(") == src.count("raise_flag(flag, 2u)") == int(mesh)
+    assert src.count("pointwalk::dispatch_box_types_and_pass(") == int(lists)
+    if lists:
+        for use in PROTOCOL_USES:
+            assert src.count(use) == 1, use
+        for text in PROTOCOL + ("over = true", "++row"):
+            assert text not in src and header.count(text) == 1, text
+        assert "if constexpr" not in src and "++next" not in src
+        assert len(re.findall(r"if \(over && flag\) raise_flag\(flag, 4u\);\n\}", src)) == 1   # ... when the lane is done
     assert ("dispatch_index" in src) == (not mesh)
     # the header: each piece once
     for define in (r"inline bool box_nodes_hold_leaves\(", r"inline bool tree_ok\(", r"inline unsigned grid_blocks\(",
                    r"inline ibvh_status prepare\(", r"IBVH_D bool leaf_triangle\(", r"IBVH_D bool hopeless\(",
-                   r"int dispatch_box_types\(", r"T radius_or_inf\(", r"__builtin_memcpy\("):
+                   r"int dispatch_box_types\(", r"T radius_or_inf\(", r"__builtin_memcpy\(", r"IBVH_D uint64_t first_row\(",
+                   r"IBVH_D void contact\(", r"IBVH_D void store_count\(", r"inline bool passes_ok\(",
+                   r"int dispatch_box_types_and_pass\(", r"static_assert\(IBVH_SPHERES_COUNT == 0 && IBVH_SPHERES_WRITE == 1 && IBVH_TRIS_COUNT == 0 && IBVH_TRIS_WRITE == 1,"):
         assert len(re.findall(define, header)) == 1, define
     prepare = _body(header, "inline ibvh_status prepare(")
     for call in FRONT_END[:-1]:
@@ -157,3 +370,42 @@ def query_unit(unit, kernel, walks=1, mesh=True, own_gather=False):
     assert dispatch.count("dispatch_index(t.index_type") == 1
     assert re.findall(r"f\(Tag<(\w+)>\{\}, Tag<(\w+)>\{\}, it\)", dispatch) == [("double", "double"), ("float", "double"), ("float", "float")]
     return src
+
+
+def check_two_pass_arguments(call, count, write, p, num, outputs, needs, absent, fake):
+    """The part of a list query's argument matrix that is the two-pass protocol's and the shared front end's.  call(base,
+    **changes) -> status, for the bases `count` and `write` — dicts of the entry's arguments under the names bvh, tris, nt,
+    mode, counts, offsets, cap and the query's own; no items, so every accepted call returns before a launch — p: a fake
+    non-NULL pointer; num: the name of the number of items; outputs: the names of the output pointers (`write` sets the
+    first); needs: the names of the item arrays a call with items cannot do without, absent: all of them, as NULL; fake: the
+    query's fake_bvh."""
+    ci = outputs[0]
+    assert call(count) == abi.OK and call(write) == abi.OK             # no items: nothing to do
+    assert call(count, offsets=p, cap=3, **{ci: p}) == abi.OK          # the count pass ignores the write pass's arguments
+    assert call(count, counts=None) == abi.ERR_INVALID_ARG             # no counts in the count pass
+    assert call(write, offsets=None) == abi.ERR_INVALID_ARG            # no offsets in the write pass
+    assert call(write, **{ci: None}) == abi.ERR_INVALID_ARG            # no output in the write pass
+    for one in outputs:                                                # ... any one output will do
+        assert call(write, **{ci: None, one: p}) == abi.OK, one
+    assert call(write, counts=p) == abi.OK and call(write, cap=0) == abi.OK
+    for mode in (-1, 2, 7):
+        assert call(count, mode=mode) == abi.ERR_INVALID_ARG and call(write, mode=mode) == abi.ERR_INVALID_ARG, mode
+    for base in (count, write):
+        for bad in ([dict(bvh=None), dict(nt=-1), {num: -1}, dict(cap=-1), dict(tris=None)] + [{num: 5, name: None} for name in needs]
+                    + [dict(bvh=fake(leaves=None)), dict(bvh=fake(nodes=None)), dict(bvh=fake(built_level=0)), dict(bvh=fake(built_level=5))]):
+            assert call(base, **bad) == abi.ERR_INVALID_ARG, bad
+        assert call(base, tris=None, nt=0) == abi.OK and call(base, **absent) == abi.OK
+        assert call(base, bvh=fake(n=1, nodes=None)) == abi.OK         # a one-leaf tree has no nodes
+        broken = fake()
+        broken.tree.virtual_leaves += 1                                # not an ImplicitTree's shape
+        assert call(base, bvh=broken) == abi.ERR_INVALID_ARG
+        # the accepted types: BBox leaves under BBox nodes of the same or a wider float type, any index type
+        for good in (dict(), dict(leaf_float=abi.F64, node_float=abi.F64), dict(node_float=abi.F64), dict(idx=abi.I64)):
+            assert call(base, bvh=fake(**good)) == abi.OK, good
+        for bad in (dict(leaf_kind=abi.BSPHERE), dict(leaf_kind=abi.BSPHERE, node_kind=abi.BSPHERE), dict(node_kind=abi.BSPHERE),
+                    dict(leaf_float=abi.F64, node_float=abi.F32), dict(leaf_float=2), dict(idx=2)):
+            # (with items to process too: refused, never launched on the fake pointers)
+            assert call(base, bvh=fake(**bad)) == abi.ERR_UNSUPPORTED and call(base, bvh=fake(**bad), **{num: 5}) == abi.ERR_UNSUPPORTED, bad
+        # the entry's own checks come first, the types next, the tree and the pointers last
+        assert call(base, bvh=fake(leaf_kind=abi.BSPHERE), mode=9) == abi.ERR_INVALID_ARG
+        assert call(base, bvh=fake(leaf_kind=abi.BSPHERE, leaves=None), tris=None) == abi.ERR_UNSUPPORTED

@@ -1,11 +1,19 @@
 """Checker of ibvh_sphere_contacts (include/ibvh.h): the brute force over all triangles — the definition of the result — built
 on closest_point_checker's evaluation (the input dtype throughout, every operation rounded once), and the sphere sets the
-tests share.  Per sphere: every triangle k with d2(k, c) <= r * r, in a caller-supplied leaf order.  Host only."""
+tests share.  Per sphere: every triangle k with d2(k, c) <= r * r, in a caller-supplied leaf order.  QUERY describes the
+query to mesh_query_kit, whose in_leaf_order, comparators and two-pass driver serve both list queries.  Host only."""
+import functools
+
 import numpy as np
 
 import closest_point_checker as cpc
+import mesh_query_kit as kit
+from implicitbvh_amd import abi
 
 REGION_NAMES = ("vertex a", "vertex b", "edge ab", "vertex c", "edge ac", "edge bc", "face")
+QUERY = kit.ListQuery("ibvh_sphere_contacts", "spheres_walk_kernel", "sphere", abi.SPHERES_COUNT, abi.SPHERES_WRITE,
+                      {"i": kit.Column("index", "index", "index", (), -7), "d": kit.Column("d2", "distance2", "float", (), -7.0),
+                       "q": kit.Column("point", "point", "float", (3,), -7.0), "g": kit.Column("region", "region", "uint8", (), 249)})
 
 
 class Contacts:
@@ -56,19 +64,7 @@ def brute_force(tris, centers, radii, leaf_order=None, idt=np.int32, chunk=128):
     return out
 
 
-def in_leaf_order(bf, leaf_order):
-    """`bf` with every sphere's list put in another leaf order, for a leaf_order that names every triangle at most once: the
-    same contacts, re-sorted (what brute_force(..., leaf_order) gives, without evaluating again)"""
-    order = np.asarray(leaf_order).astype(np.int64)
-    assert len(np.unique(order)) == len(order)
-    rank = np.full(max(int(order.max(initial=0)), int(bf.index.max(initial=0))) + 1, -1, np.int64)
-    rank[order[order >= 0]] = np.flatnonzero(order >= 0)
-    assert (rank[bf.index] >= 0).all()
-    perm = np.lexsort((rank[bf.index], bf.sphere))
-    out = Contacts()
-    out.counts, out.offsets, out.r2 = bf.counts, bf.offsets, bf.r2
-    out.sphere, out.index, out.d2, out.point, out.region = (a[perm] for a in (bf.sphere, bf.index, bf.d2, bf.point, bf.region))
-    return out
+in_leaf_order = functools.partial(kit.in_leaf_order, owner="sphere", fields=("d2", "point", "region"))   # (r2 is per sphere)
 
 
 def mean_edge(tris):

@@ -18,8 +18,9 @@ import implicitbvh_amd as ibvh  # noqa: E402
 from implicitbvh_amd import abi, api, lib  # noqa: E402
 from implicitbvh_amd.synthetic import torus_mesh  # noqa: E402
 
+import mesh_query_kit as kit  # noqa: E402
 import sphere_contacts_checker as scc  # noqa: E402
-from mesh_query_kit import FLOATS, MESHES, NP_F, NP_I, assert_one_kernel, build as _build, tf as _tf  # noqa: E402
+from mesh_query_kit import FLOATS, MESHES, NP_F, NP_I, bits as _bits, build as _build, leaf_order as _leaf_order, tf as _tf  # noqa: E402
 from test_gpu_parity import cuda  # noqa: E402
 
 NAME = "ibvh_sphere_contacts"
@@ -36,24 +37,14 @@ def _reference(mesh, flt):
     return tris, c, radii, bf
 
 
-def _bits(a):
-    return np.ascontiguousarray(a).tobytes()
+_assert_equal = functools.partial(kit.assert_equal, scc.QUERY)
+_same = functools.partial(kit.same, scc.QUERY)
+SENTINEL = {k: col.sentinel for k, col in scc.QUERY.columns.items()}
 
 
-def _leaf_order(bvh):
-    return bvh.leaves.index.cpu().numpy().astype(np.int64)
-
-
-def _assert_equal(got, exp, what, count_only=False):
-    assert got.offsets.dtype == got.counts.dtype == torch.int64, what
-    assert (got.counts.cpu().numpy() == exp.counts).all() and (got.offsets.cpu().numpy() == exp.offsets).all(), what
-    if count_only:
-        assert got.index is None and got.distance2 is None and got.point is None and got.region is None and got.sphere is None, what
-        return
-    assert got.index.shape == (len(exp.index),) and got.point.shape == (len(exp.index), 3) and got.region.dtype == torch.uint8, what
-    assert (got.index.cpu().numpy() == exp.index).all(), what
-    assert _bits(got.distance2.cpu().numpy()) == _bits(exp.d2) and _bits(got.point.cpu().numpy()) == _bits(exp.point), what
-    assert (got.region.cpu().numpy() == exp.region).all() and (got.sphere.cpu().numpy() == exp.sphere + 1).all(), what
+def _call(bvh, tris, c, r, **kw):
+    """count, scan on the host, write -> dict: counts, the outputs, both flag words and both statuses (kit.two_passes)"""
+    return kit.two_passes(scc.QUERY, bvh, tris, (c, r), **kw)
 
 
 # ---- 1. brute force, whole pipeline ------------------------------------------------------------------------------------
@@ -93,52 +84,6 @@ def test_a_scalar_radius_is_a_radius_search_around_points():
 
 
 # ---- 2. hand-made, straight through the C entry ------------------------------------------------------------------------
-SENTINEL = {"i": -7, "d": -7.0, "q": -7.0, "g": 249}
-
-
-def _call(bvh, tris, c, r, num_triangles=None, flag=0, outs="idqg", num_spheres=None, offsets=None, capacity=None, rows=None):
-    """count, scan on the host, write -> dict: counts, the outputs (prefilled with a sentinel so that 'not written' is
-    visible; `rows` of them, default the total), both flag words and both statuses"""
-    n = len(c) if num_spheres is None else num_spheres
-    nt = len(tris) if num_triangles is None else num_triangles
-    T, Cd, Rd = cuda(np.array(tris)), cuda(c), cuda(r)   # (a copy: the shared reference arrays are read-only)
-    f = getattr(lib.load(), NAME)
-    counts = torch.full((max(len(c), 1),), -7, dtype=torch.int64, device="cuda")
-    fl = torch.full((2,), flag, dtype=torch.int32, device="cuda")
-    out = {}
-    out["status_count"] = f(C.byref(bvh.struct()), api._ptr(T), nt, api._ptr(Cd), api._ptr(Rd), n, abi.SPHERES_COUNT, api._ptr(counts),
-                            None, 0, None, None, None, None, C.c_void_p(fl.data_ptr()), api._stream())
-    torch.cuda.synchronize()
-    out["counts"] = counts.cpu().numpy()
-    cn = out["counts"][:n] if out["status_count"] == 0 else np.zeros(0, np.int64)
-    total = int(cn.sum())
-    scan = (np.cumsum(cn) - cn).astype(np.int64) if offsets is None else np.asarray(offsets, np.int64)
-    out["offsets"], out["total"] = scan, total
-    m = total if rows is None else rows
-    idt = api._torch_index(bvh.types.index_type)
-    o = {"i": torch.full((max(m, 1),), SENTINEL["i"], dtype=idt, device="cuda"), "d": torch.full((max(m, 1),), SENTINEL["d"], dtype=T.dtype, device="cuda"),
-         "q": torch.full((max(m, 1), 3), SENTINEL["q"], dtype=T.dtype, device="cuda"), "g": torch.full((max(m, 1),), SENTINEL["g"], dtype=torch.uint8, device="cuda")}
-    ptr = lambda k: C.c_void_p(o[k].data_ptr()) if k in outs else None
-    Od = cuda(scan if len(scan) else np.zeros(1, np.int64))
-    out["status"] = f(C.byref(bvh.struct()), api._ptr(T), nt, api._ptr(Cd), api._ptr(Rd), n, abi.SPHERES_WRITE, None, C.c_void_p(Od.data_ptr()),
-                      m if capacity is None else capacity, ptr("i"), ptr("d"), ptr("q"), ptr("g"), C.c_void_p(fl.data_ptr() + 4), api._stream())
-    torch.cuda.synchronize()
-    out.update({k: v.cpu().numpy() for k, v in o.items()})
-    out["flag_count"], out["flag"] = (int(x) for x in fl.cpu().numpy())
-    return out
-
-
-def _same(got, exp, what=None, outs="idqg"):
-    assert got["status_count"] == 0 and got["status"] == 0, what
-    n, m = len(exp.counts), len(exp.index)
-    assert (got["counts"][:n] == exp.counts).all() and got["total"] == m, what
-    for k, e in (("i", exp.index), ("d", exp.d2), ("q", exp.point), ("g", exp.region)):
-        if k in outs:
-            assert _bits(got[k][:m]) == _bits(e.astype(got[k].dtype)), (what, k)
-        else:
-            assert (got[k] == SENTINEL[k]).all(), (what, k)
-
-
 UNIT = [0, 0, 0, 1, 0, 0, 0, 1, 0]
 HAND = [UNIT,
         [5, 5, 5, 6, 6, 6, 7, 7, 7],             # zero area: collinear
@@ -189,7 +134,7 @@ def test_hand_made_meshes_through_the_c_entry(n, built_level, flt, idx):
     for outs in subsets:
         _same(_call(bvh, tris, c, r, outs=outs), exp, outs, outs=outs)
     # num_spheres = 0 with a pre-set flag: nothing is touched
-    none = _call(bvh, tris, c, r, num_spheres=0, flag=4, rows=3)
+    none = _call(bvh, tris, c, r, num=0, flag=4, rows=3)
     assert none["status_count"] == 0 and none["status"] == 0 and none["flag_count"] == 4 and none["flag"] == 4
     assert (none["counts"] == -7).all() and all((none[k] == SENTINEL[k]).all() for k in "idqg")
     # num_triangles below the largest leaf index: those leaves are skipped in both passes, bit 1 is raised (never cleared: 4 stays)
@@ -223,55 +168,7 @@ def test_offsets_in_a_permuted_order_and_the_capacity_guard():
     exp = scc.brute_force(tris, c, radii, leaf_order=_leaf_order(bvh), idt=np.int32)
     total = len(exp.index)
     assert total > 1000 and (exp.counts > 0).sum() > 50
-    # the lists laid out in another order of the spheres: each sphere's rows land where its offset says
-    perm = np.random.default_rng(9).permutation(200)
-    offs = np.empty(200, np.int64)
-    offs[perm] = np.cumsum(exp.counts[perm]) - exp.counts[perm]
-    assert (np.diff(offs) < 0).any()
-    row = np.repeat(offs, exp.counts) + (np.arange(total) - np.repeat(exp.offsets[:-1], exp.counts))
-    assert sorted(row.tolist()) == list(range(total))
-    got = _call(bvh, tris, c, radii, offsets=offs)
-    assert got["status"] == 0 and got["flag"] == 0 and got["total"] == total
-    assert (got["i"][row] == exp.index).all() and _bits(got["d"][row]) == _bits(exp.d2) and _bits(got["q"][row]) == _bits(exp.point)
-    assert (got["g"][row] == exp.region).all()
-    # capacity one short of the total (the buffers hold the total): exactly the last row keeps its sentinel, bit 2 is raised
-    short = _call(bvh, tris, c, radii, capacity=total - 1, rows=total)
-    assert short["status"] == 0 and short["flag"] == 4 and short["flag_count"] == 0
-    for k, e in (("i", exp.index), ("d", exp.d2), ("q", exp.point), ("g", exp.region)):
-        assert _bits(short[k][:total - 1]) == _bits(e[:total - 1].astype(short[k].dtype)) and (short[k][total - 1] == SENTINEL[k]).all(), k
-    # ... the same through permuted offsets: the rows >= capacity, wherever their spheres are
-    cap = total - 37
-    short = _call(bvh, tris, c, radii, offsets=offs, capacity=cap, rows=total)
-    keep = row < cap
-    assert short["flag"] == 4 and (~keep).sum() == 37
-    assert (short["i"][row[keep]] == exp.index[keep]).all() and _bits(short["q"][row[keep]]) == _bits(exp.point[keep])
-    assert all((short[k][cap:] == SENTINEL[k]).all() for k in "idqg")
-    # negative rows and rows far beyond are refused alike, never written
-    busy = np.flatnonzero(exp.counts > 0)[:2]
-    wild = offs.copy()
-    wild[busy[0]], wild[busy[1]] = -10 ** 6, 2 ** 62
-    bad = _call(bvh, tris, c, radii, offsets=wild, rows=total)
-    ok = ~np.isin(exp.sphere, busy)
-    assert bad["status"] == 0 and bad["flag"] == 4 and (~ok).sum() >= 2
-    assert (bad["i"][row[ok]] == exp.index[ok]).all() and (bad["i"][row[~ok]] == SENTINEL["i"]).all()
-    # the guard is per ROW, not per sphere: with an offset of -1 a sphere's first contact (row -1) is refused and its later
-    # ones land in rows 0, 1, ...; the other spheres are laid out behind them, so no row is written twice
-    b = int(np.flatnonzero(exp.counts >= 3)[0])
-    cb = int(exp.counts[b])
-    edge = np.empty(200, np.int64)
-    others = np.delete(np.arange(200), b)
-    edge[others] = (cb - 1) + np.cumsum(exp.counts[others]) - exp.counts[others]
-    edge[b] = -1
-    erow = np.repeat(edge, exp.counts) + (np.arange(total) - np.repeat(exp.offsets[:-1], exp.counts))
-    lost = erow < 0
-    assert lost.sum() == 1 and exp.sphere[lost] == b and sorted(erow[~lost].tolist()) == list(range(total - 1))
-    got = _call(bvh, tris, c, radii, offsets=edge, capacity=total - 1, rows=total)
-    assert got["status"] == 0 and got["flag"] == 4
-    for k, e in (("i", exp.index), ("d", exp.d2), ("q", exp.point), ("g", exp.region)):
-        assert _bits(got[k][erow[~lost]]) == _bits(e[~lost].astype(got[k].dtype)) and (got[k][total - 1] == SENTINEL[k]).all(), k
-    # capacity 0: nothing is written
-    zero = _call(bvh, tris, c, radii, capacity=0, rows=total)
-    assert zero["status"] == 0 and zero["flag"] == 4 and all((zero[k] == SENTINEL[k]).all() for k in "idqg")
+    kit.check_offsets_and_capacity(scc.QUERY, functools.partial(_call, bvh, tris, c, radii), exp)
 
 
 # ---- 4. NaN, skin, refit, duplicates -----------------------------------------------------------------------------------
@@ -383,14 +280,6 @@ def test_each_pass_is_one_kernel_of_the_new_translation_unit():
     tris, c, radii, bf = _reference("torus40", abi.F32)
     bvh, tdev = _build(tris)
     P, R = cuda(c).t(), cuda(radii)
-    assert_one_kernel(lambda: ibvh.sphere_contacts(bvh, tdev, P, R, count_only=True, presorted=True), "spheres_walk_kernel")
-    # the write pass straight through the C entry: one launch too
-    got = ibvh.sphere_contacts(bvh, tdev, P, R, presorted=True)
-    Cd = P.t().contiguous()
-    first = got.offsets[:-1].contiguous()
-    index = torch.zeros_like(got.index)
-    region = torch.zeros_like(got.region)
-    call = lambda: lib.call(NAME, C.byref(bvh.struct()), api._ptr(tdev), len(tris), api._ptr(Cd), api._ptr(R), 800, abi.SPHERES_WRITE, None,
-                            api._ptr(first), index.shape[0], api._ptr(index), None, None, api._ptr(region), None, api._stream())
-    assert_one_kernel(call, "spheres_walk_kernel", "write")
-    assert (index == got.index).all() and (region == got.region).all()
+    # the write pass goes straight through the C entry, and writes index and region alone
+    kit.check_each_pass_is_one_kernel(scc.QUERY, bvh, tdev, functools.partial(ibvh.sphere_contacts, bvh, tdev, P, R, presorted=True),
+                                      (P.t().contiguous(), R), (), "ig")

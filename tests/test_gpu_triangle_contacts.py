@@ -19,8 +19,10 @@ import implicitbvh_amd as ibvh  # noqa: E402
 from implicitbvh_amd import abi, api, lib  # noqa: E402
 from implicitbvh_amd.synthetic import torus_mesh  # noqa: E402
 
+import mesh_query_kit as kit  # noqa: E402
 import triangle_contacts_checker as tcc  # noqa: E402
-from mesh_query_kit import FLOATS, MESHES, NP_F, NP_I, assert_one_kernel, build as _build, tf as _tf  # noqa: E402
+from mesh_query_kit import (FLOATS, MESHES, NP_F, NP_I, assert_one_kernel, bits as _bits, build as _build, leaf_order as _leaf_order,  # noqa: E402
+                            tf as _tf)
 from test_gpu_parity import cuda  # noqa: E402
 
 NAME = "ibvh_triangle_contacts"
@@ -51,14 +53,6 @@ def _two_tori():
     return both, once, twice
 
 
-def _bits(a):
-    return np.ascontiguousarray(a).tobytes()
-
-
-def _leaf_order(bvh):
-    return bvh.leaves.index.cpu().numpy().astype(np.int64)
-
-
 def _stored_boxes(bvh, n):
     """the boxes stored in the leaves, by triangle (n, 6)"""
     vol = bvh.leaves.volume.cpu().numpy()
@@ -69,18 +63,15 @@ def _stored_boxes(bvh, n):
     return boxes
 
 
-def _assert_equal(got, exp, what, count_only=False):
-    assert got.offsets.dtype == got.counts.dtype == torch.int64, what
-    assert (got.counts.cpu().numpy() == exp.counts).all() and (got.offsets.cpu().numpy() == exp.offsets).all(), what
-    if count_only:
-        assert got.index is None and got.mask is None and got.points is None and got.query is None, what
-        return
-    m = len(exp.index)
-    assert got.index.shape == (m,) and got.points.shape == (m, 2, 3) and got.mask.dtype == torch.uint8 and got.mask.shape == (m,), what
-    assert (got.index.cpu().numpy() == exp.index).all(), what
-    assert (got.mask.cpu().numpy() == exp.mask).all(), what
-    assert _bits(got.points.cpu().numpy()) == _bits(exp.points), what
-    assert (got.query.cpu().numpy() == exp.query + 1).all(), what
+_assert_equal = functools.partial(kit.assert_equal, tcc.QUERY)
+_same = functools.partial(kit.same, tcc.QUERY)
+SENTINEL = {k: col.sentinel for k, col in tcc.QUERY.columns.items()}
+
+
+def _call(bvh, tris, q, ids=None, skip=0, **kw):
+    """count, scan on the host, write -> dict: counts, the outputs, both flag words and both statuses (kit.two_passes)"""
+    ids = None if ids is None else np.asarray(ids).astype(NP_I[bvh.types.index_type])
+    return kit.two_passes(tcc.QUERY, bvh, tris, (q, ids), (skip,), **kw)
 
 
 # ---- 1. brute force, whole pipeline ------------------------------------------------------------------------------------
@@ -132,54 +123,6 @@ def test_self_intersections_of_two_tori_in_one_mesh(idx):
 
 
 # ---- 3. hand-made, straight through the C entry ------------------------------------------------------------------------
-SENTINEL = {"i": -7, "m": 249, "p": -7.0}
-
-
-def _call(bvh, tris, q, ids=None, skip=0, num_triangles=None, flag=0, outs="imp", num_queries=None, offsets=None, capacity=None, rows=None):
-    """count, scan on the host, write -> dict: counts, the outputs (prefilled with a sentinel so that 'not written' is
-    visible; `rows` of them, default the total), both flag words and both statuses"""
-    n = len(q) if num_queries is None else num_queries
-    nt = len(tris) if num_triangles is None else num_triangles
-    T, Qd = cuda(np.array(tris)), cuda(np.array(q))   # (copies: the shared reference arrays are read-only)
-    idt = api._torch_index(bvh.types.index_type)
-    Id = None if ids is None else torch.as_tensor(np.asarray(ids), device="cuda").to(idt)
-    f = getattr(lib.load(), NAME)
-    counts = torch.full((max(len(q), 1),), -7, dtype=torch.int64, device="cuda")
-    fl = torch.full((2,), flag, dtype=torch.int32, device="cuda")
-    out = {}
-    out["status_count"] = f(C.byref(bvh.struct()), api._ptr(T), nt, api._ptr(Qd), api._ptr(Id), n, abi.TRIS_COUNT, skip, api._ptr(counts),
-                            None, 0, None, None, None, C.c_void_p(fl.data_ptr()), api._stream())
-    torch.cuda.synchronize()
-    out["counts"] = counts.cpu().numpy()
-    cn = out["counts"][:n] if out["status_count"] == 0 else np.zeros(0, np.int64)
-    total = int(cn.sum())
-    scan = (np.cumsum(cn) - cn).astype(np.int64) if offsets is None else np.asarray(offsets, np.int64)
-    out["offsets"], out["total"] = scan, total
-    m = total if rows is None else rows
-    o = {"i": torch.full((max(m, 1),), SENTINEL["i"], dtype=idt, device="cuda"),
-         "m": torch.full((max(m, 1),), SENTINEL["m"], dtype=torch.uint8, device="cuda"),
-         "p": torch.full((max(m, 1), 2, 3), SENTINEL["p"], dtype=T.dtype, device="cuda")}
-    ptr = lambda k: C.c_void_p(o[k].data_ptr()) if k in outs else None
-    Od = cuda(scan if len(scan) else np.zeros(1, np.int64))
-    out["status"] = f(C.byref(bvh.struct()), api._ptr(T), nt, api._ptr(Qd), api._ptr(Id), n, abi.TRIS_WRITE, skip, None, C.c_void_p(Od.data_ptr()),
-                      m if capacity is None else capacity, ptr("i"), ptr("m"), ptr("p"), C.c_void_p(fl.data_ptr() + 4), api._stream())
-    torch.cuda.synchronize()
-    out.update({k: v.cpu().numpy() for k, v in o.items()})
-    out["flag_count"], out["flag"] = (int(x) for x in fl.cpu().numpy())
-    return out
-
-
-def _same(got, exp, what=None, outs="imp"):
-    assert got["status_count"] == 0 and got["status"] == 0, what
-    n, m = len(exp.counts), len(exp.index)
-    assert (got["counts"][:n] == exp.counts).all() and got["total"] == m, what
-    for k, e in (("i", exp.index), ("m", exp.mask), ("p", exp.points)):
-        if k in outs:
-            assert _bits(got[k][:m]) == _bits(e.astype(got[k].dtype)), (what, k)
-        else:
-            assert (got[k] == SENTINEL[k]).all(), (what, k)
-
-
 UNIT = [0, 0, 0, 1, 0, 0, 0, 1, 0]
 HAND = [UNIT,
         [5, 5, 5, 6, 6, 6, 7, 7, 7],             # zero area: collinear
@@ -243,7 +186,7 @@ def test_hand_made_meshes_through_the_c_entry(n, built_level, flt, idx):
     for outs in subsets:
         _same(_call(bvh, tris, q, outs=outs), exp, outs, outs=outs)
     # num_queries = 0 with a pre-set flag: nothing is touched
-    none = _call(bvh, tris, q, num_queries=0, flag=4, rows=3)
+    none = _call(bvh, tris, q, num=0, flag=4, rows=3)
     assert none["status_count"] == 0 and none["status"] == 0 and none["flag_count"] == 4 and none["flag"] == 4
     assert (none["counts"] == -7).all() and all((none[k] == SENTINEL[k]).all() for k in "imp")
     # num_triangles below the largest leaf index: those leaves are skipped in both passes, bit 1 is raised (never cleared: 4 stays)
@@ -292,54 +235,7 @@ def test_offsets_in_a_permuted_order_and_the_capacity_guard():
     exp = tcc.in_leaf_order(bf, _leaf_order(bvh))
     total = len(exp.index)
     assert total > 800 and (exp.counts > 0).sum() > 150
-    # the lists laid out in another order of the queries: each query's rows land where its offset says
-    perm = np.random.default_rng(9).permutation(nq)
-    offs = np.empty(nq, np.int64)
-    offs[perm] = np.cumsum(exp.counts[perm]) - exp.counts[perm]
-    assert (np.diff(offs) < 0).any()
-    row = np.repeat(offs, exp.counts) + (np.arange(total) - np.repeat(exp.offsets[:-1], exp.counts))
-    assert sorted(row.tolist()) == list(range(total))
-    got = _call(bvh, tris, q, offsets=offs)
-    assert got["status"] == 0 and got["flag"] == 0 and got["total"] == total
-    assert (got["i"][row] == exp.index).all() and (got["m"][row] == exp.mask).all() and _bits(got["p"][row]) == _bits(exp.points)
-    # capacity one short of the total (the buffers hold the total): exactly the last row keeps its sentinel, bit 2 is raised
-    short = _call(bvh, tris, q, capacity=total - 1, rows=total)
-    assert short["status"] == 0 and short["flag"] == 4 and short["flag_count"] == 0
-    for k, e in (("i", exp.index), ("m", exp.mask), ("p", exp.points)):
-        assert _bits(short[k][:total - 1]) == _bits(e[:total - 1].astype(short[k].dtype)) and (short[k][total - 1] == SENTINEL[k]).all(), k
-    # ... the same through permuted offsets: the rows >= capacity, wherever their queries are
-    cap = total - 37
-    short = _call(bvh, tris, q, offsets=offs, capacity=cap, rows=total)
-    keep = row < cap
-    assert short["flag"] == 4 and (~keep).sum() == 37
-    assert (short["i"][row[keep]] == exp.index[keep]).all() and _bits(short["p"][row[keep]]) == _bits(exp.points[keep])
-    assert all((short[k][cap:] == SENTINEL[k]).all() for k in "imp")
-    # negative rows and rows far beyond are refused alike, never written
-    busy = np.flatnonzero(exp.counts > 0)[:2]
-    wild = offs.copy()
-    wild[busy[0]], wild[busy[1]] = -10 ** 6, 2 ** 62
-    bad = _call(bvh, tris, q, offsets=wild, rows=total)
-    ok = ~np.isin(exp.query, busy)
-    assert bad["status"] == 0 and bad["flag"] == 4 and (~ok).sum() >= 2
-    assert (bad["i"][row[ok]] == exp.index[ok]).all() and (bad["i"][row[~ok]] == SENTINEL["i"]).all()
-    # the guard is per ROW, not per query: with an offset of -1 a query's first contact (row -1) is refused and its later
-    # ones land in rows 0, 1, ...; the other queries are laid out behind them, so no row is written twice
-    b = int(np.flatnonzero(exp.counts >= 3)[0])
-    cb = int(exp.counts[b])
-    edge = np.empty(nq, np.int64)
-    others = np.delete(np.arange(nq), b)
-    edge[others] = (cb - 1) + np.cumsum(exp.counts[others]) - exp.counts[others]
-    edge[b] = -1
-    erow = np.repeat(edge, exp.counts) + (np.arange(total) - np.repeat(exp.offsets[:-1], exp.counts))
-    lost = erow < 0
-    assert lost.sum() == 1 and exp.query[lost] == b and sorted(erow[~lost].tolist()) == list(range(total - 1))
-    got = _call(bvh, tris, q, offsets=edge, capacity=total - 1, rows=total)
-    assert got["status"] == 0 and got["flag"] == 4
-    for k, e in (("i", exp.index), ("m", exp.mask), ("p", exp.points)):
-        assert _bits(got[k][erow[~lost]]) == _bits(e[~lost].astype(got[k].dtype)) and (got[k][total - 1] == SENTINEL[k]).all(), k
-    # capacity 0: nothing is written
-    zero = _call(bvh, tris, q, capacity=0, rows=total)
-    assert zero["status"] == 0 and zero["flag"] == 4 and all((zero[k] == SENTINEL[k]).all() for k in "imp")
+    kit.check_offsets_and_capacity(tcc.QUERY, functools.partial(_call, bvh, tris, q), exp)
 
 
 # ---- 5. skin and refit -------------------------------------------------------------------------------------------------
@@ -428,13 +324,6 @@ def test_each_pass_is_one_kernel_of_the_new_translation_unit():
     tris, q, bf = _reference("torus40", abi.F32)
     bvh, tdev = _build(tris)
     Q = cuda(q)
-    assert_one_kernel(lambda: ibvh.triangle_contacts(bvh, tdev, Q, count_only=True, presorted=True), "tritri_walk_kernel")
-    # the write pass straight through the C entry: one launch too
-    got = ibvh.triangle_contacts(bvh, tdev, Q, presorted=True)
-    first = got.offsets[:-1].contiguous()
-    index = torch.zeros_like(got.index)
-    mask = torch.zeros_like(got.mask)
-    call = lambda: lib.call(NAME, C.byref(bvh.struct()), api._ptr(tdev), len(tris), api._ptr(Q), None, len(q), abi.TRIS_WRITE, 0, None,
-                            api._ptr(first), index.shape[0], api._ptr(index), api._ptr(mask), None, None, api._stream())
-    assert_one_kernel(call, "tritri_walk_kernel", "write")
-    assert (index == got.index).all() and (mask == got.mask).all()
+    # the write pass goes straight through the C entry, and writes index and mask alone
+    kit.check_each_pass_is_one_kernel(tcc.QUERY, bvh, tdev, functools.partial(ibvh.triangle_contacts, bvh, tdev, Q, presorted=True),
+                                      (Q, None), (0,), "im")

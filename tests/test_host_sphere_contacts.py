@@ -55,10 +55,10 @@ def test_binding_table_makefile_launch_and_python_surface():
     assert hasattr(lib.load(), NAME), "libibvh.so exports " + NAME
     for name in ("sphere_contacts", "SphereContacts"):
         assert name in ibvh.__all__ and callable(getattr(ibvh, name))
-    src = kit.query_unit(UNIT, "spheres::spheres_walk_kernel")
-    # one kernel template for both passes, the pass a template parameter reached through the two bool types
+    src = kit.query_unit(UNIT, "spheres::spheres_walk_kernel", lists=True)
+    # one kernel template for both passes, the pass a template parameter reached through the two bool types — which the shared
+    # header spells, once, with the rest of the two-pass protocol (kit.PROTOCOL, checked by query_unit)
     assert len(re.findall(r"__global__", src)) == 1 and "template <class T, class TN, class I, bool WRITE>" in src
-    assert "std::true_type{}" in src and "std::false_type{}" in src
     # the crossings query's way of keeping leaf order: a 0 / 1 bound under a constant limit of 0
     assert "pointwalk::box_bound(lo, up, p) > r2 ? T(1) : T(0)" in src and "[]() { return T(0); }" in src
     assert "raise_flag(flag, 4u)" in src and "hopeless(p, r2)" in src and "r >= T(0)" in src
@@ -103,36 +103,8 @@ def test_entry_point_validates_its_arguments_before_any_launch():
         bvh = C.byref(a["bvh"]) if a["bvh"] is not None else None
         return f(bvh, a["tris"], a["nt"], a["c"], a["r"], a["ns"], a["mode"], a["counts"], a["offsets"], a["cap"], a["ci"], a["cd"],
                  a["cq"], a["cr"], a["flag"], a["stream"])
-    assert call(count) == abi.OK and call(write) == abi.OK             # num_spheres = 0: nothing to do
-    assert call(count, offsets=p, ci=p, cap=3) == abi.OK               # the count pass ignores the write pass's arguments
-    assert call(count, counts=None) == abi.ERR_INVALID_ARG             # no counts in the count pass
-    assert call(write, offsets=None) == abi.ERR_INVALID_ARG            # no offsets in the write pass
-    assert call(write, ci=None) == abi.ERR_INVALID_ARG                 # no output in the write pass
-    for one in ("ci", "cd", "cq", "cr"):                               # ... any one output will do
-        assert call(write, **{"ci": None, one: p}) == abi.OK, one
-    assert call(write, counts=p) == abi.OK and call(write, cap=0) == abi.OK
-    for mode in (-1, 2, 7):
-        assert call(count, mode=mode) == abi.ERR_INVALID_ARG and call(write, mode=mode) == abi.ERR_INVALID_ARG, mode
-    for base in (count, write):
-        for bad in (dict(bvh=None), dict(nt=-1), dict(ns=-1), dict(cap=-1), dict(tris=None), dict(ns=5, c=None), dict(ns=5, r=None),
-                    dict(bvh=_fake_bvh(leaves=None)), dict(bvh=_fake_bvh(nodes=None)), dict(bvh=_fake_bvh(built_level=0)),
-                    dict(bvh=_fake_bvh(built_level=5))):
-            assert call(base, **bad) == abi.ERR_INVALID_ARG, bad
-        assert call(base, tris=None, nt=0) == abi.OK and call(base, c=None, r=None) == abi.OK
-        assert call(base, bvh=_fake_bvh(n=1, nodes=None)) == abi.OK    # a one-leaf tree has no nodes
-        broken = _fake_bvh()
-        broken.tree.virtual_leaves += 1                                # not an ImplicitTree's shape
-        assert call(base, bvh=broken) == abi.ERR_INVALID_ARG
-        # the accepted types: BBox leaves under BBox nodes of the same or a wider float type, any index type
-        for good in (dict(), dict(leaf_float=abi.F64, node_float=abi.F64), dict(node_float=abi.F64), dict(idx=abi.I64)):
-            assert call(base, bvh=_fake_bvh(**good)) == abi.OK, good
-        for bad in (dict(leaf_kind=abi.BSPHERE), dict(leaf_kind=abi.BSPHERE, node_kind=abi.BSPHERE), dict(node_kind=abi.BSPHERE),
-                    dict(leaf_float=abi.F64, node_float=abi.F32), dict(leaf_float=2), dict(idx=2)):
-            # (with spheres to process too: refused, never launched on the fake pointers)
-            assert call(base, bvh=_fake_bvh(**bad)) == abi.ERR_UNSUPPORTED and call(base, bvh=_fake_bvh(**bad), ns=5) == abi.ERR_UNSUPPORTED, bad
-        # the entry's own checks come first, the types next, the tree and the pointers last
-        assert call(base, bvh=_fake_bvh(leaf_kind=abi.BSPHERE), mode=9) == abi.ERR_INVALID_ARG
-        assert call(base, bvh=_fake_bvh(leaf_kind=abi.BSPHERE, leaves=None), tris=None) == abi.ERR_UNSUPPORTED
+    kit.check_two_pass_arguments(call, count, write, p, "ns", ("ci", "cd", "cq", "cr"), needs=("c", "r"), absent=dict(c=None, r=None),
+                                 fake=_fake_bvh)
 
 
 # ---- the checker --------------------------------------------------------------------------------------------------------

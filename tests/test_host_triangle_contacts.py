@@ -18,7 +18,7 @@ from implicitbvh_amd.synthetic import torus_mesh
 
 import mesh_query_kit as kit
 import triangle_contacts_checker as tcc
-from mesh_query_kit import MESHES
+from mesh_query_kit import MESHES, bits as _bits
 
 NAME = "ibvh_triangle_contacts"
 UNIT = "ibvh_tritri.hip"
@@ -66,10 +66,10 @@ def test_binding_table_makefile_launch_and_python_surface():
     assert hasattr(lib.load(), NAME), "libibvh.so exports " + NAME
     for name in ("triangle_contacts", "TriangleContacts", "self_intersections"):
         assert name in ibvh.__all__ and callable(getattr(ibvh, name))
-    src = kit.query_unit(UNIT, "tritri::tritri_walk_kernel")
-    # one kernel template for both passes, the pass a template parameter reached through the two bool types
+    src = kit.query_unit(UNIT, "tritri::tritri_walk_kernel", lists=True)
+    # one kernel template for both passes, the pass a template parameter reached through the two bool types — which the shared
+    # header spells, once, with the rest of the two-pass protocol (kit.PROTOCOL, checked by query_unit)
     assert len(re.findall(r"__global__", src)) == 1 and "template <class T, class TN, class I, bool WRITE>" in src
-    assert "std::true_type{}" in src and "std::false_type{}" in src
     # the crossings query's way of keeping leaf order: a 0 / 1 bound under a constant limit of 0
     assert "return apart ? T(1) : T(0);" in src and "[]() { return T(0); }" in src
     assert "raise_flag(flag, 4u)" in src and "skip & ~IBVH_TRIS_SKIP_SHARED_VERTEX" in src
@@ -127,52 +127,20 @@ def test_entry_point_validates_its_arguments_before_any_launch():
         bvh = C.byref(a["bvh"]) if a["bvh"] is not None else None
         return f(bvh, a["tris"], a["nt"], a["q"], a["ids"], a["nq"], a["mode"], a["skip"], a["counts"], a["offsets"], a["cap"], a["ci"],
                  a["cm"], a["cp"], a["flag"], a["stream"])
-    assert call(count) == abi.OK and call(write) == abi.OK             # num_queries = 0: nothing to do
-    assert call(count, offsets=p, ci=p, cap=3) == abi.OK               # the count pass ignores the write pass's arguments
+    kit.check_two_pass_arguments(call, count, write, p, "nq", ("ci", "cm", "cp"), needs=("q",), absent=dict(q=None), fake=_fake_bvh)
+    # what is this query's own: the optional ids, and `skip`, any bit of which other than bit 0 is refused
     assert call(count, ids=p) == abi.OK and call(write, ids=p) == abi.OK
     assert call(count, skip=1) == abi.OK and call(write, skip=abi.TRIS_SKIP_SHARED_VERTEX) == abi.OK
-    assert call(count, counts=None) == abi.ERR_INVALID_ARG             # no counts in the count pass
-    assert call(write, offsets=None) == abi.ERR_INVALID_ARG            # no offsets in the write pass
-    assert call(write, ci=None) == abi.ERR_INVALID_ARG                 # no output in the write pass
-    for one in ("ci", "cm", "cp"):                                     # ... any one output will do
-        assert call(write, **{"ci": None, one: p}) == abi.OK, one
-    assert call(write, counts=p) == abi.OK and call(write, cap=0) == abi.OK
-    for mode in (-1, 2, 7):
-        assert call(count, mode=mode) == abi.ERR_INVALID_ARG and call(write, mode=mode) == abi.ERR_INVALID_ARG, mode
-    for skip in (2, 3, 4, -1, 1 << 30):                                # any bit of `skip` other than bit 0
+    for skip in (2, 3, 4, -1, 1 << 30):
         assert call(count, skip=skip) == abi.ERR_INVALID_ARG and call(write, skip=skip) == abi.ERR_INVALID_ARG, skip
-    for base in (count, write):
-        for bad in (dict(bvh=None), dict(nt=-1), dict(nq=-1), dict(cap=-1), dict(tris=None), dict(nq=5, q=None),
-                    dict(bvh=_fake_bvh(leaves=None)), dict(bvh=_fake_bvh(nodes=None)), dict(bvh=_fake_bvh(built_level=0)),
-                    dict(bvh=_fake_bvh(built_level=5))):
-            assert call(base, **bad) == abi.ERR_INVALID_ARG, bad
-        assert call(base, tris=None, nt=0) == abi.OK and call(base, q=None) == abi.OK
-        assert call(base, bvh=_fake_bvh(n=1, nodes=None)) == abi.OK    # a one-leaf tree has no nodes
-        broken = _fake_bvh()
-        broken.tree.virtual_leaves += 1                                # not an ImplicitTree's shape
-        assert call(base, bvh=broken) == abi.ERR_INVALID_ARG
-        # the accepted types: BBox leaves under BBox nodes of the same or a wider float type, any index type
-        for good in (dict(), dict(leaf_float=abi.F64, node_float=abi.F64), dict(node_float=abi.F64), dict(idx=abi.I64)):
-            assert call(base, bvh=_fake_bvh(**good)) == abi.OK, good
-        for bad in (dict(leaf_kind=abi.BSPHERE), dict(leaf_kind=abi.BSPHERE, node_kind=abi.BSPHERE), dict(node_kind=abi.BSPHERE),
-                    dict(leaf_float=abi.F64, node_float=abi.F32), dict(leaf_float=2), dict(idx=2)):
-            # (with queries to process too: refused, never launched on the fake pointers)
-            assert call(base, bvh=_fake_bvh(**bad)) == abi.ERR_UNSUPPORTED and call(base, bvh=_fake_bvh(**bad), nq=5) == abi.ERR_UNSUPPORTED, bad
-        # the entry's own checks come first, the types next, the tree and the pointers last
-        assert call(base, bvh=_fake_bvh(leaf_kind=abi.BSPHERE), mode=9) == abi.ERR_INVALID_ARG
+    for base in (count, write):   # ... among the entry's own checks, which come before the types
         assert call(base, bvh=_fake_bvh(leaf_kind=abi.BSPHERE), skip=2, nq=5) == abi.ERR_INVALID_ARG
         assert call(base, bvh=_fake_bvh(leaf_kind=abi.BSPHERE), cap=-1, nq=5) == abi.ERR_INVALID_ARG
-        assert call(base, bvh=_fake_bvh(leaf_kind=abi.BSPHERE, leaves=None), tris=None) == abi.ERR_UNSUPPORTED
         assert call(base, bvh=_fake_bvh(leaf_float=abi.F64, node_float=abi.F32, built_level=0), q=None, nq=5) == abi.ERR_UNSUPPORTED
 
 
 # ---- 5. the checker on hand-made pairs ---------------------------------------------------------------------------------
-FLAT = [0, 0, 0, 1, 0, 0, 0, 1, 0]                           # in the plane z = 0
-PIERCING = [0.25, 0.25, -1, 0.25, 0.25, 1, 2, 2, 1]          # its edge ab goes through FLAT, FLAT's edge p2p3 through it
-TOUCHING = [0.25, 0.25, 0, 0.25, 0.25, 1, 1, 1, 1]           # its vertex a lies on FLAT's face
-COPLANAR = [0.125, 0.125, 0, 0.75, 0.125, 0, 0.125, 0.75, 0]  # overlaps FLAT in its plane
-DISJOINT = [0.25, 0.25, 0.5, 0.25, 0.25, 1, 2, 2, 1]          # boxes overlap, nothing meets
-FAR = [5, 5, 5, 6, 5, 5, 5, 6, 5]                             # boxes apart
+from triangle_contacts_checker import COPLANAR, DISJOINT, FAR, FLAT, PIERCING, TOUCHING  # noqa: E402  (the hand-made triangles)
 
 
 def _pair(q, k, dt, **kw):
@@ -261,10 +229,6 @@ def test_query_sets_meet_the_gpu_tests_non_vacuity_conditions(mesh, dt):
     assert (np.diff(rank[moved.index])[np.diff(moved.query) == 0] > 0).all()
     again = tcc.in_leaf_order(bf, perm)
     assert (again.index == moved.index).all() and _bits(again.points) == _bits(moved.points)
-
-
-def _bits(a):
-    return np.ascontiguousarray(a).tobytes()
 
 
 def test_self_test_of_two_tori_in_one_mesh():

@@ -1,11 +1,19 @@
 """Checker of ibvh_triangle_contacts (include/ibvh.h): the brute force over all triangles — the definition of the result —
 built on ray_triangle_checker's evaluation (the input dtype throughout, every operation rounded once), and the query sets the
 tests share.  Per query triangle Q: every mesh triangle K whose stored leaf box is not apart from Q's box and that one of the
-six edge-against-triangle tests finds, in a caller-supplied leaf order.  Host only."""
+six edge-against-triangle tests finds, in a caller-supplied leaf order.  QUERY describes the query to mesh_query_kit, whose
+in_leaf_order, comparators and two-pass driver serve both list queries.  Host only."""
+import functools
+
 import numpy as np
 
+import mesh_query_kit as kit
 import ray_triangle_checker as rtc
+from implicitbvh_amd import abi
 
+QUERY = kit.ListQuery("ibvh_triangle_contacts", "tritri_walk_kernel", "query", abi.TRIS_COUNT, abi.TRIS_WRITE,
+                      {"i": kit.Column("index", "index", "index", (), -7), "m": kit.Column("mask", "mask", "uint8", (), 249),
+                       "p": kit.Column("points", "points", "float", (2, 3), -7.0)})
 BIT_NAMES = ("a->b against K", "b->c against K", "c->a against K", "p1->p2 against Q", "p2->p3 against Q", "p3->p1 against Q")
 
 
@@ -117,19 +125,7 @@ def brute_force(tris, queries, leaf_order=None, leaf_boxes=None, query_ids=None,
     return out
 
 
-def in_leaf_order(bf, leaf_order):
-    """`bf` with every query's list put in another leaf order, for a leaf_order that names every triangle at most once: the
-    same contacts, re-sorted (what brute_force(..., leaf_order) gives, without evaluating again)"""
-    order = np.asarray(leaf_order).astype(np.int64)
-    assert len(np.unique(order)) == len(order)
-    rank = np.full(max(int(order.max(initial=0)), int(bf.index.max(initial=0))) + 1, -1, np.int64)
-    rank[order[order >= 0]] = np.flatnonzero(order >= 0)
-    assert (rank[bf.index] >= 0).all()
-    perm = np.lexsort((rank[bf.index], bf.query))
-    out = Contacts()
-    out.counts, out.offsets = bf.counts, bf.offsets
-    out.query, out.index, out.mask, out.points = (a[perm] for a in (bf.query, bf.index, bf.mask, bf.points))
-    return out
+in_leaf_order = functools.partial(kit.in_leaf_order, owner="query", fields=("mask", "points"))
 
 
 def swap_mask(mask):
@@ -139,6 +135,13 @@ def swap_mask(mask):
 
 
 # ---- the shared inputs -------------------------------------------------------------------------------------------------
+# hand-made triangles of the host tests
+FLAT = [0, 0, 0, 1, 0, 0, 0, 1, 0]                           # in the plane z = 0
+PIERCING = [0.25, 0.25, -1, 0.25, 0.25, 1, 2, 2, 1]          # its edge ab goes through FLAT, FLAT's edge p2p3 through it
+TOUCHING = [0.25, 0.25, 0, 0.25, 0.25, 1, 1, 1, 1]           # its vertex a lies on FLAT's face
+COPLANAR = [0.125, 0.125, 0, 0.75, 0.125, 0, 0.125, 0.75, 0]  # overlaps FLAT in its plane
+DISJOINT = [0.25, 0.25, 0.5, 0.25, 0.25, 1, 2, 2, 1]          # boxes overlap, nothing meets
+FAR = [5, 5, 5, 6, 5, 5, 5, 6, 5]                             # boxes apart
 SHIFT = (0.9, 0.05, 0.02)
 ANGLE = 0.5
 SLICERS = [[-3, -3, 0.013, 3, -3, 0.021, 0.1, 3, 0.017],
