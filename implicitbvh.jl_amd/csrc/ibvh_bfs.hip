@@ -75,8 +75,13 @@ inline bool narrow_arg_ok(int32_t narrow, bool rays) {
 // pairs, fetched once — and only the passing ones reach the queue (about a third).  The same pairs are checked as in
 // the reference, one launch earlier: num_checks (every generated pair, bfs/traverse_single.jl:25,48) and the
 // contact set are unchanged; queue traffic and volume fetches drop by 3 - 4 x.
-// A policy = check(pair, result) (does the pair pass at its level? `result`: what goes into the queue — the pair
-// itself, or the contact at leaf level) + children(pair, out) (the next level's pairs of a passing pair).
+// A policy is one level of one traversal, with the same members in all three:
+//   safe()                               a pair of its level that is always real, for lanes beyond the queue's end
+//   load(s), test(s, x, res)             the operands of the pair s of its level, and the check itself: does s
+//                                        pass?  `res`: what goes into the queue — s, or the contact at leaf level
+//   load_sides(s, parent),               the volumes of all children of the PARENT-level pair s, and the check of the
+//   test_sides(c, x, res, parent)        child c among them
+//   children(s, out)                     the next level's pairs of a passing pair s
 // ------------------------------------------------------------------------------------------
 // Register storage for a node volume OR a leaf volume, whichever the launch's (uniform) level flag says: what a lane
 // prefetches for a child stays as small as the larger of the two instead of holding both.
@@ -91,6 +96,87 @@ template <class A, class B> struct Either {
     }
 };
 
+// A volume at a tree position is an Either plus (leaf levels only) the leaf's user index.  What a check needs from memory
+// is fetched UNCONDITIONALLY (`implicit` is always a valid position of its level: the kernel hands over a real child or
+// safe()): every lane's loads for all its <= 4 children are in flight before the first test — four dependent round
+// trips per lane otherwise, and the kernel is bound by exactly that latency.
+// The two parts are filled in place, where the caller keeps them: a value returned and copied into its slot, or another
+// arrangement of the slots, costs the widest volume types VGPRs and occupancy.
+// (`is_leaf` is uniform over the launch; `with_index` = false where no check of the step reads the index)
+template <class L, class N, class I>
+IBVH_D void fetch(Either<N, L> &v, I &idx, const TreeRef<L, N> &t, bool is_leaf, int64_t implicit, bool with_index = true) {
+    if (is_leaf) {
+        const char *r = t.leaf_rec(implicit);
+        v.set(load_vol<L>(r));
+        if (with_index) idx = load_index<I>(r, t.lay);
+    } else {
+        v.set(t.node(implicit));
+    }
+}
+// The two children of the source position `p`, [0] the left and [1] the right one (`t` is at the CHILDREN's level).  A
+// virtual right child re-reads the left one (never selected); so does a side that did not descend in the parent step
+// (PairStep's one-sided phases): it holds its one position twice.
+template <class L, class N, class I>
+IBVH_D void fetch_children(Either<N, L> (&v)[2], I (&idx)[2], const TreeRef<L, N> &t, bool is_leaf, int64_t p, bool descended) {
+    const int64_t first = int64_t(1) << (t.level - 1), nreal = level_num_real(t.levels, t.virtual_leaves, t.level);
+    const int64_t c0 = descended ? 2 * p : p;
+    const int64_t c1 = (descended && (c0 + 1 - first) < nreal) ? c0 + 1 : c0;
+#pragma unroll
+    for (int k = 0; k < 2; ++k) fetch(v[k], idx[k], t, is_leaf, k ? c1 : c0);
+}
+// ... and which of the two the child position `c` is
+template <class I> IBVH_D int child_slot(I c, bool descended) { return descended ? (int)(c & 1) : 0; }
+
+// What a lane fetches for a pair of volumes (self and pair traversals).  Loaded: the two operands of one check.  Sides:
+// the children of a source pair (a, b) are combinations of {2a, 2a+1} x {2b, 2b+1}, so FOUR volumes (two adjacent pairs
+// in memory) serve all of them — fetched once per source pair instead of twice per child pair.
+template <class L, class N, class I> struct Loaded {
+    Either<N, L> a, b;
+    I ia, ib;
+};
+template <class L, class N, class I> struct Sides {
+    Either<N, L> v[2][2]; // [side a / b][left / right child]
+    I idx[2][2];
+    // the operands of the child pair c (`da` / `db`: did that side descend in the parent step?)
+    IBVH_D Loaded<L, N, I> select(IndexPair<I> c, bool da, bool db) const {
+        const int ka = child_slot(c.a, da), kb = child_slot(c.b, db);
+        Loaded<L, N, I> y;
+        y.a = ka ? v[0][1] : v[0][0];
+        y.b = kb ? v[1][1] : v[1][0];
+        y.ia = ka ? idx[0][1] : idx[0][0];
+        y.ib = kb ? idx[1][1] : idx[1][0];
+        return y;
+    }
+};
+
+// The next level's pairs of a passing pair when ONE side descends (`side` 0: a, 1: b): the left child, plus the right
+// unless it is virtual ...
+template <class I> IBVH_D int descend_one(IndexPair<I> s, int side, bool right_virtual, IndexPair<I> *out) {
+    const I a = s.a, b = s.b;
+    out[0] = side ? IndexPair<I>{a, I(2 * b)} : IndexPair<I>{I(2 * a), b};
+    if (right_virtual) return 1;
+    out[1] = side ? IndexPair<I>{a, I(2 * b + 1)} : IndexPair<I>{I(2 * a + 1), b};
+    return 2;
+}
+// ... and when BOTH do: 1, 2 or 4 pairs, by which side's right child is virtual
+template <class I> IBVH_D int descend_both(IndexPair<I> s, bool virtual_a, bool virtual_b, IndexPair<I> *out) {
+    const I a = s.a, b = s.b;
+    out[0] = {I(2 * a), I(2 * b)};
+    if (virtual_a) {
+        if (virtual_b) return 1;
+        out[1] = {I(2 * a), I(2 * b + 1)};
+        return 2;
+    }
+    if (virtual_b) {
+        out[1] = {I(2 * a + 1), I(2 * b)};
+        return 2;
+    }
+    out[1] = {I(2 * a), I(2 * b + 1)};
+    out[2] = {I(2 * a + 1), I(2 * b)};
+    out[3] = {I(2 * a + 1), I(2 * b + 1)};
+    return 4;
+}
+
 template <class I> struct Identity { // the initial queue: "children" of nothing, still to be checked
     static constexpr int MAXOUT = 1;
     static constexpr bool kIdentity = true;
@@ -103,34 +189,20 @@ template <class I> struct Identity { // the initial queue: "children" of nothing
 // _traverse_nodes_gpu! — bfs/traverse_single_gpu.jl:30-120 (same rules as traverse_single_cpu.jl:64-133) — and
 // _traverse_leaves_gpu! — :153-211
 template <class L, class N, class I> struct SelfStep {
-    using leaf_t = L;
-    using node_t = N;
     static constexpr int MAXOUT = 4;
+    static constexpr bool kIdentity = false;
+    using Loaded = bfs::Loaded<L, N, I>;
+    using Sides = bfs::Sides<L, N, I>;
     TreeRef<L, N> t;
     int leaf;        // entries are leaf pairs
     int self_checks; // (nodes) :44
     int narrow;      // (leaves) menu code
     int positions;   // (leaves) IBVH_OUTPUT_POSITIONS: 1-based leaf positions instead of user indices, left leaf first
-    // What one check needs from memory, fetched UNCONDITIONALLY (`s` is always a valid pair of this level: the kernel
-    // hands over a real child or safe()): every lane's loads for all its <= 4 children are in flight before the first
-    // test — four dependent round trips per lane otherwise, and the kernel is bound by exactly that latency.
-    struct Loaded {
-        Either<N, L> a, b;
-        I ia, ib;
-    };
     IBVH_D IndexPair<I> safe() const { const I f = I(int64_t(1) << (t.level - 1)); return {f, f}; } // the level's first node: always real
     IBVH_D Loaded load(IndexPair<I> s) const {
         Loaded x{};
-        if (leaf) {
-            const char *r1 = t.leaf_rec(s.a), *r2 = t.leaf_rec(s.b);
-            x.a.set(load_vol<L>(r1));
-            x.b.set(load_vol<L>(r2));
-            x.ia = load_index<I>(r1, t.lay);
-            x.ib = load_index<I>(r2, t.lay);
-        } else {
-            x.a.set(t.node(s.a));
-            x.b.set(t.node(s.b));
-        }
+        fetch(x.a, x.ia, t, leaf, s.a);
+        fetch(x.b, x.ib, t, leaf, s.b);
         return x;
     }
     IBVH_D bool test(IndexPair<I> s, const Loaded &x, IndexPair<I> &res) const {
@@ -148,47 +220,19 @@ template <class L, class N, class I> struct SelfStep {
         res = s;
         return s.a == s.b || iscontact(x.a.template get<N>(), x.b.template get<N>()); // (a node against itself is not tested, :52-70)
     }
-    // The children of a source pair (a, b) are combinations of {2a, 2a+1} x {2b, 2b+1}: FOUR volumes (two adjacent
-    // pairs in memory) serve all of them — fetched once per source pair instead of twice per child pair.
     // (called on the CHILD level's policy with the parent-level source pair)
-    static constexpr bool kIdentity = false;
-    struct Sides {
-        Either<N, L> v[2][2]; // [side a / b][left / right child]
-        I idx[2][2];
-    };
     IBVH_D Sides load_sides(IndexPair<I> s, const SelfStep &) const {
         Sides x{};
-        const int64_t first = int64_t(1) << (t.level - 1), nreal = level_num_real(t.levels, t.virtual_leaves, t.level);
 #pragma unroll
-        for (int side = 0; side < 2; ++side) {
-            const int64_t c0 = 2 * (int64_t)(side ? s.b : s.a);
-            const int64_t c1 = (c0 + 1 - first) < nreal ? c0 + 1 : c0; // a virtual right child re-reads the left one (never selected)
-#pragma unroll
-            for (int k = 0; k < 2; ++k) {
-                const int64_t c = k ? c1 : c0;
-                if (leaf) {
-                    const char *r = t.leaf_rec(c);
-                    x.v[side][k].set(load_vol<L>(r));
-                    x.idx[side][k] = load_index<I>(r, t.lay);
-                } else {
-                    x.v[side][k].set(t.node(c));
-                }
-            }
-        }
+        for (int side = 0; side < 2; ++side) fetch_children(x.v[side], x.idx[side], t, leaf, side ? s.b : s.a, true);
         return x;
     }
-    IBVH_D bool test_sides(IndexPair<I> s, const Sides &x, IndexPair<I> &res) const {
-        const int ka = (int)(s.a & 1), kb = (int)(s.b & 1);
-        Loaded y;
-        y.a = ka ? x.v[0][1] : x.v[0][0];
-        y.b = kb ? x.v[1][1] : x.v[1][0];
-        y.ia = ka ? x.idx[0][1] : x.idx[0][0];
-        y.ib = kb ? x.idx[1][1] : x.idx[1][0];
-        return test(s, y, res);
+    IBVH_D bool test_sides(IndexPair<I> c, const Sides &x, IndexPair<I> &res, const SelfStep &) const {
+        return test(c, x.select(c, true, true), res);
     }
     IBVH_D int children(IndexPair<I> s, IndexPair<I> *out) const {
-        const I a = s.a, b = s.b;
-        if (a == b) {
+        const I a = s.a;
+        if (a == s.b) {
             if (t.right_child_virtual(a)) {
                 if (!self_checks) return 0;
                 out[0] = {I(2 * a), I(2 * a)};
@@ -204,233 +248,140 @@ template <class L, class N, class I> struct SelfStep {
             return 1;
         }
         // node a is left of node b, so its children are real (traverse_single_cpu.jl:103-105)
-        out[0] = {I(2 * a), I(2 * b)};
-        if (t.right_child_virtual(b)) {
-            out[1] = {I(2 * a + 1), I(2 * b)};
-            return 2;
-        }
-        out[1] = {I(2 * a), I(2 * b + 1)};
-        out[2] = {I(2 * a + 1), I(2 * b)};
-        out[3] = {I(2 * a + 1), I(2 * b + 1)};
-        return 4;
+        return descend_both(s, false, t.right_child_virtual(s.b), out);
     }
 };
 
 // The six pair kernels of bfs/traverse_pair_gpu.jl:34-609 in one policy: which side is at leaf level
 // (leaf1 / leaf2) and which side descends (d1 / d2).
 template <class L, class N, class I> struct PairStep {
-    using leaf_t = L;
-    using node_t = N;
     static constexpr int MAXOUT = 4;
+    static constexpr bool kIdentity = false;
+    using Loaded = bfs::Loaded<L, N, I>;
+    using Sides = bfs::Sides<L, N, I>;
     TreeRef<L, N> t1, t2;
     int narrow, positions;
     int leaf1, leaf2, d1, d2;
-    struct Loaded { // (see SelfStep::Loaded)
-        Either<N, L> a, b;
-        I ia, ib;
-    };
     IBVH_D IndexPair<I> safe() const { return {I(int64_t(1) << (t1.level - 1)), I(int64_t(1) << (t2.level - 1))}; }
     IBVH_D Loaded load(IndexPair<I> s) const {
         Loaded x{};
-        const I a = s.a, b = s.b;
-        if (leaf1) {
-            const char *r1 = t1.leaf_rec(a);
-            x.a.set(load_vol<L>(r1));
-            if (leaf2) x.ia = load_index<I>(r1, t1.lay);
-        } else {
-            x.a.set(t1.node(a));
-        }
-        if (leaf2) {
-            const char *r2 = t2.leaf_rec(b);
-            x.b.set(load_vol<L>(r2));
-            if (leaf1) x.ib = load_index<I>(r2, t2.lay);
-        } else {
-            x.b.set(t2.node(b));
-        }
+        fetch(x.a, x.ia, t1, leaf1, s.a, leaf2); // (only a leaf-leaf check reads the indices)
+        fetch(x.b, x.ib, t2, leaf2, s.b, leaf1);
         return x;
     }
     IBVH_D bool test(IndexPair<I> s, const Loaded &x, IndexPair<I> &res) const {
-        const I a = s.a, b = s.b;
         res = s;
         if (leaf1 && leaf2) {
             // _traverse_leaves_pair_gpu! (:556-609): (leaf1.index, leaf2.index), not re-ordered
             if (!iscontact(x.a.template get<L>(), x.b.template get<L>())) return false;
             if (narrow != IBVH_NARROW_NONE) {
-                const uint64_t m1 = narrow == IBVH_NARROW_MORTON_LT ? load_morton(t1.leaf_rec(a), t1.lay) : 0;
-                const uint64_t m2 = narrow == IBVH_NARROW_MORTON_LT ? load_morton(t2.leaf_rec(b), t2.lay) : 0;
+                const uint64_t m1 = narrow == IBVH_NARROW_MORTON_LT ? load_morton(t1.leaf_rec(s.a), t1.lay) : 0;
+                const uint64_t m2 = narrow == IBVH_NARROW_MORTON_LT ? load_morton(t2.leaf_rec(s.b), t2.lay) : 0;
                 if (!narrow_eval(narrow, m1, x.ia, m2, x.ib)) return false;
             }
-            res = positions ? IndexPair<I>{I(a - t1.leaf_first + 1), I(b - t2.leaf_first + 1)} : IndexPair<I>{x.ia, x.ib};
+            res = positions ? IndexPair<I>{I(s.a - t1.leaf_first + 1), I(s.b - t2.leaf_first + 1)} : IndexPair<I>{x.ia, x.ib};
             return true;
         }
         if (leaf1) return iscontact(x.a.template get<L>(), x.b.template get<N>()); // iscontact(leaf1.volume, node2), :461-527
         if (leaf2) return iscontact(x.a.template get<N>(), x.b.template get<L>()); // :360-426
         return iscontact(x.a.template get<N>(), x.b.template get<N>());
     }
-    static constexpr bool kIdentity = false;
-    struct Sides { // (see SelfStep::Sides; a side that did not descend in the parent step holds its one node twice)
-        Either<N, L> v[2][2];
-        I idx[2][2];
-    };
     IBVH_D Sides load_sides(IndexPair<I> s, const PairStep &parent) const {
         Sides x{};
 #pragma unroll
-        for (int side = 0; side < 2; ++side) {
-            const TreeRef<L, N> &t = side ? t2 : t1;
-            const bool is_leaf = side ? leaf2 : leaf1, descended = side ? parent.d2 : parent.d1;
-            const int64_t p = (int64_t)(side ? s.b : s.a);
-            const int64_t first = int64_t(1) << (t.level - 1), nreal = level_num_real(t.levels, t.virtual_leaves, t.level);
-            const int64_t c0 = descended ? 2 * p : p;
-            const int64_t c1 = (descended && (c0 + 1 - first) < nreal) ? c0 + 1 : c0;
-#pragma unroll
-            for (int k = 0; k < 2; ++k) {
-                const int64_t c = k ? c1 : c0;
-                if (is_leaf) {
-                    const char *r = t.leaf_rec(c);
-                    x.v[side][k].set(load_vol<L>(r));
-                    x.idx[side][k] = load_index<I>(r, t.lay);
-                } else {
-                    x.v[side][k].set(t.node(c));
-                }
-            }
-        }
+        for (int side = 0; side < 2; ++side)
+            fetch_children(x.v[side], x.idx[side], side ? t2 : t1, side ? leaf2 : leaf1, side ? s.b : s.a, side ? parent.d2 : parent.d1);
         return x;
     }
-    IBVH_D bool test_sides(IndexPair<I> s, const Sides &x, IndexPair<I> &res, const PairStep &parent) const {
-        const int ka = parent.d1 ? (int)(s.a & 1) : 0, kb = parent.d2 ? (int)(s.b & 1) : 0;
-        Loaded y;
-        y.a = ka ? x.v[0][1] : x.v[0][0];
-        y.b = kb ? x.v[1][1] : x.v[1][0];
-        y.ia = ka ? x.idx[0][1] : x.idx[0][0];
-        y.ib = kb ? x.idx[1][1] : x.idx[1][0];
-        return test(s, y, res);
+    IBVH_D bool test_sides(IndexPair<I> c, const Sides &x, IndexPair<I> &res, const PairStep &parent) const {
+        return test(c, x.select(c, parent.d1, parent.d2), res);
     }
     IBVH_D int children(IndexPair<I> s, IndexPair<I> *out) const {
-        const I a = s.a, b = s.b;
-        if (d1 && d2) { // _traverse_nodes_pair_gpu! (:34-119)
-            const bool v1 = t1.right_child_virtual(a), v2 = t2.right_child_virtual(b);
-            out[0] = {I(2 * a), I(2 * b)};
-            if (v1) {
-                if (v2) return 1;
-                out[1] = {I(2 * a), I(2 * b + 1)};
-                return 2;
-            }
-            if (v2) {
-                out[1] = {I(2 * a + 1), I(2 * b)};
-                return 2;
-            }
-            out[1] = {I(2 * a), I(2 * b + 1)};
-            out[2] = {I(2 * a + 1), I(2 * b)};
-            out[3] = {I(2 * a + 1), I(2 * b + 1)};
-            return 4;
-        }
-        if (d1) { // _left_ kernels (:155-222, :360-426)
-            out[0] = {I(2 * a), b};
-            if (t1.right_child_virtual(a)) return 1;
-            out[1] = {I(2 * a + 1), b};
-            return 2;
-        }
-        // _right_ kernels (:258-325, :461-527)
-        out[0] = {a, I(2 * b)};
-        if (t2.right_child_virtual(b)) return 1;
-        out[1] = {a, I(2 * b + 1)};
-        return 2;
+        // _traverse_nodes_pair_gpu! (:34-119)
+        if (d1 && d2) return descend_both(s, t1.right_child_virtual(s.a), t2.right_child_virtual(s.b), out);
+        if (d1) return descend_one(s, 0, t1.right_child_virtual(s.a), out); // _left_ kernels (:155-222, :360-426)
+        return descend_one(s, 1, t2.right_child_virtual(s.b), out);         // _right_ kernels (:258-325, :461-527)
     }
 };
 
+template <class T> struct Ray {
+    T p[3], d[3];
+};
+// ray `iray` (1-based) of the 3 x num_rays arrays
+template <class T> IBVH_D Ray<T> load_ray(const T *points, const T *dirs, int64_t iray) {
+    Ray<T> r;
+    const int64_t r0 = 3 * (iray - 1);
+#pragma unroll
+    for (int k = 0; k < 3; ++k) {
+        r.p[k] = points[r0 + k];
+        r.d[k] = dirs[r0 + k];
+    }
+    return r;
+}
+
 // _traverse_rays_nodes_gpu! / _traverse_rays_leaves_gpu! — raytrace/breadth_first/raytrace_gpu.jl:26-179
 template <class L, class N, class I> struct RayStep {
-    using leaf_t = L;
-    using node_t = N;
     static constexpr int MAXOUT = 2;
+    static constexpr bool kIdentity = false;
     using T = typename L::elt;
     TreeRef<L, N> t;
     const T *points, *dirs;
     int leaf;
     int narrow, positions;
-    struct Loaded { // (see SelfStep::Loaded)
-        T p[3], d[3];
+    struct Loaded { // the ray and one volume
+        Ray<T> ray;
         Either<N, L> v;
         I idx;
+    };
+    struct Sides { // the ray once + the two children of its node
+        Ray<T> ray;
+        Either<N, L> v[2];
+        I idx[2];
     };
     IBVH_D IndexPair<I> safe() const { return {I(int64_t(1) << (t.level - 1)), I(1)}; } // (num_rays >= 1 whenever a level runs)
     IBVH_D Loaded load(IndexPair<I> s) const {
         Loaded x{};
-        const int64_t r0 = 3 * ((int64_t)s.b - 1);
-#pragma unroll
-        for (int k = 0; k < 3; ++k) {
-            x.p[k] = points[r0 + k];
-            x.d[k] = dirs[r0 + k];
-        }
-        if (leaf) {
-            const char *r = t.leaf_rec(s.a);
-            x.v.set(load_vol<L>(r));
-            x.idx = load_index<I>(r, t.lay);
-        } else {
-            x.v.set(t.node(s.a));
-        }
+        x.ray = load_ray(points, dirs, (int64_t)s.b);
+        fetch(x.v, x.idx, t, leaf, s.a);
         return x;
     }
     IBVH_D bool test(IndexPair<I> s, const Loaded &x, IndexPair<I> &res) const {
-        const I a = s.a, iray = s.b;
         res = s;
         if (leaf) {
             const L lv = x.v.template get<L>();
-            if (!isintersection(lv, x.p, x.d)) return false;
-            if (narrow == IBVH_NARROW_RAY_ORIGIN_OUTSIDE && !origin_outside(lv, x.p)) return false; // raytrace_gpu.jl:159
-            res = {positions ? I(a - t.leaf_first + 1) : x.idx, iray};
+            if (!isintersection(lv, x.ray.p, x.ray.d)) return false;
+            if (narrow == IBVH_NARROW_RAY_ORIGIN_OUTSIDE && !origin_outside(lv, x.ray.p)) return false; // raytrace_gpu.jl:159
+            res = {positions ? I(s.a - t.leaf_first + 1) : x.idx, s.b};
             return true;
         }
-        return isintersection(x.v.template get<N>(), x.p, x.d);
+        return isintersection(x.v.template get<N>(), x.ray.p, x.ray.d);
     }
-    static constexpr bool kIdentity = false;
-    struct Sides { // the ray once + the two children of its node
-        T p[3], d[3];
-        Either<N, L> v[2];
-        I idx[2];
-    };
     IBVH_D Sides load_sides(IndexPair<I> s, const RayStep &) const {
         Sides x{};
-        const int64_t r0 = 3 * ((int64_t)s.b - 1);
-#pragma unroll
-        for (int k = 0; k < 3; ++k) {
-            x.p[k] = points[r0 + k];
-            x.d[k] = dirs[r0 + k];
-        }
-        const int64_t first = int64_t(1) << (t.level - 1), nreal = level_num_real(t.levels, t.virtual_leaves, t.level);
-        const int64_t c0 = 2 * (int64_t)s.a, c1 = (c0 + 1 - first) < nreal ? c0 + 1 : c0;
-#pragma unroll
-        for (int k = 0; k < 2; ++k) {
-            const int64_t c = k ? c1 : c0;
-            if (leaf) {
-                const char *r = t.leaf_rec(c);
-                x.v[k].set(load_vol<L>(r));
-                x.idx[k] = load_index<I>(r, t.lay);
-            } else {
-                x.v[k].set(t.node(c));
-            }
-        }
+        x.ray = load_ray(points, dirs, (int64_t)s.b);
+        fetch_children(x.v, x.idx, t, leaf, s.a, true);
         return x;
     }
-    IBVH_D bool test_sides(IndexPair<I> s, const Sides &x, IndexPair<I> &res) const {
-        const int k = (int)(s.a & 1);
+    IBVH_D bool test_sides(IndexPair<I> c, const Sides &x, IndexPair<I> &res, const RayStep &) const {
+        const int k = child_slot(c.a, true);
         Loaded y;
-#pragma unroll
-        for (int j = 0; j < 3; ++j) {
-            y.p[j] = x.p[j];
-            y.d[j] = x.d[j];
-        }
+        y.ray = x.ray;
         y.v = k ? x.v[1] : x.v[0];
         y.idx = k ? x.idx[1] : x.idx[0];
-        return test(s, y, res);
+        return test(c, y, res);
     }
-    IBVH_D int children(IndexPair<I> s, IndexPair<I> *out) const {
-        out[0] = {I(2 * s.a), s.b};
-        if (t.right_child_virtual(s.a)) return 1;
-        out[1] = {I(2 * s.a + 1), s.b};
-        return 2;
-    }
+    IBVH_D int children(IndexPair<I> s, IndexPair<I> *out) const { return descend_one(s, 0, t.right_child_virtual(s.a), out); }
 };
+
+// What a step reads for a source pair, told apart by the parent policy.  Step 0 (Identity) tests the source pair
+// itself: it is of pb's level and brings its own operands.  Every later step tests the children of a source pair of
+// pa's level, which share their volumes; there pa and pb are two levels of ONE policy type (the second overload set
+// takes no other pairing; level_kernel asserts it).  The test itself is told apart in level_kernel: written as a
+// one-child case of the loop over the children, step 0 cost its kernels registers and, for some types, occupancy.
+template <class I, class PolB> IBVH_D IndexPair<I> source_safe(const Identity<I> &, const PolB &pb) { return pb.safe(); }
+template <class I, class PolB> IBVH_D auto source_fetch(const Identity<I> &, const PolB &pb, IndexPair<I> s) { return pb.load(s); }
+template <class Pol> IBVH_D auto source_safe(const Pol &pa, const Pol &) { return pa.safe(); }
+template <class Pol, class I> IBVH_D auto source_fetch(const Pol &pa, const Pol &pb, IndexPair<I> s) { return pb.load_sides(s, pa); }
 
 // ------------------------------------------------------------------------------------------
 // the level kernel: children of the source pairs, checked at once; wave64 ballot compaction of the passing ones +
@@ -453,6 +404,7 @@ __global__ __launch_bounds__(TPB) void level_kernel(const IndexPair<I> *__restri
                                                     int64_t capacity, unsigned long long *__restrict__ counters, int step, int chk,
                                                     PolA pa, PolB pb) {
     constexpr int MAXOUT = PolA::MAXOUT;
+    static_assert(PolA::kIdentity || std::is_same<PolA, PolB>::value, "a step joins two levels of one policy");
     // Results of MANY chunks are collected in LDS and leave in one coalesced run behind ONE global atomic on the level's
     // tail (round 2 took that atomic per chunk: every chunk of a workgroup then waited out a ~2 us round trip to L2 —
     // ~34 chunks a workgroup and level at 1e6 leaves, most of the 1.4 ms of config 2).  A wave reserves its share of the
@@ -501,17 +453,13 @@ __global__ __launch_bounds__(TPB) void level_kernel(const IndexPair<I> *__restri
     // level kernels were ~82 % waiting.  Lanes beyond the queue's end carry safe() (a valid pair of the level), so every
     // load is unconditional; vmcnt counts in order, so the wait for chunk c + 1's volumes sits at the register rotation at
     // the end of the body, a whole test-and-stage phase after they were requested.
-    using Fetched = typename std::conditional<PolA::kIdentity, typename PolB::Loaded, typename PolB::Sides>::type;
     const int64_t stride = (int64_t)gridDim.x;
     auto source_of = [&](int64_t chunk) -> IndexPair<I> {
         const int64_t i = chunk * TPB + threadIdx.x;
-        if constexpr (PolA::kIdentity) return i < num_src ? src[i] : pb.safe();
-        else return i < num_src ? src[i] : pa.safe();
+        return i < num_src ? src[i] : source_safe(pa, pb);
     };
-    auto fetch = [&](IndexPair<I> sp) -> Fetched {
-        if constexpr (PolA::kIdentity) return pb.load(sp);
-        else return pb.load_sides(sp, pa);
-    };
+    auto fetch = [&](IndexPair<I> sp) { return source_fetch(pa, pb, sp); };
+    using Fetched = decltype(fetch(IndexPair<I>{}));
     IndexPair<I> s_cur = source_of((int64_t)blockIdx.x), s_nxt = source_of((int64_t)blockIdx.x + stride);
     Fetched f_cur = fetch(s_cur);
     for (int64_t chunk = blockIdx.x; chunk * TPB < num_src; chunk += stride) {
@@ -524,16 +472,14 @@ __global__ __launch_bounds__(TPB) void level_kernel(const IndexPair<I> *__restri
         int nk = 0;
         if (i < num_src) nk = pa.children(s_cur, kids);
         generated += (unsigned long long)nk;
-        if constexpr (PolA::kIdentity) {
+        // the source pair's children share their volumes: {2a, 2a+1} x {2b, 2b+1} (or one side kept): four volume
+        // fetches per lane serve up to four checks
+        if constexpr (PolA::kIdentity) { // step 0: the source pair itself is tested
             if (nk > 0 && pb.test(s_cur, f_cur, res[0])) okm = 1u;
         } else {
-            // the source pair's children share their volumes: {2a, 2a+1} x {2b, 2b+1} (or one side kept): four volume
-            // fetches per lane serve up to four checks
 #pragma unroll
             for (int j = 0; j < MAXOUT; ++j) {
-                bool ok;
-                if constexpr (std::is_same<PolB, PairStep<typename PolB::leaf_t, typename PolB::node_t, I>>::value) ok = j < nk && pb.test_sides(kids[j], f_cur, res[j], pa);
-                else ok = j < nk && pb.test_sides(kids[j], f_cur, res[j]);
+                const bool ok = j < nk && pb.test_sides(kids[j], f_cur, res[j], pa);
                 okm |= ok ? (1u << j) : 0u;
             }
         }
@@ -718,51 +664,81 @@ inline int capacity_error(ibvh_bfs_result *res, int64_t need) {
     return IBVH_ERR_CAPACITY;
 }
 
+// pairs in the initial queue of each traversal (the fill kernels above)
 inline int64_t self_initial(const ibvh_bvh &b, int64_t start_level) {
     int64_t n = level_num_real(b.tree.levels, b.tree.virtual_leaves, start_level);
     return start_level != b.tree.levels ? n * (n - 1) / 2 + n : n * (n - 1) / 2;
 }
+inline int64_t pair_initial(const ibvh_bvh &b1, const ibvh_bvh &b2, int64_t sl1, int64_t sl2) {
+    return level_num_real(b1.tree.levels, b1.tree.virtual_leaves, sl1) * level_num_real(b2.tree.levels, b2.tree.virtual_leaves, sl2);
+}
+inline int64_t rays_initial(const ibvh_bvh &b, int64_t num_rays, int64_t start_level) {
+    return level_num_real(b.tree.levels, b.tree.virtual_leaves, start_level) * num_rays;
+}
+
+// the caller's buffers, as every entry point takes them
+struct Buffers {
+    void *bvtt1, *bvtt2;
+    int64_t capacity;
+    void *counters;
+    ibvh_bfs_result *res;
+    hipStream_t st;
+    bool ok() const { return bvtt1 && bvtt2 && counters && capacity >= 1; }
+};
+
+// One traversal: the initial queue of `total0` pairs, which `fill(queue)` writes unless the call resumes, is checked by
+// pol(0); then the children of what passed, level by level, by pol(1) .. pol(ns - 1).
+template <class I, class Fill, class Pol>
+int run_steps(const Buffers &q, int64_t total_levels, int64_t total0, Fill &&fill, int ns, Pol &&pol) {
+    Run r;
+    if (q.res->resume_step == 0 && total0 > q.capacity) return capacity_error(q.res, total0);
+    if (int e = begin(r, q.bvtt1, q.bvtt2, q.capacity, q.counters, total_levels, q.st, q.res, total0)) return e;
+    if (r.first == 0) fill((IndexPair<I> *)q.bvtt1);
+    if (int e = step<I>(r, Identity<I>{}, pol(0))) return e;
+    for (int i = 0; i + 1 < ns; ++i)
+        if (int e = step<I>(r, pol(i), pol(i + 1))) return e;
+    return finish(r, q.res);
+}
+
+template <class L_, class N_, class I_> struct Types { // what dispatch() hands to its callable
+    using L = L_;
+    using N = N_;
+    using I = I_;
+};
 
 template <class L, class N, class I>
-int run_self(const ibvh_bvh &b, int64_t start_level, int narrow, void *bvtt1, void *bvtt2, int64_t capacity, void *counters,
-             ibvh_bfs_result *res, hipStream_t st) {
+int run_self(Types<L, N, I>, const ibvh_bvh &b, int64_t start_level, int narrow, const Buffers &q) {
     ibvh_layout lay;
     LeafLayout dl;
     layout_of(b.types, lay, &dl);
-    Run r;
     const int64_t levels = b.tree.levels;
     const int64_t n0 = level_num_real(levels, b.tree.virtual_leaves, start_level);
     const int64_t total0 = self_initial(b, start_level);
-    if (res->resume_step == 0 && total0 > capacity) return capacity_error(res, total0);
-    if (int e = begin(r, bvtt1, bvtt2, capacity, counters, levels, st, res, total0)) return e;
-    if (r.first == 0 && total0 > 0)
-        IBVH_LAUNCH((fill_self_kernel<I>), dim3((unsigned)ceil_div(total0, TPB)), dim3(TPB), 0, st, (IndexPair<I> *)bvtt1,
-                           n0, int64_t(1) << (start_level - 1), start_level != levels ? 1 : 0, total0);
-    auto at = [&](int64_t level) {
+    auto fill = [&](IndexPair<I> *queue) {
+        if (total0 > 0)
+            IBVH_LAUNCH((fill_self_kernel<I>), dim3((unsigned)ceil_div(total0, TPB)), dim3(TPB), 0, q.st, queue, n0,
+                        int64_t(1) << (start_level - 1), start_level != levels ? 1 : 0, total0);
+    };
+    auto at = [&](int i) {
+        const int64_t level = start_level + i;
         return SelfStep<L, N, I>{make_ref<L, N>(b, dl, level), level == levels ? 1 : 0, level < levels - 1 ? 1 : 0 /* self_checks (:44) */,
                                  narrow & IBVH_NARROW_MASK, (narrow & IBVH_OUTPUT_POSITIONS) ? 1 : 0};
     };
-    if (int e = step<I>(r, Identity<I>{}, at(start_level))) return e; // the initial queue is checked ...
-    for (int64_t level = start_level; level < levels; ++level)       // ... then children of what passed, level by level
-        if (int e = step<I>(r, at(level), at(level + 1))) return e;
-    return finish(r, res);
+    return run_steps<I>(q, levels, total0, fill, (int)(levels - start_level) + 1, at);
 }
 
 template <class L, class N, class I>
-int run_pair(const ibvh_bvh &b1, const ibvh_bvh &b2, int64_t sl1, int64_t sl2, int narrow, void *bvtt1, void *bvtt2,
-             int64_t capacity, void *counters, ibvh_bfs_result *res, hipStream_t st) {
+int run_pair(Types<L, N, I>, const ibvh_bvh &b1, const ibvh_bvh &b2, int64_t sl1, int64_t sl2, int narrow, const Buffers &q) {
     ibvh_layout lay;
     LeafLayout dl;
     layout_of(b1.types, lay, &dl);
-    Run r;
     const int64_t L1 = b1.tree.levels, L2 = b2.tree.levels;
     const int64_t nr1 = level_num_real(L1, b1.tree.virtual_leaves, sl1), nr2 = level_num_real(L2, b2.tree.virtual_leaves, sl2);
-    const int64_t total0 = nr1 * nr2;
-    if (res->resume_step == 0 && total0 > capacity) return capacity_error(res, total0);
-    if (int e = begin(r, bvtt1, bvtt2, capacity, counters, L1 + L2, st, res, total0)) return e;
-    if (r.first == 0)
-        IBVH_LAUNCH((fill_product_kernel<I>), dim3((unsigned)ceil_div(total0, TPB)), dim3(TPB), 0, st, (IndexPair<I> *)bvtt1,
-                           nr1, nr2, int64_t(1) << (sl1 - 1), int64_t(1) << (sl2 - 1));
+    const int64_t total0 = pair_initial(b1, b2, sl1, sl2);
+    auto fill = [&](IndexPair<I> *queue) {
+        IBVH_LAUNCH((fill_product_kernel<I>), dim3((unsigned)ceil_div(total0, TPB)), dim3(TPB), 0, q.st, queue, nr1, nr2,
+                    int64_t(1) << (sl1 - 1), int64_t(1) << (sl2 - 1));
+    };
     // the six-phase descent of bfs/traverse_pair.jl:50-143 as a list of (levels, which side is a leaf, which descends)
     PairStep<L, N, I> seq[132];
     int ns = 0;
@@ -802,36 +778,29 @@ int run_pair(const ibvh_bvh &b1, const ibvh_bvh &b2, int64_t sl1, int64_t sl2, i
     }
     // leaf-leaf: what passes is the contact list (num_checks is not incremented after it, bfs/traverse_pair.jl:146-150)
     add(true, true, false, false);
-    if (int e = step<I>(r, Identity<I>{}, seq[0])) return e;
-    for (int i = 0; i + 1 < ns; ++i)
-        if (int e = step<I>(r, seq[i], seq[i + 1])) return e;
-    return finish(r, res);
+    return run_steps<I>(q, L1 + L2, total0, fill, ns, [&](int i) { return seq[i]; });
 }
 
 template <class L, class N, class I>
-int run_rays(const ibvh_bvh &b, const void *points, const void *dirs, int64_t num_rays, int64_t start_level, int narrow,
-             void *bvtt1, void *bvtt2, int64_t capacity, void *counters, ibvh_bfs_result *res, hipStream_t st) {
+int run_rays(Types<L, N, I>, const ibvh_bvh &b, const void *points, const void *dirs, int64_t num_rays, int64_t start_level,
+             int narrow, const Buffers &q) {
     using T = typename L::elt;
     ibvh_layout lay;
     LeafLayout dl;
     layout_of(b.types, lay, &dl);
-    Run r;
     const int64_t levels = b.tree.levels;
     const int64_t nr = level_num_real(levels, b.tree.virtual_leaves, start_level);
-    const int64_t total0 = nr * num_rays;
-    if (res->resume_step == 0 && total0 > capacity) return capacity_error(res, total0);
-    if (int e = begin(r, bvtt1, bvtt2, capacity, counters, levels, st, res, total0)) return e;
-    if (r.first == 0)
-        IBVH_LAUNCH((fill_product_kernel<I>), dim3((unsigned)ceil_div(total0, TPB)), dim3(TPB), 0, st, (IndexPair<I> *)bvtt1, nr,
-                           num_rays, int64_t(1) << (start_level - 1), int64_t(1));
-    auto at = [&](int64_t level) {
+    const int64_t total0 = rays_initial(b, num_rays, start_level);
+    auto fill = [&](IndexPair<I> *queue) {
+        IBVH_LAUNCH((fill_product_kernel<I>), dim3((unsigned)ceil_div(total0, TPB)), dim3(TPB), 0, q.st, queue, nr, num_rays,
+                    int64_t(1) << (start_level - 1), int64_t(1));
+    };
+    auto at = [&](int i) {
+        const int64_t level = start_level + i;
         return RayStep<L, N, I>{make_ref<L, N>(b, dl, level), (const T *)points, (const T *)dirs, level == levels ? 1 : 0,
                                 narrow & IBVH_NARROW_MASK, (narrow & IBVH_OUTPUT_POSITIONS) ? 1 : 0};
     };
-    if (int e = step<I>(r, Identity<I>{}, at(start_level))) return e;
-    for (int64_t level = start_level; level < levels; ++level)
-        if (int e = step<I>(r, at(level), at(level + 1))) return e;
-    return finish(r, res);
+    return run_steps<I>(q, levels, total0, fill, (int)(levels - start_level) + 1, at);
 }
 
 inline int check_levels(const ibvh_bvh &b, int64_t sl) {
@@ -841,9 +810,19 @@ inline int check_levels(const ibvh_bvh &b, int64_t sl) {
     return IBVH_OK;
 }
 
+// What every traversal entry does first with its in / out argument: the resume fields are input and stay, the rest is
+// reset to "nothing found" (what a call that has nothing to traverse returns).  False: the resume fields are invalid.
+inline bool reset_result(ibvh_bfs_result *result) {
+    const ibvh_bfs_result in = *result;
+    *result = {0, 0, 1, 0, in.resume_step, in.resume_num};
+    return in.resume_step >= 0 && in.resume_num >= 0;
+}
+
 template <class F> int dispatch(const ibvh_types &t, F &&f) {
     return dispatch_leaf_node(t, [&](auto lt, auto nt) -> int {
-        return dispatch_index(t.index_type, [&](auto it) -> int { return f(lt, nt, it); });
+        return dispatch_index(t.index_type, [&](auto it) -> int {
+            return f(Types<typename decltype(lt)::type, typename decltype(nt)::type, typename decltype(it)::type>{});
+        });
     });
 }
 
@@ -872,73 +851,61 @@ ibvh_status ibvh_bfs_pair_initial_capacity(const ibvh_bvh *bvh1, const ibvh_bvh 
     if (!bvh1 || !bvh2 || !pairs_out) return IBVH_ERR_INVALID_ARG;
     if (int e = check_levels(*bvh1, sl1)) return (ibvh_status)e;
     if (int e = check_levels(*bvh2, sl2)) return (ibvh_status)e;
-    *pairs_out = level_num_real(bvh1->tree.levels, bvh1->tree.virtual_leaves, sl1) *
-                 level_num_real(bvh2->tree.levels, bvh2->tree.virtual_leaves, sl2);
+    *pairs_out = pair_initial(*bvh1, *bvh2, sl1, sl2);
     return IBVH_OK;
 }
 ibvh_status ibvh_bfs_rays_initial_capacity(const ibvh_bvh *bvh, int64_t num_rays, int64_t start_level, int64_t *pairs_out) {
     if (!bvh || !pairs_out || num_rays < 0) return IBVH_ERR_INVALID_ARG;
     if (int e = check_levels(*bvh, start_level)) return (ibvh_status)e;
-    *pairs_out = level_num_real(bvh->tree.levels, bvh->tree.virtual_leaves, start_level) * num_rays;
+    *pairs_out = rays_initial(*bvh, num_rays, start_level);
     return IBVH_OK;
 }
 
+// (each entry keeps the order of its checks: the status of a call that fails several, and whether *result was reset
+// before a refusal, are observable)
 ibvh_status ibvh_traverse_bfs(const ibvh_bvh *bvh, int64_t start_level, int32_t narrow, void *bvtt1, void *bvtt2,
                               int64_t capacity, void *counters, ibvh_bfs_result *result, void *stream) {
     if (!bvh || !result) return IBVH_ERR_INVALID_ARG;
-    const ibvh_bfs_result in = *result;
-    *result = {0, 0, 1, 0, in.resume_step, in.resume_num};
-    if (in.resume_step < 0 || in.resume_num < 0) return IBVH_ERR_INVALID_ARG;
+    if (!reset_result(result)) return IBVH_ERR_INVALID_ARG;
     if (int e = check_levels(*bvh, start_level)) return (ibvh_status)e;
     if (!narrow_arg_ok(narrow, false)) return IBVH_ERR_INVALID_ARG;
     if (bvh->tree.real_nodes <= 1) return IBVH_OK; // bfs/traverse_single.jl:17-21
-    if (!bvtt1 || !bvtt2 || !counters || capacity < 1) return IBVH_ERR_INVALID_ARG;
+    const Buffers q{bvtt1, bvtt2, capacity, counters, result, (hipStream_t)stream};
+    if (!q.ok()) return IBVH_ERR_INVALID_ARG;
     if (bvh->types.index_type == IBVH_I32 && bvh->tree.levels > 31) return IBVH_ERR_OVERFLOW;
-    return (ibvh_status)dispatch(bvh->types, [&](auto lt, auto nt, auto it) -> int {
-        return run_self<typename decltype(lt)::type, typename decltype(nt)::type, typename decltype(it)::type>(
-            *bvh, start_level, narrow, bvtt1, bvtt2, capacity, counters, result, (hipStream_t)stream);
-    });
+    return (ibvh_status)dispatch(bvh->types, [&](auto t) -> int { return run_self(t, *bvh, start_level, narrow, q); });
 }
 
 ibvh_status ibvh_traverse_pair_bfs(const ibvh_bvh *bvh1, const ibvh_bvh *bvh2, int64_t sl1, int64_t sl2, int32_t narrow,
                                    void *bvtt1, void *bvtt2, int64_t capacity, void *counters, ibvh_bfs_result *result,
                                    void *stream) {
     if (!bvh1 || !bvh2 || !result) return IBVH_ERR_INVALID_ARG;
-    const ibvh_bfs_result in = *result;
-    *result = {0, 0, 1, 0, in.resume_step, in.resume_num};
-    if (in.resume_step < 0 || in.resume_num < 0) return IBVH_ERR_INVALID_ARG;
+    if (!reset_result(result)) return IBVH_ERR_INVALID_ARG;
     if (int e = check_levels(*bvh1, sl1)) return (ibvh_status)e;
     if (int e = check_levels(*bvh2, sl2)) return (ibvh_status)e;
     if (!same_types(bvh1->types, bvh2->types)) return IBVH_ERR_UNSUPPORTED;
     if (!narrow_arg_ok(narrow, false)) return IBVH_ERR_INVALID_ARG;
-    if (!bvtt1 || !bvtt2 || !counters || capacity < 1) return IBVH_ERR_INVALID_ARG;
+    const Buffers q{bvtt1, bvtt2, capacity, counters, result, (hipStream_t)stream};
+    if (!q.ok()) return IBVH_ERR_INVALID_ARG;
     if (bvh1->types.index_type == IBVH_I32 && (bvh1->tree.levels > 31 || bvh2->tree.levels > 31)) return IBVH_ERR_OVERFLOW;
-    return (ibvh_status)dispatch(bvh1->types, [&](auto lt, auto nt, auto it) -> int {
-        return run_pair<typename decltype(lt)::type, typename decltype(nt)::type, typename decltype(it)::type>(
-            *bvh1, *bvh2, sl1, sl2, narrow, bvtt1, bvtt2, capacity, counters, result, (hipStream_t)stream);
-    });
+    return (ibvh_status)dispatch(bvh1->types, [&](auto t) -> int { return run_pair(t, *bvh1, *bvh2, sl1, sl2, narrow, q); });
 }
 
 ibvh_status ibvh_traverse_rays_bfs(const ibvh_bvh *bvh, const void *points, const void *dirs, int64_t num_rays,
                                    int64_t start_level, int32_t narrow, void *bvtt1, void *bvtt2, int64_t capacity,
                                    void *counters, ibvh_bfs_result *result, void *stream) {
-    if (!bvh || !result || num_rays < 0 || !narrow_arg_ok(narrow, true)) return IBVH_ERR_INVALID_ARG;
-    const ibvh_bfs_result in = *result;
-    *result = {0, 0, 1, 0, in.resume_step, in.resume_num};
-    if (in.resume_step < 0 || in.resume_num < 0) return IBVH_ERR_INVALID_ARG;
+    if (!bvh || !result || num_rays < 0 || !narrow_arg_ok(narrow, true)) return IBVH_ERR_INVALID_ARG; // (before the reset)
+    if (!reset_result(result)) return IBVH_ERR_INVALID_ARG;
     if (int e = check_levels(*bvh, start_level)) return (ibvh_status)e;
     if (bvh->types.leaf_float != bvh->types.node_float) return IBVH_ERR_UNSUPPORTED;
     if (num_rays == 0) return IBVH_OK;
-    if (!points || !dirs || !bvtt1 || !bvtt2 || !counters || capacity < 1) return IBVH_ERR_INVALID_ARG;
+    const Buffers q{bvtt1, bvtt2, capacity, counters, result, (hipStream_t)stream};
+    if (!points || !dirs || !q.ok()) return IBVH_ERR_INVALID_ARG;
     if (bvh->types.index_type == IBVH_I32 && (bvh->tree.levels > 31 || num_rays > INT32_MAX)) return IBVH_ERR_OVERFLOW;
-    return (ibvh_status)dispatch(bvh->types, [&](auto lt, auto nt, auto it) -> int {
-        using L = typename decltype(lt)::type;
-        using N = typename decltype(nt)::type;
-        using I = typename decltype(it)::type;
-        if constexpr (!std::is_same<typename L::elt, typename N::elt>::value) return (int)IBVH_ERR_UNSUPPORTED;
-        else
-            return run_rays<L, N, I>(*bvh, points, dirs, num_rays, start_level, narrow, bvtt1, bvtt2, capacity, counters, result,
-                                     (hipStream_t)stream);
+    return (ibvh_status)dispatch(bvh->types, [&](auto t) -> int {
+        using T = decltype(t);
+        if constexpr (!std::is_same<typename T::L::elt, typename T::N::elt>::value) return (int)IBVH_ERR_UNSUPPORTED;
+        else return run_rays(t, *bvh, points, dirs, num_rays, start_level, narrow, q);
     });
 }
 
