@@ -91,6 +91,11 @@ TRIS_COUNT, TRIS_WRITE = 0, 1
 TRIS_SKIP_SHARED_VERTEX = 1
 TRIANGLE_CONTACTS_ARGTYPES = ([C.POINTER(Bvh), C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p, C.c_int64, C.c_int32, C.c_int32, C.c_void_p,
                                C.c_void_p, C.c_int64] + [C.c_void_p] * 5)
+# ibvh_sweep_spheres(bvh, triangles, num_triangles, centers, displacements, radii, num_spheres, t_max, mode, hit_index, hit_t,
+#                    hit_point, hit_feature, touched, flag, stream)
+SWEEP_CLOSEST, SWEEP_ANY = 0, 1
+SWEEP_SPHERES_ARGTYPES = ([C.POINTER(Bvh), C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p, C.c_int32]
+                          + [C.c_void_p] * 7)
 
 
 class BuildDesc(C.Structure):

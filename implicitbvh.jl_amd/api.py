@@ -33,7 +33,7 @@ __all__ = [
     "resolve_triangles", "raycast", "RayHits", "closest_points", "ClosestPoints",
     "nearest_leaves", "NearestLeaves", "point_crossings", "PointCrossings", "points_inside", "signed_distance",
     "cast_rays", "RayCast", "sphere_contacts", "SphereContacts",
-    "triangle_contacts", "TriangleContacts", "self_intersections",
+    "triangle_contacts", "TriangleContacts", "self_intersections", "sweep_spheres", "SphereSweep",
 ]
 
 NARROW_MORTON_LT = abi.NARROW_MORTON_LT
@@ -1673,6 +1673,83 @@ def sphere_contacts(bvh, triangles, centers, radii, count_only=False, presorted=
     walk = lambda: (order, (p, r if order is None else r[order]))
     return _contact_lists(SphereContacts, what, bvh, tris, n, walk, tail=(),
                           outs=((idt, ()), (ft, ()), (ft, (3,)), (torch.uint8, ())), count_only=count_only)
+
+
+# ---------------------------------------------------------------------------------------------
+# swept spheres: the first time of contact of each moving sphere with the mesh (ibvh_sweep_spheres; no reference counterpart)
+# ---------------------------------------------------------------------------------------------
+class SphereSweep:
+    """Per moving sphere: .index (N,) the first triangle it touches, by user index (0 = miss), .t (N,) the time of contact t*
+    (+Inf = miss; 0 = touching at the start), .point (N, 3) the point of the triangle it touches (0 on a miss), .feature (N,)
+    uint8 the feature that point lies on (0 vertex p1, 1 vertex p2, 2 edge p1p2, 3 vertex p3, 4 edge p1p3, 5 edge p2p3,
+    6 face; 0 on a miss), .hit (N,) bool = index != 0."""
+
+    def __init__(self, index, t, point, feature):
+        self.index, self.t, self.point, self.feature = index, t, point, feature
+
+    @property
+    def hit(self):
+        return self.index != 0
+
+
+def _per_item(value, n, ft, what, name):
+    """`value`, a number for all or an (N,) CUDA tensor of dtype ft -> the (N,) contiguous tensor"""
+    torch = _torch()
+    if isinstance(value, torch.Tensor):
+        if tuple(value.shape) == (n,) and value.dtype == ft and value.is_cuda:
+            return value.contiguous()
+    elif isinstance(value, (int, float, np.integer, np.floating)) and not isinstance(value, bool):
+        return torch.full((n,), float(value), dtype=ft, device="cuda")
+    raise ValueError(f"{what}: {name} must be a number or an (N,) {ft} tensor on the GPU")
+
+
+def sweep_spheres(bvh, triangles, centers, displacements, radii, t_max=None, any_hit=False, presorted=False):
+    """For every sphere of radius radii[i] whose centre moves along centers[:, i] + t * displacements[:, i] the first
+    triangle of the mesh `bvh` was built over that it touches, when, where and on which feature -> SphereSweep; with
+    any_hit=True only whether it touches anything within its limit -> (N,) bool tensor (the walk ends at its first hit).
+    Continuous collision detection: no tunnelling through thin walls, grazing contacts included.  One launch (include/ibvh.h,
+    ibvh_sweep_spheres: the start position — the evaluation of sphere_contacts —, the seven candidates — the face by the exact
+    test of resolve_triangles, three edge cylinders, three vertex spheres —, the clamp t* = max(t, entry of the leaf's box
+    grown by the radius), the tie rule — smallest t*, then the smaller index — and why pruning on the best hit so far loses
+    nothing are spelled out there); exact: bit-equal to a brute force over all triangles.
+
+    bvh: BBox leaves made from `triangles` (bounding_volumes_from_triangles(triangles, BBox(dtype)); a skin margin and
+    refit are fine) under BBox nodes of the same or a wider float type.  triangles: (n, 9) / (n, 3, 3) CUDA tensor of the
+    leaves' dtype, user index k = row k - 1.  centers, displacements: (3, N) CUDA tensors of that dtype, as for traverse_rays.
+    radii: an (N,) CUDA tensor of that dtype, or one number for all; a negative or NaN radius touches nothing.  t_max: None
+    (unbounded), a number — 1 = the whole displacement —, or an (N,) tensor of per-sphere limits; a hit needs t* <= t_max
+    (inclusive), a NaN or negative limit gives a miss.  A sphere that touches the mesh where it starts reports t = 0 and the
+    closest point of the touched triangle with the smallest index.  The device walks the batch in Morton order of the
+    centres (lanes of a wave then share nodes) and the outputs are put back in the caller's order; presorted=True walks it
+    as given.
+
+    ValueError: sphere leaves or nodes, nodes narrower than the leaves, a wrong dtype, device or shape, and a leaf whose
+    index lies outside 1..n (flag bit 1; such leaves are skipped)."""
+    torch = _require_gpu()
+    what = "sweep_spheres"
+    tris, ft, idt = _mesh_query_setup(bvh, triangles, what)
+    p, n, _, order = _query_points(centers, ft, None, presorted, what)
+    if not (isinstance(displacements, torch.Tensor) and displacements.dim() == 2 and tuple(displacements.shape) == (3, n)):
+        raise ValueError(f"{what}: size(displacements) == size(centers) == (3, N) must hold")
+    if displacements.dtype != ft or not displacements.is_cuda:
+        raise ValueError(f"{what}: displacements must be a {ft} tensor on the GPU (device='cuda')")
+    d = displacements.t().contiguous()
+    r = _per_item(radii, n, ft, what, "radii")
+    lim = None if t_max is None else _per_item(t_max, n, ft, what, "t_max")
+    if order is not None:
+        d, r = d[order], r[order]
+        lim = None if lim is None else lim[order]
+    if any_hit:
+        outs = (None, None, None, None, torch.empty(n, dtype=torch.uint8, device="cuda"))
+    else:
+        outs = (torch.empty(n, dtype=idt, device="cuda"), torch.empty(n, dtype=ft, device="cuda"),
+                torch.empty((n, 3), dtype=ft, device="cuda"), torch.empty(n, dtype=torch.uint8, device="cuda"), None)
+    if n > 0:
+        _mesh_query_call("ibvh_sweep_spheres", what, bvh, tris, _ptr(p), _ptr(d), _ptr(r), n, _ptr(lim),
+                         abi.SWEEP_ANY if any_hit else abi.SWEEP_CLOSEST, *[_ptr(o) for o in outs])
+    if any_hit:
+        return _unpermute(order, (outs[4],))[0] != 0
+    return SphereSweep(*_unpermute(order, outs[:4]))
 
 
 # ---------------------------------------------------------------------------------------------

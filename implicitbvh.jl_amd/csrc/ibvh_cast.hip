@@ -17,6 +17,7 @@
 // ibvh_raytri.hip resolves candidate lists with.  Ray, inverse direction and best hit live in registers.
 #include "ibvh_pointwalk.hpp"
 #include "ibvh_raytest.hpp"
+#include "ibvh_slab.hpp"
 
 #include <limits>
 #include <type_traits>
@@ -25,25 +26,7 @@ namespace ibvh {
 namespace cast {
 
 using pointwalk::kBlock;
-
-// entry(box) of include/ibvh.h: the slab test's tmin where the ray meets the box, +Inf where it does not.  An axis the ray
-// does not move along admits or refuses by comparing the origin; the selects keep a NaN where the header says they do.
-template <class T> IBVH_D T slab_entry(const T *lo, const T *up, const T *p, const T *d, const T *inv) {
-    const T inf = std::numeric_limits<T>::infinity();
-    T tmin = -inf, tmax = inf;
-    bool ok = true;
-#pragma unroll
-    for (int k = 0; k < 3; ++k) {
-        const bool still = d[k] == T(0);
-        const T t1 = (lo[k] - p[k]) * inv[k], t2 = (up[k] - p[k]) * inv[k];
-        const T tnear = t2 < t1 ? t2 : t1, tfar = t2 > t1 ? t2 : t1;
-        const T nmin = tnear > tmin ? tnear : tmin, nmax = tfar < tmax ? tfar : tmax;
-        ok &= !still | ((lo[k] <= p[k]) & (p[k] <= up[k]));
-        tmin = still ? tmin : nmin;
-        tmax = still ? tmax : nmax;
-    }
-    return (ok & (tmin <= tmax) & (tmax >= T(0))) ? tmin : inf;
-}
+using slab::slab_entry; // entry(box) of include/ibvh.h, the copy ibvh_sweep.hip prunes with too
 
 // T: the leaves', triangles' and rays' float type; TN: the nodes' (the same or wider — a node box then holds values of T,
 // widened exactly, and narrows back exactly); ANY: only "is there a hit", the walk ends at the first one

@@ -3,7 +3,8 @@
 // shrinks while they walk, ibvh_crossings.hip (the triangles an axis ray from the point crosses), ibvh_spheres.hip (every
 // triangle within a sphere's radius of the point) and ibvh_tritri.hip (every triangle a query triangle cuts), whose bound is
 // a fixed yes / no, and ibvh_cast.hip (the closest or any hit
-// of a ray from the point), whose bound is the ray's entry distance into a box.  No reference counterpart: every traversal of
+// of a ray from the point), whose bound is the ray's entry distance into a box; ibvh_sweep.hip (the first contact of a sphere
+// moving from the point) walks on that bound too, with the boxes grown by its radius.  No reference counterpart: every traversal of
 // ImplicitBVH.jl is a fixed-volume overlap test (traverse/, raytrace/).
 //
 // For the kernels: the workgroup size, the distance queries' point-box bound (box_bound) and NaN test (hopeless), the walk,

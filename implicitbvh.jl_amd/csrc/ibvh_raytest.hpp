@@ -1,6 +1,6 @@
-// ibvh_raytest.hpp — the exact ray-triangle test of include/ibvh.h (ibvh_rays_resolve_triangles), ONE copy for the three
-// queries that pin it bit for bit: ibvh_raytri.hip (the nearest hit of a candidate list), ibvh_cast.hip (the ray cast) and
-// ibvh_tritri.hip (a triangle's edges against another triangle).
+// ibvh_raytest.hpp — the exact ray-triangle test of include/ibvh.h (ibvh_rays_resolve_triangles), ONE copy for the four
+// queries that pin it bit for bit: ibvh_raytri.hip (the nearest hit of a candidate list), ibvh_cast.hip (the ray cast),
+// ibvh_tritri.hip (a triangle's edges against another triangle) and ibvh_sweep.hip (a moving sphere against a face).
 // No reference counterpart: ImplicitBVH.jl stops at the candidate list (raytrace/leaf_vs_tree/leaf_vs_tree.jl:170-228).
 #pragma once
 #include "ibvh_common.hpp"

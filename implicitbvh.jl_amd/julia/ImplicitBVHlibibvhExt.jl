@@ -306,6 +306,10 @@ c_triangle_contacts(bvh, triangles, num_triangles, queries, query_ids, num_queri
     ccall((:ibvh_triangle_contacts, libibvh), Cint,
           (Ref{IbvhBvh}, Ptr{Cvoid}, Int64, Ptr{Cvoid}, Ptr{Cvoid}, Int64, Int32, Int32, Ptr{Cvoid}, Ptr{Cvoid}, Int64, Ptr{Cvoid}, Ptr{Cvoid}, Ptr{Cvoid}, Ptr{Cvoid}, Ptr{Cvoid}),
           bvh, triangles, num_triangles, queries, query_ids, num_queries, mode, skip, counts, offsets, capacity, contact_index, contact_mask, contact_points, flag, stream)
+c_sweep_spheres(bvh, triangles, num_triangles, centers, displacements, radii, num_spheres, t_max, mode, hit_index, hit_t, hit_point, hit_feature, touched, flag, stream) =
+    ccall((:ibvh_sweep_spheres, libibvh), Cint,
+          (Ref{IbvhBvh}, Ptr{Cvoid}, Int64, Ptr{Cvoid}, Ptr{Cvoid}, Ptr{Cvoid}, Int64, Ptr{Cvoid}, Int32, Ptr{Cvoid}, Ptr{Cvoid}, Ptr{Cvoid}, Ptr{Cvoid}, Ptr{Cvoid}, Ptr{Cvoid}, Ptr{Cvoid}),
+          bvh, triangles, num_triangles, centers, displacements, radii, num_spheres, t_max, mode, hit_index, hit_t, hit_point, hit_feature, touched, flag, stream)
 c_lvt_scratch_bytes(types, n_items, cache_slots, out) =
     ccall((:ibvh_lvt_scratch_bytes, libibvh), Cint,
           (Ref{IbvhTypes}, Int64, Int32, Ref{Csize_t}),
@@ -944,6 +948,66 @@ the higher one as `index`; never a triangle with itself or with a neighbour that
 function self_intersections(bvh::RocBVH{I}, triangles::ROCMatrix{T}; count_only::Bool=false) where {I, T}
     ids = ROCVector{I}(collect(I(1):I(size(triangles, 2))))
     triangle_contacts(bvh, triangles, triangles; query_ids=ids, skip_shared_vertices=true, count_only)
+end
+
+# ---- swept spheres: the first time of contact of each moving sphere with the mesh (include/ibvh.h, ibvh_sweep_spheres) --
+const IBVH_SWEEP_CLOSEST = Int32(0)
+const IBVH_SWEEP_ANY = Int32(1)
+"""
+    sweep_spheres(bvh::BVH, triangles::ROCMatrix{T}, centers::ROCMatrix{T}, displacements::ROCMatrix{T}, radii;
+                  t_max=nothing, any_hit=false, presorted=false) -> (; index, t, point, feature, hit)  |  ROCVector{Bool}
+
+For every sphere of radius `radii[i]` (or one number for all) whose centre moves along `centers[:, i] + t * displacements[:, i]`
+the first triangle of the mesh `bvh` was built over that it touches, in one launch: `index[i]` its user index (0 = miss),
+`t[i]` the time of contact (`Inf` = miss, 0 = touching at the start), `point[:, i]` the point of the triangle it touches,
+`feature[i]` the feature that point lies on (0 vertex p1, 1 vertex p2, 2 edge p1p2, 3 vertex p3, 4 edge p1p3, 5 edge p2p3,
+6 face), `hit[i] = index[i] != 0`.  With `any_hit=true` only whether the sphere touches anything within its limit (the walk
+ends at the first hit).  `t_max`: `nothing` (unbounded) or a `ROCVector{T}` of per-sphere limits, inclusive (1 = the whole
+displacement).  The result is the lexicographic minimum of (t*, index) over ALL triangles' hits — bit-equal to a brute force;
+the seven candidates per triangle, the clamp t* = max(t, entry of the leaf box grown by the radius), the limit and why pruning
+loses nothing are spelled out in include/ibvh.h.  A negative or NaN radius touches nothing.  `triangles` is 9 x n (column k =
+p1 p2 p3 of the triangle with user index k).  The BVH must have `BBox{T}` leaves made from the triangles (a skin margin and
+`refit!` are fine) under `BBox` nodes of `T` or wider; anything else raises ArgumentError.  The device walks the batch along a
+Morton curve through the centres and the outputs come back in the caller's order; `presorted=true` walks it as given.  Not a
+method of ImplicitBVH: the reference has no such query.
+"""
+function sweep_spheres(bvh::RocBVH{I}, triangles::ROCMatrix{T}, centers::ROCMatrix{T}, displacements::ROCMatrix{T},
+                       radii::Union{Real, ROCVector{T}}; t_max::Union{Nothing, ROCVector{T}}=nothing, any_hit::Bool=false,
+                       presorted::Bool=false) where {I, T}
+    d = bvh_desc(bvh)
+    isnothing(d) && throw(ArgumentError("sweep_spheres: no libibvh instantiation for this BVH's types"))
+    leaf_volume_type(bvh.leaves) === BBox{T} && eltype(bvh.nodes) <: BBox && sizeof(eltype(bvh.nodes)) >= sizeof(BBox{T}) ||
+        throw(ArgumentError("sweep_spheres: the BVH must have BBox{$T} leaves under BBox nodes of $T or wider"))
+    size(triangles, 1) == 9 || throw(ArgumentError("sweep_spheres: triangles must be 9 x n (p1 p2 p3 per column)"))
+    size(centers, 1) == size(displacements, 1) == 3 || throw(ArgumentError("size(centers, 1) == size(displacements, 1) == 3 must hold"))
+    size(centers, 2) == size(displacements, 2) || throw(ArgumentError("size(centers, 2) == size(displacements, 2) must hold"))
+    n = size(centers, 2)
+    radii isa Real || length(radii) == n || throw(ArgumentError("sweep_spheres: length(radii) == size(centers, 2) must hold"))
+    isnothing(t_max) || length(t_max) == n || throw(ArgumentError("sweep_spheres: length(t_max) == size(centers, 2) must hold"))
+    r = radii isa Real ? fill!(similar(centers, T, n), T(radii)) : radii
+    index = any_hit ? nothing : similar(centers, I, n)
+    t = any_hit ? nothing : similar(centers, T, n)
+    point = any_hit ? nothing : similar(centers, T, 3, n)
+    feature = any_hit ? nothing : similar(centers, UInt8, n)
+    touched = any_hit ? similar(centers, UInt8, n) : nothing
+    n == 0 && return any_hit ? (touched .!= 0x00) : (; index, t, point, feature, hit=index .!= 0)
+    order = presorted ? nothing : point_morton_order(centers)
+    perm = isnothing(order) ? nothing : ROCVector{Int64}(order)
+    c = isnothing(perm) ? centers : centers[:, perm]
+    dis = isnothing(perm) ? displacements : displacements[:, perm]
+    rw = isnothing(perm) ? r : r[perm]
+    lim = isnothing(t_max) || isnothing(perm) ? t_max : t_max[perm]
+    flag = scratch!(:sweep_flag, 4)
+    fill!(flag, 0x00)
+    check(c_sweep_spheres(d, devptr(triangles), Int64(size(triangles, 2)), devptr(c), devptr(dis), devptr(rw), Int64(n), devptr(lim),
+                          any_hit ? IBVH_SWEEP_ANY : IBVH_SWEEP_CLOSEST, devptr(index), devptr(t), devptr(point), devptr(feature),
+                          devptr(touched), devptr(flag), stream_ptr()), "ibvh_sweep_spheres")
+    Array(flag)[1] & 0x02 != 0 && throw(ArgumentError("sweep_spheres: a leaf's index lies outside 1:$(size(triangles, 2))"))
+    if !isnothing(order)
+        inv = ROCVector{Int64}(invperm(order))
+        any_hit ? (touched = touched[inv]) : ((index, t, point, feature) = (index[inv], t[inv], point[:, inv], feature[inv]))
+    end
+    any_hit ? (touched .!= 0x00) : (; index, t, point, feature, hit=index .!= 0)
 end
 
 # ---- k nearest leaves for a batch of query points (include/ibvh.h, ibvh_nearest_leaves) ------------------------------

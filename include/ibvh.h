@@ -48,6 +48,7 @@ extern "C" {
  *      (additive under 7 in the same way); ibvh_sphere_contacts and IBVH_SPHERES_COUNT / IBVH_SPHERES_WRITE (additive
  *      under 7 likewise: one more entry point);
  *      ibvh_triangle_contacts and IBVH_TRIS_COUNT / IBVH_TRIS_WRITE (additive under 7 likewise: one more entry point);
+ *      ibvh_sweep_spheres and IBVH_SWEEP_CLOSEST / IBVH_SWEEP_ANY (additive under 7 likewise: one more entry point);
  *      argument checks only, no layout or argument list moves: ibvh_key_histogram takes
  *      what fits its LDS staging (10 rows at 12-bit digits) and refuses shift > 63 and a negative prefix_shift,
  *      ibvh_pack_records / ibvh_dist_plan answer IBVH_ERR_OVERFLOW for an index past IBVH_I32 */
@@ -844,6 +845,111 @@ ibvh_status ibvh_triangle_contacts(const ibvh_bvh *bvh, const void *triangles, i
                                    const void *queries, const void *query_ids, int64_t num_queries, int32_t mode, int32_t skip,
                                    void *counts, const void *offsets, int64_t capacity,
                                    void *contact_index, void *contact_mask, void *contact_points, void *flag, void *stream);
+
+/* ----------------------------------------------------------------------------------- */
+/* swept spheres: the first time of contact of each moving sphere with the mesh          */
+/* ----------------------------------------------------------------------------------- */
+/* For every sphere of radius r whose centre moves from p to p + d (position p + t d): the FIRST triangle of the mesh the BVH
+ * was built over (ibvh_volumes_from_triangles with IBVH_BBOX) that it touches — which one, the time t, the point of the
+ * triangle it touches and the FEATURE that point lies on — or only whether it touches anything within its limit.  The
+ * narrow phase of continuous collision detection for particles against a surface: ibvh_sphere_contacts finds a contact only
+ * after penetration, and ibvh_cast_rays on the centres misses every grazing contact and is late by up to r on the others.
+ * No reference counterpart (the reference has no moving volumes and no exact triangle test); ONE launch, NO host
+ * synchronisation, no atomics, no LDS, no scratch buffer.
+ *   triangles  : num_triangles x 9 values (p1 p2 p3) of bvh->types.leaf_float, `flt` below; user index k is row k - 1
+ *   centers, displacements : num_spheres x 3 row-major values of `flt`, processed in the order given (neighbours in memory
+ *                that are neighbours in space walk the same nodes: sort a scattered batch along a Morton curve first)
+ *   radii      : num_spheres values of `flt`, one per sphere; required
+ *   t_max      : optional DEVICE array of num_spheres values of `flt`, the end of each sphere's motion (1 = the whole
+ *                displacement); NULL = unbounded
+ *   mode       : IBVH_SWEEP_CLOSEST or IBVH_SWEEP_ANY
+ * IBVH_SWEEP_CLOSEST outputs — each optional, at least one non-NULL; what was not asked for is not written; `touched`
+ * must be NULL:
+ *   hit_index   : num_spheres x I, the winning triangle's user index; 0 = miss
+ *   hit_t       : num_spheres x flt; +Inf = miss
+ *   hit_point   : num_spheres x 3 x flt, the point of the triangle the sphere touches; 0, 0, 0 on a miss
+ *   hit_feature : num_spheres x uint8, the feature that point lies on, in ibvh_sphere_contacts' codes —
+ *                 0 vertex a, 1 vertex b, 2 edge ab, 3 vertex c, 4 edge ac, 5 edge bc, 6 face  (a = p1, b = p2, c = p3);
+ *                 0 on a miss
+ * IBVH_SWEEP_ANY output:
+ *   touched    : num_spheres x uint8, 1 = the sphere touches something within its limit, 0 = it does not; required, and the
+ *                other four outputs must be NULL: WHICH triangle stopped the walk depends on the walk order.
+ * All arguments are validated before any launch, with the statuses of ibvh_cast_rays and in its order: a wrong combination of
+ * outputs, an unknown mode, NULL required pointers, negative sizes, a tree shape that is not an ImplicitTree's:
+ * IBVH_ERR_INVALID_ARG.  num_spheres == 0: IBVH_OK, nothing is touched.
+ * The result is defined independently of how it is found, in `flt`, every operation rounded once (nothing fused; correctly
+ * rounded divide and square root), every comparison false on NaN, so that it can be pinned bit for bit.  dot(x, y) =
+ * (x0 y0 + x1 y1) + x2 y2 and cross are those of ibvh_rays_resolve_triangles.  Per sphere (p, d, r) and triangle
+ * k = (a, b, c):
+ * 1. Radius and limit.  A sphere with !(r >= 0) — a negative or NaN radius — hits nothing; as in ibvh_sphere_contacts no
+ *    flag bit is raised for it.  L = min(t_max[i], largest finite flt) = t_max[i] > largest ? largest : t_max[i], the
+ *    select of ibvh_cast_rays.  A NaN or negative limit gives no hit.  r2 = r * r;  dd = dot(d, d).
+ * 2. Already touching.  d2, q, region = the evaluation of ibvh_closest_triangles for (k, p), unchanged.  If d2 <= r2:
+ *    t_k = 0, the point is q and the feature is region — the bits ibvh_sphere_contacts computes.
+ * 3. Otherwise, if d2 > r2 (false on NaN: a triangle with a NaN d2 — a NaN vertex, a NaN centre — is not hit), seven
+ *    candidates, each with a t, a point and a validity:
+ *    face:   n = cross(b - a, c - a);  len = sqrt(dot(n, n));  s0 = dot(n, p - a);  side = s0 >= 0 ? 1 : -1
+ *            o = p - ((side * r) / len) * n, per component
+ *            t and validity: the exact test of ibvh_rays_resolve_triangles for the ray (o, d) against k
+ *            (det != 0 && u >= 0 && v >= 0 && u + v <= 1 && t >= 0);  point = o + t * d, per component
+ *    edges (x, y) = (a, b), (b, c), (c, a):
+ *            e = y - x;  m = p - x;  ee = dot(e, e);  me = dot(m, e);  de = dot(d, e);  md = dot(m, d)
+ *            A = ee * dd - de * de;  B = ee * md - de * me;  C = ee * (dot(m, m) - r2) - me * me
+ *            disc = B * B - A * C;  t = (-B - sqrt(disc)) / A;  s = me + t * de
+ *            valid iff A > 0 && disc >= 0 && t >= 0 && s >= 0 && s <= ee;  point = x + (s / ee) * e, per component
+ *    vertices x = a, b, c:
+ *            m = p - x;  B = dot(m, d);  C = dot(m, m) - r2;  disc = B * B - dd * C;  t = (-B - sqrt(disc)) / dd
+ *            valid iff dd > 0 && disc >= 0 && t >= 0;  point = x
+ *    t_k = the smallest valid t, with its candidate's point and feature; AMONG EQUAL t THE FIRST CANDIDATE in the order
+ *    face, ab, bc, ca, a, b, c (a later candidate replaces an earlier one iff its t is strictly smaller).  No valid candidate,
+ *    or none with a t below +Inf: k is not hit.
+ *    Why the seven suffice: the set of centres within r of the triangle is the union of a prism (the triangle moved by up
+ *    to r along +-n), three cylinders around the edges and three spheres around the vertices; the prism's side walls lie
+ *    inside the cylinders, so the first point of the centre's ray in the union — the sphere starts outside it, step 2 — lies
+ *    on one of the prism's two faces, on a cylinder between its edge's ends, or on a sphere.  Only the prism face on p's side
+ *    can be met first.
+ * 4. Clamp and limit.  The grown box of a box [lo, up] is [lo_j - r, up_j + r], j = 0, 1, 2, computed in `flt`.
+ *    t*_k = max(t_k, entry(grown leaf box of k)) = entry > t_k ? entry : t_k, where entry is the slab test of ibvh_cast_rays,
+ *    unchanged, for the ray (p, d), and the leaf box is the stored leaf volume, skin included.  Triangle k is a hit of sphere
+ *    i iff steps 2 or 3 gave a t_k, its grown leaf box is admitted, and t*_k <= L (the limit is inclusive).
+ * 5. IBVH_SWEEP_CLOSEST is the LEXICOGRAPHIC MINIMUM of (t*_k, k) over all hits: the smallest t*, and among equal t* the
+ *    SMALLER INDEX.  The outputs carry t* and the point and feature of steps 2 / 3 unchanged.  IBVH_SWEEP_ANY is 1 iff a
+ *    hit exists.
+ * Why pruning is lossless WITHOUT an epsilon: lo_j - r and up_j + r are round-to-nearest, hence monotone in lo_j and up_j,
+ *   and every box of the tree contains the boxes below it exactly (min / max, exact widening, a skin margin, ibvh_refit), so
+ *   the grown box of a node contains the grown box of everything below it exactly.  The argument of ibvh_cast_rays then
+ *   carries over word for word: the COMPUTED entry is monotone in the corners, an admitted box has admitted ancestors, and
+ *   t*_k >= entry(grown leaf_k) >= entry(every grown ancestor).  A node or leaf is skipped iff entry > limit() — strictly: an
+ *   equal t* under it may carry a smaller index.  limit() starts at L; the closest query lowers it to the best t* found so
+ *   far, the any query drops it to -Inf on the first hit.  Traversal order and work mapping therefore cannot change the
+ *   result.
+ * Limits.  d == 0 makes every candidate of step 3 invalid (det == 0, A == 0, dd == 0): the query reduces to "is anything
+ *   touching now".  A triangle whose computed normal is zero (zero area) has no face candidate (len == 0 makes o NaN or the
+ *   exact test's det 0); its edges and vertices still answer.  hit_t == 0 names a triangle of the sphere's
+ *   ibvh_sphere_contacts list — the one with the smallest index — except where rounding leaves the centre outside that
+ *   triangle's grown leaf box (then its t* is the box's entry, or it is no hit).  Which of several features that meet at one
+ *   t is reported follows the candidate order; it is not a geometric statement: a sphere that lands exactly on a corner
+ *   reports the first edge that ends there.  The quadratics lose digits where the path grazes a feature (disc near 0) and
+ *   for |d| much smaller or larger than the mesh: t is what the operations above give, not the nearest float to the true time.
+ * Accepted BVHs — exactly those of ibvh_cast_rays: leaf_kind == node_kind == IBVH_BBOX, triangles and spheres of
+ *   leaf_float, node_float the same as or wider than leaf_float; any index and Morton type.  Anything else — sphere leaves,
+ *   sphere nodes, F64 leaves under F32 nodes — is IBVH_ERR_UNSUPPORTED, never an answer.  Exact PROVIDED every leaf's box
+ *   contains its triangle's box: a skin margin on the leaves is allowed, and so is a BVH after ibvh_refit.  Levels above
+ *   bvh->built_level are not read.
+ * NaN: a triangle with a NaN vertex has a NaN d2 and is never hit (step 3); a NaN centre or displacement hits nothing.  But,
+ *   as for ibvh_closest_triangles, a NaN leaf box can make merge.jl's `a < b ? a : b` produce a node box that does NOT contain
+ *   the NaN-free leaves below it: on a mesh with NaN vertices the other triangles' hits are only guaranteed in trees of at
+ *   most two leaves.
+ * Guards: the triangle is read through the leaf record's .index, not its position.  A leaf whose index lies outside
+ * 1..num_triangles is skipped, nothing outside the array is read, and bit 1 of `flag` (value 2) is set — the flag contract of
+ * ibvh_rays_resolve_triangles: optional, 4 bytes the GPU can write, a plain load and store, never cleared by the library
+ * (zero it before the call). */
+enum { IBVH_SWEEP_CLOSEST = 0, IBVH_SWEEP_ANY = 1 };
+ibvh_status ibvh_sweep_spheres(const ibvh_bvh *bvh, const void *triangles, int64_t num_triangles,
+                               const void *centers, const void *displacements, const void *radii, int64_t num_spheres,
+                               const void *t_max, int32_t mode,
+                               void *hit_index, void *hit_t, void *hit_point, void *hit_feature, void *touched,
+                               void *flag, void *stream);
 
 /* ----------------------------------------------------------------------------------- */
 /* breadth-first traversal (BFSTraversal): level-synchronous pair queues                 */
