@@ -96,6 +96,10 @@ TRIANGLE_CONTACTS_ARGTYPES = ([C.POINTER(Bvh), C.c_void_p, C.c_int64, C.c_void_p
 SWEEP_CLOSEST, SWEEP_ANY = 0, 1
 SWEEP_SPHERES_ARGTYPES = ([C.POINTER(Bvh), C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p, C.c_int32]
                           + [C.c_void_p] * 7)
+# ibvh_triangle_distances(bvh, triangles, num_triangles, queries, num_queries, skip, max_distance2, closest_index, closest_d2,
+#                         point_query, point_mesh, closest_kind, flag, stream)
+TRIDIST_CUT = 15  # closest_kind of a pair the cut rule decided (include/ibvh.h)
+TRIANGLE_DISTANCES_ARGTYPES = [C.POINTER(Bvh), C.c_void_p, C.c_int64, C.c_void_p, C.c_int64, C.c_int32] + [C.c_void_p] * 8
 
 
 class BuildDesc(C.Structure):

@@ -34,6 +34,7 @@ __all__ = [
     "nearest_leaves", "NearestLeaves", "point_crossings", "PointCrossings", "points_inside", "signed_distance",
     "cast_rays", "RayCast", "sphere_contacts", "SphereContacts",
     "triangle_contacts", "TriangleContacts", "self_intersections", "sweep_spheres", "SphereSweep",
+    "triangle_distances", "TriangleDistances", "mesh_distance", "MeshDistance", "self_clearance",
 ]
 
 NARROW_MORTON_LT = abi.NARROW_MORTON_LT
@@ -1825,6 +1826,98 @@ def self_intersections(bvh, triangles, count_only=False):
     tris, _, idt = _mesh_query_setup(bvh, triangles, "self_intersections")
     ids = torch.arange(1, tris.shape[0] + 1, dtype=idt, device="cuda")
     return triangle_contacts(bvh, tris, tris, query_ids=ids, skip_shared_vertices=True, count_only=count_only)
+
+
+# ---------------------------------------------------------------------------------------------
+# triangle-vs-mesh distance: the closest mesh triangle per query triangle (ibvh_triangle_distances; no reference counterpart)
+# ---------------------------------------------------------------------------------------------
+class TriangleDistances:
+    """Per query triangle: .index (N,) the closest mesh triangle's user index (0 = none), .d2 (N,) the SQUARED distance (+Inf
+    = none; 0 = the two cut each other), .point_query (N, 3) the closest point on the query triangle, .point_mesh (N, 3) the
+    closest point on the mesh triangle (zeros = none), .kind (N,) uint8 the deciding candidate: 0-2 the query's vertex a, b,
+    c against the mesh triangle, 3-5 the mesh triangle's vertex p1, p2, p3 against the query, 6 + 3 i + j the query's edge i
+    (ab, bc, ca) against the mesh triangle's edge j (p1p2, p2p3, p3p1), 15 an edge of one cuts the other (0 = none)."""
+
+    def __init__(self, index, d2, point_query, point_mesh, kind):
+        self.index, self.d2, self.point_query, self.point_mesh, self.kind = index, d2, point_query, point_mesh, kind
+
+
+class MeshDistance:
+    """The one closest pair of two meshes: .distance (float; inf = none), .query the 1-based position of the query triangle
+    (0 = none), .index the mesh triangle's user index (0 = none), .point_query and .point_mesh (3,) tensors."""
+
+    def __init__(self, distance, query, index, point_query, point_mesh):
+        self.distance, self.query, self.index, self.point_query, self.point_mesh = distance, query, index, point_query, point_mesh
+
+
+def triangle_distances(bvh, triangles, queries, max_distance=None, skip_shared_vertices=False, presorted=False):
+    """For every query triangle the closest triangle of the mesh `bvh` was built over, the squared distance, the closest
+    point on each of the two and the deciding pair of features -> TriangleDistances (include/ibvh.h, ibvh_triangle_distances:
+    the cut rule — the six edge tests of triangle_contacts give distance 0 —, the fifteen candidates — six vertex-against-
+    triangle evaluations of closest_points and nine edge pairs —, the tie rule — smallest distance, then the smaller index —
+    and why pruning on the gap between boxes loses nothing are spelled out there).  One launch, exact: bit-equal to a brute
+    force over all pairs.  Coplanar and touching pairs are decided by rounding.
+
+    bvh: BBox leaves made from `triangles` (bounding_volumes_from_triangles(triangles, BBox(dtype)); a skin margin and
+    refit are fine) under BBox nodes of the same or a wider float type.  triangles: (n, 9) / (n, 3, 3) CUDA tensor of the
+    leaves' dtype, user index k = row k - 1.  queries: (N, 9) / (N, 3, 3) CUDA tensor of that dtype.  max_distance: search
+    radius (None = unbounded); it is squared in the triangles' dtype on the host and a triangle qualifies iff its squared
+    distance <= that product.  skip_shared_vertices=True ignores every mesh triangle with a vertex equal to one of the
+    query's.  A query with a NaN coordinate has no answer.  The device walks the batch in Morton order of the queries'
+    centroids (lanes of a wave then share nodes) and the outputs are put back in the caller's order; presorted=True walks
+    it as given.
+
+    ValueError: sphere leaves or nodes, nodes narrower than the leaves, a wrong dtype, device or shape, and a leaf whose
+    index lies outside 1..n (flag bit 1; such leaves are skipped)."""
+    torch = _require_gpu()
+    what = "triangle_distances"
+    tris, ft, idt = _mesh_query_setup(bvh, triangles, what)
+    if not isinstance(queries, torch.Tensor) or not (
+            (queries.dim() == 2 and queries.shape[1] == 9) or (queries.dim() == 3 and tuple(queries.shape[1:]) == (3, 3))):
+        raise ValueError(f"{what}: queries must be an (N, 9) or (N, 3, 3) tensor (a b c per triangle)")
+    if queries.dtype != ft or not queries.is_cuda:
+        raise ValueError(f"{what}: queries must be a {ft} tensor on the GPU (device='cuda')")
+    q = queries.reshape(queries.shape[0], 9).contiguous()
+    n = int(q.shape[0])
+    radius2 = None
+    if max_distance is not None:
+        npdt = np.float32 if ft == torch.float32 else np.float64
+        with np.errstate(over="ignore"):
+            m = npdt(max_distance) * npdt(max_distance)
+        radius2 = C.byref((C.c_float if ft == torch.float32 else C.c_double)(m))
+    outs = (torch.empty(n, dtype=idt, device="cuda"), torch.empty(n, dtype=ft, device="cuda"),
+            torch.empty((n, 3), dtype=ft, device="cuda"), torch.empty((n, 3), dtype=ft, device="cuda"),
+            torch.empty(n, dtype=torch.uint8, device="cuda"))
+    if n == 0:
+        return TriangleDistances(*outs)
+    order = None if presorted else _morton_order((q[:, 0:3] + q[:, 3:6] + q[:, 6:9]) / 3)
+    skip = abi.TRIS_SKIP_SHARED_VERTEX if skip_shared_vertices else 0
+    walked = q if order is None else q[order]   # (held until the call returns: the launch reads it)
+    _mesh_query_call("ibvh_triangle_distances", what, bvh, tris, _ptr(walked), n, skip, radius2, *[_ptr(o) for o in outs])
+    return TriangleDistances(*_unpermute(order, outs))
+
+
+def mesh_distance(bvh, triangles, queries, max_distance=None, skip_shared_vertices=False, presorted=False):
+    """The one closest pair between the query triangles and the mesh `bvh` was built over -> MeshDistance:
+    triangle_distances, reduced on the device to its smallest d2 — among equal ones the lowest query position — and read
+    back once.  distance inf and query = index = 0 when no pair qualifies."""
+    torch = _torch()
+    td = triangle_distances(bvh, triangles, queries, max_distance, skip_shared_vertices, presorted)
+    n = int(td.d2.shape[0])
+    if n == 0:
+        zero = torch.zeros(3, dtype=td.d2.dtype, device="cuda")
+        return MeshDistance(float("inf"), 0, 0, zero, zero.clone())
+    smallest = td.d2.min()
+    pos = torch.where(td.d2 == smallest, torch.arange(n, device="cuda"), n).min()   # the first of the smallest
+    index, d2 = int(td.index[pos].item()), float(td.d2[pos].item())
+    return MeshDistance(float(np.sqrt(d2)), int(pos.item()) + 1 if index else 0, index, td.point_query[pos], td.point_mesh[pos])
+
+
+def self_clearance(bvh, triangles, max_distance=None):
+    """How close each triangle of ONE mesh comes to the rest of it -> TriangleDistances with the mesh's triangles as the
+    queries: triangle_distances(bvh, triangles, triangles, skip_shared_vertices=True).  No triangle reports itself or a
+    neighbour that shares a vertex with it; d2 = 0 marks a self-intersection, a small d2 one about to happen."""
+    return triangle_distances(bvh, triangles, triangles, max_distance=max_distance, skip_shared_vertices=True)
 
 
 # ---------------------------------------------------------------------------------------------

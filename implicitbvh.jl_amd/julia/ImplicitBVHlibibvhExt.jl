@@ -310,6 +310,10 @@ c_sweep_spheres(bvh, triangles, num_triangles, centers, displacements, radii, nu
     ccall((:ibvh_sweep_spheres, libibvh), Cint,
           (Ref{IbvhBvh}, Ptr{Cvoid}, Int64, Ptr{Cvoid}, Ptr{Cvoid}, Ptr{Cvoid}, Int64, Ptr{Cvoid}, Int32, Ptr{Cvoid}, Ptr{Cvoid}, Ptr{Cvoid}, Ptr{Cvoid}, Ptr{Cvoid}, Ptr{Cvoid}, Ptr{Cvoid}),
           bvh, triangles, num_triangles, centers, displacements, radii, num_spheres, t_max, mode, hit_index, hit_t, hit_point, hit_feature, touched, flag, stream)
+c_triangle_distances(bvh, triangles, num_triangles, queries, num_queries, skip, max_distance2, closest_index, closest_d2, point_query, point_mesh, closest_kind, flag, stream) =
+    ccall((:ibvh_triangle_distances, libibvh), Cint,
+          (Ref{IbvhBvh}, Ptr{Cvoid}, Int64, Ptr{Cvoid}, Int64, Int32, Ptr{Cvoid}, Ptr{Cvoid}, Ptr{Cvoid}, Ptr{Cvoid}, Ptr{Cvoid}, Ptr{Cvoid}, Ptr{Cvoid}, Ptr{Cvoid}),
+          bvh, triangles, num_triangles, queries, num_queries, skip, max_distance2, closest_index, closest_d2, point_query, point_mesh, closest_kind, flag, stream)
 c_lvt_scratch_bytes(types, n_items, cache_slots, out) =
     ccall((:ibvh_lvt_scratch_bytes, libibvh), Cint,
           (Ref{IbvhTypes}, Int64, Int32, Ref{Csize_t}),
@@ -1008,6 +1012,79 @@ function sweep_spheres(bvh::RocBVH{I}, triangles::ROCMatrix{T}, centers::ROCMatr
         any_hit ? (touched = touched[inv]) : ((index, t, point, feature) = (index[inv], t[inv], point[:, inv], feature[inv]))
     end
     any_hit ? (touched .!= 0x00) : (; index, t, point, feature, hit=index .!= 0)
+end
+
+# ---- triangle-vs-mesh distance: the closest mesh triangle per query triangle (include/ibvh.h, ibvh_triangle_distances) --
+"""
+    triangle_distances(bvh::BVH, triangles::ROCMatrix{T}, queries::ROCMatrix{T}; max_distance=nothing,
+                       skip_shared_vertices=false, presorted=false) -> (; index, d2, point_query, point_mesh, kind)
+
+For every query triangle (column of the 9 x N `queries`: a b c) the closest triangle of the mesh `bvh` was built over, in one
+launch: `index[i]` its user index (0 = none), `d2[i]` the squared distance (`Inf` = none, 0 = the two cut each other),
+`point_query[:, i]` and `point_mesh[:, i]` the closest points on the query and on the mesh triangle (zeros = none), `kind[i]`
+the deciding candidate: 0-2 the query's vertex a, b, c against the mesh triangle, 3-5 the mesh triangle's vertex p1, p2, p3
+against the query, 6 + 3i + j the query's edge i (ab, bc, ca) against the mesh triangle's edge j (p1p2, p2p3, p3p1), 15 an edge
+of one cuts the other.  The result is the lexicographic minimum of (squared distance, index) over ALL triangles — bit-equal to
+a brute force over all pairs; the cut rule, the fifteen candidates, the tie rule and why pruning on the gap between boxes loses
+nothing are spelled out in include/ibvh.h.  Coplanar and touching pairs are decided by rounding; a query with a NaN coordinate
+has no answer.  `max_distance` is squared in `T` on the host; `skip_shared_vertices=true` ignores every mesh triangle with a
+vertex equal to one of the query's (a mesh against itself: self-clearance).  `triangles` is 9 x n (column k = p1 p2 p3 of the
+triangle with user index k).  The BVH must have `BBox{T}` leaves made from the triangles (a skin margin and `refit!` are fine)
+under `BBox` nodes of `T` or wider; anything else raises ArgumentError.  The device walks the batch along a Morton curve
+through the queries' centroids and the outputs come back in the caller's order; `presorted=true` walks it as given.  Not a
+method of ImplicitBVH: the reference has no such query.
+"""
+function triangle_distances(bvh::RocBVH{I}, triangles::ROCMatrix{T}, queries::ROCMatrix{T}; max_distance=nothing,
+                            skip_shared_vertices::Bool=false, presorted::Bool=false) where {I, T}
+    d = bvh_desc(bvh)
+    isnothing(d) && throw(ArgumentError("triangle_distances: no libibvh instantiation for this BVH's types"))
+    leaf_volume_type(bvh.leaves) === BBox{T} && eltype(bvh.nodes) <: BBox && sizeof(eltype(bvh.nodes)) >= sizeof(BBox{T}) ||
+        throw(ArgumentError("triangle_distances: the BVH must have BBox{$T} leaves under BBox nodes of $T or wider"))
+    size(triangles, 1) == 9 || throw(ArgumentError("triangle_distances: triangles must be 9 x n (p1 p2 p3 per column)"))
+    size(queries, 1) == 9 || throw(ArgumentError("triangle_distances: queries must be 9 x N (a b c per column)"))
+    n = size(queries, 2)
+    index = similar(queries, I, n)
+    d2 = similar(queries, T, n)
+    point_query = similar(queries, T, 3, n)
+    point_mesh = similar(queries, T, 3, n)
+    kind = similar(queries, UInt8, n)
+    n == 0 && return (; index, d2, point_query, point_mesh, kind)
+    skip = skip_shared_vertices ? IBVH_TRIS_SKIP_SHARED_VERTEX : Int32(0)
+    radius2 = isnothing(max_distance) ? C_NULL : Ref(T(max_distance) * T(max_distance))
+    order = presorted ? nothing : point_morton_order((queries[1:3, :] .+ queries[4:6, :] .+ queries[7:9, :]) ./ T(3))
+    q = isnothing(order) ? queries : queries[:, ROCVector{Int64}(order)]
+    flag = scratch!(:tridist_flag, 4)
+    fill!(flag, 0x00)
+    GC.@preserve radius2 begin
+        r2 = radius2 === C_NULL ? Ptr{Cvoid}(C_NULL) : Ptr{Cvoid}(Base.unsafe_convert(Ptr{T}, radius2))
+        check(c_triangle_distances(d, devptr(triangles), Int64(size(triangles, 2)), devptr(q), Int64(n), skip, r2, devptr(index),
+                                   devptr(d2), devptr(point_query), devptr(point_mesh), devptr(kind), devptr(flag), stream_ptr()),
+              "ibvh_triangle_distances")
+    end
+    Array(flag)[1] & 0x02 != 0 && throw(ArgumentError("triangle_distances: a leaf's index lies outside 1:$(size(triangles, 2))"))
+    isnothing(order) && return (; index, d2, point_query, point_mesh, kind)
+    inv = ROCVector{Int64}(invperm(order))
+    (; index=index[inv], d2=d2[inv], point_query=point_query[:, inv], point_mesh=point_mesh[:, inv], kind=kind[inv])
+end
+
+"""
+    mesh_distance(bvh::BVH, triangles::ROCMatrix{T}, queries::ROCMatrix{T}; max_distance=nothing,
+                  skip_shared_vertices=false, presorted=false) -> (; distance, query, index, point_query, point_mesh)
+
+The one closest pair between the query triangles and the mesh: `triangle_distances` reduced on the device to its smallest
+squared distance — among equal ones the lowest query position — and read back once.  `distance` is `Inf` and `query`,
+`index` are 0 when no pair qualifies.
+"""
+function mesh_distance(bvh::RocBVH{I}, triangles::ROCMatrix{T}, queries::ROCMatrix{T}; max_distance=nothing,
+                       skip_shared_vertices::Bool=false, presorted::Bool=false) where {I, T}
+    r = triangle_distances(bvh, triangles, queries; max_distance, skip_shared_vertices, presorted)
+    n = length(r.d2)
+    n == 0 && return (; distance=T(Inf), query=0, index=I(0), point_query=zeros(T, 3), point_mesh=zeros(T, 3))
+    smallest = minimum(r.d2)
+    pos = minimum(ifelse.(r.d2 .== smallest, ROCVector{Int64}(collect(1:n)), n + 1))   # the first of the smallest
+    index = Array(r.index[pos:pos])[1]
+    (; distance=sqrt(Array(r.d2[pos:pos])[1]), query=index == 0 ? 0 : pos, index,
+     point_query=Array(r.point_query[:, pos]), point_mesh=Array(r.point_mesh[:, pos]))
 end
 
 # ---- k nearest leaves for a batch of query points (include/ibvh.h, ibvh_nearest_leaves) ------------------------------

@@ -49,6 +49,7 @@ extern "C" {
  *      under 7 likewise: one more entry point);
  *      ibvh_triangle_contacts and IBVH_TRIS_COUNT / IBVH_TRIS_WRITE (additive under 7 likewise: one more entry point);
  *      ibvh_sweep_spheres and IBVH_SWEEP_CLOSEST / IBVH_SWEEP_ANY (additive under 7 likewise: one more entry point);
+ *      ibvh_triangle_distances (additive under 7 likewise: one more entry point);
  *      argument checks only, no layout or argument list moves: ibvh_key_histogram takes
  *      what fits its LDS staging (10 rows at 12-bit digits) and refuses shift > 63 and a negative prefix_shift,
  *      ibvh_pack_records / ibvh_dist_plan answer IBVH_ERR_OVERFLOW for an index past IBVH_I32 */
@@ -950,6 +951,104 @@ ibvh_status ibvh_sweep_spheres(const ibvh_bvh *bvh, const void *triangles, int64
                                const void *t_max, int32_t mode,
                                void *hit_index, void *hit_t, void *hit_point, void *hit_feature, void *touched,
                                void *flag, void *stream);
+
+/* ----------------------------------------------------------------------------------- */
+/* triangle-vs-mesh distance: the closest mesh triangle per query triangle               */
+/* ----------------------------------------------------------------------------------- */
+/* For every query triangle Q = (a, b, c): the CLOSEST triangle K = (p1, p2, p3) of the mesh the BVH was built over
+ * (ibvh_volumes_from_triangles with IBVH_BBOX) — which one, the squared distance, the closest point on each of the two and
+ * the pair of features they lie on.  The distance query beside ibvh_triangle_contacts ("do they touch") and
+ * ibvh_sweep_spheres ("when"): clearance between parts, the gap that sizes a contact solver's next step, proximity lists
+ * and, with a mesh as its own queries and the skip flag, self-clearance.  ibvh_closest_triangles on Q's vertices misses
+ * every edge-against-edge pair and every pair that already cuts.  No reference counterpart (the reference's traversal of
+ * two meshes ends at pairs of triangle BOXES); ONE launch, NO host synchronisation, no atomics, no LDS, no scratch buffer,
+ * no candidate list.
+ *   triangles  : num_triangles x 9 values (p1 p2 p3) of bvh->types.leaf_float, `flt` below; user index k is row k - 1
+ *   queries    : num_queries x 9 values (a b c) of `flt`, processed in the order given (neighbours in memory that are
+ *                neighbours in space walk the same nodes: sort a scattered batch along a Morton curve first)
+ *   skip       : 0 or IBVH_TRIS_SKIP_SHARED_VERTEX (bit 0): a K that shares a vertex with Q is no answer.  Equal means ==
+ *                on all three coordinates, over the nine vertex pairs (the rule of ibvh_triangle_contacts).
+ *   max_distance2 : HOST pointer to one value of `flt`, the SQUARED search radius; NULL = +Inf (unbounded)
+ * Outputs — every pointer optional, at least one non-NULL; what was not asked for is not written:
+ *   closest_index : num_queries x I, the winning triangle's user index; 0 = none
+ *   closest_d2    : num_queries x flt; +Inf = none
+ *   point_query   : num_queries x 3 x flt, xQ, the closest point on Q; 0, 0, 0 = none
+ *   point_mesh    : num_queries x 3 x flt, xK, the closest point on K; 0, 0, 0 = none
+ *   closest_kind  : num_queries x uint8, the deciding candidate (below); 0 = none
+ * All arguments are validated before any launch, in the order of the other point-walk entries.  The entry's own checks: NULL
+ * bvh, negative sizes, any bit of `skip` other than bit 0, no output at all: IBVH_ERR_INVALID_ARG.  Then the type
+ * combination (below): IBVH_ERR_UNSUPPORTED.  Then a tree shape that is not an ImplicitTree's or a missing array:
+ * IBVH_ERR_INVALID_ARG.  num_queries == 0: IBVH_OK, nothing is touched.
+ * The result is defined independently of how it is found, in `flt` throughout, every operation rounded once (nothing fused;
+ * correctly rounded divide), every comparison false on NaN, so that it can be pinned bit for bit.
+ * x . y = (x0*y0 + x1*y1) + x2*y2.  A triangle's exact box: lo_k / up_k = the minimum / maximum of its three vertices' k-th
+ * coordinates, folded from the first vertex with `x < m ? x : m` / `x > m ? x : m` (exact).  The result (d2, xQ, xK, kind)
+ * of a pair (Q, K) comes from two rules.
+ *   The CUT rule, only if K's exact box is not apart from Q's exact box (apart: the six strict comparisons of
+ *     ibvh_triangle_contacts, qup_k < lo_k || qlo_k > up_k for some k): the six edge tests of ibvh_triangle_contacts in its
+ *     order — a->b, b->c, c->a against K, p1->p2, p2->p3, p3->p1 against Q; seg(P0, P1, Tri) = the ray-triangle test of
+ *     ibvh_rays_resolve_triangles with p = P0, d = P1 - P0 is true AND t <= 1.  If any hits: d2 = 0, xQ = xK = P0 + t * d of
+ *     the FIRST test that hit (one rounded product and one rounded sum per coordinate), kind = 15.
+ *   The CANDIDATE rule, if the cut rule did not decide: fifteen candidates, evaluated in this order; candidate 0 starts the
+ *     result and a later one replaces it iff its d2 is strictly smaller (so the FIRST of the smallest wins, and a NaN d2 of
+ *     candidate 0 stays).
+ *       kind 0, 1, 2      : vertex a, b, c of Q against K: the evaluation of ibvh_closest_triangles for (K, vertex);
+ *                           xQ = the vertex, xK = its q, d2 = its d2
+ *       kind 3, 4, 5      : vertex p1, p2, p3 of K against Q: the same evaluation for (Q, vertex); xQ = its q, xK = the vertex
+ *       kind 6 + 3 i + j  : edge i of Q (0: a->b, 1: b->c, 2: c->a) against edge j of K (0: p1->p2, 1: p2->p3, 2: p3->p1):
+ *                           the segment-segment evaluation below for (P1, Q1) = Q's edge and (P2, Q2) = K's edge
+ *     The segment-segment evaluation (Ericson, Real-Time Collision Detection 5.1.9; exact tests, no epsilon):
+ *       d1 = Q1 - P1;  d2v = Q2 - P2;  r = P1 - P2;  A = d1 . d1;  E = d2v . d2v;  F = d2v . r;  s = t = 0
+ *       unit(x) = x < 0 ? 0 : (x > 1 ? 1 : x)
+ *       if A == 0:  if E != 0: t = unit(F / E)
+ *       else:  C = d1 . r
+ *         if E == 0:  s = unit(-C / A)
+ *         else:  B = d1 . d2v;  den = A*E - B*B;  if den > 0: s = unit((B*F - C*E) / den)
+ *                t = (B*s + F) / E
+ *                if t < 0: t = 0, s = unit(-C / A)    else if t > 1: t = 1, s = unit((B - C) / A)
+ *       y1 = P1 + s*d1;  y2 = P2 + t*d2v per component; each is then clamped into its own segment's box,
+ *       x = y < lo ? lo : (y > up ? up : y) with lo / up = `P < Q ? P : Q` / `P > Q ? P : Q`;  xQ = x1, xK = x2;
+ *       e = xQ - xK;  d2 = (e0*e0 + e1*e1) + e2*e2.
+ *   Per query the answer is the LEXICOGRAPHIC MINIMUM of (d2, index) over ALL mesh triangles with d2 <= max_distance2, with
+ *   bit 0 of skip clear or no vertex of Q equal to a vertex of K, and with an index that names a row of `triangles`: the tie
+ *   rule of ibvh_closest_triangles.  A query with a NaN coordinate (or a NaN radius) has no answer; a pair whose d2 is NaN
+ *   never wins.  The outputs carry the winner's bits unchanged.
+ * Why the fifteen suffice: the closest points of two triangles that do not cut each other can be chosen with one of them on
+ *   the boundary of its triangle — a vertex of one against the other triangle, or an edge against an edge.  Two triangles
+ *   that cut have an edge of one through the other, which is what the cut rule tests.
+ * Why pruning is lossless WITHOUT an epsilon.  (1) Every xQ lies in Q's exact box: a vertex does, and the point-triangle and
+ *   segment-segment points are clamped into their triangle's / segment's box, which lies inside it.  (2) Every xK lies in K's
+ *   exact box likewise, which lies in K's leaf box and in every box above it (min / max, widening conversions, a skin margin
+ *   and ibvh_refit keep containment exact).  (3) The bound of a box B = [lo, up] is
+ *       g_k = max(0, lo_k - qup_k, qlo_k - up_k) (both differences rounded);  lb(B) = (g0*g0 + g1*g1) + g2*g2
+ *   the same operation order as d2; round-to-nearest subtraction, multiplication and addition are monotone, so the COMPUTED
+ *   lb(B) <= the COMPUTED d2 of every pair under B.  (4) A cut pair has exact boxes that are not apart, so both differences
+ *   are <= 0 in every box above it and lb = 0 = its d2.  The walk skips a node or a leaf iff lb > best d2 so far — strictly:
+ *   lb == best may hide an equal d2 of smaller index.  The best d2 starts at max_distance2 or, if that is smaller, at the
+ *   squared distance from Q's vertex a to the closest triangle S the query may answer with (ibvh_closest_triangles' walk and
+ *   evaluation): that value is candidate 0 of the pair (Q, S), so the answer's d2 cannot exceed it, and S is still reached.
+ *   The definition reads the triangle's OWN box, not the stored one: leaf boxes with a skin give the same result.
+ * What follows from the definition: coplanar and touching pairs are decided by rounding — the cut tests of a coplanar pair
+ *   have det == 0 wherever the products are exact and rounding noise elsewhere, and a pair that touches in a point or along
+ *   an edge gets d2 = 0 from the cut rule or a d2 of a few ulps from a candidate, with kind accordingly.  Without the skip flag
+ *   a mesh against itself answers every query with d2 = 0 (itself or a neighbour).  d2 is what the operations above give,
+ *   within a few ulps of the true squared distance for well-shaped triangles, not its nearest float.
+ * Accepted BVHs — exactly those of ibvh_closest_triangles: leaf_kind == node_kind == IBVH_BBOX, triangles and queries of
+ *   leaf_float, node_float the same as or wider than leaf_float; any index and Morton type.  Anything else — sphere leaves,
+ *   sphere nodes, F64 leaves under F32 nodes — is IBVH_ERR_UNSUPPORTED, never an answer.  Exact PROVIDED every leaf's box
+ *   contains its triangle's box.  Levels above bvh->built_level are not read.
+ * NaN: as for ibvh_closest_triangles, a NaN leaf box can make merge.jl's `a < b ? a : b` produce a node box that does NOT
+ *   contain the NaN-free leaves below it: on a mesh with NaN vertices the other triangles' answers are only guaranteed in
+ *   trees of at most two leaves.
+ * Guards: the triangle is read through the leaf record's .index, not its position.  A leaf whose index lies outside
+ * 1..num_triangles is skipped, nothing outside the array is read, and bit 1 of `flag` (value 2) is set — the flag contract of
+ * ibvh_rays_resolve_triangles: optional, 4 bytes the GPU can write, a plain load and store, never cleared by the library
+ * (zero it before the call). */
+ibvh_status ibvh_triangle_distances(const ibvh_bvh *bvh, const void *triangles, int64_t num_triangles,
+                                    const void *queries, int64_t num_queries, int32_t skip,
+                                    const void *max_distance2, void *closest_index, void *closest_d2,
+                                    void *point_query, void *point_mesh, void *closest_kind,
+                                    void *flag, void *stream);
 
 /* ----------------------------------------------------------------------------------- */
 /* breadth-first traversal (BFSTraversal): level-synchronous pair queues                 */
