@@ -100,6 +100,15 @@ SWEEP_SPHERES_ARGTYPES = ([C.POINTER(Bvh), C.c_void_p, C.c_int64, C.c_void_p, C.
 #                         point_query, point_mesh, closest_kind, flag, stream)
 TRIDIST_CUT = 15  # closest_kind of a pair the cut rule decided (include/ibvh.h)
 TRIANGLE_DISTANCES_ARGTYPES = [C.POINTER(Bvh), C.c_void_p, C.c_int64, C.c_void_p, C.c_int64, C.c_int32] + [C.c_void_p] * 8
+# ibvh_capsule_contacts(bvh, triangles, num_triangles, starts, ends, radii, num_capsules, mode, counts, offsets, capacity,
+#                       contact_index, contact_d2, contact_point_segment, contact_point_mesh, contact_kind, flag, stream)
+CAPSULES_COUNT, CAPSULES_WRITE = 0, 1
+SEGTRI_CUT = 5  # kind of a pair the cut rule decided (include/ibvh.h, ibvh_capsule_contacts)
+CAPSULE_CONTACTS_ARGTYPES = ([C.POINTER(Bvh), C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64, C.c_int32, C.c_void_p,
+                              C.c_void_p, C.c_int64] + [C.c_void_p] * 7)
+# ibvh_segment_distances(bvh, triangles, num_triangles, starts, ends, num_segments, max_distance2, closest_index, closest_d2,
+#                        point_segment, point_mesh, closest_kind, flag, stream)
+SEGMENT_DISTANCES_ARGTYPES = [C.POINTER(Bvh), C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p, C.c_int64] + [C.c_void_p] * 8
 
 
 class BuildDesc(C.Structure):

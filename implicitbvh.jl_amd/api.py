@@ -35,6 +35,7 @@ __all__ = [
     "cast_rays", "RayCast", "sphere_contacts", "SphereContacts",
     "triangle_contacts", "TriangleContacts", "self_intersections", "sweep_spheres", "SphereSweep",
     "triangle_distances", "TriangleDistances", "mesh_distance", "MeshDistance", "self_clearance",
+    "capsule_contacts", "CapsuleContacts", "segment_distances", "SegmentDistances",
 ]
 
 NARROW_MORTON_LT = abi.NARROW_MORTON_LT
@@ -1573,7 +1574,7 @@ def cast_rays(bvh, triangles, points, directions, t_max=None, any_hit=False, pre
     return RayCast(*_unpermute(order, outs[:3]))
 
 
-# ---- the list queries, sphere_contacts and triangle_contacts: one shape of result, one count / scan / write sequence ----
+# ---- the list queries, sphere_contacts, triangle_contacts and capsule_contacts: one shape of result, one count / scan / write sequence ----
 class _ContactLists:
     """Lists of contacts grouped by the item (sphere, query triangle) that owns them, in the caller's order: item i (0-based)
     owns rows offsets[i] : offsets[i + 1] of every per-contact field; .index is the first of those."""
@@ -1918,6 +1919,118 @@ def self_clearance(bvh, triangles, max_distance=None):
     queries: triangle_distances(bvh, triangles, triangles, skip_shared_vertices=True).  No triangle reports itself or a
     neighbour that shares a vertex with it; d2 = 0 marks a self-intersection, a small d2 one about to happen."""
     return triangle_distances(bvh, triangles, triangles, max_distance=max_distance, skip_shared_vertices=True)
+
+
+# ---------------------------------------------------------------------------------------------
+# capsules and segments against a mesh (ibvh_capsule_contacts, ibvh_segment_distances; no reference counterpart)
+# ---------------------------------------------------------------------------------------------
+class CapsuleContacts(_ContactLists):
+    """The contacts of N capsules with a mesh, M in all, grouped by capsule in the caller's order and, within a capsule, in
+    the order of the triangles' leaves in the BVH: capsule s (0-based) owns rows offsets[s] : offsets[s + 1].
+    .offsets (N + 1,) int64, .counts (N,) int64; per contact .index (M,) the triangle's user index, .distance2 (M,) the
+    SQUARED distance between segment and triangle (0 = the segment crosses it), .point_segment (M, 3) the closest point on
+    the segment, .point_mesh (M, 3) the closest point on the triangle, .kind (M,) uint8 the rule that decided (0, 1 the end
+    a, b against the triangle; 2, 3, 4 the segment against the edge p1p2, p2p3, p3p1; 5 the segment crosses the triangle)
+    and .capsule (M,) the 1-based number of the capsule the row belongs to (computed when first asked for).  After
+    count_only=True the per-contact fields are None."""
+
+    def __init__(self, offsets, index=None, distance2=None, point_segment=None, point_mesh=None, kind=None):
+        super().__init__(offsets, index)
+        self.distance2, self.point_segment, self.point_mesh, self.kind = distance2, point_segment, point_mesh, kind
+
+    capsule = property(_ContactLists._owner_column)
+    ENTRY = ("ibvh_capsule_contacts", abi.CAPSULES_COUNT, abi.CAPSULES_WRITE)
+
+
+class SegmentDistances:
+    """Per segment: .index (N,) the closest mesh triangle's user index (0 = none), .d2 (N,) the SQUARED distance (+Inf = none;
+    0 = the segment crosses it), .point_segment (N, 3) the closest point on the segment, .point_mesh (N, 3) the closest point
+    on the triangle (zeros = none), .kind (N,) uint8 the rule that decided, as in CapsuleContacts (0 = none)."""
+
+    def __init__(self, index, d2, point_segment, point_mesh, kind):
+        self.index, self.d2, self.point_segment, self.point_mesh, self.kind = index, d2, point_segment, point_mesh, kind
+
+
+def _query_segments(starts, ends, ft, presorted, what):
+    """The segment queries' common input: the (3, N) CUDA tensors `starts` and `ends` of dtype ft, checked -> the two (N, 3)
+    contiguous tensors, N, and the Morton order of the midpoints (None: presorted, or nothing to sort)."""
+    torch = _torch()
+    for name, x in (("starts", starts), ("ends", ends)):
+        if not (isinstance(x, torch.Tensor) and x.dim() == 2 and x.shape[0] == 3):
+            raise ValueError(f"{what}: size({name}, 1) == 3 must hold")
+        if x.dtype != ft or not x.is_cuda:
+            raise ValueError(f"{what}: {name} must be a {ft} tensor on the GPU (device='cuda')")
+    if tuple(starts.shape) != tuple(ends.shape):
+        raise ValueError(f"{what}: size(starts) == size(ends) == (3, N) must hold")
+    a, b = starts.t().contiguous(), ends.t().contiguous()  # (N, 3) row-major == (3, N) column-major
+    n = int(a.shape[0])
+    order = None if presorted or n == 0 else _morton_order(0.5 * a.to(torch.float64) + 0.5 * b.to(torch.float64))
+    return a, b, n, order
+
+
+def capsule_contacts(bvh, triangles, starts, ends, radii, count_only=False, presorted=False):
+    """For every capsule — the segment starts[:, i] -> ends[:, i] with the radius radii[i] — ALL triangles of the mesh `bvh`
+    was built over that lie within the radius of the segment, with the squared distance, the closest point on the segment
+    and on the triangle and the rule that decided -> CapsuleContacts (include/ibvh.h, ibvh_capsule_contacts: the segment-
+    triangle evaluation — the exact test of resolve_triangles where the segment crosses, else the two ends by the
+    evaluation of closest_points and the three edges by that of triangle_distances —, the slab clause, the order and why
+    pruning loses nothing are spelled out there).  Two launches, a count and a write, around a scan of the counts here;
+    exact: bit-equal to a brute force over all triangles.
+
+    bvh: BBox leaves made from `triangles` (bounding_volumes_from_triangles(triangles, BBox(dtype)); a skin margin and
+    refit are fine) under BBox nodes of the same or a wider float type.  triangles: (n, 9) / (n, 3, 3) CUDA tensor of the
+    leaves' dtype, user index k = row k - 1.  starts, ends: (3, N) CUDA tensors of that dtype, like the centers of
+    sphere_contacts.  radii: an (N,) CUDA tensor of that dtype, or one number for all.  A triangle is a contact iff its
+    squared distance <= r * r, squared in that dtype; a negative or NaN radius and a NaN in a segment touch nothing; a
+    segment of length zero is a sphere.  count_only=True stops after the first pass.  The device walks the batch in Morton
+    order of the segments' midpoints (lanes of a wave then share nodes) and writes each capsule's rows where the caller's
+    order wants them; presorted=True walks it as given.  The total is read on the host between the passes, as in traverse.
+
+    ValueError: sphere leaves or nodes, nodes narrower than the leaves, a wrong dtype, device or shape, and a leaf whose
+    index lies outside 1..n (flag bit 1; such leaves are skipped)."""
+    torch = _require_gpu()
+    what = "capsule_contacts"
+    tris, ft, idt = _mesh_query_setup(bvh, triangles, what)
+    a, b, n, order = _query_segments(starts, ends, ft, presorted, what)
+    r = _per_item(radii, n, ft, what, "radii")
+    walk = lambda: (order, (a, b, r) if order is None else (a[order], b[order], r[order]))
+    return _contact_lists(CapsuleContacts, what, bvh, tris, n, walk, tail=(),
+                          outs=((idt, ()), (ft, ()), (ft, (3,)), (ft, (3,)), (torch.uint8, ())), count_only=count_only)
+
+
+def segment_distances(bvh, triangles, starts, ends, max_distance=None, presorted=False):
+    """For every segment starts[:, i] -> ends[:, i] the closest triangle of the mesh `bvh` was built over, the squared
+    distance, the closest point on the segment and on the triangle and the rule that decided -> SegmentDistances
+    (include/ibvh.h, ibvh_segment_distances: the evaluation of capsule_contacts, the tie rule — smallest distance, then the
+    smaller index — and why pruning on the gap between boxes loses nothing are spelled out there).  One launch, exact:
+    bit-equal to a brute force over all triangles.
+
+    bvh, triangles, starts, ends: as for capsule_contacts.  max_distance: search radius (None = unbounded); it is squared
+    in the triangles' dtype on the host and a triangle qualifies iff its squared distance <= that product.  A segment with
+    a NaN coordinate has no answer.  The device walks the batch in Morton order of the segments' midpoints and the outputs
+    are put back in the caller's order; presorted=True walks it as given.
+
+    ValueError: sphere leaves or nodes, nodes narrower than the leaves, a wrong dtype, device or shape, and a leaf whose
+    index lies outside 1..n (flag bit 1; such leaves are skipped)."""
+    torch = _require_gpu()
+    what = "segment_distances"
+    tris, ft, idt = _mesh_query_setup(bvh, triangles, what)
+    a, b, n, order = _query_segments(starts, ends, ft, presorted, what)
+    radius2 = None
+    if max_distance is not None:
+        npdt = np.float32 if ft == torch.float32 else np.float64
+        with np.errstate(over="ignore"):
+            m = npdt(max_distance) * npdt(max_distance)
+        radius2 = C.byref((C.c_float if ft == torch.float32 else C.c_double)(m))
+    outs = (torch.empty(n, dtype=idt, device="cuda"), torch.empty(n, dtype=ft, device="cuda"),
+            torch.empty((n, 3), dtype=ft, device="cuda"), torch.empty((n, 3), dtype=ft, device="cuda"),
+            torch.empty(n, dtype=torch.uint8, device="cuda"))
+    if n == 0:
+        return SegmentDistances(*outs)
+    if order is not None:
+        a, b = a[order], b[order]   # (held until the call returns: the launch reads them)
+    _mesh_query_call("ibvh_segment_distances", what, bvh, tris, _ptr(a), _ptr(b), n, radius2, *[_ptr(o) for o in outs])
+    return SegmentDistances(*_unpermute(order, outs))
 
 
 # ---------------------------------------------------------------------------------------------

@@ -1,7 +1,8 @@
 // ibvh_pointtri.hpp — the point-triangle evaluation of include/ibvh.h (ibvh_closest_triangles): the closest point q of a
 // triangle to a point p, the squared distance, and which branch of the region walk decided.  ONE copy, so that the queries
-// that answer with it — ibvh_closest.hip (the closest triangle), ibvh_spheres.hip (every triangle within a radius) and
-// ibvh_sweep.hip (a moving sphere's start position) — compute the same bits.  No reference counterpart: ImplicitBVH.jl has no point-triangle distance.
+// that answer with it — ibvh_closest.hip (the closest triangle), ibvh_spheres.hip (every triangle within a radius),
+// ibvh_sweep.hip (a moving sphere's start position), ibvh_tridist.hip (a vertex against a triangle) and ibvh_segtri.hpp (a
+// segment's end against a triangle) — compute the same bits.  No reference counterpart: ImplicitBVH.jl has no point-triangle distance.
 #pragma once
 #include "ibvh_common.hpp"
 

@@ -1,6 +1,7 @@
 // ibvh_segseg.hpp — the segment-segment evaluation of include/ibvh.h (ibvh_triangle_distances): the closest points x1 of the
 // segment p1 -> q1 and x2 of the segment p2 -> q2, and their squared distance.  ONE copy, beside ibvh_pointtri.hpp, so that
-// whatever answers with it computes the same bits.  No reference counterpart: ImplicitBVH.jl has no segment distance.
+// whatever answers with it — ibvh_tridist.hip, and ibvh_segtri.hpp for ibvh_capsules.hip and ibvh_segdist.hip — computes the
+// same bits.  No reference counterpart: ImplicitBVH.jl has no segment distance.
 #pragma once
 #include "ibvh_common.hpp"
 #include "ibvh_pointtri.hpp"

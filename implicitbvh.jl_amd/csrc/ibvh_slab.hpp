@@ -1,6 +1,7 @@
-// ibvh_slab.hpp — the slab test of include/ibvh.h (ibvh_cast_rays): where a ray enters a box.  ONE copy for the two queries
-// that prune on it and pin it bit for bit: ibvh_cast.hip (a ray against the leaves' boxes) and ibvh_sweep.hip (a moving
-// sphere's centre against the boxes grown by its radius).  No reference counterpart: the reference's isintersection answers
+// ibvh_slab.hpp — the slab test of include/ibvh.h (ibvh_cast_rays): where a ray enters a box.  ONE copy for the three queries
+// that prune on it and pin it bit for bit: ibvh_cast.hip (a ray against the leaves' boxes), ibvh_sweep.hip (a moving
+// sphere's centre against the boxes grown by its radius) and ibvh_capsules.hip (a capsule's segment against the boxes grown
+// by its radius).  No reference counterpart: the reference's isintersection answers
 // yes / no for the whole line and its 0 * Inf is NaN on a box face.
 #pragma once
 #include "ibvh_common.hpp"

@@ -314,6 +314,14 @@ c_triangle_distances(bvh, triangles, num_triangles, queries, num_queries, skip, 
     ccall((:ibvh_triangle_distances, libibvh), Cint,
           (Ref{IbvhBvh}, Ptr{Cvoid}, Int64, Ptr{Cvoid}, Int64, Int32, Ptr{Cvoid}, Ptr{Cvoid}, Ptr{Cvoid}, Ptr{Cvoid}, Ptr{Cvoid}, Ptr{Cvoid}, Ptr{Cvoid}, Ptr{Cvoid}),
           bvh, triangles, num_triangles, queries, num_queries, skip, max_distance2, closest_index, closest_d2, point_query, point_mesh, closest_kind, flag, stream)
+c_capsule_contacts(bvh, triangles, num_triangles, starts, ends, radii, num_capsules, mode, counts, offsets, capacity, contact_index, contact_d2, contact_point_segment, contact_point_mesh, contact_kind, flag, stream) =
+    ccall((:ibvh_capsule_contacts, libibvh), Cint,
+          (Ref{IbvhBvh}, Ptr{Cvoid}, Int64, Ptr{Cvoid}, Ptr{Cvoid}, Ptr{Cvoid}, Int64, Int32, Ptr{Cvoid}, Ptr{Cvoid}, Int64, Ptr{Cvoid}, Ptr{Cvoid}, Ptr{Cvoid}, Ptr{Cvoid}, Ptr{Cvoid}, Ptr{Cvoid}, Ptr{Cvoid}),
+          bvh, triangles, num_triangles, starts, ends, radii, num_capsules, mode, counts, offsets, capacity, contact_index, contact_d2, contact_point_segment, contact_point_mesh, contact_kind, flag, stream)
+c_segment_distances(bvh, triangles, num_triangles, starts, ends, num_segments, max_distance2, closest_index, closest_d2, point_segment, point_mesh, closest_kind, flag, stream) =
+    ccall((:ibvh_segment_distances, libibvh), Cint,
+          (Ref{IbvhBvh}, Ptr{Cvoid}, Int64, Ptr{Cvoid}, Ptr{Cvoid}, Int64, Ptr{Cvoid}, Ptr{Cvoid}, Ptr{Cvoid}, Ptr{Cvoid}, Ptr{Cvoid}, Ptr{Cvoid}, Ptr{Cvoid}, Ptr{Cvoid}),
+          bvh, triangles, num_triangles, starts, ends, num_segments, max_distance2, closest_index, closest_d2, point_segment, point_mesh, closest_kind, flag, stream)
 c_lvt_scratch_bytes(types, n_items, cache_slots, out) =
     ccall((:ibvh_lvt_scratch_bytes, libibvh), Cint,
           (Ref{IbvhTypes}, Int64, Int32, Ref{Csize_t}),
@@ -1085,6 +1093,118 @@ function mesh_distance(bvh::RocBVH{I}, triangles::ROCMatrix{T}, queries::ROCMatr
     index = Array(r.index[pos:pos])[1]
     (; distance=sqrt(Array(r.d2[pos:pos])[1]), query=index == 0 ? 0 : pos, index,
      point_query=Array(r.point_query[:, pos]), point_mesh=Array(r.point_mesh[:, pos]))
+end
+
+# ---- capsules and segments against a mesh (include/ibvh.h, ibvh_capsule_contacts and ibvh_segment_distances) ----------
+const IBVH_CAPSULES_COUNT = Int32(0)
+const IBVH_CAPSULES_WRITE = Int32(1)
+
+# the segment queries' common checks -> the BVH's descriptor
+function segment_query_desc(what, bvh, triangles, starts::ROCMatrix{T}, ends) where {T}
+    d = bvh_desc(bvh)
+    isnothing(d) && throw(ArgumentError("$what: no libibvh instantiation for this BVH's types"))
+    leaf_volume_type(bvh.leaves) === BBox{T} && eltype(bvh.nodes) <: BBox && sizeof(eltype(bvh.nodes)) >= sizeof(BBox{T}) ||
+        throw(ArgumentError("$what: the BVH must have BBox{$T} leaves under BBox nodes of $T or wider"))
+    size(triangles, 1) == 9 || throw(ArgumentError("$what: triangles must be 9 x n (p1 p2 p3 per column)"))
+    size(starts, 1) == 3 && size(starts) == size(ends) || throw(ArgumentError("$what: size(starts) == size(ends) == (3, N) must hold"))
+    d
+end
+
+"""
+    capsule_contacts(bvh::BVH, triangles::ROCMatrix{T}, starts::ROCMatrix{T}, ends::ROCMatrix{T}, radii;
+                     count_only=false, presorted=false)
+        -> (; offsets, counts, index, distance2, point_segment, point_mesh, kind)
+
+For every capsule (the segment `starts[:, i]` -> `ends[:, i]` with the radius `radii[i]`, or one number for all) ALL triangles
+of the mesh `bvh` was built over that lie within the radius of the segment.  Capsule `i` owns rows
+`offsets[i] + 1 : offsets[i + 1]` of the per-contact outputs: `index` the triangle's user index, `distance2` the squared
+distance (0 = the segment crosses the triangle), `point_segment[:, j]` and `point_mesh[:, j]` the closest points on the
+segment and on the triangle, `kind[j]` the rule that decided (0, 1 the end a, b against the triangle; 2, 3, 4 the segment
+against the edge p1p2, p2p3, p3p1; 5 the segment crosses the triangle).  Within a capsule the rows follow the order of the
+triangles' leaves in `bvh.leaves`.  A negative or NaN radius and a NaN in a segment touch nothing; a segment of length zero is a
+sphere.  Bit-equal to a brute force over all triangles; the evaluation, the slab clause, the order and why pruning loses nothing
+are spelled out in include/ibvh.h.  Two launches, a count and a write, around a `cumsum` of the counts on the device array;
+`count_only=true` stops after the first (the per-contact outputs are `nothing`).  The BVH must have `BBox{T}` leaves made from
+the triangles (a skin margin and `refit!` are fine) under `BBox` nodes of `T` or wider; anything else raises ArgumentError.  The
+device walks the batch along a Morton curve through the segments' midpoints and writes each capsule's rows where the caller's
+order wants them; `presorted=true` walks it as given.  Not a method of ImplicitBVH: the reference has no such query.
+"""
+function capsule_contacts(bvh::RocBVH{I}, triangles::ROCMatrix{T}, starts::ROCMatrix{T}, ends::ROCMatrix{T},
+                          radii::Union{Real, ROCVector{T}}; count_only::Bool=false, presorted::Bool=false) where {I, T}
+    d = segment_query_desc("capsule_contacts", bvh, triangles, starts, ends)
+    n = size(starts, 2)
+    radii isa Real || length(radii) == n || throw(ArgumentError("capsule_contacts: length(radii) == size(starts, 2) must hold"))
+    r = radii isa Real ? fill!(similar(starts, T, n), T(radii)) : radii
+    offsets = fill!(similar(starts, Int64, n + 1), 0)
+    none(m) = (similar(starts, I, m), similar(starts, T, m), similar(starts, T, 3, m), similar(starts, T, 3, m), similar(starts, UInt8, m))
+    nothings = (; index=nothing, distance2=nothing, point_segment=nothing, point_mesh=nothing, kind=nothing)
+    named(o) = (; index=o[1], distance2=o[2], point_segment=o[3], point_mesh=o[4], kind=o[5])
+    n == 0 && return (; offsets, counts=similar(starts, Int64, 0), (count_only ? nothings : named(none(0)))...)
+    order = presorted ? nothing : point_morton_order((starts .+ ends) ./ T(2))
+    perm = isnothing(order) ? nothing : ROCVector{Int64}(order)
+    a = isnothing(perm) ? starts : starts[:, perm]
+    b = isnothing(perm) ? ends : ends[:, perm]
+    rw = isnothing(perm) ? r : r[perm]
+    flag = scratch!(:capsules_flag, 4)
+    fill!(flag, 0x00)
+    walked = similar(starts, Int64, n)
+    nt = Int64(size(triangles, 2))
+    check(c_capsule_contacts(d, devptr(triangles), nt, devptr(a), devptr(b), devptr(rw), Int64(n), IBVH_CAPSULES_COUNT, devptr(walked),
+                             C_NULL, Int64(0), C_NULL, C_NULL, C_NULL, C_NULL, C_NULL, devptr(flag), stream_ptr()), "ibvh_capsule_contacts")
+    Array(flag)[1] & 0x02 != 0 && throw(ArgumentError("capsule_contacts: a leaf's index lies outside 1:$nt"))
+    # the counts back in the caller's order, scanned there: a capsule's rows then follow its predecessor's in that order
+    counts = isnothing(perm) ? walked : walked[ROCVector{Int64}(invperm(order))]
+    offsets[2:end] .= cumsum(counts)
+    count_only && return (; offsets, counts, nothings...)
+    total = Array(offsets[end:end])[1]                           # the one read between the passes
+    out = none(total)
+    total == 0 && return (; offsets, counts, named(out)...)
+    first_row = isnothing(perm) ? offsets[1:n] : offsets[1:n][perm]   # ... gathered back into walk order
+    check(c_capsule_contacts(d, devptr(triangles), nt, devptr(a), devptr(b), devptr(rw), Int64(n), IBVH_CAPSULES_WRITE, C_NULL,
+                             devptr(first_row), Int64(total), devptr(out[1]), devptr(out[2]), devptr(out[3]), devptr(out[4]),
+                             devptr(out[5]), devptr(flag), stream_ptr()), "ibvh_capsule_contacts")
+    Array(flag)[1] & 0x04 != 0 && error("capsule_contacts: the write pass found more contacts than the count pass")
+    (; offsets, counts, named(out)...)
+end
+
+"""
+    segment_distances(bvh::BVH, triangles::ROCMatrix{T}, starts::ROCMatrix{T}, ends::ROCMatrix{T}; max_distance=nothing,
+                      presorted=false) -> (; index, d2, point_segment, point_mesh, kind)
+
+For every segment `starts[:, i]` -> `ends[:, i]` the closest triangle of the mesh `bvh` was built over, in one launch:
+`index[i]` its user index (0 = none), `d2[i]` the squared distance (`Inf` = none, 0 = the segment crosses it),
+`point_segment[:, i]` and `point_mesh[:, i]` the closest points (zeros = none), `kind[i]` the rule that decided, as for
+`capsule_contacts`.  The result is the lexicographic minimum of (squared distance, index) over ALL triangles — bit-equal to a
+brute force; the evaluation, the tie rule and why pruning on the gap between boxes loses nothing are spelled out in
+include/ibvh.h.  `max_distance` is squared in `T` on the host; a segment with a NaN coordinate has no answer.  BVH, triangles
+and the walk order are those of `capsule_contacts`.  Not a method of ImplicitBVH: the reference has no such query.
+"""
+function segment_distances(bvh::RocBVH{I}, triangles::ROCMatrix{T}, starts::ROCMatrix{T}, ends::ROCMatrix{T};
+                           max_distance=nothing, presorted::Bool=false) where {I, T}
+    d = segment_query_desc("segment_distances", bvh, triangles, starts, ends)
+    n = size(starts, 2)
+    index = similar(starts, I, n)
+    d2 = similar(starts, T, n)
+    point_segment = similar(starts, T, 3, n)
+    point_mesh = similar(starts, T, 3, n)
+    kind = similar(starts, UInt8, n)
+    n == 0 && return (; index, d2, point_segment, point_mesh, kind)
+    radius2 = isnothing(max_distance) ? C_NULL : Ref(T(max_distance) * T(max_distance))
+    order = presorted ? nothing : point_morton_order((starts .+ ends) ./ T(2))
+    a = isnothing(order) ? starts : starts[:, ROCVector{Int64}(order)]
+    b = isnothing(order) ? ends : ends[:, ROCVector{Int64}(order)]
+    flag = scratch!(:segdist_flag, 4)
+    fill!(flag, 0x00)
+    GC.@preserve radius2 begin
+        r2 = radius2 === C_NULL ? Ptr{Cvoid}(C_NULL) : Ptr{Cvoid}(Base.unsafe_convert(Ptr{T}, radius2))
+        check(c_segment_distances(d, devptr(triangles), Int64(size(triangles, 2)), devptr(a), devptr(b), Int64(n), r2, devptr(index),
+                                  devptr(d2), devptr(point_segment), devptr(point_mesh), devptr(kind), devptr(flag), stream_ptr()),
+              "ibvh_segment_distances")
+    end
+    Array(flag)[1] & 0x02 != 0 && throw(ArgumentError("segment_distances: a leaf's index lies outside 1:$(size(triangles, 2))"))
+    isnothing(order) && return (; index, d2, point_segment, point_mesh, kind)
+    inv = ROCVector{Int64}(invperm(order))
+    (; index=index[inv], d2=d2[inv], point_segment=point_segment[:, inv], point_mesh=point_mesh[:, inv], kind=kind[inv])
 end
 
 # ---- k nearest leaves for a batch of query points (include/ibvh.h, ibvh_nearest_leaves) ------------------------------

@@ -54,6 +54,8 @@ SIGNATURES = {
     "ibvh_triangle_contacts": abi.TRIANGLE_CONTACTS_ARGTYPES,
     "ibvh_sweep_spheres": abi.SWEEP_SPHERES_ARGTYPES,
     "ibvh_triangle_distances": abi.TRIANGLE_DISTANCES_ARGTYPES,
+    "ibvh_capsule_contacts": abi.CAPSULE_CONTACTS_ARGTYPES,
+    "ibvh_segment_distances": abi.SEGMENT_DISTANCES_ARGTYPES,
     "ibvh_bfs_initial_capacity": [_P(abi.Bvh), _i64, _P(_i64)],
     "ibvh_bfs_pair_initial_capacity": [_P(abi.Bvh), _P(abi.Bvh), _i64, _i64, _P(_i64)],
     "ibvh_bfs_rays_initial_capacity": [_P(abi.Bvh), _i64, _i64, _P(_i64)],

@@ -50,6 +50,8 @@ extern "C" {
  *      ibvh_triangle_contacts and IBVH_TRIS_COUNT / IBVH_TRIS_WRITE (additive under 7 likewise: one more entry point);
  *      ibvh_sweep_spheres and IBVH_SWEEP_CLOSEST / IBVH_SWEEP_ANY (additive under 7 likewise: one more entry point);
  *      ibvh_triangle_distances (additive under 7 likewise: one more entry point);
+ *      ibvh_capsule_contacts and IBVH_CAPSULES_COUNT / IBVH_CAPSULES_WRITE, ibvh_segment_distances (additive under 7
+ *      likewise: two more entry points);
  *      argument checks only, no layout or argument list moves: ibvh_key_histogram takes
  *      what fits its LDS staging (10 rows at 12-bit digits) and refuses shift > 63 and a negative prefix_shift,
  *      ibvh_pack_records / ibvh_dist_plan answer IBVH_ERR_OVERFLOW for an index past IBVH_I32 */
@@ -1049,6 +1051,127 @@ ibvh_status ibvh_triangle_distances(const ibvh_bvh *bvh, const void *triangles, 
                                     const void *max_distance2, void *closest_index, void *closest_d2,
                                     void *point_query, void *point_mesh, void *closest_kind,
                                     void *flag, void *stream);
+
+/* ----------------------------------------------------------------------------------- */
+/* capsule-vs-mesh contacts: every triangle within r of each segment                     */
+/* ----------------------------------------------------------------------------------- */
+/* For every capsule (a segment S = a -> b with a radius r): ALL triangles K = (p1, p2, p3) of the mesh the BVH was built
+ * over (ibvh_volumes_from_triangles with IBVH_BBOX) that lie within r of S — which ones, the squared distance, the closest
+ * point on the segment and on the triangle, and the rule that decided.  The primitive between the sphere
+ * (ibvh_sphere_contacts) and the triangle (ibvh_triangle_contacts): robot links, character controllers, cables, rods and
+ * fibres, the swept volume of a particle over a step.  No reference counterpart (the reference's traversals end at pairs of
+ * BOXES, and the box of a long diagonal segment is far looser than the segment); a variable-length answer in TWO calls of
+ * ONE launch each — count, the caller's scan, write — with NO host synchronisation inside either, no LDS, no scratch
+ * buffer, no read-modify-write of memory.
+ *   triangles  : num_triangles x 9 values (p1 p2 p3) of bvh->types.leaf_float, `flt` below; user index k is row k - 1
+ *   starts     : num_capsules x 3 row-major values of `flt`, the ends a; processed in the order given (neighbours in memory
+ *                that are neighbours in space walk the same nodes: sort a scattered batch along a Morton curve first)
+ *   ends       : num_capsules x 3 row-major values of `flt`, the ends b
+ *   radii      : num_capsules values of `flt`, one per capsule
+ *   mode       : IBVH_CAPSULES_COUNT or IBVH_CAPSULES_WRITE
+ * counts, offsets, capacity and the two passes are those of ibvh_sphere_contacts, word for word: the count pass needs
+ *   `counts` (num_capsules x int64) and touches no output; the caller scans; the write pass needs `offsets` (num_capsules x
+ *   int64, ANY exclusive prefix sum, not necessarily monotone) and puts contact j of capsule s in row offsets[s] + j; a row
+ *   >= capacity or < 0 is never written and sets bit 2 of `flag` (value 4), per ROW.
+ *   contact_index         : capacity x I, the triangle's user index
+ *   contact_d2            : capacity x flt, the squared distance d2
+ *   contact_point_segment : capacity x 3 x flt, xs, the closest point on S
+ *   contact_point_mesh    : capacity x 3 x flt, xk, the closest point on K
+ *   contact_kind          : capacity x uint8, the rule that decided, 0 - 5 (below)
+ *   each optional, at least one non-NULL; what was not asked for is not written.
+ * All arguments are validated before any launch, in the order of the other point-walk entries.  The entry's own checks: NULL
+ * bvh, negative sizes or capacity, an unknown mode, no `counts` in the count pass, no `offsets` or no output at all in the
+ * write pass: IBVH_ERR_INVALID_ARG.  Then the type combination (below): IBVH_ERR_UNSUPPORTED.  Then a tree shape that is not
+ * an ImplicitTree's or a missing array: IBVH_ERR_INVALID_ARG.  num_capsules == 0: IBVH_OK, nothing is touched.
+ * The result is defined independently of how it is found, in `flt` throughout, every operation rounded once (nothing fused;
+ * correctly rounded divide), every comparison false on NaN, so that it can be pinned bit for bit.
+ * The SEGMENT-TRIANGLE EVALUATION (d2, xs, xk, kind) of a pair (S, K).  S's exact box: slo_k / sup_k = `a_k < b_k ? a_k : b_k`
+ * / `a_k > b_k ? a_k : b_k`.  K's exact box: the fold of ibvh_triangle_distances.
+ *   The CUT rule, only if K's exact box is not apart from S's exact box (apart: the six strict comparisons of
+ *     ibvh_triangle_distances, sup_k < lo_k || slo_k > up_k for some k): the ray-triangle test of
+ *     ibvh_rays_resolve_triangles with p = a, d = b - a is true AND t <= 1.  If it hits: d2 = 0, xs = xk = a + t * d (one
+ *     rounded product and one rounded sum per coordinate), kind = 5.
+ *   The CANDIDATE rule, otherwise: five candidates, evaluated in this order; candidate 0 starts the result and a later one
+ *     replaces it iff its d2 is strictly smaller (so the FIRST of the smallest wins, and a NaN d2 of candidate 0 stays).
+ *       kind 0, 1     : the end a, b against K: the evaluation of ibvh_closest_triangles for (K, end); xs = the end,
+ *                       xk = its q, d2 = its d2
+ *       kind 2, 3, 4  : S against K's edge p1->p2, p2->p3, p3->p1: the segment-segment evaluation of
+ *                       ibvh_triangle_distances for (P1, Q1) = (a, b) and (P2, Q2) = the edge; xs = x1, which is clamped
+ *                       into S's box, xk = x2, which is clamped into the edge's box
+ *   The triangle's feature under xk is NOT reported: the segment-segment evaluation does not classify where on the edge
+ *   its point lies.
+ * r2 = r * r, rounded once.  The contacts of capsule s are ALL triangles k that pass both clauses:
+ *   (i)  the SLAB clause: entry <= 1, where entry is entry(box) of ibvh_cast_rays for the ray p = a, d = b - a,
+ *        inv_k = 1 / d_k, against leaf k's STORED box grown by r: [lo_k - r, up_k + r], each rounded once (the grown box of
+ *        ibvh_sweep_spheres);
+ *   (ii) the DISTANCE clause: d2 <= r2 by the evaluation above (false on NaN).
+ *   In real arithmetic (ii) implies (i): a point of K within r of a + t * d, 0 <= t <= 1, lies in the box, so a + t * d lies
+ *   in the grown box.  (i) is part of the definition so that the walk can prune on it without loss; it decides only pairs
+ *   that rounding puts on the grown box's face.  Because (i) reads the STORED box, a skin margin on the leaves can only
+ *   admit more such pairs, never fewer.
+ *   A capsule has NO contacts if !(r >= 0) — a negative or NaN radius — or if a coordinate of a or b is NaN.  A segment of
+ *   length zero is valid: every axis is "still" in the slab test, the cut rule cannot hit (det == 0), and the capsule is a
+ *   sphere.  r = 0 keeps the triangles S touches as computed; r = +Inf admits every triangle with a non-NaN d2.
+ * Order: the contacts of one capsule come in LEAF ORDER — ascending position of the triangle's leaf in bvh->leaves — in both
+ *   passes, which is what lets them agree.  A triangle that two leaves name appears twice, once per leaf.
+ * Why pruning is lossless WITHOUT an epsilon.  The walk refuses a node or a leaf iff the squared gap between its box and S's
+ *   exact box — lb(B) of ibvh_triangle_distances with S's box in place of Q's — exceeds r2, or the slab entry of its box
+ *   grown by r exceeds 1 (both comparisons false on NaN: such a box is entered).  The gap: steps (1) - (4) of
+ *   ibvh_triangle_distances hold with S for Q — every xs lies in S's exact box (an end does; x1 is clamped into it), every xk
+ *   lies in K's exact box and so in every box above it, the gap is computed in d2's operation order by monotone operations,
+ *   and a cut pair's boxes are not apart (lb = 0 = its d2) — so the COMPUTED lb(B) never exceeds a COMPUTED d2 under B, and
+ *   a box with lb > r2 holds no triangle that passes (ii).  The slab: the argument of ibvh_sweep_spheres — lo - r and up + r
+ *   are monotone, so the grown box of a node contains the grown boxes below it exactly; the slab entry is monotone in the
+ *   corners; so a leaf that passes (i) has ancestors that pass.  Why the order holds: as for ibvh_sphere_contacts.
+ * Accepted BVHs — exactly those of ibvh_closest_triangles: leaf_kind == node_kind == IBVH_BBOX, triangles and capsules of
+ *   leaf_float, node_float the same as or wider than leaf_float; any index and Morton type.  Anything else — sphere leaves,
+ *   sphere nodes, F64 leaves under F32 nodes — is IBVH_ERR_UNSUPPORTED, never an answer.  Exact PROVIDED every leaf's box
+ *   contains its triangle's box: a skin margin on the leaves is allowed, and so is a BVH after ibvh_refit.  Levels above
+ *   bvh->built_level are not read.  NaN vertices: the caveat of ibvh_sphere_contacts.
+ * Guards: those of ibvh_sphere_contacts — a leaf whose index lies outside 1..num_triangles is skipped in BOTH passes alike
+ * and sets bit 1 of `flag` (value 2); the same flag contract. */
+enum { IBVH_CAPSULES_COUNT = 0, IBVH_CAPSULES_WRITE = 1 };
+ibvh_status ibvh_capsule_contacts(const ibvh_bvh *bvh, const void *triangles, int64_t num_triangles,
+                                  const void *starts, const void *ends, const void *radii, int64_t num_capsules,
+                                  int32_t mode, void *counts, const void *offsets, int64_t capacity,
+                                  void *contact_index, void *contact_d2, void *contact_point_segment,
+                                  void *contact_point_mesh, void *contact_kind, void *flag, void *stream);
+
+/* ----------------------------------------------------------------------------------- */
+/* segment-to-mesh distance: the closest mesh triangle per segment                       */
+/* ----------------------------------------------------------------------------------- */
+/* For every segment S = a -> b: the CLOSEST triangle of the mesh the BVH was built over — which one, the squared distance,
+ * the closest point on S and on the triangle, and the rule that decided.  The distance query beside ibvh_capsule_contacts:
+ * the clearance of a link, a rod or a step's path.  No reference counterpart; ONE launch, NO host synchronisation, no
+ * read-modify-write of memory, no LDS, no scratch buffer, no candidate list.
+ *   triangles, starts, ends : as for ibvh_capsule_contacts (num_segments rows)
+ *   max_distance2 : HOST pointer to one value of `flt`, the SQUARED search radius; NULL = +Inf (unbounded)
+ * Outputs — every pointer optional, at least one non-NULL; what was not asked for is not written:
+ *   closest_index : num_segments x I, the winning triangle's user index; 0 = none
+ *   closest_d2    : num_segments x flt; +Inf = none
+ *   point_segment : num_segments x 3 x flt, xs; 0, 0, 0 = none
+ *   point_mesh    : num_segments x 3 x flt, xk; 0, 0, 0 = none
+ *   closest_kind  : num_segments x uint8, the deciding rule, 0 - 5; 0 = none
+ * All arguments are validated before any launch, in the order of the other point-walk entries: NULL bvh, negative sizes, no
+ * output at all: IBVH_ERR_INVALID_ARG; the type combination: IBVH_ERR_UNSUPPORTED; the tree shape or a missing array:
+ * IBVH_ERR_INVALID_ARG.  num_segments == 0: IBVH_OK, nothing is touched.
+ * Per segment the answer is the LEXICOGRAPHIC MINIMUM of (d2, index) over ALL mesh triangles with d2 <= max_distance2
+ *   (inclusive, false on NaN) and an index that names a row of `triangles`, where (d2, xs, xk, kind) is the segment-triangle
+ *   evaluation of ibvh_capsule_contacts: the tie rule of ibvh_closest_triangles.  There is NO slab clause here.  A segment
+ *   with a NaN coordinate (or a NaN radius) has no answer; a pair whose d2 is NaN never wins.  The outputs carry the
+ *   winner's bits unchanged.
+ * Why pruning is lossless WITHOUT an epsilon: the gap argument of ibvh_capsule_contacts.  The walk skips a node or a leaf iff
+ *   lb > best d2 so far — strictly: lb == best may hide an equal d2 of smaller index.  The best d2 starts at max_distance2
+ *   or, if that is smaller, at the squared distance from the end a to the closest triangle F the query may answer with
+ *   (ibvh_closest_triangles' walk and evaluation): that value is candidate 0 of the pair (S, F), bit for bit, so the
+ *   answer's d2 cannot exceed it, and F is still reached.  The definition reads the triangle's OWN box, not the stored one:
+ *   leaf boxes with a skin give the same result.
+ * Accepted BVHs, NaN and guards: those of ibvh_triangle_distances. */
+ibvh_status ibvh_segment_distances(const ibvh_bvh *bvh, const void *triangles, int64_t num_triangles,
+                                   const void *starts, const void *ends, int64_t num_segments,
+                                   const void *max_distance2, void *closest_index, void *closest_d2,
+                                   void *point_segment, void *point_mesh, void *closest_kind,
+                                   void *flag, void *stream);
 
 /* ----------------------------------------------------------------------------------- */
 /* breadth-first traversal (BFSTraversal): level-synchronous pair queues                 */
