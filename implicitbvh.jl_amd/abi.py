@@ -109,6 +109,11 @@ CAPSULE_CONTACTS_ARGTYPES = ([C.POINTER(Bvh), C.c_void_p, C.c_int64, C.c_void_p,
 # ibvh_segment_distances(bvh, triangles, num_triangles, starts, ends, num_segments, max_distance2, closest_index, closest_d2,
 #                        point_segment, point_mesh, closest_kind, flag, stream)
 SEGMENT_DISTANCES_ARGTYPES = [C.POINTER(Bvh), C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p, C.c_int64] + [C.c_void_p] * 8
+# ibvh_box_contacts(bvh, triangles, num_triangles, centers, half_extents, rotations, num_boxes, mode, counts, offsets, capacity,
+#                   contact_index, contact_inside, flag, stream)
+BOXES_COUNT, BOXES_WRITE = 0, 1
+BOX_CONTACTS_ARGTYPES = ([C.POINTER(Bvh), C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64, C.c_int32, C.c_void_p,
+                          C.c_void_p, C.c_int64] + [C.c_void_p] * 4)
 
 
 class BuildDesc(C.Structure):

@@ -36,6 +36,7 @@ __all__ = [
     "triangle_contacts", "TriangleContacts", "self_intersections", "sweep_spheres", "SphereSweep",
     "triangle_distances", "TriangleDistances", "mesh_distance", "MeshDistance", "self_clearance",
     "capsule_contacts", "CapsuleContacts", "segment_distances", "SegmentDistances",
+    "box_contacts", "BoxContacts", "voxelize",
 ]
 
 NARROW_MORTON_LT = abi.NARROW_MORTON_LT
@@ -1574,7 +1575,7 @@ def cast_rays(bvh, triangles, points, directions, t_max=None, any_hit=False, pre
     return RayCast(*_unpermute(order, outs[:3]))
 
 
-# ---- the list queries, sphere_contacts, triangle_contacts and capsule_contacts: one shape of result, one count / scan / write sequence ----
+# ---- the list queries, sphere_contacts, triangle_contacts, capsule_contacts and box_contacts: one shape of result, one count / scan / write sequence ----
 class _ContactLists:
     """Lists of contacts grouped by the item (sphere, query triangle) that owns them, in the caller's order: item i (0-based)
     owns rows offsets[i] : offsets[i + 1] of every per-contact field; .index is the first of those."""
@@ -2031,6 +2032,102 @@ def segment_distances(bvh, triangles, starts, ends, max_distance=None, presorted
         a, b = a[order], b[order]   # (held until the call returns: the launch reads them)
     _mesh_query_call("ibvh_segment_distances", what, bvh, tris, _ptr(a), _ptr(b), n, radius2, *[_ptr(o) for o in outs])
     return SegmentDistances(*_unpermute(order, outs))
+
+
+# ---------------------------------------------------------------------------------------------
+# boxes against a mesh (ibvh_box_contacts; no reference counterpart)
+# ---------------------------------------------------------------------------------------------
+class BoxContacts(_ContactLists):
+    """The contacts of N boxes with a mesh, M in all, grouped by box in the caller's order and, within a box, in the order
+    of the triangles' leaves in the BVH: box s (0-based) owns rows offsets[s] : offsets[s + 1].
+    .offsets (N + 1,) int64, .counts (N,) int64; per contact .index (M,) the triangle's user index, .inside (M,) uint8 the
+    vertices the box holds (bit 0, 1, 2 = p1, p2, p3; 7 = the triangle lies wholly inside, 0 = the box cuts it without
+    holding a vertex) and .box (M,) the 1-based number of the box the row belongs to (computed when first asked for).
+    After count_only=True the per-contact fields are None."""
+
+    def __init__(self, offsets, index=None, inside=None):
+        super().__init__(offsets, index)
+        self.inside = inside
+
+    box = property(_ContactLists._owner_column)
+    ENTRY = ("ibvh_box_contacts", abi.BOXES_COUNT, abi.BOXES_WRITE)
+
+
+def _half_extents(value, n, ft, what):
+    """`value` — one number or three numbers for all boxes, or a (3, N) CUDA tensor of dtype ft -> the (N, 3) contiguous tensor"""
+    torch = _torch()
+    number = lambda x: isinstance(x, (int, float, np.integer, np.floating)) and not isinstance(x, bool)
+    if isinstance(value, torch.Tensor):
+        if tuple(value.shape) == (3, n) and value.dtype == ft and value.is_cuda:
+            return value.t().contiguous()
+    elif number(value):
+        return torch.full((n, 3), float(value), dtype=ft, device="cuda")
+    elif isinstance(value, (tuple, list)) and len(value) == 3 and all(number(x) for x in value):
+        return torch.tensor([float(x) for x in value], dtype=ft, device="cuda").repeat(n, 1)
+    raise ValueError(f"{what}: half_extents must be a number, three numbers or a (3, N) {ft} tensor on the GPU")
+
+
+def box_contacts(bvh, triangles, centers, half_extents, rotations=None, count_only=False, presorted=False):
+    """For every box — the centre centers[:, i], the half extents half_extents[:, i] along its own axes and, optionally, the
+    rotation rotations[i], whose ROWS are those axes in world coordinates — ALL triangles of the mesh `bvh` was built over
+    that the box overlaps, and which of their vertices it holds -> BoxContacts (include/ibvh.h, ibvh_box_contacts: the hull,
+    the box clause, the 13 separating axes in their operation order, the order and why pruning loses nothing are spelled
+    out there).  Two launches, a count and a write, around a scan of the counts here; exact: bit-equal to a brute force
+    over all triangles.
+
+    bvh: BBox leaves made from `triangles` (bounding_volumes_from_triangles(triangles, BBox(dtype)); a skin margin and
+    refit are fine) under BBox nodes of the same or a wider float type.  triangles: (n, 9) / (n, 3, 3) CUDA tensor of the
+    leaves' dtype, user index k = row k - 1.  centers: (3, N) CUDA tensor of that dtype, like the centers of
+    sphere_contacts.  half_extents: a (3, N) CUDA tensor of that dtype, or one number, or three numbers for all boxes.
+    rotations: an (N, 3, 3) CUDA tensor of that dtype, assumed orthonormal (not checked), or None: axis-aligned boxes, the
+    identity in the same arithmetic.  A half extent that is negative or NaN and a NaN or an infinity in a centre or a
+    rotation touch nothing; a half extent of zero is valid (a plate, a segment, a point).  count_only=True stops after the
+    first pass.  The device walks the batch in Morton order of the centres (lanes of a wave then share nodes) and writes
+    each box's rows where the caller's order wants them; presorted=True walks it as given.  The total is read on the host
+    between the passes, as in traverse.
+
+    ValueError: sphere leaves or nodes, nodes narrower than the leaves, a wrong dtype, device or shape, and a leaf whose
+    index lies outside 1..n (flag bit 1; such leaves are skipped)."""
+    torch = _require_gpu()
+    what = "box_contacts"
+    tris, ft, idt = _mesh_query_setup(bvh, triangles, what)
+    c, n, _, order = _query_points(centers, ft, None, presorted, what)
+    h = _half_extents(half_extents, n, ft, what)
+    r = None
+    if rotations is not None:
+        if not (isinstance(rotations, torch.Tensor) and tuple(rotations.shape) == (n, 3, 3) and rotations.dtype == ft and rotations.is_cuda):
+            raise ValueError(f"{what}: rotations must be None or an (N, 3, 3) {ft} tensor on the GPU")
+        r = rotations.contiguous()
+    walk = lambda: (order, (c, h, r) if order is None else (c, h[order], None if r is None else r[order]))
+    return _contact_lists(BoxContacts, what, bvh, tris, n, walk, tail=(), outs=((idt, ()), (torch.uint8, ())), count_only=count_only)
+
+
+def voxelize(bvh, triangles, origin, spacing, shape):
+    """The cells of a regular grid that the mesh `bvh` was built over passes through -> bool CUDA tensor of `shape` (nx, ny,
+    nz): cell (i, j, k) is the axis-aligned box with the centre origin + (i + 0.5, j + 0.5, k + 0.5) * spacing and the half
+    extent spacing / 2, both computed in the BVH's float type, and it is True iff box_contacts' count pass finds at least one
+    triangle for it (touching counts).  One launch: the count pass alone, in the grid's own order (z fastest), which is
+    coherent enough to walk as given.  origin: three numbers; spacing: one number, or three."""
+    torch = _require_gpu()
+    what = "voxelize"
+    number = lambda x: isinstance(x, (int, float, np.integer, np.floating)) and not isinstance(x, bool)
+    if not (isinstance(shape, (tuple, list)) and len(shape) == 3 and all(isinstance(s, (int, np.integer)) and not isinstance(s, bool) and s >= 0 for s in shape)):
+        raise ValueError(f"{what}: shape must be three non-negative integers (nx, ny, nz)")
+    if not (isinstance(origin, (tuple, list, np.ndarray)) and len(origin) == 3 and all(number(x) for x in origin)):
+        raise ValueError(f"{what}: origin must be three numbers")
+    if number(spacing):
+        spacing = (spacing,) * 3
+    if not (isinstance(spacing, (tuple, list, np.ndarray)) and len(spacing) == 3 and all(number(x) for x in spacing)):
+        raise ValueError(f"{what}: spacing must be a number or three numbers")
+    ft = _torch_float(bvh.types.leaf_float)
+    step = torch.tensor([float(x) for x in spacing], dtype=ft, device="cuda")
+    start = torch.tensor([float(x) for x in origin], dtype=ft, device="cuda")
+    axes = [torch.arange(int(s), dtype=ft, device="cuda") + 0.5 for s in shape]
+    cells = torch.stack(torch.meshgrid(*axes, indexing="ij"), dim=0).reshape(3, -1)   # (3, nx * ny * nz), z fastest
+    centers = start[:, None] + cells * step[:, None]
+    half = (step / 2)[:, None].expand(3, centers.shape[1])
+    got = box_contacts(bvh, triangles, centers, half, count_only=True, presorted=True)
+    return (got.counts > 0).reshape(tuple(int(s) for s in shape))
 
 
 # ---------------------------------------------------------------------------------------------

@@ -7,7 +7,8 @@
 // moving from the point) walks on that bound too, with the boxes grown by its radius; ibvh_capsules.hip (every triangle within
 // a capsule's radius of its segment) is handed a yes / no from the gap between boxes and that grown entry, and
 // ibvh_segdist.hip (the closest triangle per segment) prunes on the gap between boxes as ibvh_tridist.hip (the closest
-// triangle per query triangle) does.  No reference counterpart: every traversal of
+// triangle per query triangle) does; ibvh_boxes.hip (every triangle an oriented box overlaps) is handed a yes / no from
+// "the box is apart from the query's hull", as ibvh_tritri.hip is.  No reference counterpart: every traversal of
 // ImplicitBVH.jl is a fixed-volume overlap test (traverse/, raytrace/).
 //
 // For the kernels: the workgroup size, the distance queries' point-box bound (box_bound) and NaN test (hopeless), the walk,
@@ -217,6 +218,7 @@ template <class F> int dispatch_box_types(const ibvh_types &t, F &&f) {
 // The list queries' two passes.  Their public mode enums are one pair of values, which the rule below relies on.
 static_assert(IBVH_SPHERES_COUNT == 0 && IBVH_SPHERES_WRITE == 1 && IBVH_TRIS_COUNT == 0 && IBVH_TRIS_WRITE == 1, "one pair");
 static_assert(IBVH_CAPSULES_COUNT == 0 && IBVH_CAPSULES_WRITE == 1, "the same pair"); // (ibvh_capsules.hip)
+static_assert(IBVH_BOXES_COUNT == 0 && IBVH_BOXES_WRITE == 1, "the same pair"); // (ibvh_boxes.hip)
 
 // a valid mode; the count pass needs counts, the write pass offsets and at least one output (else IBVH_ERR_INVALID_ARG)
 inline bool passes_ok(int32_t mode, const void *counts, const void *offsets, bool any_output) {

@@ -322,6 +322,10 @@ c_segment_distances(bvh, triangles, num_triangles, starts, ends, num_segments, m
     ccall((:ibvh_segment_distances, libibvh), Cint,
           (Ref{IbvhBvh}, Ptr{Cvoid}, Int64, Ptr{Cvoid}, Ptr{Cvoid}, Int64, Ptr{Cvoid}, Ptr{Cvoid}, Ptr{Cvoid}, Ptr{Cvoid}, Ptr{Cvoid}, Ptr{Cvoid}, Ptr{Cvoid}, Ptr{Cvoid}),
           bvh, triangles, num_triangles, starts, ends, num_segments, max_distance2, closest_index, closest_d2, point_segment, point_mesh, closest_kind, flag, stream)
+c_box_contacts(bvh, triangles, num_triangles, centers, half_extents, rotations, num_boxes, mode, counts, offsets, capacity, contact_index, contact_inside, flag, stream) =
+    ccall((:ibvh_box_contacts, libibvh), Cint,
+          (Ref{IbvhBvh}, Ptr{Cvoid}, Int64, Ptr{Cvoid}, Ptr{Cvoid}, Ptr{Cvoid}, Int64, Int32, Ptr{Cvoid}, Ptr{Cvoid}, Int64, Ptr{Cvoid}, Ptr{Cvoid}, Ptr{Cvoid}, Ptr{Cvoid}),
+          bvh, triangles, num_triangles, centers, half_extents, rotations, num_boxes, mode, counts, offsets, capacity, contact_index, contact_inside, flag, stream)
 c_lvt_scratch_bytes(types, n_items, cache_slots, out) =
     ccall((:ibvh_lvt_scratch_bytes, libibvh), Cint,
           (Ref{IbvhTypes}, Int64, Int32, Ref{Csize_t}),
@@ -1205,6 +1209,80 @@ function segment_distances(bvh::RocBVH{I}, triangles::ROCMatrix{T}, starts::ROCM
     isnothing(order) && return (; index, d2, point_segment, point_mesh, kind)
     inv = ROCVector{Int64}(invperm(order))
     (; index=index[inv], d2=d2[inv], point_segment=point_segment[:, inv], point_mesh=point_mesh[:, inv], kind=kind[inv])
+end
+
+# ---- boxes against a mesh (include/ibvh.h, ibvh_box_contacts) ----------------------------------------------------------
+const IBVH_BOXES_COUNT = Int32(0)
+const IBVH_BOXES_WRITE = Int32(1)
+
+"""
+    box_contacts(bvh::BVH, triangles::ROCMatrix{T}, centers::ROCMatrix{T}, half_extents, rotations=nothing;
+                 count_only=false, presorted=false) -> (; offsets, counts, index, inside)
+
+For every box (the centre `centers[:, i]`, the half extents `half_extents[:, i]` along its own axes — a 3 x N matrix, one
+number, or three numbers for all — and, optionally, `rotations[:, i]`, nine values ROW-major whose rows are the box's axes in
+world coordinates, assumed orthonormal and not checked; `nothing` = axis-aligned boxes) ALL triangles of the mesh `bvh` was
+built over that the box overlaps.  Box `i` owns rows `offsets[i] + 1 : offsets[i + 1]` of the per-contact outputs: `index` the
+triangle's user index, `inside[j]` the vertices the box holds (bit 0, 1, 2 = p1, p2, p3; 7 = the triangle lies wholly inside,
+0 = the box cuts it without holding a vertex).  Within a box the rows follow the order of the triangles' leaves in
+`bvh.leaves`.  A negative or NaN half extent and a NaN or an infinity in a centre or a rotation touch nothing; a half extent of
+zero is valid.  Bit-equal to a brute force over all triangles; the hull, the box clause, the 13 separating axes, the order and
+why pruning loses nothing are spelled out in include/ibvh.h.  Two launches, a count and a write, around a `cumsum` of the counts
+on the device array; `count_only=true` stops after the first (the per-contact outputs are `nothing`).  The BVH must have
+`BBox{T}` leaves made from the triangles (a skin margin and `refit!` are fine) under `BBox` nodes of `T` or wider; anything else
+raises ArgumentError.  The device walks the batch along a Morton curve through the centres and writes each box's rows where the
+caller's order wants them; `presorted=true` walks it as given.  Not a method of ImplicitBVH: the reference has no such query.
+"""
+function box_contacts(bvh::RocBVH{I}, triangles::ROCMatrix{T}, centers::ROCMatrix{T},
+                      half_extents::Union{Real, NTuple{3, Real}, AbstractVector{<:Real}, ROCMatrix{T}},
+                      rotations::Union{Nothing, ROCMatrix{T}}=nothing; count_only::Bool=false, presorted::Bool=false) where {I, T}
+    d = bvh_desc(bvh)
+    isnothing(d) && throw(ArgumentError("box_contacts: no libibvh instantiation for this BVH's types"))
+    leaf_volume_type(bvh.leaves) === BBox{T} && eltype(bvh.nodes) <: BBox && sizeof(eltype(bvh.nodes)) >= sizeof(BBox{T}) ||
+        throw(ArgumentError("box_contacts: the BVH must have BBox{$T} leaves under BBox nodes of $T or wider"))
+    size(triangles, 1) == 9 || throw(ArgumentError("box_contacts: triangles must be 9 x n (p1 p2 p3 per column)"))
+    size(centers, 1) == 3 || throw(ArgumentError("box_contacts: centers must be 3 x N"))
+    n = size(centers, 2)
+    h = if half_extents isa ROCMatrix
+        size(half_extents) == (3, n) || throw(ArgumentError("box_contacts: size(half_extents) == size(centers) == (3, N) must hold"))
+        half_extents
+    elseif half_extents isa Real
+        fill!(similar(centers, T, 3, n), T(half_extents))
+    else
+        length(half_extents) == 3 || throw(ArgumentError("box_contacts: half_extents must be one number, three numbers or 3 x N"))
+        ROCMatrix{T}(repeat(T.(collect(half_extents)), 1, n))
+    end
+    isnothing(rotations) || size(rotations) == (9, n) || throw(ArgumentError("box_contacts: rotations must be 9 x N (row-major per box)"))
+    offsets = fill!(similar(centers, Int64, n + 1), 0)
+    none(m) = (similar(centers, I, m), similar(centers, UInt8, m))
+    nothings = (; index=nothing, inside=nothing)
+    named(o) = (; index=o[1], inside=o[2])
+    n == 0 && return (; offsets, counts=similar(centers, Int64, 0), (count_only ? nothings : named(none(0)))...)
+    order = presorted ? nothing : point_morton_order(centers)
+    perm = isnothing(order) ? nothing : ROCVector{Int64}(order)
+    c = isnothing(perm) ? centers : centers[:, perm]
+    hw = isnothing(perm) ? h : h[:, perm]
+    rw = isnothing(rotations) ? nothing : (isnothing(perm) ? rotations : rotations[:, perm])
+    rptr = isnothing(rw) ? Ptr{Cvoid}(C_NULL) : devptr(rw)
+    flag = scratch!(:boxes_flag, 4)
+    fill!(flag, 0x00)
+    walked = similar(centers, Int64, n)
+    nt = Int64(size(triangles, 2))
+    check(c_box_contacts(d, devptr(triangles), nt, devptr(c), devptr(hw), rptr, Int64(n), IBVH_BOXES_COUNT, devptr(walked),
+                         C_NULL, Int64(0), C_NULL, C_NULL, devptr(flag), stream_ptr()), "ibvh_box_contacts")
+    Array(flag)[1] & 0x02 != 0 && throw(ArgumentError("box_contacts: a leaf's index lies outside 1:$nt"))
+    # the counts back in the caller's order, scanned there: a box's rows then follow its predecessor's in that order
+    counts = isnothing(perm) ? walked : walked[ROCVector{Int64}(invperm(order))]
+    offsets[2:end] .= cumsum(counts)
+    count_only && return (; offsets, counts, nothings...)
+    total = Array(offsets[end:end])[1]                           # the one read between the passes
+    out = none(total)
+    total == 0 && return (; offsets, counts, named(out)...)
+    first_row = isnothing(perm) ? offsets[1:n] : offsets[1:n][perm]   # ... gathered back into walk order
+    check(c_box_contacts(d, devptr(triangles), nt, devptr(c), devptr(hw), rptr, Int64(n), IBVH_BOXES_WRITE, C_NULL,
+                         devptr(first_row), Int64(total), devptr(out[1]), devptr(out[2]), devptr(flag), stream_ptr()), "ibvh_box_contacts")
+    Array(flag)[1] & 0x04 != 0 && error("box_contacts: the write pass found more contacts than the count pass")
+    (; offsets, counts, named(out)...)
 end
 
 # ---- k nearest leaves for a batch of query points (include/ibvh.h, ibvh_nearest_leaves) ------------------------------

@@ -52,6 +52,7 @@ extern "C" {
  *      ibvh_triangle_distances (additive under 7 likewise: one more entry point);
  *      ibvh_capsule_contacts and IBVH_CAPSULES_COUNT / IBVH_CAPSULES_WRITE, ibvh_segment_distances (additive under 7
  *      likewise: two more entry points);
+ *      ibvh_box_contacts and IBVH_BOXES_COUNT / IBVH_BOXES_WRITE (additive under 7 likewise: one more entry point);
  *      argument checks only, no layout or argument list moves: ibvh_key_histogram takes
  *      what fits its LDS staging (10 rows at 12-bit digits) and refuses shift > 63 and a negative prefix_shift,
  *      ibvh_pack_records / ibvh_dist_plan answer IBVH_ERR_OVERFLOW for an index past IBVH_I32 */
@@ -1172,6 +1173,92 @@ ibvh_status ibvh_segment_distances(const ibvh_bvh *bvh, const void *triangles, i
                                    const void *max_distance2, void *closest_index, void *closest_d2,
                                    void *point_segment, void *point_mesh, void *closest_kind,
                                    void *flag, void *stream);
+
+/* ----------------------------------------------------------------------------------- */
+/* box-vs-mesh contacts: every triangle an oriented box overlaps                         */
+/* ----------------------------------------------------------------------------------- */
+/* For every box (a centre c, half extents h and, optionally, a rotation R): ALL triangles K = (p1, p2, p3) of the mesh the
+ * BVH was built over (ibvh_volumes_from_triangles with IBVH_BBOX) that the box overlaps — which ones, and which of their
+ * vertices lie in the box.  The shape beside the sphere (ibvh_sphere_contacts), the triangle (ibvh_triangle_contacts) and the
+ * capsule (ibvh_capsule_contacts): an oriented box as a robot link, a vehicle hull or a rigid body's proxy; an axis-aligned
+ * one as a voxel, a region of interest or a culling cell.  No reference counterpart (the reference's traversals end at
+ * pairs of BOXES, and the axis-aligned hull of a rotated box is up to sqrt(3) wider per axis than the box); a
+ * variable-length answer in TWO calls of ONE launch each — count, the caller's scan, write — with NO host synchronisation
+ * inside either, no LDS, no scratch buffer, no read-modify-write of memory.
+ *   triangles    : num_triangles x 9 values (p1 p2 p3) of bvh->types.leaf_float, `flt` below; user index k is row k - 1
+ *   centers      : num_boxes x 3 row-major values of `flt`, c; processed in the order given (neighbours in memory that are
+ *                  neighbours in space walk the same nodes: sort a scattered batch along a Morton curve first)
+ *   half_extents : num_boxes x 3 row-major values of `flt`, h: the box's half width along its own axis 0, 1, 2
+ *   rotations    : num_boxes x 9 row-major values of `flt`, R: row k (values 3k, 3k + 1, 3k + 2) is the box's axis u_k in
+ *                  world coordinates, ASSUMED orthonormal.  NULL = the identity for every box, in the SAME arithmetic
+ *                  (u = 1 0 0, 0 1 0, 0 0 1 takes R's place; one kernel, no second code path): an axis-aligned box.
+ *                  A matrix that is not orthonormal is OUTSIDE the contract, and the device does NOT check it: the result
+ *                  is then what the arithmetic below gives, the overlap with the image of [-h, h] under no rigid motion.
+ *   mode         : IBVH_BOXES_COUNT or IBVH_BOXES_WRITE
+ * counts, offsets, capacity and the two passes are those of ibvh_sphere_contacts, word for word: the count pass needs
+ *   `counts` (num_boxes x int64) and touches no output; the caller scans; the write pass needs `offsets` (num_boxes x
+ *   int64, ANY exclusive prefix sum, not necessarily monotone) and puts contact j of box s in row offsets[s] + j; a row
+ *   >= capacity or < 0 is never written and sets bit 2 of `flag` (value 4), per ROW.
+ *   contact_index  : capacity x I, the triangle's user index (1-based)
+ *   contact_inside : capacity x uint8, the INSIDE mask (below), 0 - 7
+ *   each optional, at least one non-NULL; what was not asked for is not written.
+ * All arguments are validated before any launch, in the order of the other point-walk entries.  The entry's own checks: NULL
+ * bvh, negative sizes or capacity, an unknown mode, no `counts` in the count pass, no `offsets` or no output at all in the
+ * write pass: IBVH_ERR_INVALID_ARG.  Then the type combination (below): IBVH_ERR_UNSUPPORTED.  Then a tree shape that is not
+ * an ImplicitTree's or a missing array (centers or half_extents with boxes to process; rotations may always be NULL):
+ * IBVH_ERR_INVALID_ARG.  num_boxes == 0: IBVH_OK, nothing is touched.
+ * The result is defined independently of how it is found, in `flt` throughout, every operation rounded once (nothing fused;
+ * nothing divides), every comparison false on NaN, so that it can be pinned bit for bit.  |x| clears the sign bit.
+ * The HULL Q of a box, computed once per box: e_k = ((|R_0k| * h_0 + |R_1k| * h_1) + |R_2k| * h_2) — column k of R, i.e.
+ *   values k, 3 + k, 6 + k — and Q = [c_k - e_k, c_k + e_k], each rounded once.
+ * The LOCAL coordinates of a world point x: w = x - c per component, then v[k] = ((u_k0 * w_0 + u_k1 * w_1) + u_k2 * w_2)
+ *   for k = 0, 1, 2.  v_1, v_2, v_3 are those of p1, p2, p3.
+ * Triangle K, in a leaf with the stored box L = [lo, up], is a contact of the box iff both clauses hold:
+ *   (i)  the BOX clause: L is not apart from Q (apart: the six strict comparisons of ibvh_triangle_contacts,
+ *        Qup_k < lo_k || Qlo_k > up_k for some k; every one false on NaN);
+ *   (ii) the SAT clause: none of 13 axes separates the triangle from [-h, h] in the box's frame (Akenine-Möller 2001).  An
+ *        axis with the triangle's projections P_1, P_2, P_3 and the box's radius rad OVERLAPS iff min <= rad and
+ *        max >= -rad, where min / max are folded from P_1: `P_2 < m ? P_2 : m`, then `P_3 < m ? P_3 : m` (and `>`).
+ *        Touching counts as overlapping.  With the edges e_0 = v_2 - v_1, e_1 = v_3 - v_2, e_2 = v_1 - v_3 (per component):
+ *          the three box axes, k = 0, 1, 2: P_i = v_i[k], rad = h_k;
+ *          the triangle's normal n = e_0 x e_1, n_0 = e_0[1] * e_1[2] - e_0[2] * e_1[1], n_1 = e_0[2] * e_1[0] - e_0[0] * e_1[2],
+ *            n_2 = e_0[0] * e_1[1] - e_0[1] * e_1[0]: d = ((n_0 * v_1[0] + n_1 * v_1[1]) + n_2 * v_1[2]),
+ *            rad = ((|n_0| * h_0 + |n_1| * h_1) + |n_2| * h_2); it overlaps iff d <= rad and d >= -rad;
+ *          the nine axes a = axis_k x e_j, for j = 0, 1, 2 and within j for k = 0, 1, 2, by their two non-zero components,
+ *          with e = e_j:  k = 0: P_i = e[1] * v_i[2] - e[2] * v_i[1], rad = |e[2]| * h_1 + |e[1]| * h_2;
+ *                         k = 1: P_i = e[2] * v_i[0] - e[0] * v_i[2], rad = |e[2]| * h_0 + |e[0]| * h_2;
+ *                         k = 2: P_i = e[0] * v_i[1] - e[1] * v_i[0], rad = |e[1]| * h_0 + |e[0]| * h_1.
+ *        The clause is the AND of all 13; the order they are tested in does not enter the result.
+ *        For a ZERO-AREA triangle the 13 axes are CONSERVATIVE: n and some a are 0, such an axis separates nothing
+ *        (0 <= 0), so the test may report a contact where the exact sets are disjoint, and never loses one.
+ *   In real arithmetic (ii) implies (i): a common point of box and triangle lies in Q and in L.  (i) is part of the
+ *   definition so that the walk can prune on it without loss; it decides only pairs that rounding puts on a face of the
+ *   hull.  Because (i) reads the STORED box, a skin margin on the leaves can only admit more such pairs, never fewer.
+ * The INSIDE mask of a contact: bit i - 1 (value 1, 2, 4 for p1, p2, p3) is set iff |v_i[k]| <= h_k for all k.  7: the
+ *   triangle lies wholly inside the box; 0: the box cuts it without holding a vertex.
+ * INVALID boxes: a box has NO contacts if some h_k is not >= 0 — negative or NaN — or if a value of c or R is NaN or
+ *   infinite.  A half extent of zero is valid: a plate, a segment or a point.  An INFINITE half extent is not refused: the
+ *   result is what the arithmetic gives (0 * Inf = NaN fails its comparison).
+ * Order: the contacts of one box come in LEAF ORDER — ascending position of the triangle's leaf in bvh->leaves — in both
+ *   passes, which is what lets them agree: contact j of the count pass is row j of the write pass.  A triangle that two
+ *   leaves name appears twice, once per leaf.
+ * Why pruning is lossless WITHOUT an epsilon.  The walk refuses a node or a leaf iff its box is apart from Q (a NaN in Q
+ *   refuses nothing).  Every box of the tree contains the boxes below it exactly (minima and maxima, no rounding), so a box
+ *   that is apart from Q lies over leaf boxes that are apart from Q, and those clause (i) refuses by definition.  Why the
+ *   order holds: as for ibvh_sphere_contacts — the walk is handed 0 / 1 under a constant limit of 0.
+ * Accepted BVHs — exactly those of ibvh_capsule_contacts: leaf_kind == node_kind == IBVH_BBOX, triangles and boxes of
+ *   leaf_float, node_float the same as or wider than leaf_float; any index and Morton type.  Anything else — sphere leaves,
+ *   sphere nodes, F64 leaves under F32 nodes — is IBVH_ERR_UNSUPPORTED, never an answer.  Exact PROVIDED every leaf's box
+ *   contains its triangle's box: a skin margin on the leaves is allowed, and so is a BVH after ibvh_refit.  Levels above
+ *   bvh->built_level are not read.  NaN vertices: a triangle with one fails a comparison of (ii) and is no contact.
+ * Guards: those of ibvh_sphere_contacts — a leaf whose index lies outside 1..num_triangles is skipped in BOTH passes alike
+ * and sets bit 1 of `flag` (value 2); the same flag contract. */
+enum { IBVH_BOXES_COUNT = 0, IBVH_BOXES_WRITE = 1 };
+ibvh_status ibvh_box_contacts(const ibvh_bvh *bvh, const void *triangles, int64_t num_triangles,
+                              const void *centers, const void *half_extents, const void *rotations,
+                              int64_t num_boxes, int32_t mode, void *counts, const void *offsets,
+                              int64_t capacity, void *contact_index, void *contact_inside,
+                              void *flag, void *stream);
 
 /* ----------------------------------------------------------------------------------- */
 /* breadth-first traversal (BFSTraversal): level-synchronous pair queues                 */
