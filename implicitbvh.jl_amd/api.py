@@ -1399,6 +1399,17 @@ def _query_points(points, ft, max_distance, presorted, what):
     return (p if order is None else p[order]), n, radius2, order
 
 
+def _companion(value, n, ft, what, name, of):
+    """`value`, the (3, N) CUDA tensor of dtype ft that goes with the (3, N) points named `of` (a ray's direction, a sphere's
+    displacement), checked -> the (N, 3) contiguous tensor"""
+    torch = _torch()
+    if not (isinstance(value, torch.Tensor) and value.dim() == 2 and tuple(value.shape) == (3, n)):
+        raise ValueError(f"{what}: size({name}) == size({of}) == (3, N) must hold")
+    if value.dtype != ft or not value.is_cuda:
+        raise ValueError(f"{what}: {name} must be a {ft} tensor on the GPU (device='cuda')")
+    return value.t().contiguous()
+
+
 def _unpermute(order, outputs):
     """The outputs' rows back in the caller's order (order: what _query_points returned)."""
     if order is None:
@@ -1543,21 +1554,8 @@ def cast_rays(bvh, triangles, points, directions, t_max=None, any_hit=False, pre
     torch = _require_gpu()
     tris, ft, idt = _mesh_query_setup(bvh, triangles, "cast_rays")
     p, n, _, order = _query_points(points, ft, None, presorted, "cast_rays")
-    if not (isinstance(directions, torch.Tensor) and directions.dim() == 2 and tuple(directions.shape) == (3, n)):
-        raise ValueError("cast_rays: size(directions) == size(points) == (3, N) must hold")
-    if directions.dtype != ft or not directions.is_cuda:
-        raise ValueError(f"cast_rays: directions must be a {ft} tensor on the GPU (device='cuda')")
-    d = directions.t().contiguous()
-    lim = None
-    if t_max is not None:
-        if isinstance(t_max, torch.Tensor):
-            if tuple(t_max.shape) != (n,) or t_max.dtype != ft or not t_max.is_cuda:
-                raise ValueError(f"cast_rays: t_max must be a number or an (N,) {ft} tensor on the GPU")
-            lim = t_max.contiguous()
-        elif isinstance(t_max, (int, float, np.integer, np.floating)) and not isinstance(t_max, bool):
-            lim = torch.full((n,), float(t_max), dtype=ft, device="cuda")
-        else:
-            raise ValueError(f"cast_rays: t_max must be a number or an (N,) {ft} tensor on the GPU")
+    d = _companion(directions, n, ft, "cast_rays", "directions", "points")
+    lim = None if t_max is None else _per_item(t_max, n, ft, "cast_rays", "t_max")
     if order is not None:
         d = d[order]
         lim = None if lim is None else lim[order]
@@ -1665,14 +1663,7 @@ def sphere_contacts(bvh, triangles, centers, radii, count_only=False, presorted=
     what = "sphere_contacts"
     tris, ft, idt = _mesh_query_setup(bvh, triangles, what)
     p, n, _, order = _query_points(centers, ft, None, presorted, what)
-    if isinstance(radii, torch.Tensor):
-        if tuple(radii.shape) != (n,) or radii.dtype != ft or not radii.is_cuda:
-            raise ValueError(f"{what}: radii must be a number or an (N,) {ft} tensor on the GPU")
-        r = radii.contiguous()
-    elif isinstance(radii, (int, float, np.integer, np.floating)) and not isinstance(radii, bool):
-        r = torch.full((n,), float(radii), dtype=ft, device="cuda")
-    else:
-        raise ValueError(f"{what}: radii must be a number or an (N,) {ft} tensor on the GPU")
+    r = _per_item(radii, n, ft, what, "radii")
     walk = lambda: (order, (p, r if order is None else r[order]))
     return _contact_lists(SphereContacts, what, bvh, tris, n, walk, tail=(),
                           outs=((idt, ()), (ft, ()), (ft, (3,)), (torch.uint8, ())), count_only=count_only)
@@ -1732,11 +1723,7 @@ def sweep_spheres(bvh, triangles, centers, displacements, radii, t_max=None, any
     what = "sweep_spheres"
     tris, ft, idt = _mesh_query_setup(bvh, triangles, what)
     p, n, _, order = _query_points(centers, ft, None, presorted, what)
-    if not (isinstance(displacements, torch.Tensor) and displacements.dim() == 2 and tuple(displacements.shape) == (3, n)):
-        raise ValueError(f"{what}: size(displacements) == size(centers) == (3, N) must hold")
-    if displacements.dtype != ft or not displacements.is_cuda:
-        raise ValueError(f"{what}: displacements must be a {ft} tensor on the GPU (device='cuda')")
-    d = displacements.t().contiguous()
+    d = _companion(displacements, n, ft, what, "displacements", "centers")
     r = _per_item(radii, n, ft, what, "radii")
     lim = None if t_max is None else _per_item(t_max, n, ft, what, "t_max")
     if order is not None:

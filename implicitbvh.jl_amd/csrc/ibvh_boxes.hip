@@ -6,7 +6,7 @@
 // box is up to sqrt(3) wider per axis than the box.
 //
 // A triangle k is a contact iff (i) leaf k's STORED box is not apart from the query's hull Q = c -+ e,
-// e_k = ((|R_0k| * h_0 + |R_1k| * h_1) + |R_2k| * h_2) — the six strict comparisons of ibvh_tritri.hip, every one false on NaN —
+// e_k = ((|R_0k| * h_0 + |R_1k| * h_1) + |R_2k| * h_2) — ibvh_trigeom.hpp's six strict comparisons, every one false on NaN —
 // and (ii) none of ibvh_tribox.hpp's 13 axes separates the triangle's local vertices
 // v_k = ((u_k0 * w_0 + u_k1 * w_1) + u_k2 * w_2), w = p - c, from [-h, h].  In real arithmetic (ii) implies (i): a point of
 // the box lies in its hull, a point of K in its leaf's box.  (i) is part of the definition so that the walk can prune on it
@@ -26,6 +26,7 @@
 // registers to its row.  rotations == NULL is the identity in the SAME arithmetic: one kernel, no second code path.
 #include "ibvh_pointwalk.hpp"
 #include "ibvh_tribox.hpp"
+#include "ibvh_trigeom.hpp"
 
 namespace ibvh {
 namespace boxes {
@@ -60,11 +61,8 @@ __global__ __launch_bounds__(pointwalk::kBlock) void boxes_walk_kernel(
         T qlo[3], qup[3]; // the hull Q
         tribox::hull(q, qlo, qup);
         uint64_t next = pointwalk::first_row<WRITE>(offsets, item);
-        // 0 = the box may hold a contact, 1 = it is apart from Q (six strict comparisons, false on NaN: such a box is entered)
-        auto box = [&](const T *lo, const T *up) -> T {
-            const bool apart = (qup[0] < lo[0]) | (qlo[0] > up[0]) | (qup[1] < lo[1]) | (qlo[1] > up[1]) | (qup[2] < lo[2]) | (qlo[2] > up[2]);
-            return apart ? T(1) : T(0);
-        };
+        // 0 = the box may hold a contact, 1 = it is apart from Q (false on NaN: such a box is entered)
+        auto box = [&](const T *lo, const T *up) -> T { return trigeom::apart(qlo, qup, lo, up) ? T(1) : T(0); };
         // only a leaf that passes — clause (i) on its stored box — gathers its triangle (36 / 72 bytes) and turns it into
         // the box's frame
         auto visit = [&](const char *rec) {
@@ -123,7 +121,7 @@ ibvh_status ibvh_box_contacts(const ibvh_bvh *bvh, const void *triangles, int64_
         IBVH_LAUNCH_CHECK();
         return IBVH_OK;
     };
-    return (ibvh_status)pointwalk::dispatch_box_types_and_pass(bvh->types, mode == IBVH_BOXES_WRITE, launch);
+    return (ibvh_status)pointwalk::dispatch_box_types_and_bool(bvh->types, mode == IBVH_BOXES_WRITE, launch);
 }
 
 } // extern "C"

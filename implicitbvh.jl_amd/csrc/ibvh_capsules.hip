@@ -62,7 +62,7 @@ __global__ __launch_bounds__(pointwalk::kBlock) void capsules_walk_kernel(
         // grown by r beyond its end (both false on NaN: such a box is entered)
         auto box = [&](const T *lo, const T *up) -> T {
             const T glo[3] = {lo[0] - r, lo[1] - r, lo[2] - r}, gup[3] = {up[0] + r, up[1] + r, up[2] + r};
-            const T gap = segtri::box_gap(lo, up, slo, sup), entry = slab::slab_entry(glo, gup, a, d, inv);
+            const T gap = trigeom::box_gap(lo, up, slo, sup), entry = slab::slab_entry(glo, gup, a, d, inv);
             return ((gap > r2) | (entry > T(1))) ? T(1) : T(0);
         };
         // only a leaf that passes — clause (i) on its stored box included — gathers its triangle (36 / 72 bytes)
@@ -70,7 +70,7 @@ __global__ __launch_bounds__(pointwalk::kBlock) void capsules_walk_kernel(
             I index;
             raytri::Tri<T> K;
             if (pointwalk::leaf_triangle(rec, lay, tris, num_triangles, index, K.v)) {
-                segtri::Pair<T> p;
+                trigeom::Pair<T> p;
                 segtri::evaluate(a, b, slo, sup, K, p);
                 if (p.d2 <= r2) { // clause (ii) (false on NaN)
                     pointwalk::contact<WRITE>(next, capacity, over, [&](uint64_t row) {
@@ -78,7 +78,7 @@ __global__ __launch_bounds__(pointwalk::kBlock) void capsules_walk_kernel(
                         if (out_d2) out_d2[row] = p.d2;
 #pragma unroll
                         for (int k = 0; k < 3; ++k) {
-                            if (out_xs) out_xs[3 * row + k] = p.xs[k];
+                            if (out_xs) out_xs[3 * row + k] = p.xq[k];
                             if (out_xk) out_xk[3 * row + k] = p.xk[k];
                         }
                         if (out_kind) out_kind[row] = (uint8_t)p.kind;
@@ -131,7 +131,7 @@ ibvh_status ibvh_capsule_contacts(const ibvh_bvh *bvh, const void *triangles, in
         IBVH_LAUNCH_CHECK();
         return IBVH_OK;
     };
-    return (ibvh_status)pointwalk::dispatch_box_types_and_pass(bvh->types, mode == IBVH_CAPSULES_WRITE, launch);
+    return (ibvh_status)pointwalk::dispatch_box_types_and_bool(bvh->types, mode == IBVH_CAPSULES_WRITE, launch);
 }
 
 } // extern "C"

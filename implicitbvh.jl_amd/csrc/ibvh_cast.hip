@@ -20,7 +20,6 @@
 #include "ibvh_slab.hpp"
 
 #include <limits>
-#include <type_traits>
 
 namespace ibvh {
 namespace cast {
@@ -61,8 +60,7 @@ __global__ __launch_bounds__(pointwalk::kBlock) void cast_walk_kernel(
                     const T ts = entry > t ? entry : t; // t*: the clamp
                     if constexpr (ANY) {
                         occluded |= ts <= L;
-                    } else if ((ts < best) | ((ts == best) & ((best_index == 0) | (index < best_index)))) {
-                        // (t*, index) lexicographically; the first one only has to be within the limit (best == L)
+                    } else if (pointwalk::wins(ts, index, best, best_index)) { // (t*, index) lexicographically; best starts at L
                         best = ts;
                         best_index = index;
                         best_u = u;
@@ -126,11 +124,7 @@ ibvh_status ibvh_cast_rays(const ibvh_bvh *bvh, const void *triangles, int64_t n
         IBVH_LAUNCH_CHECK();
         return IBVH_OK;
     };
-    // the mode is a template parameter: the any-hit kernel carries no best hit
-    auto modes = [&](auto ft, auto nt, auto it) -> int {
-        return any ? launch(ft, nt, it, std::true_type{}) : launch(ft, nt, it, std::false_type{});
-    };
-    return (ibvh_status)pointwalk::dispatch_box_types(bvh->types, modes);
+    return (ibvh_status)pointwalk::dispatch_box_types_and_bool(bvh->types, any, launch);
 }
 
 } // extern "C"

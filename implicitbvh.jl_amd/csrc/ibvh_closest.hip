@@ -42,8 +42,7 @@ __global__ __launch_bounds__(kBlock) void closest_walk_kernel(TreeDev tree, int 
             int region; // (not part of this query's answer)
             if (pointwalk::leaf_triangle(rec, lay, tris, num_triangles, index, tr)) {
                 const T d2 = closest_on_triangle(tr, p, q, region);
-                // (d2, index) lexicographically; the first one only has to be within the radius (best == max_d2)
-                if ((d2 < best) | ((d2 == best) & ((best_index == 0) | (index < best_index)))) {
+                if (pointwalk::wins(d2, index, best, best_index)) { // (d2, index) lexicographically; best starts at the radius
                     best = d2;
                     best_index = index;
                     bq[0] = q[0];

@@ -1,22 +1,26 @@
-// ibvh_pointwalk.hpp — what the six queries that walk one point (ray origin, query triangle) per lane through a BVH have in
-// common: ibvh_closest.hip (the closest triangle) and ibvh_nearest.hip (the k nearest leaf centres), which prune on a bound that
-// shrinks while they walk, ibvh_crossings.hip (the triangles an axis ray from the point crosses), ibvh_spheres.hip (every
-// triangle within a sphere's radius of the point) and ibvh_tritri.hip (every triangle a query triangle cuts), whose bound is
-// a fixed yes / no, and ibvh_cast.hip (the closest or any hit
-// of a ray from the point), whose bound is the ray's entry distance into a box; ibvh_sweep.hip (the first contact of a sphere
-// moving from the point) walks on that bound too, with the boxes grown by its radius; ibvh_capsules.hip (every triangle within
-// a capsule's radius of its segment) is handed a yes / no from the gap between boxes and that grown entry, and
-// ibvh_segdist.hip (the closest triangle per segment) prunes on the gap between boxes as ibvh_tridist.hip (the closest
-// triangle per query triangle) does; ibvh_boxes.hip (every triangle an oriented box overlaps) is handed a yes / no from
-// "the box is apart from the query's hull", as ibvh_tritri.hip is.  No reference counterpart: every traversal of
-// ImplicitBVH.jl is a fixed-volume overlap test (traverse/, raytrace/).
+// ibvh_pointwalk.hpp — what the queries that walk one item (a point, a ray, a triangle, a segment, a box) per lane through a
+// BVH have in common.  Per unit: what the walk bounds a box by, and whether the query keeps a best answer or lists all.
+//   ibvh_closest.hip    the squared distance from the point to the box                         best: the closest triangle
+//   ibvh_nearest.hip    the same                                                               best: the k nearest leaf centres
+//   ibvh_crossings.hip  0 / 1: an axis ray from the point can / cannot meet the box            sums: the crossings, their orientations
+//   ibvh_cast.hip       the ray's entry distance into the box (ibvh_slab.hpp)                  best: the closest hit, or any hit
+//   ibvh_sweep.hip      that entry, into the box grown by the sphere's radius                  best: the first contact, or any
+//   ibvh_tridist.hip    the squared gap between the box and the triangle's box                 best: the closest triangle
+//   ibvh_segdist.hip    the squared gap between the box and the segment's box                  best: the closest triangle
+//   ibvh_spheres.hip    0 / 1: the point's squared distance to the box is within r * r or not  list: the triangles within r
+//   ibvh_tritri.hip     0 / 1: the box is not / is apart from the triangle's box               list: the triangles it cuts
+//   ibvh_capsules.hip   0 / 1: that gap within r * r and the grown entry within 1, or not      list: the triangles within r
+//   ibvh_boxes.hip      0 / 1: the box is not / is apart from the oriented box's hull          list: the triangles it overlaps
+// No reference counterpart: every traversal of ImplicitBVH.jl is a fixed-volume overlap test (traverse/, raytrace/).
 //
 // For the kernels: the workgroup size, the distance queries' point-box bound (box_bound) and NaN test (hopeless), the walk,
-// the mesh queries' gather of a leaf's triangle (leaf_triangle), and the list queries' rows (first_row, contact, store_count:
-// the count / write protocol of ibvh_spheres.hip and ibvh_tritri.hip).  For the entry points: the rules they share and prepare(),
-// the one place that applies them, in the one order a call with several faults is refused in; the (T, TN, I) dispatch of a tree
-// with box leaves, and the list queries' (T, TN, I, pass); their two-pass argument rule (passes_ok); the optional radius.  An
-// entry point keeps its own checks (counts, axis, k, skip, which outputs it has) and its launch.
+// the mesh queries' gather of a leaf's triangle (leaf_triangle), the best-answer queries' tie rule (wins), and the list
+// queries' rows (first_row, contact, store_count: the count / write protocol).  For the entry points: the rules they share
+// and prepare(), the one place that applies them, in the one order a call with several faults is refused in; the
+// (T, TN, I) dispatch of a tree with box leaves, and the same with a bool as a fourth tag — the pass of a list query, the
+// any-hit mode of ibvh_cast.hip and ibvh_sweep.hip —; the list queries' two-pass argument rule (passes_ok); the optional
+// radius.  An entry point keeps its own checks (counts, axis, k, skip, which outputs it has) and its launch.  The box and
+// triangle primitives are ibvh_trigeom.hpp's, the two pair distances' seeded walk is ibvh_pairwalk.hpp's.
 //
 // A query hands the walk three things: bound(lo, up), its lower bound for a box (box_bound below for the distance queries;
 // 0 / 1 = "the ray can / cannot meet the box" for the crossings; the slab test's entry distance for the ray cast), limit(),
@@ -159,6 +163,12 @@ template <class T> IBVH_D bool hopeless(const T *p, T max_d2) {
     return !((p[0] == p[0]) & (p[1] == p[1]) & (p[2] == p[2]) & (max_d2 == max_d2));
 }
 
+// The best-answer queries' tie rule: (x, index) lies lexicographically below (best, best_index); the first one only has to
+// be within the limit `best` starts from (best_index == 0: nothing yet).  Every comparison is false on NaN
+template <class T, class I> IBVH_D bool wins(T x, I index, T best, I best_index) {
+    return (x < best) | ((x == best) & ((best_index == 0) | (index < best_index)));
+}
+
 // ---- the entry points' common front end (host) ---------------------------------------------------------------------
 
 // the lossless bound needs boxes above the leaves, holding the leaves' values exactly (else IBVH_ERR_UNSUPPORTED)
@@ -225,11 +235,12 @@ inline bool passes_ok(int32_t mode, const void *counts, const void *offsets, boo
     return mode == IBVH_SPHERES_WRITE ? offsets && any_output : mode == IBVH_SPHERES_COUNT && counts;
 }
 
-// dispatch_box_types with the pass as a fourth tag, std::bool_constant<write>: the pass is a template parameter of the
-// kernel, so the counting kernel carries no outputs and reads no offsets
-template <class F> int dispatch_box_types_and_pass(const ibvh_types &t, bool write, F &&f) {
+// dispatch_box_types with a bool as a fourth tag, std::bool_constant<flag>, so that it is a template parameter of the kernel:
+// the pass of a list query (write: the counting kernel carries no outputs and reads no offsets), the any-hit mode of
+// ibvh_cast.hip and ibvh_sweep.hip (the any-hit kernel carries no best hit)
+template <class F> int dispatch_box_types_and_bool(const ibvh_types &t, bool flag, F &&f) {
     return dispatch_box_types(t, [&](auto ft, auto nt, auto it) -> int {
-        return write ? f(ft, nt, it, std::true_type{}) : f(ft, nt, it, std::false_type{});
+        return flag ? f(ft, nt, it, std::true_type{}) : f(ft, nt, it, std::false_type{});
     });
 }
 

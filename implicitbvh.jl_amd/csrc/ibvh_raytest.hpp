@@ -1,7 +1,7 @@
 // ibvh_raytest.hpp — the exact ray-triangle test of include/ibvh.h (ibvh_rays_resolve_triangles), ONE copy for the
 // queries that pin it bit for bit: ibvh_raytri.hip (the nearest hit of a candidate list), ibvh_cast.hip (the ray cast),
-// ibvh_tritri.hip (a triangle's edges against another triangle), ibvh_sweep.hip (a moving sphere against a face) and
-// ibvh_segtri.hpp (a segment against a triangle, for ibvh_capsules.hip and ibvh_segdist.hip).
+// ibvh_sweep.hip (a moving sphere against a face) and ibvh_trigeom.hpp's segment_cuts (a segment against a triangle: the
+// edges of ibvh_tritri.hip and ibvh_tridist.hip, the segment of ibvh_segtri.hpp for ibvh_capsules.hip and ibvh_segdist.hip).
 // No reference counterpart: ImplicitBVH.jl stops at the candidate list (raytrace/leaf_vs_tree/leaf_vs_tree.jl:170-228).
 #pragma once
 #include "ibvh_common.hpp"

@@ -15,16 +15,16 @@
 // clause here: the answer has no radius to grow a box by.
 //
 // The walk itself — work mapping, near child first, the trail word, the pop, the strict skip — is ibvh_pointwalk.hpp's, the
-// gather its leaf_triangle.  S, its box, the best pair so far and the trail live in registers: one lane, one segment, one
-// launch.
+// gather its leaf_triangle, the bound ibvh_trigeom.hpp's box_gap.  S, its box, the best pair so far and the trail live in
+// registers: one lane, one segment, one launch.
 //
-// The lane walks twice.  First ibvh_closest.hip's walk from the end a: the squared distance from a to the closest triangle
-// the query may answer with is candidate 0 of that pair, bit for bit, so no answer lies beyond it, and the second walk — the
-// query's own — starts from that limit, not from the radius: an unbounded query then prunes from its first node on.
+// The lane walks twice, by ibvh_pairwalk.hpp's routine: first ibvh_closest.hip's walk from the end a — the point candidate 0
+// of ibvh_segtri.hpp's evaluation is evaluated from, which is what that routine's argument asks of its caller —, then the
+// query's own walk from the limit the first one found, not from the radius: an unbounded query then prunes from its first
+// node on.
+#include "ibvh_pairwalk.hpp"
 #include "ibvh_pointwalk.hpp"
 #include "ibvh_segtri.hpp"
-
-#include <limits>
 
 namespace ibvh {
 namespace segdist {
@@ -45,60 +45,20 @@ __global__ __launch_bounds__(pointwalk::kBlock) void segdist_walk_kernel(
         const T b[3] = {ends[3 * item], ends[3 * item + 1], ends[3 * item + 2]};
         T slo[3], sup[3]; // S's box: exact
         segtri::segment_box(a, b, slo, sup);
-        segtri::Pair<T> best; // best.d2 is the limit: it starts at the radius, or at the first limit below
-        const T zero[3] = {T(0), T(0), T(0)};
-        best.put(max_d2, zero, zero, 0);
-        I best_index = 0;
         // the bound of include/ibvh.h: the squared gap between S's box and the box, in d2's operation order
-        auto box = [&](const T *lo, const T *up) -> T { return segtri::box_gap(lo, up, slo, sup); };
+        auto box = [&](const T *lo, const T *up) -> T { return trigeom::box_gap(lo, up, slo, sup); };
         // only a leaf that passes gathers its triangle (36 / 72 bytes); false: it names none
         auto gather = [&](const char *rec, I &index, raytri::Tri<T> &K) -> bool {
             const bool named = pointwalk::leaf_triangle(rec, lay, tris, num_triangles, index, K.v);
             bad |= !named;
             return named;
         };
-        auto visit = [&](const char *rec) {
-            I index;
-            raytri::Tri<T> K; // p1 p2 p3
-            if (!gather(rec, index, K)) return;
-            segtri::Pair<T> r;
-            segtri::evaluate(a, b, slo, sup, K, r);
-            // (d2, index) lexicographically; the first one only has to be within the limit it starts from (best_index == 0)
-            if ((r.d2 < best.d2) | ((r.d2 == best.d2) & ((best_index == 0) | (index < best_index)))) {
-                best = r;
-                best_index = index;
-            }
-        };
+        auto pair = [&](const raytri::Tri<T> &K, trigeom::Pair<T> &r) { segtri::evaluate(a, b, slo, sup, K, r); };
         // a NaN in the segment or in the radius has no answer, and a NaN could not prune
-        if (!pointwalk::hopeless(a, max_d2) && !pointwalk::hopeless(b, max_d2)) {
-            // A first limit, so that an unbounded query does not start blind: the squared distance from the end a to the closest
-            // triangle F the query may answer with, by ibvh_closest.hip's walk (a fifth of a pair per visit).  That value IS
-            // candidate 0 of the pair (S, F), bit for bit, so that pair's d2 cannot exceed it and the answer's neither: nothing
-            // beyond it can win or tie, and F itself is still reached (its bounds do not exceed its d2).
-            T seed = max_d2;
-            auto near_a = [&](const char *rec) {
-                I index;
-                raytri::Tri<T> K;
-                T x[3];
-                int region;
-                if (!gather(rec, index, K)) return;
-                const T d2 = pointtri::closest_on_triangle(K.v, a, x, region);
-                seed = d2 < seed ? d2 : seed;
-            };
-            auto box_a = [&](const T *lo, const T *up) { return pointwalk::box_bound(lo, up, a); };
-            pointwalk::walk<BBox<T>, TN>(tree, built_level, leaves, lay, nodes, box_a, [&]() { return seed; }, near_a);
-            best.d2 = seed;
-            pointwalk::walk<BBox<T>, TN>(tree, built_level, leaves, lay, nodes, box, [&]() { return best.d2; }, visit);
-        }
-        const bool hit = best_index != 0;
-        if (out_index) out_index[item] = best_index;
-        if (out_d2) out_d2[item] = hit ? best.d2 : std::numeric_limits<T>::infinity();
-#pragma unroll
-        for (int k = 0; k < 3; ++k) {
-            if (out_xs) out_xs[3 * item + k] = hit ? best.xs[k] : T(0);
-            if (out_xk) out_xk[3 * item + k] = hit ? best.xk[k] : T(0);
-        }
-        if (out_kind) out_kind[item] = hit ? (uint8_t)best.kind : (uint8_t)0;
+        const bool nan = pointwalk::hopeless(a, max_d2) || pointwalk::hopeless(b, max_d2);
+        trigeom::Pair<T> best;
+        const I best_index = pairwalk::closest_pair<I>(tree, built_level, leaves, lay, nodes, nan, a, max_d2, box, gather, pair, best);
+        pairwalk::store_pair(item, best_index, best, out_index, out_d2, out_xs, out_xk, out_kind);
     }
     if (bad && flag) raise_flag(flag, 2u);
 }

@@ -105,7 +105,7 @@ ibvh_status ibvh_sphere_contacts(const ibvh_bvh *bvh, const void *triangles, int
         IBVH_LAUNCH_CHECK();
         return IBVH_OK;
     };
-    return (ibvh_status)pointwalk::dispatch_box_types_and_pass(bvh->types, mode == IBVH_SPHERES_WRITE, launch);
+    return (ibvh_status)pointwalk::dispatch_box_types_and_bool(bvh->types, mode == IBVH_SPHERES_WRITE, launch);
 }
 
 } // extern "C"

@@ -24,7 +24,6 @@
 #include "ibvh_slab.hpp"
 
 #include <limits>
-#include <type_traits>
 
 namespace ibvh {
 namespace sweep {
@@ -150,8 +149,7 @@ __global__ __launch_bounds__(pointwalk::kBlock) void sweep_walk_kernel(
                 const T ts = entry > k.t ? entry : k.t; // t*: the clamp (+Inf: no candidate, or the grown box refused)
                 if constexpr (ANY) {
                     touched |= ts <= L;
-                } else if ((ts < best) | ((ts == best) & ((best_index == 0) | (index < best_index)))) {
-                    // (t*, index) lexicographically; the first one only has to be within the limit (best == L)
+                } else if (pointwalk::wins(ts, index, best, best_index)) { // (t*, index) lexicographically; best starts at L
                     best = ts;
                     best_index = index;
                     best_feature = k.feature;
@@ -220,11 +218,7 @@ ibvh_status ibvh_sweep_spheres(const ibvh_bvh *bvh, const void *triangles, int64
         IBVH_LAUNCH_CHECK();
         return IBVH_OK;
     };
-    // the mode is a template parameter: the any kernel carries no best hit
-    auto modes = [&](auto ft, auto nt, auto it) -> int {
-        return any ? launch(ft, nt, it, std::true_type{}) : launch(ft, nt, it, std::false_type{});
-    };
-    return (ibvh_status)pointwalk::dispatch_box_types(bvh->types, modes);
+    return (ibvh_status)pointwalk::dispatch_box_types_and_bool(bvh->types, any, launch);
 }
 
 } // extern "C"

@@ -12,20 +12,19 @@
 // depth-first walk from left to right, whose leaf visits come in ascending leaf position whatever a visit does, so the
 // counting pass and the writing pass see the same contacts in the same order.
 //
-// The walk itself is ibvh_pointwalk.hpp's, the gather its leaf_triangle, the edge test ibvh_raytest.hpp's ray_triangle — the
-// copy ibvh_raytri.hip and ibvh_cast.hip answer with; the rows of the two passes and the entry point's two-pass rule are
+// The walk itself is ibvh_pointwalk.hpp's, the gather its leaf_triangle; Q's box, "apart", the shared-vertex skip and the
+// edge test (segment_cuts, on ibvh_raytest.hpp's ray_triangle — the copy ibvh_raytri.hip and ibvh_cast.hip answer with) are
+// ibvh_trigeom.hpp's, shared with ibvh_tridist.hip; the rows of the two passes and the entry point's two-pass rule are
 // ibvh_pointwalk.hpp's too, shared with ibvh_spheres.hip.  Q, its box and the running row live in registers, the six tests
 // name their vertices statically; a contact goes straight from registers to its row.
 #include "ibvh_pointwalk.hpp"
 #include "ibvh_raytest.hpp"
+#include "ibvh_trigeom.hpp"
 
 namespace ibvh {
 namespace tritri {
 
 using pointwalk::kBlock;
-
-// equal vertices: == on all three coordinates (false on NaN)
-template <class T> IBVH_D bool same_vertex(const T *x, const T *y) { return (x[0] == y[0]) & (x[1] == y[1]) & (x[2] == y[2]); }
 
 // T: the leaves', triangles' and queries' float type; TN: the nodes' (the same or wider — a node box then holds values of T,
 // widened exactly, and narrows back exactly); WRITE: the second pass, which puts contact j of query i in row offsets[i] + j;
@@ -39,30 +38,19 @@ __global__ __launch_bounds__(pointwalk::kBlock) void tritri_walk_kernel(
     bool bad = false, over = false;
     for (int64_t item = (int64_t)blockIdx.x * kBlock + threadIdx.x; item < num_queries; item += (int64_t)gridDim.x * kBlock) {
         raytri::Tri<T> Q; // a b c
-#pragma unroll
-        for (int k = 0; k < 9; ++k) Q.v[k] = queries[9 * item + k];
-        // Q's box, folded from a: exact
-        T qlo[3], qup[3];
         bool nan = false;
 #pragma unroll
-        for (int k = 0; k < 3; ++k) {
-            T lo = Q.v[k], up = Q.v[k];
-            lo = Q.v[3 + k] < lo ? Q.v[3 + k] : lo;
-            up = Q.v[3 + k] > up ? Q.v[3 + k] : up;
-            lo = Q.v[6 + k] < lo ? Q.v[6 + k] : lo;
-            up = Q.v[6 + k] > up ? Q.v[6 + k] : up;
-            qlo[k] = lo;
-            qup[k] = up;
-            nan |= !((Q.v[k] == Q.v[k]) & (Q.v[3 + k] == Q.v[3 + k]) & (Q.v[6 + k] == Q.v[6 + k]));
+        for (int k = 0; k < 9; ++k) {
+            Q.v[k] = queries[9 * item + k];
+            nan |= !(Q.v[k] == Q.v[k]);
         }
+        T qlo[3], qup[3]; // Q's box: exact
+        trigeom::triangle_box(Q.v, qlo, qup);
         I qid = 0;
         if (query_ids) qid = query_ids[item];
         uint64_t next = pointwalk::first_row<WRITE>(offsets, item);
-        // 0 = the box may hold a contact, 1 = it is apart from Q's (six strict comparisons, false on NaN: such a box is entered)
-        auto box = [&](const T *lo, const T *up) -> T {
-            const bool apart = (qup[0] < lo[0]) | (qlo[0] > up[0]) | (qup[1] < lo[1]) | (qlo[1] > up[1]) | (qup[2] < lo[2]) | (qlo[2] > up[2]);
-            return apart ? T(1) : T(0);
-        };
+        // 0 = the box may hold a contact, 1 = it is apart from Q's (false on NaN: such a box is entered)
+        auto box = [&](const T *lo, const T *up) -> T { return trigeom::apart(qlo, qup, lo, up) ? T(1) : T(0); };
         // only a leaf whose box is not apart gathers its triangle (36 / 72 bytes)
         auto visit = [&](const char *rec) {
             I index;
@@ -72,23 +60,13 @@ __global__ __launch_bounds__(pointwalk::kBlock) void tritri_walk_kernel(
                 return;
             }
             if (query_ids && !(index > qid)) return;
-            if (skip & IBVH_TRIS_SKIP_SHARED_VERTEX) {
-                bool shared = false;
-#pragma unroll
-                for (int i = 0; i < 3; ++i)
-#pragma unroll
-                    for (int j = 0; j < 3; ++j) shared |= same_vertex(Q.v + 3 * i, K.v + 3 * j);
-                if (shared) return;
-            }
+            if ((skip & IBVH_TRIS_SKIP_SHARED_VERTEX) && trigeom::shares_vertex(Q.v, K.v)) return;
             unsigned mask = 0;
             T first[3], last[3]; // the points of the lowest and the highest set bit
-            // the segment p0 -> p1 against a triangle: the ray test with d = p1 - p0, and t <= 1
             auto seg = [&](const T *p0, const T *p1, const raytri::Tri<T> &tri, unsigned bit) {
                 if (!WRITE && mask != 0) return; // counting needs one set bit, not which: the first hit ends the six
-                const T d[3] = {p1[0] - p0[0], p1[1] - p0[1], p1[2] - p0[2]};
-                T t, u, v;
-                if (raytri::ray_triangle(tri, p0, d, t, u, v) & (t <= T(1))) {
-                    const T x[3] = {p0[0] + t * d[0], p0[1] + t * d[1], p0[2] + t * d[2]};
+                T x[3];
+                if (trigeom::segment_cuts(tri, p0, p1, x)) {
                     if (mask == 0) first[0] = x[0], first[1] = x[1], first[2] = x[2];
                     last[0] = x[0], last[1] = x[1], last[2] = x[2];
                     mask |= bit;
@@ -155,7 +133,7 @@ ibvh_status ibvh_triangle_contacts(const ibvh_bvh *bvh, const void *triangles, i
         IBVH_LAUNCH_CHECK();
         return IBVH_OK;
     };
-    return (ibvh_status)pointwalk::dispatch_box_types_and_pass(bvh->types, mode == IBVH_TRIS_WRITE, launch);
+    return (ibvh_status)pointwalk::dispatch_box_types_and_bool(bvh->types, mode == IBVH_TRIS_WRITE, launch);
 }
 
 } // extern "C"

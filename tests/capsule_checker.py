@@ -240,3 +240,24 @@ def reference(mesh, dt, n=N_CAPSULES):
     for x in (tris,) + tuple(v for bf in (contacts, distances) for v in vars(bf).values() if isinstance(v, np.ndarray)):
         x.setflags(write=False)
     return tris, a, b, radii, contacts, distances
+
+
+# ---- the hand-made inputs of the GPU tests (capsule contacts, segment distances, box contacts) -----------------------------
+CAPSULES_PER_MESH = {"torus40": N_CAPSULES, "torus64x63": 100}   # 3,200 triangles; 8,064: a leaf count that is no power of two
+nan, inf = np.nan, np.inf
+FLAT = [0, 0, 0, 1, 0, 0, 0, 1, 0]
+HAND = [FLAT,
+        [0, 0, 0.5, 1, 0, 0.5, 0, 1, 0.5],       # FLAT moved up by 0.5
+        [5, 5, 5, 6, 6, 6, 7, 7, 7],             # zero area: collinear
+        [3, 0, 0, 4, 0, 0, 3, 1, 0],
+        [0, 0, 3, 1, 0, 3, 0, 1, 3]]
+# (a, b, r): through FLAT's face; parallel above it at height r exactly and one unit below; end-on above a vertex; crossing
+# an edge at a skew; zero length, off and on the face; INSIDE FLAT's plane, over the face and beside it; a long diagonal one;
+# negative, NaN, -0.0 and infinite radii; a NaN in a and in b; an infinite end
+HAND_CAPSULES = [((0.25, 0.25, -1), (0.25, 0.25, 1), 0), ((0.25, 0.25, 0.25), (0.5, 0.25, 0.25), 0.25),
+                 ((0.25, 0.25, 0.25), (0.5, 0.25, 0.25), float(np.nextafter(np.float32(0.25), np.float32(0)))),
+                 ((0, 0, 3.5), (0, 0, 3.25), 0.25), ((0.25, -1, -1), (0.75, -1, 1), 1), ((0.25, 0.25, 0.25), (0.25, 0.25, 0.25), 0.25),
+                 ((0.25, 0.25, 0), (0.25, 0.25, 0), 0), ((0.125, 0.125, 0), (0.5, 0.25, 0), 0.125), ((1.5, 1.5, 0), (3, -1, 0), 1),
+                 ((-1, -1, -1), (7, 7, 7.5), 0.5), ((0.25, 0.25, 0.25), (0.5, 0.25, 0.25), -1), ((0.25, 0.25, 0.25), (0.5, 0.25, 0.25), nan),
+                 ((0.25, 0.25, 0), (0.5, 0.25, 0), -0.0), ((0.25, 0.25, 0.25), (0.5, 0.25, 0.25), inf), ((0.25, 0.25, -inf), (0.5, 0.25, 0.25), -inf),
+                 ((nan, 0.25, 0.25), (0.5, 0.25, 0.25), 1), ((0.25, 0.25, 0.25), (0.5, nan, 0.25), inf), ((0.25, 0.25, 0.25), (0.5, 0.25, inf), 1)]

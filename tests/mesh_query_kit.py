@@ -1,11 +1,12 @@
-"""What the tests of the six point-walk queries — closest_points, point_crossings, cast_rays, nearest_leaves, sphere_contacts,
-triangle_contacts — share: the type tables and meshes, the mesh-BVH builder and the one-kernel check of the GPU tests; the fake
-ibvh_bvh, the header / Julia matchers and the source-text facts about the shared front end (csrc/ibvh_pointwalk.hpp) of the
-host tests.  For the two list queries, sphere_contacts and triangle_contacts, also everything about their count / write
-protocol, which is one protocol: the description of a list query (ListQuery), the checkers' re-sorting into a leaf order, the
-two passes through the C entry point, the two comparators, the offsets-and-capacity scenario, the one-kernel-per-pass check
-and the entry points' common argument matrix.  Each query's checker, hand-made meshes and reference builders stay with its
-own tests.  Importing this needs no GPU."""
+"""What the tests of the twelve point-walk queries share — closest_points, nearest_leaves, point_crossings, points_inside,
+cast_rays, sweep_spheres, triangle_distances, segment_distances and the four list queries sphere_contacts, triangle_contacts,
+capsule_contacts, box_contacts —: the type tables and meshes, the mesh-BVH builder, the leaves' stored boxes and the one-kernel
+check of the GPU tests; the fake ibvh_bvh, the header / Julia matchers, the chain of boxes above a box and the source-text
+facts about the shared front end (csrc/ibvh_pointwalk.hpp) of the host tests.  For the four list queries also everything
+about their count / write protocol, which is one protocol: the description of a list query (ListQuery), the checkers'
+re-sorting into a leaf order, the two passes through the C entry point, the two comparators, the offsets-and-capacity
+scenario, the one-kernel-per-pass check and the entry points' common argument matrix.  Each query's checker, hand-made meshes
+and reference builders stay with its own tests.  Importing this needs no GPU."""
 import collections
 import ctypes as C
 import os
@@ -134,6 +135,17 @@ def assert_equal(query, got, exp, what, count_only=False):
 # ---- the list queries: GPU tests ----------------------------------------------------------------------------------------------
 def leaf_order(bvh):
     return bvh.leaves.index.cpu().numpy().astype(np.int64)
+
+
+def stored_boxes(bvh, n):
+    """(n, 6): the box stored in each triangle's leaf, by triangle — what a clause on the STORED box reads; a triangle no leaf
+    names keeps zeros, a leaf that names none is left out"""
+    vol = bvh.leaves.volume.cpu().numpy()
+    boxes = np.zeros((n, 6), vol.dtype)
+    order = leaf_order(bvh)
+    ok = (order >= 1) & (order <= n)
+    boxes[order[ok] - 1] = vol[ok]
+    return boxes
 
 
 def two_passes(query, bvh, tris, head, tail=(), num=None, num_triangles=None, flag=0, outs=None, offsets=None, capacity=None, rows=None):
@@ -290,6 +302,17 @@ def julia_ccall(name, function):
     return src
 
 
+def chain(rng, lo, up, dt, levels=5):
+    """boxes above (lo, up) as a tree builds them: each the exact minimum / maximum with another random box"""
+    out = []
+    for _ in range(levels):
+        centre, size = rng.random(lo.shape) * 4 - 2, rng.random(lo.shape) * 0.5
+        other_lo, other_up = (centre - size).astype(dt), (centre + size).astype(dt)
+        lo, up = np.where(other_lo < lo, other_lo, lo), np.where(other_up > up, other_up, up)
+        out.append((lo, up))
+    return out
+
+
 BANNED = ("hipLaunchKernelGGL", "<<<", "atomic", "hipMemcpy", "hipStreamSynchronize", "hipDeviceSynchronize", "hipEventSynchronize",
           "__shared__", "hipMalloc")
 # what only the shared front end spells: the rules, the layout, the grid and the triangle gather
@@ -308,15 +331,45 @@ PROTOCOL = ("std::true_type{}", "std::false_type{}", "row < (uint64_t)capacity",
 # ... and the unit's use of it, once each
 PROTOCOL_USES = ("pointwalk::first_row<WRITE>(offsets, item)", "pointwalk::contact<WRITE>(next, capacity, over, [&](uint64_t row) {",
                  "pointwalk::store_count<WRITE>(counts, item, next)", "pointwalk::passes_ok(mode, counts, offsets, ",
-                 "pointwalk::dispatch_box_types_and_pass(bvh->types, mode == ", "raise_flag(flag, 4u)")
+                 "pointwalk::dispatch_box_types_and_bool(bvh->types, mode == ", "raise_flag(flag, 4u)")
 
 
-def query_unit(unit, kernel, walks=1, mesh=True, own_gather=False, lists=False):
-    """The source-text facts about a query's translation unit and the header it shares with the other five -> the unit's
+def pair_routine(src):
+    """The unit `src` answers with the closest pair through csrc/ibvh_pairwalk.hpp, once: the routine walks twice — first from
+    the seed point on the shared point-box bound, which seeds the limit of the second —, applies the shared tie rule once and
+    stores the five outputs; its comment states what the loss-free seed asks of the caller -> the header's text"""
+    pw = read("implicitbvh.jl_amd", "csrc", "ibvh_pairwalk.hpp")
+    assert re.search(r'^#include "ibvh_pairwalk.hpp"$', src, flags=re.M)
+    assert src.count("pairwalk::closest_pair<I>(tree, built_level, leaves, lay, nodes, nan, ") == src.count("pairwalk::closest_pair") == 1
+    assert src.count("max_d2, box, gather, pair, best);") == 1
+    assert src.count("pairwalk::store_pair(item, best_index, best, out_index, out_d2, ") == src.count("pairwalk::store_pair") == 1
+    for text in ("seed", "best.d2", "closest_on_triangle(K.v", "box_bound", "wins(", "infinity()", "hit ?"):
+        assert text not in src, text
+    assert pw.count("pointwalk::walk<") == 2 and pw.count("pointwalk::wins(r.d2, index, best.d2, best_index)") == 1
+    assert pw.count("pointwalk::box_bound(lo, up, seed_point)") == 1 and pw.count("pointtri::closest_on_triangle(K.v, seed_point, x, region)") == 1
+    assert pw.index("[&]() { return seed; }") < pw.index("best.d2 = seed;") < pw.index("[&]() { return best.d2; }")
+    assert pw.count("seed = d2 < seed ? d2 : seed;") == 1 and pw.count("best.put(max_d2, zero, zero, 0);") == 1
+    assert pw.count("if (hopeless) return best_index;") == 1 and pw.index("if (hopeless)") < pw.index("pointwalk::walk<")
+    for line in ("if (out_index) out_index[item] = best_index;", "if (out_d2) out_d2[item] = hit ? best.d2 : std::numeric_limits<T>::infinity();",
+                 "if (out_xq) out_xq[3 * item + k] = hit ? best.xq[k] : T(0);", "if (out_xk) out_xk[3 * item + k] = hit ? best.xk[k] : T(0);",
+                 "if (out_kind) out_kind[item] = hit ? (uint8_t)best.kind : (uint8_t)0;", "const bool hit = best_index != 0;"):
+        assert pw.count(line) == 1, line
+    flat = " ".join(pw.replace("//", " ").split())
+    for phrase in ("THE CALLER'S OBLIGATION: seed_point is the first point candidate 0 of evaluate() is evaluated from",
+                   "IS candidate 0 of the pair (item, F), bit for bit", "nothing beyond it can win or tie", "F itself is still reached"):
+        assert phrase in flat, phrase
+    for banned in BANNED + ("fma", "__shared__"):
+        assert banned not in pw, banned
+    return pw
+
+
+def query_unit(unit, kernel, walks=1, mesh=True, own_gather=False, lists=False, any_mode=False, pair=False):
+    """The source-text facts about a query's translation unit and the header it shares with the other ten -> the unit's
     text.  The Makefile builds it; its ONE launch — of `kernel`, on the shared grid and block size — goes through the profiling
     wrapper and is checked; it calls the shared walk (`walks` times), the shared prologue once and, a mesh query, the shared
     gather (own_gather: spells its statements out once, with the reason), dispatch and raise_flag; it spells none of BANNED and
-    none of FRONT_END itself.  A list query (lists) dispatches on the pass too and uses each piece of the shared count / write
+    none of FRONT_END itself.  A query with an any-hit mode (any_mode) dispatches on it through the shared four-tag dispatch.  A
+    list query (lists) dispatches on the pass through the same and uses each piece of the shared count / write
     protocol once, which the header defines once and the unit does not spell.  The header defines each shared piece once, refuses in the documented order and dispatches three
     (T, TN) pairs per index type."""
     mk = read("implicitbvh.jl_amd", "csrc", "Makefile")
@@ -329,7 +382,9 @@ def query_unit(unit, kernel, walks=1, mesh=True, own_gather=False, lists=False):
     for text in (src, header):
         for banned in BANNED:
             assert banned not in text, banned
-    assert re.search(r'^#include "ibvh_pointwalk.hpp"$', src, flags=re.M) and src.count("pointwalk::walk<") == walks
+    assert re.search(r'^#include "ibvh_pointwalk.hpp"$', src, flags=re.M) and src.count("pointwalk::walk<") == (0 if pair else walks)
+    if pair:  # a closest-pair query: its two walks, its tie rule and its five stores are the shared lane routine's
+        assert walks == 2 and pair_routine(src)
     assert "__builtin_clzll" not in src and "void raise_flag(" not in src
     assert src.count("pointwalk::prepare(bvh, " + ("true" if mesh else "false") + ", ") == src.count("pointwalk::prepare(") == 1
     for piece in FRONT_END[:-1]:
@@ -339,8 +394,13 @@ def query_unit(unit, kernel, walks=1, mesh=True, own_gather=False, lists=False):
         why = src[src.index("only a leaf that passes gathers its triangle"):src.index("__builtin_memcpy")]
         assert "statements of pointwalk::leaf_triangle" in why and "(DESIGN.md)" in why
         assert "index >= 1 && (int64_t)index <= num_triangles" in why and "index >= 1 && (int64_t)index <= num_triangles" in header
-    assert src.count("pointwalk::dispatch_box_types(") + src.count("pointwalk::dispatch_box_types_and_pass(") == src.count("raise_flag(flag, 2u)") == int(mesh)
-    assert src.count("pointwalk::dispatch_box_types_and_pass(") == int(lists)
+    assert src.count("pointwalk::dispatch_box_types(") + src.count("pointwalk::dispatch_box_types_and_bool(") == src.count("raise_flag(flag, 2u)") == int(mesh)
+    # a bool as a fourth tag: a list query's pass, the any-hit mode (any_mode) of the ray cast and the sweep; only the header
+    # turns the bool into the two types
+    assert src.count("pointwalk::dispatch_box_types_and_bool(") == int(lists or any_mode) and not (lists and any_mode)
+    assert src.count("pointwalk::dispatch_box_types_and_bool(bvh->types, any, launch)") == int(any_mode)
+    for text in PROTOCOL[:2]:
+        assert text not in src and header.count(text) == 1, text
     if lists:
         for use in PROTOCOL_USES:
             assert src.count(use) == 1, use
@@ -354,7 +414,7 @@ def query_unit(unit, kernel, walks=1, mesh=True, own_gather=False, lists=False):
                    r"inline ibvh_status prepare\(", r"IBVH_D bool leaf_triangle\(", r"IBVH_D bool hopeless\(",
                    r"int dispatch_box_types\(", r"T radius_or_inf\(", r"__builtin_memcpy\(", r"IBVH_D uint64_t first_row\(",
                    r"IBVH_D void contact\(", r"IBVH_D void store_count\(", r"inline bool passes_ok\(",
-                   r"int dispatch_box_types_and_pass\(", r"static_assert\(IBVH_SPHERES_COUNT == 0 && IBVH_SPHERES_WRITE == 1 && IBVH_TRIS_COUNT == 0 && IBVH_TRIS_WRITE == 1,"):
+                   r"int dispatch_box_types_and_bool\(", r"IBVH_D bool wins\(", r"static_assert\(IBVH_SPHERES_COUNT == 0 && IBVH_SPHERES_WRITE == 1 && IBVH_TRIS_COUNT == 0 && IBVH_TRIS_WRITE == 1,"):
         assert len(re.findall(define, header)) == 1, define
     prepare = _body(header, "inline ibvh_status prepare(")
     for call in FRONT_END[:-1]:

@@ -18,9 +18,9 @@ import implicitbvh_amd as ibvh  # noqa: E402
 from implicitbvh_amd import abi, api, lib  # noqa: E402
 
 import box_contacts_checker as bc  # noqa: E402
+from capsule_checker import HAND  # noqa: E402
 import mesh_query_kit as kit  # noqa: E402
-from mesh_query_kit import FLOATS, NP_F, NP_I, build as _build, leaf_order as _leaf_order, tf as _tf  # noqa: E402
-from test_gpu_capsule_contacts import HAND, _stored_boxes  # noqa: E402
+from mesh_query_kit import FLOATS, NP_F, NP_I, build as _build, leaf_order as _leaf_order, stored_boxes as _stored_boxes, tf as _tf  # noqa: E402
 from test_gpu_parity import cuda  # noqa: E402
 
 NAME = "ibvh_box_contacts"

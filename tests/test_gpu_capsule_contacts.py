@@ -17,13 +17,13 @@ import implicitbvh_amd as ibvh  # noqa: E402
 from implicitbvh_amd import abi, api, lib  # noqa: E402
 
 import capsule_checker as cc  # noqa: E402
+from capsule_checker import CAPSULES_PER_MESH as CAPSULES, HAND, HAND_CAPSULES  # noqa: E402
 import mesh_query_kit as kit  # noqa: E402
-from mesh_query_kit import FLOATS, NP_F, NP_I, build as _build, leaf_order as _leaf_order, tf as _tf  # noqa: E402
+from mesh_query_kit import FLOATS, NP_F, NP_I, build as _build, leaf_order as _leaf_order, stored_boxes as _stored_boxes, tf as _tf  # noqa: E402
 from sphere_contacts_checker import mean_edge  # noqa: E402
 from test_gpu_parity import cuda  # noqa: E402
 
 NAME = "ibvh_capsule_contacts"
-CAPSULES = {"torus40": cc.N_CAPSULES, "torus64x63": 100}   # 3,200 triangles; 8,064: a leaf count that is no power of two
 _assert_equal = functools.partial(kit.assert_equal, cc.QUERY)
 _same = functools.partial(kit.same, cc.QUERY)
 SENTINEL = {k: col.sentinel for k, col in cc.QUERY.columns.items()}
@@ -37,13 +37,6 @@ def _reference(mesh, flt):
 def _call(bvh, tris, a, b, r, **kw):
     """count, scan on the host, write -> dict: counts, the outputs, both flag words and both statuses (kit.two_passes)"""
     return kit.two_passes(cc.QUERY, bvh, tris, (a, b, r), **kw)
-
-
-def _stored_boxes(bvh, n):
-    """(n, 6): the box stored in each triangle's leaf, by triangle — what the slab clause reads"""
-    boxes = np.empty((n, 6), NP_F[bvh.types.leaf_float])
-    boxes[_leaf_order(bvh) - 1] = bvh.leaves.volume.cpu().numpy()[:n]
-    return boxes
 
 
 # ---- 1. brute force, whole pipeline ------------------------------------------------------------------------------------
@@ -86,25 +79,6 @@ def test_one_radius_for_all():
 
 
 # ---- 2. hand-made, straight through the C entry ------------------------------------------------------------------------
-nan, inf = np.nan, np.inf
-FLAT = [0, 0, 0, 1, 0, 0, 0, 1, 0]
-HAND = [FLAT,
-        [0, 0, 0.5, 1, 0, 0.5, 0, 1, 0.5],       # FLAT moved up by 0.5
-        [5, 5, 5, 6, 6, 6, 7, 7, 7],             # zero area: collinear
-        [3, 0, 0, 4, 0, 0, 3, 1, 0],
-        [0, 0, 3, 1, 0, 3, 0, 1, 3]]
-# (a, b, r): through FLAT's face; parallel above it at height r exactly and one unit below; end-on above a vertex; crossing
-# an edge at a skew; zero length, off and on the face; INSIDE FLAT's plane, over the face and beside it; a long diagonal one;
-# negative, NaN, -0.0 and infinite radii; a NaN in a and in b; an infinite end
-HAND_CAPSULES = [((0.25, 0.25, -1), (0.25, 0.25, 1), 0), ((0.25, 0.25, 0.25), (0.5, 0.25, 0.25), 0.25),
-                 ((0.25, 0.25, 0.25), (0.5, 0.25, 0.25), float(np.nextafter(np.float32(0.25), np.float32(0)))),
-                 ((0, 0, 3.5), (0, 0, 3.25), 0.25), ((0.25, -1, -1), (0.75, -1, 1), 1), ((0.25, 0.25, 0.25), (0.25, 0.25, 0.25), 0.25),
-                 ((0.25, 0.25, 0), (0.25, 0.25, 0), 0), ((0.125, 0.125, 0), (0.5, 0.25, 0), 0.125), ((1.5, 1.5, 0), (3, -1, 0), 1),
-                 ((-1, -1, -1), (7, 7, 7.5), 0.5), ((0.25, 0.25, 0.25), (0.5, 0.25, 0.25), -1), ((0.25, 0.25, 0.25), (0.5, 0.25, 0.25), nan),
-                 ((0.25, 0.25, 0), (0.5, 0.25, 0), -0.0), ((0.25, 0.25, 0.25), (0.5, 0.25, 0.25), inf), ((0.25, 0.25, -inf), (0.5, 0.25, 0.25), -inf),
-                 ((nan, 0.25, 0.25), (0.5, 0.25, 0.25), 1), ((0.25, 0.25, 0.25), (0.5, nan, 0.25), inf), ((0.25, 0.25, 0.25), (0.5, 0.25, inf), 1)]
-
-
 def _hand(n, dt):
     a, b, r = (np.array([c[j] for c in HAND_CAPSULES], dt) for j in range(3))
     return np.array(HAND[:n], dt), a, b, r

@@ -15,8 +15,8 @@ import implicitbvh_amd as ibvh  # noqa: E402
 from implicitbvh_amd import abi, api, lib  # noqa: E402
 
 import capsule_checker as cc  # noqa: E402
+from capsule_checker import CAPSULES_PER_MESH as CAPSULES, HAND, HAND_CAPSULES  # noqa: E402
 from mesh_query_kit import FLOATS, NP_F, assert_one_kernel, bits, build as _build, tf as _tf  # noqa: E402
-from test_gpu_capsule_contacts import CAPSULES, HAND, HAND_CAPSULES  # noqa: E402
 from test_gpu_parity import cuda  # noqa: E402
 
 NAME = "ibvh_segment_distances"

@@ -22,7 +22,7 @@ from implicitbvh_amd.synthetic import torus_mesh  # noqa: E402
 import mesh_query_kit as kit  # noqa: E402
 import triangle_contacts_checker as tcc  # noqa: E402
 from mesh_query_kit import (FLOATS, MESHES, NP_F, NP_I, assert_one_kernel, bits as _bits, build as _build, leaf_order as _leaf_order,  # noqa: E402
-                            tf as _tf)
+                            stored_boxes as _stored_boxes, tf as _tf)
 from test_gpu_parity import cuda  # noqa: E402
 
 NAME = "ibvh_triangle_contacts"
@@ -51,16 +51,6 @@ def _two_tori():
     for a in (both, once.index, once.mask, once.points, once.query, twice.index, twice.mask, twice.points, twice.query):
         a.setflags(write=False)
     return both, once, twice
-
-
-def _stored_boxes(bvh, n):
-    """the boxes stored in the leaves, by triangle (n, 6)"""
-    vol = bvh.leaves.volume.cpu().numpy()
-    boxes = np.zeros((n, 6), vol.dtype)
-    order = _leaf_order(bvh)
-    ok = (order >= 1) & (order <= n)
-    boxes[order[ok] - 1] = vol[ok]
-    return boxes
 
 
 _assert_equal = functools.partial(kit.assert_equal, tcc.QUERY)

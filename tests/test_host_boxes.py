@@ -19,7 +19,6 @@ from implicitbvh_amd import abi, lib
 
 import box_contacts_checker as bc
 import mesh_query_kit as kit
-from test_host_capsules import chain
 from triangle_distance_checker import boxes_apart
 
 NAME = "ibvh_box_contacts"
@@ -75,7 +74,10 @@ def test_binding_tables_makefile_launch_and_python_surface():
     src = kit.query_unit(UNIT, "boxes::boxes_walk_kernel", lists=True)
     assert len(re.findall(r"__global__", src)) == 1 and "template <class T, class TN, class I, bool WRITE>\n__global__" in src
     assert "fma" not in src and "1e-" not in src and "[]() { return T(0); }" in src and "mode == IBVH_BOXES_WRITE" in src
-    for line in ("const bool apart = (qup[0] < lo[0]) | (qlo[0] > up[0]) | (qup[1] < lo[1]) | (qlo[1] > up[1]) | (qup[2] < lo[2]) | (qlo[2] > up[2]);",
+    geom = kit.read("implicitbvh.jl_amd", "csrc", "ibvh_trigeom.hpp")
+    assert geom.count("return (qup[0] < lo[0]) | (qlo[0] > up[0]) | (qup[1] < lo[1]) | (qlo[1] > up[1]) | (qup[2] < lo[2]) | (qlo[2] > up[2]);") == 1
+    assert "qup[0] < lo[0]" not in src and re.search(r'^#include "ibvh_trigeom.hpp"$', src, flags=re.M)
+    for line in ("return trigeom::apart(qlo, qup, lo, up) ? T(1) : T(0);",
                  "tribox::hull(q, qlo, qup);", "tribox::to_local(q, K + 3 * i, v + 3 * i);", "if (tribox::overlaps(q.h, v)) {",
                  "tribox::inside_mask(q.h, v)", "finite = finite + (q.c[k] - q.c[k]);", "finite = finite + (q.u[k] - q.u[k]);",
                  "if (rotations) q.u[k] = rotations[9 * item + k];", "!pointwalk::hopeless(q.c, finite)",
@@ -274,7 +276,7 @@ def test_being_apart_from_the_hull_is_monotone_up_a_chain_of_boxes(dt):
     qlo, qup = bc.hull(c[pick], h[pick], R[pick])
     klo, kup = bc.tcc.fold_box(tris)
     skin = (klo - dt(1e-3), kup + dt(1e-3))
-    levels = [(klo, kup), skin] + chain(rng, klo, kup, dt)
+    levels = [(klo, kup), skin] + kit.chain(rng, klo, kup, dt)
     apart = [boxes_apart(qlo[:, None], qup[:, None], lo[None], up[None]) for lo, up in levels]
     for lo, up in levels:
         assert (lo <= klo).all() and (up >= kup).all()

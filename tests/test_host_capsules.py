@@ -78,16 +78,19 @@ def test_binding_tables_makefile_launches_and_python_surface():
     assert len(re.findall(r"__global__", src)) == 1 and "template <class T, class TN, class I, bool WRITE>\n__global__" in src
     assert "fma" not in src and "[]() { return T(0); }" in src and "mode == IBVH_CAPSULES_WRITE" in src
     for line in ("const T glo[3] = {lo[0] - r, lo[1] - r, lo[2] - r}, gup[3] = {up[0] + r, up[1] + r, up[2] + r};",
-                 "segtri::box_gap(lo, up, slo, sup)", "slab::slab_entry(glo, gup, a, d, inv)", "(gap > r2) | (entry > T(1))",
+                 "trigeom::box_gap(lo, up, slo, sup)", "slab::slab_entry(glo, gup, a, d, inv)", "(gap > r2) | (entry > T(1))",
                  "if (p.d2 <= r2) {", "const T inv[3] = {T(1) / d[0], T(1) / d[1], T(1) / d[2]};",
                  "(r >= T(0)) && !pointwalk::hopeless(a, r2) && !pointwalk::hopeless(b, r2)"):
         assert line in src, line
     # the distances: two walks, the first from the end a on the shared point-box bound, which seeds the limit of the second
-    src = kit.query_unit(UNITS[DISTANCES], "segdist::segdist_walk_kernel", walks=2)
+    src = kit.query_unit(UNITS[DISTANCES], "segdist::segdist_walk_kernel", walks=2, pair=True)
     assert len(re.findall(r"__global__", src)) == 1 and "template <class T, class TN, class I>\n__global__" in src
     assert "fma" not in src and "slab" not in src.replace("no slab", "")
-    assert src.count("pointwalk::box_bound(lo, up, a)") == 1 and src.count("pointtri::closest_on_triangle(K.v, a, x, region)") == 1
-    assert src.index("[&]() { return seed; }") < src.index("best.d2 = seed;") < src.index("[&]() { return best.d2; }")
+    # (the shared lane routine, kit.pair_routine: checked by query_unit) from the end a — the point candidate 0 is evaluated from
+    assert src.count("nodes, nan, a, max_d2, box, gather, pair, best);") == 1 and src.count("trigeom::box_gap(lo, up, slo, sup)") == 1
+    assert src.count("const bool nan = pointwalk::hopeless(a, max_d2) || pointwalk::hopeless(b, max_d2);") == 1
+    seg = kit.read("implicitbvh.jl_amd", "csrc", "ibvh_segtri.hpp")
+    assert seg.index("if (c == 0) r.put(d2, p, x, 0);") < seg.index("else r.offer(d2, p, x, 1);") and "sel(c == 0, a[0], b[0])" in seg
     header = kit.read("implicitbvh.jl_amd", "csrc", "ibvh_pointwalk.hpp")
     assert len(re.findall(r"static_assert\(IBVH_CAPSULES_COUNT == 0 && IBVH_CAPSULES_WRITE == 1,", header)) == 1
     assert "ibvh_capsules.hip" in header[:header.index("#pragma once")] and "ibvh_segdist.hip" in header[:header.index("#pragma once")]
@@ -99,22 +102,28 @@ def test_the_segment_triangle_evaluation_exists_once_and_both_units_include_it()
     text = {f: kit.read("implicitbvh.jl_amd", "csrc", f) for f in sources}
     assert [f for f in sources if "namespace segtri" in text[f]] == ["ibvh_segtri.hpp"]
     seg = text["ibvh_segtri.hpp"]
-    assert len(re.findall(r"IBVH_D void evaluate\(", seg)) == 1 and len(re.findall(r"IBVH_D T box_gap\(", seg)) == 1
+    geom = text["ibvh_trigeom.hpp"]
+    assert len(re.findall(r"IBVH_D void evaluate\(", seg)) == 1 and len(re.findall(r"IBVH_D T box_gap\(", geom)) == 1 and "box_gap" not in seg
     for unit in UNITS.values():
         assert re.search(r'^#include "ibvh_segtri.hpp"$', text[unit], flags=re.M), unit
         assert text[unit].count("segtri::evaluate(a, b, slo, sup, K, ") == 1 and text[unit].count("segtri::segment_box(a, b, slo, sup)") == 1
         assert "closest_on_segments" not in text[unit] and "ray_triangle" not in text[unit]
     # it is built from the one copy of each piece, the cut rule under the box clause first, the candidates rolled
-    for home in ("ibvh_pointtri.hpp", "ibvh_raytest.hpp", "ibvh_segseg.hpp"):
+    for home in ("ibvh_pointtri.hpp", "ibvh_raytest.hpp", "ibvh_segseg.hpp", "ibvh_trigeom.hpp"):
         assert re.search(r'^#include "' + home + '"$', seg, flags=re.M), home
-    assert seg.count("pointtri::closest_on_triangle(") == seg.count("segseg::closest_on_segments(") == seg.count("raytri::ray_triangle(") == 1
-    assert seg.index("if (!apart) {") < seg.index("raytri::ray_triangle(K, a, d, t, u, v) & (t <= T(1))") < seg.index("pointtri::closest_on_triangle(")
+    assert seg.count("pointtri::closest_on_triangle(") == seg.count("segseg::closest_on_segments(") == seg.count("trigeom::segment_cuts(K, a, b, ") == 1
+    assert "ray_triangle(" not in seg and geom.count("raytri::ray_triangle(tri, p0, d, t, u, v) & (t <= T(1))") == 1
+    assert seg.index("const bool apart = trigeom::apart(slo, sup, klo, kup);") < seg.index("if (!apart) {") < seg.index("trigeom::segment_cuts(")
+    assert seg.index("trigeom::segment_cuts(") < seg.index("pointtri::closest_on_triangle(")
     assert seg.index("pointtri::closest_on_triangle(") < seg.index("segseg::closest_on_segments(a, b, p2, q2, x, y)")
     assert seg.count("#pragma unroll 1") == 2 and "fma" not in seg and "1e-" not in seg
-    for line in ("lo[k] = a[k] < b[k] ? a[k] : b[k];", "up[k] = a[k] > b[k] ? a[k] : b[k];", "if (d < d2) put(d, s, k, c);",
-                 "const T below = lo[k] - sup[k], above = slo[k] - up[k];", "const T m = below > above ? below : above;",
-                 "g[k] = m > T(0) ? m : T(0);", "return (g[0] * g[0] + g[1] * g[1]) + g[2] * g[2];", "constexpr int kCut = 5;"):
+    for line in ("lo[k] = a[k] < b[k] ? a[k] : b[k];", "up[k] = a[k] > b[k] ? a[k] : b[k];", "constexpr int kCut = 5;",
+                 "trigeom::edge_of(K.v, c, p2, q2);"):
         assert line in seg, line
+    # ... the pair and the gap, with the query's box where S's stood: the one copy, ibvh_trigeom.hpp's
+    for line in ("if (d < d2) put(d, q, k, c);", "const T below = lo[k] - qup[k], above = qlo[k] - up[k];", "const T m = below > above ? below : above;",
+                 "g[k] = m > T(0) ? m : T(0);", "return (g[0] * g[0] + g[1] * g[1]) + g[2] * g[2];"):
+        assert geom.count(line) == 1 and line not in seg, line
     assert "NOT reported" in seg and "does not classify" in seg
     import __graft_entry__ as entry
     assert {os.path.join(csrc, f) for f in ("ibvh_segtri.hpp",) + tuple(UNITS.values())} <= set(entry.kernel_sources(kit.ROOT))
@@ -308,17 +317,6 @@ def test_float32_agrees_with_the_same_evaluation_in_float64():
 
 
 # ---- what makes pruning lossless -------------------------------------------------------------------------------------------
-def chain(rng, lo, up, dt, levels=5):
-    """boxes above (lo, up) as a tree builds them: each the exact minimum / maximum with another random box"""
-    out = []
-    for _ in range(levels):
-        centre, size = rng.random(lo.shape) * 4 - 2, rng.random(lo.shape) * 0.5
-        other_lo, other_up = (centre - size).astype(dt), (centre + size).astype(dt)
-        lo, up = np.where(other_lo < lo, other_lo, lo), np.where(other_up > up, other_up, up)
-        out.append((lo, up))
-    return out
-
-
 @pytest.mark.parametrize("dt", DTYPES, ids=IDS)
 def test_the_gap_of_a_box_never_exceeds_a_distance_under_it_and_the_slab_clause_is_monotone(dt):
     rng = np.random.default_rng(71)
@@ -329,7 +327,7 @@ def test_the_gap_of_a_box_never_exceeds_a_distance_under_it_and_the_slab_clause_
     slo, sup = cc.segment_box(A, B)
     klo, kup = cc.triangle_box(tris)
     skin = (klo - dt(1e-3), kup + dt(1e-3))
-    boxes = [(klo, kup), skin] + chain(rng, klo, kup, dt)
+    boxes = [(klo, kup), skin] + kit.chain(rng, klo, kup, dt)
     entries = []
     for lo, up in boxes:
         assert (lo <= klo).all() and (up >= kup).all()

@@ -45,6 +45,7 @@ def test_binding_table_makefile_launch_and_python_surface():
         assert name in ibvh.__all__ and callable(getattr(ibvh, name))
     src = kit.query_unit("ibvh_closest.hip", "closest::closest_walk_kernel")
     assert "pointwalk::hopeless(p, max_d2)" in src and "pointwalk::radius_or_inf<T>(max_distance2)" in src
+    assert src.count("if (pointwalk::wins(d2, index, best, best_index)) {") == 1 and "best_index == 0" not in src   # the shared tie rule
     # raise_flag is shared with the ray resolve, defined once
     assert "void raise_flag(" in kit.read("implicitbvh.jl_amd", "csrc", "ibvh_common.hpp")
     assert "void raise_flag(" not in kit.read("implicitbvh.jl_amd", "csrc", "ibvh_raytri.hip")

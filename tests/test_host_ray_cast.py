@@ -57,7 +57,7 @@ def test_binding_table_makefile_launch_and_python_surface():
     for name in ("cast_rays", "RayCast"):
         assert name in ibvh.__all__ and callable(getattr(ibvh, name))
     # the walk (one call per mode), its block size and grid, the prologue, the gather and the flag are the shared ones
-    src = kit.query_unit("ibvh_cast.hip", "cast::cast_walk_kernel", walks=2)
+    src = kit.query_unit("ibvh_cast.hip", "cast::cast_walk_kernel", walks=2, any_mode=True)
     assert "box_bound" not in src
     # the exact test is the shared one: defined once, in the header both translation units include
     shared = kit.read("implicitbvh.jl_amd", "csrc", "ibvh_raytest.hpp")
@@ -67,9 +67,14 @@ def test_binding_table_makefile_launch_and_python_surface():
     for unit in (src, resolve):
         assert re.search(r'^#include "ibvh_raytest.hpp"$', unit, flags=re.M) and "ray_triangle(tr, p, d, t, u, v)" in unit
         assert "void cross3(" not in unit and "1) / det" not in unit
-    # three (T, TN) instantiations times two index types — the shared dispatch — times the two modes
-    assert "pointwalk::dispatch_box_types(bvh->types, modes)" in src and "template <class T, class TN, class I, bool ANY>" in src
-    assert "any ? launch(ft, nt, it, std::true_type{}) : launch(ft, nt, it, std::false_type{})" in src
+    # three (T, TN) instantiations times two index types times the two modes: the shared four-tag dispatch (query_unit), whose
+    # bool the launch turns into the kernel's template parameter; the tie rule is the shared one
+    assert "template <class T, class TN, class I, bool ANY>" in src and "constexpr bool ANY = decltype(mt)::value;" in src
+    assert "const bool any = mode == " in src and "modes" not in src and "type_traits" not in src
+    header = kit.read("implicitbvh.jl_amd", "csrc", "ibvh_pointwalk.hpp")
+    assert header.count("return flag ? f(ft, nt, it, std::true_type{}) : f(ft, nt, it, std::false_type{});") == 1
+    assert "the any-hit mode of ibvh_cast.hip and ibvh_sweep.hip" in " ".join(header[:header.index("#pragma once")].replace("//", " ").split())
+    assert src.count("} else if (pointwalk::wins(ts, index, best, best_index)) {") == 1 and "best_index == 0" not in src
 
 
 def test_julia_wrapper_binds_it_with_the_ctypes_signature_and_the_docs_name_it():

@@ -77,11 +77,16 @@ def test_binding_table_makefile_launch_and_python_surface():
     for name in ("sweep_spheres", "SphereSweep"):
         assert name in ibvh.__all__ and callable(getattr(ibvh, name))
     # the walk (one call per mode), its block size and grid, the prologue, the gather and the flag are the shared ones
-    src = kit.query_unit(UNIT, "sweep::sweep_walk_kernel", walks=2)
+    src = kit.query_unit(UNIT, "sweep::sweep_walk_kernel", walks=2, any_mode=True)
     assert "box_bound" not in src and "__shared__" not in src and len(re.findall(r"__global__", src)) == 1
-    # three (T, TN) instantiations times two index types — the shared dispatch — times the two modes
-    assert "pointwalk::dispatch_box_types(bvh->types, modes)" in src and "template <class T, class TN, class I, bool ANY>" in src
-    assert "any ? launch(ft, nt, it, std::true_type{}) : launch(ft, nt, it, std::false_type{})" in src
+    # three (T, TN) instantiations times two index types times the two modes: the shared four-tag dispatch (query_unit), whose
+    # bool the launch turns into the kernel's template parameter; the tie rule is the shared one
+    assert "template <class T, class TN, class I, bool ANY>" in src and "constexpr bool ANY = decltype(mt)::value;" in src
+    assert "const bool any = mode == " in src and "modes" not in src and "type_traits" not in src
+    header = kit.read("implicitbvh.jl_amd", "csrc", "ibvh_pointwalk.hpp")
+    assert header.count("return flag ? f(ft, nt, it, std::true_type{}) : f(ft, nt, it, std::false_type{});") == 1
+    assert "the any-hit mode of ibvh_cast.hip and ibvh_sweep.hip" in " ".join(header[:header.index("#pragma once")].replace("//", " ").split())
+    assert src.count("} else if (pointwalk::wins(ts, index, best, best_index)) {") == 1 and "best_index == 0" not in src
     # the bound is the slab entry of the box grown by r; nothing fused, the square root is the library's
     assert "lo[0] - r, lo[1] - r, lo[2] - r" in src and "up[0] + r, up[1] + r, up[2] + r" in src and "slab_entry(glo, gup, p, d, inv)" in src
     assert "ibvh_sqrt(" in src and "sqrtf" not in src and "fma" not in src

@@ -71,13 +71,22 @@ def test_binding_table_makefile_launch_and_python_surface():
     # header spells, once, with the rest of the two-pass protocol (kit.PROTOCOL, checked by query_unit)
     assert len(re.findall(r"__global__", src)) == 1 and "template <class T, class TN, class I, bool WRITE>" in src
     # the crossings query's way of keeping leaf order: a 0 / 1 bound under a constant limit of 0
-    assert "return apart ? T(1) : T(0);" in src and "[]() { return T(0); }" in src
+    assert src.count("return trigeom::apart(qlo, qup, lo, up) ? T(1) : T(0);") == 1 and "[]() { return T(0); }" in src
+    assert src.count("trigeom::triangle_box(Q.v, qlo, qup);") == 1
+    assert src.count("if ((skip & IBVH_TRIS_SKIP_SHARED_VERTEX) && trigeom::shares_vertex(Q.v, K.v)) return;") == 1
     assert "raise_flag(flag, 4u)" in src and "skip & ~IBVH_TRIS_SKIP_SHARED_VERTEX" in src
     # the six tests name their vertices statically, in the documented order
     calls = re.findall(r"^\s*seg\(([^;]*)\);", src, flags=re.M)
     assert calls == ["Q.v, Q.v + 3, K, 1u", "Q.v + 3, Q.v + 6, K, 2u", "Q.v + 6, Q.v, K, 4u", "K.v, K.v + 3, Q, 8u", "K.v + 3, K.v + 6, Q, 16u",
                      "K.v + 6, K.v, Q, 32u"]
-    assert "& (t <= T(1))" in src and "p0[0] + t * d[0], p0[1] + t * d[1], p0[2] + t * d[2]" in src
+    # each is the shared cut test — the ray test with d = p1 - p0, t <= 1, the point p0 + t d — and the count pass's early-out
+    # stays around the call
+    seg = src[src.index("auto seg = [&]"):src.index("seg(Q.v, Q.v + 3, K, 1u);")]
+    assert seg.index("if (!WRITE && mask != 0) return;") < seg.index("if (trigeom::segment_cuts(tri, p0, p1, x)) {") and src.count("trigeom::segment_cuts(") == 1
+    geom = kit.read("implicitbvh.jl_amd", "csrc", "ibvh_trigeom.hpp")
+    cut = geom[geom.index("IBVH_D bool segment_cuts("):]
+    for line in ("const T d[3] = {p1[0] - p0[0], p1[1] - p0[1], p1[2] - p0[2]};", "& (t <= T(1))", "x[k] = p0[k] + t * d[k];", "WRITE"):
+        assert (line in cut) == (line != "WRITE"), line
 
 
 def test_the_edge_test_exists_once_and_the_unit_includes_it():
@@ -86,7 +95,10 @@ def test_the_edge_test_exists_once_and_the_unit_includes_it():
     for define in (r"\bbool ray_triangle\s*\([^)]*\)\s*\{", r"\bvoid cross3\s*\([^)]*\)\s*\{"):
         assert [f for f in sources if re.search(define, kit.read("implicitbvh.jl_amd", "csrc", f))] == [SHARED], define
     text = kit.read("implicitbvh.jl_amd", "csrc", UNIT)
-    assert re.search(r'^#include "' + SHARED + '"$', text, flags=re.M) and text.count("raytri::ray_triangle(tri, p0, d, t, u, v)") == 1
+    assert re.search(r'^#include "' + SHARED + '"$', text, flags=re.M) and "ray_triangle(" not in text
+    geom = kit.read("implicitbvh.jl_amd", "csrc", "ibvh_trigeom.hpp")
+    assert re.search(r'^#include "ibvh_trigeom.hpp"$', text, flags=re.M) and re.search(r'^#include "' + SHARED + '"$', geom, flags=re.M)
+    assert geom.count("raytri::ray_triangle(tri, p0, d, t, u, v)") == 1
     assert "cross3" not in text and "dot3" not in text
     import __graft_entry__ as entry
     assert {os.path.join(csrc, SHARED), os.path.join(csrc, UNIT)} <= set(entry.kernel_sources(kit.ROOT))

@@ -60,32 +60,77 @@ def test_binding_table_makefile_launch_and_python_surface():
     for name in ("triangle_distances", "TriangleDistances", "mesh_distance", "MeshDistance", "self_clearance"):
         assert name in ibvh.__all__ and callable(getattr(ibvh, name))
     # the walk, its block size and grid, the prologue, the gather, the dispatch and the flag are the shared ones
-    src = kit.query_unit(UNIT, "tridist::tridist_walk_kernel", walks=2, lists=False)
+    src = kit.query_unit(UNIT, "tridist::tridist_walk_kernel", walks=2, pair=True)
     assert len(re.findall(r"__global__", src)) == 1 and "template <class T, class TN, class I>\n__global__" in src
-    assert "fma" not in src and "[&]() { return best.d2; }" in src
-    # the first walk: the shared point-box bound from Q's vertex a, which seeds the limit of the second
-    assert src.count("pointwalk::box_bound(lo, up, Q.v)") == 1 and "[&]() { return seed; }" in src and "best.d2 = seed;" in src
-    assert src.index("[&]() { return seed; }") < src.index("best.d2 = seed;") < src.index("[&]() { return best.d2; }")
-    # the bound: both differences, the larger, not below zero; d2's order
+    assert "fma" not in src
+    # the first walk starts from Q's vertex a — the point candidate 0 is evaluated from, which the seed's argument rests on
+    assert src.count("nodes, nan, Q.v, max_d2, box, gather, pair, best);") == 1
+    assert src.index("if (c == 0) r.put(d2, xq, xk, 0);") < src.index("else r.offer(d2, xq, xk, c);")
+    # the bound: both differences, the larger, not below zero; d2's order — the shared box_gap, with Q's box
+    assert src.count("trigeom::box_gap(lo, up, qlo, qup)") == 1
+    geom = kit.read("implicitbvh.jl_amd", "csrc", "ibvh_trigeom.hpp")
     for line in ("const T below = lo[k] - qup[k], above = qlo[k] - up[k];", "const T m = below > above ? below : above;",
                  "g[k] = m > T(0) ? m : T(0);", "return (g[0] * g[0] + g[1] * g[1]) + g[2] * g[2];"):
-        assert line in src, line
+        assert geom.count(line) == 1 and line not in src, line
     # the candidates are loops, one at a time; the cut tests run only under the box clause
-    assert src.count("#pragma unroll 1") == 3 and src.count("pointtri::closest_on_triangle(") == 2   # the candidates' and the seed's
-    assert src.count("segseg::closest_on_segments(") == 1 and src.count("raytri::ray_triangle(") == 1
-    assert src.index("if (!apart) {") < src.index("raytri::ray_triangle(") < src.index("pointtri::closest_on_triangle(tri.v, y, x, region)")
-    assert src.count("pointtri::closest_on_triangle(K.v, Q.v, x, region)") == 1
+    assert src.count("#pragma unroll 1") == 3 and src.count("pointtri::closest_on_triangle(") == 1   # the candidates'; the seed's is the routine's
+    assert src.count("segseg::closest_on_segments(") == 1 and src.count("trigeom::segment_cuts(tri, p0, p1, x)") == 1
+    assert "ray_triangle(" not in src and geom.count("raytri::ray_triangle(tri, p0, d, t, u, v) & (t <= T(1))") == 1
+    assert src.index("const bool apart = trigeom::apart(qlo, qup, klo, kup);") < src.index("if (!apart) {") < src.index("trigeom::segment_cuts(")
+    assert src.index("trigeom::segment_cuts(") < src.index("pointtri::closest_on_triangle(tri.v, y, x, region)")
+
+
+# what the mesh queries compute with in more than one unit: (what defines it, its one home); no other source defines it
+SHARED_PIECES = (
+    (r"\bclosest_on_triangle\s*\([^)]*\)\s*\{", "ibvh_pointtri.hpp"), (r"\bbool ray_triangle\s*\([^)]*\)\s*\{", "ibvh_raytest.hpp"),
+    (r"\bclosest_on_segments\s*\([^)]*\)\s*\{", "ibvh_segseg.hpp"),
+    (r"IBVH_D void triangle_box\(", "ibvh_trigeom.hpp"), (r"IBVH_D bool apart\(", "ibvh_trigeom.hpp"), (r"IBVH_D T box_gap\(", "ibvh_trigeom.hpp"),
+    (r"IBVH_D bool same_vertex\(", "ibvh_trigeom.hpp"), (r"IBVH_D bool shares_vertex\(", "ibvh_trigeom.hpp"), (r"IBVH_D T sel\(", "ibvh_trigeom.hpp"),
+    (r"IBVH_D void vertex_of\(", "ibvh_trigeom.hpp"), (r"IBVH_D void edge_of\(", "ibvh_trigeom.hpp"), (r"\bstruct Pair\b", "ibvh_trigeom.hpp"),
+    (r"IBVH_D bool segment_cuts\(", "ibvh_trigeom.hpp"), (r"IBVH_D I closest_pair\(", "ibvh_pairwalk.hpp"),
+    (r"IBVH_D void store_pair\(", "ibvh_pairwalk.hpp"), (r"IBVH_D bool wins\(T x, I index, T best, I best_index\)", "ibvh_pointwalk.hpp"),
+    (r"int dispatch_box_types_and_bool\(", "ibvh_pointwalk.hpp"))
+# ... the operations behind them, which no other source spells: (the text, its one home)
+SPELLED_ONCE = (
+    ("l = v[3 + k] < l ? v[3 + k] : l;", "ibvh_trigeom.hpp"), ("u = v[6 + k] > u ? v[6 + k] : u;", "ibvh_trigeom.hpp"),
+    ("(qup[0] < lo[0]) | (qlo[0] > up[0]) | (qup[1] < lo[1]) | (qlo[1] > up[1]) | (qup[2] < lo[2]) | (qlo[2] > up[2])", "ibvh_trigeom.hpp"),
+    ("below > above ? below : above", "ibvh_trigeom.hpp"), ("(x[0] == y[0]) & (x[1] == y[1]) & (x[2] == y[2])", "ibvh_trigeom.hpp"),
+    ("shared |= same_vertex(Q + 3 * i, K + 3 * j)", "ibvh_trigeom.hpp"), ("return c ? a : b;", "ibvh_trigeom.hpp"),
+    ("sel(i == 1, v[3 + k], sel(i == 2, v[6 + k], v[k]))", "ibvh_trigeom.hpp"), ("sel(i == 0, v[3 + k], sel(i == 1, v[6 + k], v[k]))", "ibvh_trigeom.hpp"),
+    ("if (d < d2) put(d, q, k, c);", "ibvh_trigeom.hpp"), ("& (t <= T(1))", "ibvh_trigeom.hpp"), ("x[k] = p0[k] + t * d[k];", "ibvh_trigeom.hpp"),
+    ("(x < best) | ((x == best) & ((best_index == 0) | (index < best_index)))", "ibvh_pointwalk.hpp"),
+    ("std::true_type{}", "ibvh_pointwalk.hpp"), ("seed = d2 < seed ? d2 : seed;", "ibvh_pairwalk.hpp"),
+    ("hit ? best.d2 : std::numeric_limits<T>::infinity()", "ibvh_pairwalk.hpp"))
+# ... and how often each unit that used to spell one calls it now: as often as it spelled it
+CALLS = {
+    "trigeom::triangle_box(": {"ibvh_tritri.hip": 1, "ibvh_tridist.hip": 2, "ibvh_segtri.hpp": 1},
+    "trigeom::apart(": {"ibvh_tritri.hip": 1, "ibvh_boxes.hip": 1, "ibvh_tridist.hip": 1, "ibvh_segtri.hpp": 1},
+    "trigeom::box_gap(": {"ibvh_tridist.hip": 1, "ibvh_segdist.hip": 1, "ibvh_capsules.hip": 1},
+    "trigeom::shares_vertex(Q.v, K.v)": {"ibvh_tritri.hip": 1, "ibvh_tridist.hip": 1},
+    "trigeom::segment_cuts(": {"ibvh_tritri.hip": 1, "ibvh_tridist.hip": 1, "ibvh_segtri.hpp": 1},
+    "trigeom::Pair<T>": {"ibvh_tridist.hip": 3, "ibvh_segtri.hpp": 1, "ibvh_segdist.hip": 2, "ibvh_capsules.hip": 1, "ibvh_pairwalk.hpp": 3},
+    "pointwalk::wins(": {"ibvh_closest.hip": 1, "ibvh_cast.hip": 1, "ibvh_sweep.hip": 1, "ibvh_pairwalk.hpp": 1},
+    "pairwalk::closest_pair<I>(": {"ibvh_tridist.hip": 1, "ibvh_segdist.hip": 1},
+    "pairwalk::store_pair(": {"ibvh_tridist.hip": 1, "ibvh_segdist.hip": 1},
+    "pointwalk::dispatch_box_types_and_bool(": {"ibvh_cast.hip": 1, "ibvh_sweep.hip": 1, "ibvh_spheres.hip": 1, "ibvh_tritri.hip": 1,
+                                                "ibvh_capsules.hip": 1, "ibvh_boxes.hip": 1}}
 
 
 def test_the_shared_routines_exist_once_and_the_unit_includes_them():
     csrc = os.path.join(kit.ROOT, "implicitbvh.jl_amd", "csrc")
     sources = [f for f in sorted(os.listdir(csrc)) if f.endswith((".hip", ".hpp", ".inc"))]
     text = {f: kit.read("implicitbvh.jl_amd", "csrc", f) for f in sources}
-    for define, home in ((r"\bclosest_on_triangle\s*\([^)]*\)\s*\{", "ibvh_pointtri.hpp"), (r"\bbool ray_triangle\s*\([^)]*\)\s*\{", "ibvh_raytest.hpp"),
-                         (r"\bclosest_on_segments\s*\([^)]*\)\s*\{", "ibvh_segseg.hpp")):
+    for define, home in SHARED_PIECES:
         assert [f for f in sources if re.search(define, text[f])] == [home], define
         assert len(re.findall(define, text[home])) == 1
         assert re.search(r'^#include "' + home + '"$', text[UNIT], flags=re.M), home
+    for spelled, home in SPELLED_ONCE:
+        assert [f for f in sources if spelled in text[f]] == [home] and text[home].count(spelled) == 1, spelled
+    assert [f for f in sources if "best_index == 0" in text[f]] == ["ibvh_pointwalk.hpp"]
+    for call, users in CALLS.items():
+        assert {f: text[f].count(call) for f in sources if call in text[f]} == users, call
+    # the two shapes of the six edge tests stay two: named statically for the contacts, one rolled loop for the distances
+    assert "#pragma unroll 1" not in text["ibvh_tritri.hip"] and "#pragma unroll 1" not in text["ibvh_trigeom.hpp"]
     seg = text["ibvh_segseg.hpp"]
     assert "using pointtri::dot3;" in seg and "T dot3(" not in seg       # dot3 associates as in ibvh_pointtri.hpp: it IS that one
     for line in ("if (a == T(0)) {", "if (e != T(0)) t = unit(f / e);", "if (e == T(0)) {", "const T den = a * e - b * b;",
