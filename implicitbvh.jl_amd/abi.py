@@ -114,6 +114,10 @@ SEGMENT_DISTANCES_ARGTYPES = [C.POINTER(Bvh), C.c_void_p, C.c_int64, C.c_void_p,
 BOXES_COUNT, BOXES_WRITE = 0, 1
 BOX_CONTACTS_ARGTYPES = ([C.POINTER(Bvh), C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64, C.c_int32, C.c_void_p,
                           C.c_void_p, C.c_int64] + [C.c_void_p] * 4)
+# ibvh_cast_spheres(bvh, points, displacements, radii, num, t_max, skip, mode, hit_index, hit_t, touched, stream)
+SPHERECAST_CLOSEST, SPHERECAST_ANY = 0, 1
+CAST_SPHERES_ARGTYPES = ([C.POINTER(Bvh), C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p, C.c_int32]
+                         + [C.c_void_p] * 4)
 
 
 class BuildDesc(C.Structure):

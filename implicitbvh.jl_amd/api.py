@@ -36,7 +36,7 @@ __all__ = [
     "triangle_contacts", "TriangleContacts", "self_intersections", "sweep_spheres", "SphereSweep",
     "triangle_distances", "TriangleDistances", "mesh_distance", "MeshDistance", "self_clearance",
     "capsule_contacts", "CapsuleContacts", "segment_distances", "SegmentDistances",
-    "box_contacts", "BoxContacts", "voxelize",
+    "box_contacts", "BoxContacts", "voxelize", "cast_spheres", "SphereCast",
 ]
 
 NARROW_MORTON_LT = abi.NARROW_MORTON_LT
@@ -1740,6 +1740,87 @@ def sweep_spheres(bvh, triangles, centers, displacements, radii, t_max=None, any
     if any_hit:
         return _unpermute(order, (outs[4],))[0] != 0
     return SphereSweep(*_unpermute(order, outs[:4]))
+
+
+# ---------------------------------------------------------------------------------------------
+# rays and swept spheres against a sphere cloud: the first leaf hit (ibvh_cast_spheres; no reference counterpart)
+# ---------------------------------------------------------------------------------------------
+class SphereCast:
+    """Per query: .index (N,) the first leaf sphere it touches, by user index (0 = miss), .t (N,) the time of contact t* in
+    units of the displacement (+Inf = miss; 0 = touching at the start), .hit (N,) bool = index != 0."""
+
+    def __init__(self, index, t):
+        self.index, self.t = index, t
+
+    @property
+    def hit(self):
+        return self.index != 0
+
+    def positions(self, points, displacements):
+        """(3, N): where each query's centre is at contact, points + t * displacements; NaN columns for the misses.  Torch."""
+        torch = _torch()
+        t = torch.where(self.hit, self.t, torch.zeros_like(self.t))
+        x = points + t[None, :] * displacements
+        return torch.where(self.hit[None, :], x, torch.full_like(x, float("nan")))
+
+    def normals(self, spheres, points, displacements):
+        """(3, N): the unit vector from the hit leaf's centre to the query's centre at contact — the contact normal, which
+        points from the leaf towards the query —, gathered from `spheres`, the (n, 4) tensor the BVH was built from (user
+        index k = row k - 1); NaN columns for the misses and where the two centres coincide.  Torch."""
+        torch = _torch()
+        rows = (self.index.to(torch.int64) - 1).clamp_(min=0)
+        v = self.positions(points, displacements) - spheres[rows, :3].t()
+        return v / torch.linalg.vector_norm(v, dim=0, keepdim=True)
+
+
+def cast_spheres(bvh, points, displacements, radii=None, t_max=None, skip=None, any_hit=False, presorted=False):
+    """For every query sphere of radius radii[i] whose centre moves along points[:, i] + t * displacements[:, i] (radius 0: a
+    ray) the first leaf sphere of the cloud `bvh` was built over that it touches and when -> SphereCast; with any_hit=True
+    only whether it touches anything within its limit -> (N,) bool tensor (the walk ends at its first hit).  One launch
+    (include/ibvh.h, ibvh_cast_spheres: the touching test — the bits of the pair traversals' iscontact —, the quadratic, the
+    clamps t* = max(t, entry of the leaf's own box grown by the radius, entry of the stored box directly above the leaf grown
+    likewise), the tie rule — smallest t*, then the smaller index — and why pruning on the best hit so far loses nothing are
+    spelled out there); exact: bit-equal to a brute force over all leaves.
+
+    bvh: BSphere leaves under BBox nodes of the same or a wider float type (refit is fine).  points, displacements: (3, N) CUDA
+    tensors of the leaves' dtype, as for traverse_rays; t = 1 is the end of the displacement.  radii: None (rays), one number
+    for all, or an (N,) CUDA tensor of that dtype; a negative or NaN radius touches nothing.  t_max: None (unbounded), a
+    number — 1 = the whole displacement —, or an (N,) tensor of per-query limits; a hit needs t* <= t_max (inclusive), a NaN
+    or negative limit gives a miss.  skip: None, or an (N,) integer CUDA tensor, per query the user index of one leaf to
+    ignore (0 = none): a particle of the cloud swept against the cloud skips itself.  The device walks the batch in Morton
+    order of the points (lanes of a wave then share nodes) and the outputs are put back in the caller's order;
+    presorted=True walks it as given.
+
+    ValueError: box leaves, sphere nodes, nodes narrower than the leaves, a wrong dtype, device or shape."""
+    torch = _require_gpu()
+    what = "cast_spheres"
+    t = bvh.types
+    if t.leaf_kind != abi.BSPHERE:
+        raise ValueError(f"{what}: the BVH must have BSphere leaves (cast_rays and sweep_spheres query a mesh's BBox leaves)")
+    _check_box_nodes(bvh, what, "leaves' boxes")
+    ft, idt = _torch_float(t.leaf_float), _torch_index(t.index_type)
+    p, n, _, order = _query_points(points, ft, None, presorted, what)
+    d = _companion(displacements, n, ft, what, "displacements", "points")
+    r = None if radii is None else _per_item(radii, n, ft, what, "radii")
+    lim = None if t_max is None else _per_item(t_max, n, ft, what, "t_max")
+    if skip is not None:
+        if not (isinstance(skip, torch.Tensor) and tuple(skip.shape) == (n,) and skip.is_cuda
+                and skip.dtype in (torch.int32, torch.int64)):
+            raise ValueError(f"{what}: skip must be an (N,) integer tensor on the GPU")
+        skip = skip.to(idt).contiguous()
+    if order is not None:
+        d = d[order]
+        r, lim, skip = (None if x is None else x[order] for x in (r, lim, skip))
+    if any_hit:
+        outs = (None, None, torch.empty(n, dtype=torch.uint8, device="cuda"))
+    else:
+        outs = (torch.empty(n, dtype=idt, device="cuda"), torch.empty(n, dtype=ft, device="cuda"), None)
+    if n > 0:
+        lib.call("ibvh_cast_spheres", C.byref(bvh.struct()), _ptr(p), _ptr(d), _ptr(r), n, _ptr(lim), _ptr(skip),
+                 abi.SPHERECAST_ANY if any_hit else abi.SPHERECAST_CLOSEST, *[_ptr(o) for o in outs], _stream())
+    if any_hit:
+        return _unpermute(order, (outs[2],))[0] != 0
+    return SphereCast(*_unpermute(order, outs[:2]))
 
 
 # ---------------------------------------------------------------------------------------------

@@ -11,6 +11,7 @@
 //   ibvh_tritri.hip     0 / 1: the box is not / is apart from the triangle's box               list: the triangles it cuts
 //   ibvh_capsules.hip   0 / 1: that gap within r * r and the grown entry within 1, or not      list: the triangles within r
 //   ibvh_boxes.hip      0 / 1: the box is not / is apart from the oriented box's hull          list: the triangles it overlaps
+//   ibvh_spherecast.hip the centre's entry into the box grown by the radius, over SPHERE leaves  best: the first leaf, or any
 // No reference counterpart: every traversal of ImplicitBVH.jl is a fixed-volume overlap test (traverse/, raytrace/).
 //
 // For the kernels: the workgroup size, the distance queries' point-box bound (box_bound) and NaN test (hopeless), the walk,

@@ -326,6 +326,10 @@ c_box_contacts(bvh, triangles, num_triangles, centers, half_extents, rotations, 
     ccall((:ibvh_box_contacts, libibvh), Cint,
           (Ref{IbvhBvh}, Ptr{Cvoid}, Int64, Ptr{Cvoid}, Ptr{Cvoid}, Ptr{Cvoid}, Int64, Int32, Ptr{Cvoid}, Ptr{Cvoid}, Int64, Ptr{Cvoid}, Ptr{Cvoid}, Ptr{Cvoid}, Ptr{Cvoid}),
           bvh, triangles, num_triangles, centers, half_extents, rotations, num_boxes, mode, counts, offsets, capacity, contact_index, contact_inside, flag, stream)
+c_cast_spheres(bvh, points, displacements, radii, num, t_max, skip, mode, hit_index, hit_t, touched, stream) =
+    ccall((:ibvh_cast_spheres, libibvh), Cint,
+          (Ref{IbvhBvh}, Ptr{Cvoid}, Ptr{Cvoid}, Ptr{Cvoid}, Int64, Ptr{Cvoid}, Ptr{Cvoid}, Int32, Ptr{Cvoid}, Ptr{Cvoid}, Ptr{Cvoid}, Ptr{Cvoid}),
+          bvh, points, displacements, radii, num, t_max, skip, mode, hit_index, hit_t, touched, stream)
 c_lvt_scratch_bytes(types, n_items, cache_slots, out) =
     ccall((:ibvh_lvt_scratch_bytes, libibvh), Cint,
           (Ref{IbvhTypes}, Int64, Int32, Ref{Csize_t}),
@@ -1323,6 +1327,60 @@ function nearest_leaves(bvh::RocBVH{I}, points::ROCMatrix{T}; k::Integer=1, max_
     isnothing(order) && return (; index, d2)
     inv = ROCVector{Int64}(invperm(order))
     (; index=index[:, inv], d2=d2[:, inv])
+end
+
+# ---- rays and swept spheres against a sphere cloud: the first leaf hit (include/ibvh.h, ibvh_cast_spheres) ---------------
+const IBVH_SPHERECAST_CLOSEST = Int32(0)
+const IBVH_SPHERECAST_ANY = Int32(1)
+"""
+    cast_spheres(bvh::BVH, points::ROCMatrix{T}, displacements::ROCMatrix{T}; radii=nothing, t_max=nothing, skip=nothing,
+                 any_hit=false, presorted=false) -> (; index, t, hit)  |  ROCVector{Bool}
+
+For every query sphere of radius `radii[i]` (one number for all, or `nothing`: rays) whose centre moves along
+`points[:, i] + t * displacements[:, i]` the first leaf sphere of the cloud `bvh` was built over that it touches, in one launch:
+`index[i]` its user index (0 = miss), `t[i]` the time of contact in units of the displacement (`Inf` = miss, 0 = touching at
+the start), `hit[i] = index[i] != 0`.  With `any_hit=true` only whether the query touches anything within its limit (the walk
+ends at the first hit).  `t_max`: `nothing` (unbounded) or a `ROCVector{T}` of per-query limits, inclusive (1 = the whole
+displacement).  `skip`: `nothing` or a `ROCVector{I}`, per query the user index of one leaf to ignore (0 = none): a particle
+of the cloud swept against the cloud skips itself.  The result is the lexicographic minimum of (t*, index) over ALL leaves'
+hits — bit-equal to a brute force; the touching test (the bits of `iscontact`), the quadratic, the clamps t* = max(t, entry of
+the leaf's own box grown by the radius, entry of the stored box directly above the leaf grown likewise) and why pruning
+loses nothing are spelled out in include/ibvh.h.  A negative or NaN radius touches nothing.  The BVH must have `BSphere{T}`
+leaves under `BBox` nodes of `T` or wider; anything else raises ArgumentError.  The device walks the batch along a Morton curve
+through the points and the outputs come back in the caller's order; `presorted=true` walks it as given.  Not a method of
+ImplicitBVH: the reference has no such query.
+"""
+function cast_spheres(bvh::RocBVH{I}, points::ROCMatrix{T}, displacements::ROCMatrix{T};
+                      radii::Union{Nothing, Real, ROCVector{T}}=nothing, t_max::Union{Nothing, ROCVector{T}}=nothing,
+                      skip::Union{Nothing, ROCVector{I}}=nothing, any_hit::Bool=false, presorted::Bool=false) where {I, T}
+    d = bvh_desc(bvh)
+    isnothing(d) && throw(ArgumentError("cast_spheres: no libibvh instantiation for this BVH's types"))
+    leaf_volume_type(bvh.leaves) === BSphere{T} && eltype(bvh.nodes) <: BBox && sizeof(eltype(bvh.nodes)) >= sizeof(BBox{T}) ||
+        throw(ArgumentError("cast_spheres: the BVH must have BSphere{$T} leaves under BBox nodes of $T or wider"))
+    size(points, 1) == size(displacements, 1) == 3 || throw(ArgumentError("size(points, 1) == size(displacements, 1) == 3 must hold"))
+    size(points, 2) == size(displacements, 2) || throw(ArgumentError("size(points, 2) == size(displacements, 2) must hold"))
+    n = size(points, 2)
+    isnothing(radii) || radii isa Real || length(radii) == n || throw(ArgumentError("cast_spheres: length(radii) == size(points, 2) must hold"))
+    isnothing(t_max) || length(t_max) == n || throw(ArgumentError("cast_spheres: length(t_max) == size(points, 2) must hold"))
+    isnothing(skip) || length(skip) == n || throw(ArgumentError("cast_spheres: length(skip) == size(points, 2) must hold"))
+    r = radii isa Real ? fill!(similar(points, T, n), T(radii)) : radii
+    index = any_hit ? nothing : similar(points, I, n)
+    t = any_hit ? nothing : similar(points, T, n)
+    touched = any_hit ? similar(points, UInt8, n) : nothing
+    n == 0 && return any_hit ? (touched .!= 0x00) : (; index, t, hit=index .!= 0)
+    order = presorted ? nothing : point_morton_order(points)
+    perm = isnothing(order) ? nothing : ROCVector{Int64}(order)
+    permuted(x) = isnothing(x) || isnothing(perm) ? x : x[perm]
+    p = isnothing(perm) ? points : points[:, perm]
+    dis = isnothing(perm) ? displacements : displacements[:, perm]
+    check(c_cast_spheres(d, devptr(p), devptr(dis), devptr(permuted(r)), Int64(n), devptr(permuted(t_max)), devptr(permuted(skip)),
+                         any_hit ? IBVH_SPHERECAST_ANY : IBVH_SPHERECAST_CLOSEST, devptr(index), devptr(t), devptr(touched),
+                         stream_ptr()), "ibvh_cast_spheres")
+    if !isnothing(order)
+        inv = ROCVector{Int64}(invperm(order))
+        any_hit ? (touched = touched[inv]) : ((index, t) = (index[inv], t[inv]))
+    end
+    any_hit ? (touched .!= 0x00) : (; index, t, hit=index .!= 0)
 end
 
 """

@@ -57,6 +57,7 @@ SIGNATURES = {
     "ibvh_capsule_contacts": abi.CAPSULE_CONTACTS_ARGTYPES,
     "ibvh_segment_distances": abi.SEGMENT_DISTANCES_ARGTYPES,
     "ibvh_box_contacts": abi.BOX_CONTACTS_ARGTYPES,
+    "ibvh_cast_spheres": abi.CAST_SPHERES_ARGTYPES,
     "ibvh_bfs_initial_capacity": [_P(abi.Bvh), _i64, _P(_i64)],
     "ibvh_bfs_pair_initial_capacity": [_P(abi.Bvh), _P(abi.Bvh), _i64, _i64, _P(_i64)],
     "ibvh_bfs_rays_initial_capacity": [_P(abi.Bvh), _i64, _i64, _P(_i64)],

@@ -53,6 +53,7 @@ extern "C" {
  *      ibvh_capsule_contacts and IBVH_CAPSULES_COUNT / IBVH_CAPSULES_WRITE, ibvh_segment_distances (additive under 7
  *      likewise: two more entry points);
  *      ibvh_box_contacts and IBVH_BOXES_COUNT / IBVH_BOXES_WRITE (additive under 7 likewise: one more entry point);
+ *      ibvh_cast_spheres and IBVH_SPHERECAST_CLOSEST / IBVH_SPHERECAST_ANY (additive under 7 likewise: one more entry point);
  *      argument checks only, no layout or argument list moves: ibvh_key_histogram takes
  *      what fits its LDS staging (10 rows at 12-bit digits) and refuses shift > 63 and a negative prefix_shift,
  *      ibvh_pack_records / ibvh_dist_plan answer IBVH_ERR_OVERFLOW for an index past IBVH_I32 */
@@ -1259,6 +1260,89 @@ ibvh_status ibvh_box_contacts(const ibvh_bvh *bvh, const void *triangles, int64_
                               int64_t num_boxes, int32_t mode, void *counts, const void *offsets,
                               int64_t capacity, void *contact_index, void *contact_inside,
                               void *flag, void *stream);
+
+/* ----------------------------------------------------------------------------------- */
+/* rays and swept spheres against a sphere cloud: the first leaf hit                     */
+/* ----------------------------------------------------------------------------------- */
+/* For every query — a sphere of radius r >= 0 whose centre moves from p to p + d (position p + t d; r = 0 is a ray) — the
+ * FIRST leaf sphere of the cloud the BVH was built over that it touches and the time t, or only whether it touches anything
+ * within its limit.  t is in units of d: t = 1 is the end of the displacement.  Lidar and camera rays into a granular bed,
+ * line of sight and shadowing between particles, a projectile or fast particle that must not tunnel through a layer, "is the
+ * path from a to b free".  ibvh_traverse_rays_* list every (leaf, ray) whose bounding sphere the whole LINE meets, a list of
+ * unbounded length the caller would have to reduce.  No reference counterpart; ONE launch, NO host synchronisation, no
+ * atomics, no LDS, no scratch buffer, no candidate list.
+ *   points, displacements : num x 3 row-major values of bvh->types.leaf_float, `flt` below, processed in the order given
+ *                (neighbours in memory that are neighbours in space walk the same nodes: sort a scattered batch along a
+ *                Morton curve first)
+ *   radii      : optional DEVICE array of num values of `flt`; NULL = 0 for all (rays)
+ *   t_max      : optional DEVICE array of num values of `flt`, the end of each query's motion; NULL = unbounded
+ *   skip       : optional DEVICE array of num x I, per query the user index of ONE leaf to ignore — a particle of the cloud
+ *                swept against the cloud skips itself, and so does a ray that starts on a particle's surface —; 0 names no
+ *                leaf; NULL = none
+ *   mode       : IBVH_SPHERECAST_CLOSEST or IBVH_SPHERECAST_ANY
+ * The output rules are those of ibvh_sweep_spheres.  IBVH_SPHERECAST_CLOSEST — each optional, at least one non-NULL; what
+ * was not asked for is not written; `touched` must be NULL:
+ *   hit_index  : num x I, the winning leaf's user index; 0 = miss
+ *   hit_t      : num x flt; +Inf = miss
+ * IBVH_SPHERECAST_ANY:
+ *   touched    : num x uint8, 1 = the query touches something within its limit, 0 = it does not; required, and the other
+ *                two outputs must be NULL: WHICH leaf stopped the walk depends on the walk order.
+ * There is no flag argument: no index is used to read anything, so there is none to guard.
+ * All arguments are validated before any launch, in the order of ibvh_sweep_spheres: the entry's own checks (a NULL bvh, a
+ * negative num, an unknown mode, a wrong combination of outputs: IBVH_ERR_INVALID_ARG), then the types
+ * (IBVH_ERR_UNSUPPORTED), then the tree's shape and the required pointers (IBVH_ERR_INVALID_ARG).  num == 0: IBVH_OK, nothing
+ * is touched.
+ * The result is defined independently of how it is found, in `flt` = T, every operation rounded once (nothing fused;
+ * correctly rounded divide and square root), every comparison false on NaN, so that it can be pinned bit for bit.
+ * dot(x, y) = (x0 y0 + x1 y1) + x2 y2;  max(a, b) is the select a > b ? a : b.  For query (p, d, r, L, s) and the leaf with
+ * centre c, radius R and user index k:
+ * 1. Sums.  S = R + r;  m = p - c;  mm = dot(m, m).
+ * 2. Touching at the start iff mm <= S * S — the bits of the library's own iscontact(BSphere, BSphere) (iscontact.jl), so a
+ *    pair traversal and this query agree on who overlaps.  Then t_k = 0.
+ * 3. Otherwise, provided mm > S * S:  B = dot(m, d);  dd = dot(d, d);  Cq = mm - S * S;  disc = B * B - dd * Cq;
+ *    t_k = (-B - sqrt(disc)) / dd, valid iff dd > 0 && disc >= 0 && t_k >= 0 — exactly the operations of
+ *    ibvh_sweep_spheres' vertex candidate.  No valid t_k: k is not hit.  A NaN in the leaf makes every comparison false: no
+ *    hit.  A query with a NaN in p or d, or with !(r >= 0), touches nothing.
+ * 4. Own box.  own_k = entry(lo - r, up + r) for the ray (p, d), where (lo, up) = (c - R, c + R) in T — the leaf's volume as
+ *    a box (convert, merge.jl:47-51), which the walk bounds the leaf with —, the grown box [lo_j - r, up_j + r] is computed
+ *    in T, and entry is the slab test of ibvh_cast_rays, unchanged (+Inf: the ray does not meet the box).
+ * 5. Parent box.  parent_k = the same entry of the STORED box of the node directly above leaf k — its values narrowed to T,
+ *    which is exact, and grown by r the same way —, where that level exists and is built (tree.levels >= 2 and
+ *    built_level <= tree.levels - 1); otherwise -Inf.
+ * 6. Clamped time.  t*_k = max(max(t_k, own_k), parent_k).
+ * 7. Hit.  Leaf k is a hit iff k != s and t*_k <= L, inclusive, where L = min(t_max, largest finite flt) = t_max > largest ?
+ *    largest : t_max.  A NaN or negative L admits nothing.
+ * 8. IBVH_SPHERECAST_CLOSEST is the LEXICOGRAPHIC MINIMUM of (t*_k, k) over ALL hits: the smallest t*, and among equal t*
+ *    the SMALLER INDEX.  IBVH_SPHERECAST_ANY is 1 iff a hit exists.  A miss is index 0, t +Inf.
+ * The hazard, and why step 5 is there.  The mesh queries argue "every box of the tree contains the boxes below it exactly".
+ *   With sphere leaves that is FALSE at the lowest node level: merging two spheres into a box (merge.jl:58-81) returns the box
+ *   of b alone when length + a.r <= b.r holds in ROUNDED arithmetic, and the box of a need not lie inside it.  Of 4e6 random
+ *   Float32 pairs that are internally tangent along a coordinate axis the shortcut fired for about half, and for 3.3 % of
+ *   those the inner sphere's box pokes out of the outer's by an ulp.  A query that starts at the poking tip and does not move
+ *   along that axis is admitted by the leaf's own box and refused by the parent's stored box: a walk never reaches the leaf
+ *   although steps 1 to 4 alone give a touch at t = 0.  With step 5 such a query is a miss BY DEFINITION, which a brute force
+ *   can state without walking the tree: it needs the leaf order and the stored boxes of one level.
+ * Why pruning is then lossless WITHOUT an epsilon: above the lowest node level every merge is an exact minimum / maximum
+ *   with an exact widening (and ibvh_refit repeats the build's merges), lo_j - r and up_j + r are round-to-nearest, hence
+ *   monotone, and the COMPUTED slab entry is monotone in the corners (the argument of ibvh_sweep_spheres), so
+ *   t*_k >= parent_k >= entry(every grown ancestor), and the walk's bound of the leaf itself is own_k <= t*_k.  A node or leaf
+ *   is skipped iff entry > limit() — strictly: an equal t* under it may carry a smaller index — so a skipped box holds
+ *   nothing that can still win or tie.  limit() starts at L; the closest query lowers it to the best t* so far, the any query
+ *   drops it to -Inf on the first hit.  Traversal order and work mapping therefore cannot change the result.
+ * Limits.  d == 0 makes step 3 invalid (dd == 0): the query reduces to "what does this sphere overlap now", index order
+ *   deciding.  The quadratic loses digits where the path grazes a leaf (disc near 0) and for |d| much smaller or larger than
+ *   the cloud: t is what the operations above give, not the nearest float to the true time.  hit_t == 0 names a leaf that
+ *   iscontact reports, except where rounding leaves the start outside a grown box of steps 4 / 5 (then t* is that box's
+ *   entry, or the leaf is no hit).  A leaf with a NaN can make a box above it fail to contain its NaN-free neighbours, as
+ *   for ibvh_nearest_leaves.
+ * Accepted BVHs: leaf_kind == IBVH_BSPHERE, node_kind == IBVH_BBOX, node_float the same as or wider than leaf_float; any
+ *   index and Morton type.  Anything else — box leaves, sphere nodes, F64 leaves under F32 nodes — is IBVH_ERR_UNSUPPORTED,
+ *   never an answer.  A BVH after ibvh_refit is fine (no skin is needed: the definition reads the stored boxes).  Levels above
+ *   bvh->built_level are not read. */
+enum { IBVH_SPHERECAST_CLOSEST = 0, IBVH_SPHERECAST_ANY = 1 };
+ibvh_status ibvh_cast_spheres(const ibvh_bvh *bvh, const void *points, const void *displacements,
+                              const void *radii, int64_t num, const void *t_max, const void *skip, int32_t mode,
+                              void *hit_index, void *hit_t, void *touched, void *stream);
 
 /* ----------------------------------------------------------------------------------- */
 /* breadth-first traversal (BFSTraversal): level-synchronous pair queues                 */
