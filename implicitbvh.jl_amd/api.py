@@ -1524,6 +1524,8 @@ class RayCast:
     """Per ray: .index (N,) the closest exactly hit triangle's user index (0 = miss), .t (N,) the hit parameter t* (+Inf =
     miss), .uv (N, 2) the barycentric weights of p2, p3 (0, 0 on a miss), .hit (N,) bool = index != 0."""
 
+    ENTRY = ("ibvh_cast_rays", abi.CAST_CLOSEST, abi.CAST_ANY)
+
     def __init__(self, index, t, uv):
         self.index, self.t, self.uv = index, t, uv
 
@@ -1556,21 +1558,7 @@ def cast_rays(bvh, triangles, points, directions, t_max=None, any_hit=False, pre
     p, n, _, order = _query_points(points, ft, None, presorted, "cast_rays")
     d = _companion(directions, n, ft, "cast_rays", "directions", "points")
     lim = None if t_max is None else _per_item(t_max, n, ft, "cast_rays", "t_max")
-    if order is not None:
-        d = d[order]
-        lim = None if lim is None else lim[order]
-    if any_hit:
-        occluded = torch.empty(n, dtype=torch.uint8, device="cuda")
-        outs = (None, None, None, occluded)
-    else:
-        outs = (torch.empty(n, dtype=idt, device="cuda"), torch.empty(n, dtype=ft, device="cuda"),
-                torch.empty((n, 2), dtype=ft, device="cuda"), None)
-    if n > 0:
-        _mesh_query_call("ibvh_cast_rays", "cast_rays", bvh, tris, _ptr(p), _ptr(d), n, _ptr(lim),
-                         abi.CAST_ANY if any_hit else abi.CAST_CLOSEST, *[_ptr(o) for o in outs])
-    if any_hit:
-        return _unpermute(order, (outs[3],))[0] != 0
-    return RayCast(*_unpermute(order, outs[:3]))
+    return _first_hit(RayCast, "cast_rays", bvh, tris, p, order, (d,), (lim,), ((idt, ()), (ft, ()), (ft, (2,))), any_hit)
 
 
 # ---- the list queries, sphere_contacts, triangle_contacts, capsule_contacts and box_contacts: one shape of result, one count / scan / write sequence ----
@@ -1620,6 +1608,28 @@ def _contact_lists(result, what, bvh, tris, n, walk, tail, outs, count_only):
         if word & 4:
             raise RuntimeError(f"{what}: the write pass found more contacts than the count pass (inputs changed between them?)")
     return result(offsets, *columns)
+
+
+def _first_hit(result, what, bvh, tris, p, order, head, tail, outs, any_hit):
+    """A first-hit query's one launch -> result(*closest outputs), with any_hit the (N,) bool mask.  result.ENTRY: (entry,
+    closest mode, any-hit mode); the launch is entry(bvh, [triangles, n,] p, *head, N, *tail, mode, *closest outputs, the
+    any-hit byte, ...): through _mesh_query_call over a mesh, straight over a cloud (tris None).  p: the (N, 3) points in walk
+    order; order: that permutation (None = none), which the other per-item tensors, head and tail (None = absent), are put in
+    here.  outs: (dtype, trailing shape) per closest output.  No items: no launch."""
+    torch = _torch()
+    entry, closest, any_mode = result.ENTRY
+    n = int(p.shape[0])
+    head, tail = ([x if order is None or x is None else x[order] for x in xs] for xs in (head, tail))  # (held to the end)
+    made = [torch.empty((n,) + shape, dtype=dt, device="cuda") for dt, shape in (((torch.uint8, ()),) if any_hit else outs)]
+    slots = [None] * len(outs) + made if any_hit else made + [None]
+    if n > 0:
+        args = [_ptr(x) for x in [p] + head] + [n] + [_ptr(x) for x in tail] + [any_mode if any_hit else closest] + [_ptr(o) for o in slots]
+        if tris is None:
+            lib.call(entry, C.byref(bvh.struct()), *args, _stream())
+        else:
+            _mesh_query_call(entry, what, bvh, tris, *args)
+    made = _unpermute(order, tuple(made))
+    return made[0] != 0 if any_hit else result(*made)
 
 
 # ---------------------------------------------------------------------------------------------
@@ -1678,6 +1688,8 @@ class SphereSweep:
     uint8 the feature that point lies on (0 vertex p1, 1 vertex p2, 2 edge p1p2, 3 vertex p3, 4 edge p1p3, 5 edge p2p3,
     6 face; 0 on a miss), .hit (N,) bool = index != 0."""
 
+    ENTRY = ("ibvh_sweep_spheres", abi.SWEEP_CLOSEST, abi.SWEEP_ANY)
+
     def __init__(self, index, t, point, feature):
         self.index, self.t, self.point, self.feature = index, t, point, feature
 
@@ -1726,20 +1738,8 @@ def sweep_spheres(bvh, triangles, centers, displacements, radii, t_max=None, any
     d = _companion(displacements, n, ft, what, "displacements", "centers")
     r = _per_item(radii, n, ft, what, "radii")
     lim = None if t_max is None else _per_item(t_max, n, ft, what, "t_max")
-    if order is not None:
-        d, r = d[order], r[order]
-        lim = None if lim is None else lim[order]
-    if any_hit:
-        outs = (None, None, None, None, torch.empty(n, dtype=torch.uint8, device="cuda"))
-    else:
-        outs = (torch.empty(n, dtype=idt, device="cuda"), torch.empty(n, dtype=ft, device="cuda"),
-                torch.empty((n, 3), dtype=ft, device="cuda"), torch.empty(n, dtype=torch.uint8, device="cuda"), None)
-    if n > 0:
-        _mesh_query_call("ibvh_sweep_spheres", what, bvh, tris, _ptr(p), _ptr(d), _ptr(r), n, _ptr(lim),
-                         abi.SWEEP_ANY if any_hit else abi.SWEEP_CLOSEST, *[_ptr(o) for o in outs])
-    if any_hit:
-        return _unpermute(order, (outs[4],))[0] != 0
-    return SphereSweep(*_unpermute(order, outs[:4]))
+    return _first_hit(SphereSweep, what, bvh, tris, p, order, (d, r), (lim,),
+                      ((idt, ()), (ft, ()), (ft, (3,)), (torch.uint8, ())), any_hit)
 
 
 # ---------------------------------------------------------------------------------------------
@@ -1748,6 +1748,8 @@ def sweep_spheres(bvh, triangles, centers, displacements, radii, t_max=None, any
 class SphereCast:
     """Per query: .index (N,) the first leaf sphere it touches, by user index (0 = miss), .t (N,) the time of contact t* in
     units of the displacement (+Inf = miss; 0 = touching at the start), .hit (N,) bool = index != 0."""
+
+    ENTRY = ("ibvh_cast_spheres", abi.SPHERECAST_CLOSEST, abi.SPHERECAST_ANY)
 
     def __init__(self, index, t):
         self.index, self.t = index, t
@@ -1808,19 +1810,7 @@ def cast_spheres(bvh, points, displacements, radii=None, t_max=None, skip=None, 
                 and skip.dtype in (torch.int32, torch.int64)):
             raise ValueError(f"{what}: skip must be an (N,) integer tensor on the GPU")
         skip = skip.to(idt).contiguous()
-    if order is not None:
-        d = d[order]
-        r, lim, skip = (None if x is None else x[order] for x in (r, lim, skip))
-    if any_hit:
-        outs = (None, None, torch.empty(n, dtype=torch.uint8, device="cuda"))
-    else:
-        outs = (torch.empty(n, dtype=idt, device="cuda"), torch.empty(n, dtype=ft, device="cuda"), None)
-    if n > 0:
-        lib.call("ibvh_cast_spheres", C.byref(bvh.struct()), _ptr(p), _ptr(d), _ptr(r), n, _ptr(lim), _ptr(skip),
-                 abi.SPHERECAST_ANY if any_hit else abi.SPHERECAST_CLOSEST, *[_ptr(o) for o in outs], _stream())
-    if any_hit:
-        return _unpermute(order, (outs[2],))[0] != 0
-    return SphereCast(*_unpermute(order, outs[:2]))
+    return _first_hit(SphereCast, what, bvh, None, p, order, (d, r), (lim, skip), ((idt, ()), (ft, ())), any_hit)
 
 
 # ---------------------------------------------------------------------------------------------

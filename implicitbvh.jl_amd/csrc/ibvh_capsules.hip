@@ -61,8 +61,7 @@ __global__ __launch_bounds__(pointwalk::kBlock) void capsules_walk_kernel(
         // 0 = the box may hold a contact, 1 = it cannot: its gap to S's box exceeds r * r, or the segment's ray enters the box
         // grown by r beyond its end (both false on NaN: such a box is entered)
         auto box = [&](const T *lo, const T *up) -> T {
-            const T glo[3] = {lo[0] - r, lo[1] - r, lo[2] - r}, gup[3] = {up[0] + r, up[1] + r, up[2] + r};
-            const T gap = trigeom::box_gap(lo, up, slo, sup), entry = slab::slab_entry(glo, gup, a, d, inv);
+            const T gap = trigeom::box_gap(lo, up, slo, sup), entry = slab::grown_entry(lo, up, r, a, d, inv);
             return ((gap > r2) | (entry > T(1))) ? T(1) : T(0);
         };
         // only a leaf that passes — clause (i) on its stored box included — gathers its triangle (36 / 72 bytes)

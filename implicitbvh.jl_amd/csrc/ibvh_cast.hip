@@ -12,10 +12,11 @@
 // t* >= entry(leaf) >= entry(every ancestor): a box whose entry exceeds the limit holds nothing that could still win.
 //
 // The walk itself — work mapping, the trail word, the pop, the strict skip — is ibvh_pointwalk.hpp's, here with the slab
-// entry as the bound.  The limit starts at the ray's own t_max; the closest hit lowers it to the best t* so far, the any-hit
-// query drops it to -Inf at its first hit, which ends the walk.  The exact test is ibvh_raytest.hpp's, the one copy
-// ibvh_raytri.hip resolves candidate lists with.  Ray, inverse direction and best hit live in registers.
-#include "ibvh_pointwalk.hpp"
+// entry as the bound.  The limit, the answer and the walk under the mode's limit — from the ray's own t_max down to the best
+// t* so far, or to -Inf at the first hit — are ibvh_firsthit.hpp's, as are the stores of index and t*.  The exact test is
+// ibvh_raytest.hpp's, the one copy ibvh_raytri.hip resolves candidate lists with.  Ray, inverse direction and best hit live
+// in registers.
+#include "ibvh_firsthit.hpp"
 #include "ibvh_raytest.hpp"
 #include "ibvh_slab.hpp"
 
@@ -35,18 +36,14 @@ __global__ __launch_bounds__(pointwalk::kBlock) void cast_walk_kernel(
     const T *__restrict__ tris, int64_t num_triangles, const T *__restrict__ points, const T *__restrict__ dirs, int64_t num_rays,
     const T *__restrict__ t_max, I *__restrict__ out_index, T *__restrict__ out_t, T *__restrict__ out_uv,
     uint8_t *__restrict__ out_occluded, uint32_t *flag) {
-    const T inf = std::numeric_limits<T>::infinity();
     bool bad = false;
     for (int64_t item = (int64_t)blockIdx.x * kBlock + threadIdx.x; item < num_rays; item += (int64_t)gridDim.x * kBlock) {
         const T p[3] = {points[3 * item], points[3 * item + 1], points[3 * item + 2]};
         const T d[3] = {dirs[3 * item], dirs[3 * item + 1], dirs[3 * item + 2]};
         const T inv[3] = {T(1) / d[0], T(1) / d[1], T(1) / d[2]};
-        // L of include/ibvh.h: a hit is finite (a NaN limit stays NaN and admits nothing)
-        const T given = t_max ? t_max[item] : inf;
-        const T L = given > std::numeric_limits<T>::max() ? std::numeric_limits<T>::max() : given;
-        T best = L, best_u = T(0), best_v = T(0);
-        I best_index = 0;
-        bool occluded = false;
+        const T L = firsthit::limit(t_max, item);
+        firsthit::Answer<T, I> answer(L);
+        T best_u = T(0), best_v = T(0);
         auto box = [&](const T *lo, const T *up) { return slab_entry(lo, up, p, d, inv); };
         // only a leaf that passes gathers its triangle (36 / 72 bytes)
         auto visit = [&](const char *rec) {
@@ -58,36 +55,17 @@ __global__ __launch_bounds__(pointwalk::kBlock) void cast_walk_kernel(
                 T t, u, v;
                 if (raytri::ray_triangle(tr, p, d, t, u, v)) {
                     const T ts = entry > t ? entry : t; // t*: the clamp
-                    if constexpr (ANY) {
-                        occluded |= ts <= L;
-                    } else if (pointwalk::wins(ts, index, best, best_index)) { // (t*, index) lexicographically; best starts at L
-                        best = ts;
-                        best_index = index;
-                        best_u = u;
-                        best_v = v;
-                    }
+                    firsthit::offer<ANY>(answer, ts, index, [&]() { best_u = u, best_v = v; });
                 }
             } else {
                 bad = true;
             }
         };
         // t* >= t >= 0: a negative or NaN limit admits nothing, and a NaN could not prune
-        if (L >= T(0)) {
-            if constexpr (ANY)
-                pointwalk::walk<BBox<T>, TN>(tree, built_level, leaves, lay, nodes, box, [&]() { return occluded ? -inf : L; }, visit);
-            else
-                pointwalk::walk<BBox<T>, TN>(tree, built_level, leaves, lay, nodes, box, [&]() { return best; }, visit);
-        }
-        if constexpr (ANY) {
-            out_occluded[item] = occluded ? 1 : 0;
-        } else {
-            const bool hit = best_index != 0;
-            if (out_index) out_index[item] = best_index;
-            if (out_t) out_t[item] = hit ? best : inf;
-            if (out_uv) {
-                out_uv[2 * item] = best_u;
-                out_uv[2 * item + 1] = best_v;
-            }
+        if (L >= T(0)) firsthit::walk<ANY, BBox<T>, TN>(tree, built_level, leaves, lay, nodes, answer, box, visit);
+        firsthit::store<ANY>(answer, item, out_index, out_t, out_occluded);
+        if constexpr (!ANY) {
+            if (out_uv) out_uv[2 * item] = best_u, out_uv[2 * item + 1] = best_v;
         }
     }
     if (bad && flag) raise_flag(flag, 2u);
@@ -104,9 +82,8 @@ ibvh_status ibvh_cast_rays(const ibvh_bvh *bvh, const void *triangles, int64_t n
                            const void *directions, int64_t num_rays, const void *t_max, int32_t mode, void *hit_index,
                            void *hit_t, void *hit_uv, void *occluded, void *flag, void *stream) {
     if (!bvh || num_triangles < 0 || num_rays < 0) return IBVH_ERR_INVALID_ARG;
-    if (mode != IBVH_CAST_CLOSEST && mode != IBVH_CAST_ANY) return IBVH_ERR_INVALID_ARG;
+    if (!firsthit::outputs_ok(mode, occluded, hit_index || hit_t || hit_uv)) return IBVH_ERR_INVALID_ARG;
     const bool any = mode == IBVH_CAST_ANY;
-    if (any ? (!occluded || hit_index || hit_t || hit_uv) : (occluded || (!hit_index && !hit_t && !hit_uv))) return IBVH_ERR_INVALID_ARG;
     // box leaves: the lossless bound needs boxes that contain their triangles' boxes exactly, all the way up
     pointwalk::Prepared pre;
     const bool pointers_ok = (num_triangles == 0 || triangles) && (num_rays == 0 || (points && directions));

@@ -19,9 +19,11 @@
 // queries' rows (first_row, contact, store_count: the count / write protocol).  For the entry points: the rules they share
 // and prepare(), the one place that applies them, in the one order a call with several faults is refused in; the
 // (T, TN, I) dispatch of a tree with box leaves, and the same with a bool as a fourth tag — the pass of a list query, the
-// any-hit mode of ibvh_cast.hip and ibvh_sweep.hip —; the list queries' two-pass argument rule (passes_ok); the optional
-// radius.  An entry point keeps its own checks (counts, axis, k, skip, which outputs it has) and its launch.  The box and
-// triangle primitives are ibvh_trigeom.hpp's, the two pair distances' seeded walk is ibvh_pairwalk.hpp's.
+// any-hit mode of ibvh_cast.hip, ibvh_sweep.hip and ibvh_spherecast.hip —; the list queries' two-pass argument rule
+// (passes_ok); the optional radius.  An entry point keeps its own checks (counts, axis, k, skip, which outputs it has) and
+// its launch.  The box and triangle primitives are ibvh_trigeom.hpp's, the two pair distances' seeded walk is
+// ibvh_pairwalk.hpp's, the three first-hit queries' closest / any-hit protocol — the limit, the answer, the walk under the
+// mode's limit, the common stores, the mode / outputs rule — is ibvh_firsthit.hpp's.
 //
 // A query hands the walk three things: bound(lo, up), its lower bound for a box (box_bound below for the distance queries;
 // 0 / 1 = "the ray can / cannot meet the box" for the crossings; the slab test's entry distance for the ray cast), limit(),
@@ -237,8 +239,8 @@ inline bool passes_ok(int32_t mode, const void *counts, const void *offsets, boo
 }
 
 // dispatch_box_types with a bool as a fourth tag, std::bool_constant<flag>, so that it is a template parameter of the kernel:
-// the pass of a list query (write: the counting kernel carries no outputs and reads no offsets), the any-hit mode of
-// ibvh_cast.hip and ibvh_sweep.hip (the any-hit kernel carries no best hit)
+// the pass of a list query (write: the counting kernel carries no outputs and reads no offsets), the any-hit mode of the
+// first-hit queries (ibvh_firsthit.hpp: the any-hit kernel carries no best hit)
 template <class F> int dispatch_box_types_and_bool(const ibvh_types &t, bool flag, F &&f) {
     return dispatch_box_types(t, [&](auto ft, auto nt, auto it) -> int {
         return flag ? f(ft, nt, it, std::true_type{}) : f(ft, nt, it, std::false_type{});

@@ -1,7 +1,7 @@
-// ibvh_slab.hpp — the slab test of include/ibvh.h (ibvh_cast_rays): where a ray enters a box.  ONE copy for the three queries
-// that prune on it and pin it bit for bit: ibvh_cast.hip (a ray against the leaves' boxes), ibvh_sweep.hip (a moving
-// sphere's centre against the boxes grown by its radius) and ibvh_capsules.hip (a capsule's segment against the boxes grown
-// by its radius).  No reference counterpart: the reference's isintersection answers
+// ibvh_slab.hpp — the slab test of include/ibvh.h (ibvh_cast_rays): where a ray enters a box.  ONE copy for the four queries
+// that prune on it and pin it bit for bit: ibvh_cast.hip (a ray against the leaves' boxes), and ibvh_sweep.hip,
+// ibvh_spherecast.hip (a moving sphere's centre) and ibvh_capsules.hip (a capsule's segment) against the boxes grown by the
+// radius (grown_entry).  No reference counterpart: the reference's isintersection answers
 // yes / no for the whole line and its 0 * Inf is NaN on a box face.
 #pragma once
 #include "ibvh_common.hpp"
@@ -28,6 +28,13 @@ template <class T> IBVH_D T slab_entry(const T *lo, const T *up, const T *p, con
         tmax = still ? tmax : nmax;
     }
     return (ok & (tmin <= tmax) & (tmax >= T(0))) ? tmin : inf;
+}
+
+// that entry into the box grown by r.  lo - r and up + r are round-to-nearest, hence monotone: a grown box contains the
+// grown box of whatever the box itself contains, so the entry stays a lossless bound (ibvh_sweep.hip)
+template <class T> IBVH_D T grown_entry(const T *lo, const T *up, T r, const T *p, const T *d, const T *inv) {
+    const T glo[3] = {lo[0] - r, lo[1] - r, lo[2] - r}, gup[3] = {up[0] + r, up[1] + r, up[2] + r};
+    return slab_entry(glo, gup, p, d, inv);
 }
 
 } // namespace slab

@@ -18,12 +18,13 @@
 // can still win or tie: every box on the path to a leaf that could enter the answer has a bound <= its t* <= the limit.
 //
 // The walk — work mapping, the trail word, the pop, the strict skip — is ibvh_pointwalk.hpp's, unchanged, with ibvh_slab.hpp's
-// entry of the grown box as the bound; the leaf's time is ibvh_raysphere.hpp's.  The limit starts at the query's own t_max;
-// the closest query lowers it to the best t* so far, the any query drops it to -Inf at its first hit, which ends the walk.
+// entry of the grown box (grown_entry) as the bound; the leaf's time is ibvh_raysphere.hpp's.  The limit, the answer and the
+// walk under the mode's limit — from the query's own t_max down to the best t* so far, or to -Inf at the first hit — are
+// ibvh_firsthit.hpp's.
 // visit() finds the parent from the record pointer: the leaf's position is (rec - leaves) / stride, the parent's implicit
 // index (leaf_first + position) >> 1, its memory index that minus the virtual nodes before its level; the lane read that box
 // a few steps earlier in the same descent.  Query, inverse displacement and best hit live in registers.
-#include "ibvh_pointwalk.hpp"
+#include "ibvh_firsthit.hpp"
 #include "ibvh_raysphere.hpp"
 #include "ibvh_slab.hpp"
 
@@ -33,8 +34,6 @@ namespace ibvh {
 namespace spherecast {
 
 using pointwalk::kBlock;
-using pointwalk::wins; // (the best-answer queries' tie rule)
-using slab::slab_entry;
 
 // T: the leaves' and queries' float type; TN: the nodes' (the same or wider — a node box then holds values of T, widened
 // exactly, and narrows back exactly); ANY: only "does it touch anything", the walk ends at the first hit
@@ -44,7 +43,6 @@ __global__ __launch_bounds__(pointwalk::kBlock) void cast_walk_kernel(
     const T *__restrict__ points, const T *__restrict__ disps, const T *__restrict__ radii, int64_t num,
     const T *__restrict__ t_max, const I *__restrict__ skip, I *__restrict__ out_index, T *__restrict__ out_t,
     uint8_t *__restrict__ out_touched) {
-    const T inf = std::numeric_limits<T>::infinity();
     const int levels = (int)tree.levels;
     // the level directly above the leaves, where it exists and is built: its first node's implicit index minus its memory index
     const bool has_parent = levels >= 2 && built_level <= levels - 1;
@@ -58,18 +56,11 @@ __global__ __launch_bounds__(pointwalk::kBlock) void cast_walk_kernel(
         const T r = radii ? radii[item] : T(0);
         const T dd = raysphere::dot3(d, d);
         const I ignored = skip ? skip[item] : I(0);
-        // L of include/ibvh.h: a hit is finite (a NaN limit stays NaN and admits nothing)
-        const T given = t_max ? t_max[item] : inf;
-        const T L = given > std::numeric_limits<T>::max() ? std::numeric_limits<T>::max() : given;
-        T best = L;
-        I best_index = 0;
-        bool touched = false;
+        const T L = firsthit::limit(t_max, item);
+        firsthit::Answer<T, I> answer(L);
         // the entry of the centre's ray into a box grown by r (monotone roundings: above the lowest node level a grown node
         // holds its grown children)
-        auto grown = [&](const T *lo, const T *up) {
-            const T glo[3] = {lo[0] - r, lo[1] - r, lo[2] - r}, gup[3] = {up[0] + r, up[1] + r, up[2] + r};
-            return slab_entry(glo, gup, p, d, inv);
-        };
+        auto grown = [&](const T *lo, const T *up) { return slab::grown_entry(lo, up, r, p, d, inv); };
         auto visit = [&](const char *rec) {
             const BSphere<T> s = load_vol<BSphere<T>>(rec);
             const I index = load_index<I>(rec, lay);
@@ -85,31 +76,13 @@ __global__ __launch_bounds__(pointwalk::kBlock) void cast_walk_kernel(
                 const T above = grown(lo, up);
                 ts = ts > above ? ts : above;
             }
-            if (index != ignored) {
-                if constexpr (ANY) {
-                    touched |= ts <= L;
-                } else if (wins(ts, index, best, best_index)) { // (t*, index) lexicographically; best starts at L
-                    best = ts;
-                    best_index = index;
-                }
-            }
+            if (index != ignored) firsthit::offer<ANY>(answer, ts, index, []() {}); // (no payload)
         };
         // a NaN in the query, a negative or NaN radius touch nothing; t* >= 0: a negative or NaN limit admits nothing, and a
         // NaN could not prune
         const bool numbers = (p[0] == p[0]) & (p[1] == p[1]) & (p[2] == p[2]) & (d[0] == d[0]) & (d[1] == d[1]) & (d[2] == d[2]);
-        if (numbers & (r >= T(0)) & (L >= T(0))) {
-            if constexpr (ANY)
-                pointwalk::walk<BSphere<T>, TN>(tree, built_level, leaves, lay, nodes, grown, [&]() { return touched ? -inf : L; }, visit);
-            else
-                pointwalk::walk<BSphere<T>, TN>(tree, built_level, leaves, lay, nodes, grown, [&]() { return best; }, visit);
-        }
-        if constexpr (ANY) {
-            out_touched[item] = touched ? 1 : 0;
-        } else {
-            const bool hit = best_index != 0;
-            if (out_index) out_index[item] = best_index;
-            if (out_t) out_t[item] = hit ? best : inf;
-        }
+        if (numbers & (r >= T(0)) & (L >= T(0))) firsthit::walk<ANY, BSphere<T>, TN>(tree, built_level, leaves, lay, nodes, answer, grown, visit);
+        firsthit::store<ANY>(answer, item, out_index, out_t, out_touched);
     }
 }
 
@@ -125,10 +98,8 @@ ibvh_status ibvh_cast_spheres(const ibvh_bvh *bvh, const void *points, const voi
                               int64_t num, const void *t_max, const void *skip, int32_t mode, void *hit_index, void *hit_t,
                               void *touched, void *stream) {
     if (!bvh || num < 0) return IBVH_ERR_INVALID_ARG;
-    if (mode != IBVH_SPHERECAST_CLOSEST && mode != IBVH_SPHERECAST_ANY) return IBVH_ERR_INVALID_ARG;
+    if (!firsthit::outputs_ok(mode, touched, hit_index || hit_t)) return IBVH_ERR_INVALID_ARG;
     const bool any = mode == IBVH_SPHERECAST_ANY;
-    const bool closest_outputs = hit_index || hit_t;
-    if (any ? (!touched || closest_outputs) : (touched || !closest_outputs)) return IBVH_ERR_INVALID_ARG;
     // sphere leaves only (the definition is theirs), under boxes that hold their values exactly
     if (bvh->types.leaf_kind != IBVH_BSPHERE) return IBVH_ERR_UNSUPPORTED;
     pointwalk::Prepared pre;

@@ -12,13 +12,13 @@
 // still win.
 //
 // The walk itself — work mapping, the trail word, the pop, the strict skip — is ibvh_pointwalk.hpp's, with ibvh_slab.hpp's
-// entry of the grown box as the bound.  The limit starts at the sphere's own t_max; the closest query lowers it to the best
-// t* so far, the any query drops it to -Inf at its first hit, which ends the walk.  A triangle's time of contact is that of
-// the centre's ray against the triangle grown by r: the two faces of its prism, three cylinders, three spheres.  The start
-// position is ibvh_pointtri.hpp's evaluation (the bits ibvh_spheres.hip computes), the face is ibvh_raytest.hpp's exact test
-// from the origin moved by r along the normal; the cylinders and spheres are the quadratics below.  Sphere, inverse
-// displacement and best hit live in registers.
-#include "ibvh_pointwalk.hpp"
+// entry of the grown box (grown_entry) as the bound.  The limit, the answer and the walk under the mode's limit — from the
+// sphere's own t_max down to the best t* so far, or to -Inf at the first hit — are ibvh_firsthit.hpp's.  A triangle's time
+// of contact is that of the centre's ray against the triangle grown by r: the two faces of its prism, three cylinders, three
+// spheres.  The start position is ibvh_pointtri.hpp's evaluation (the bits ibvh_spheres.hip computes), the face is
+// ibvh_raytest.hpp's exact test from the origin moved by r along the normal; the cylinders and spheres are the quadratics
+// below.  Sphere, inverse displacement and best hit live in registers.
+#include "ibvh_firsthit.hpp"
 #include "ibvh_pointtri.hpp"
 #include "ibvh_raytest.hpp"
 #include "ibvh_slab.hpp"
@@ -30,7 +30,6 @@ namespace sweep {
 
 using pointwalk::kBlock;
 using raytri::dot3;
-using slab::slab_entry;
 
 // the first touch of one triangle so far: t_k (+Inf: none yet), where, and on which feature (ibvh_sphere_contacts' codes)
 template <class T> struct Touch {
@@ -110,18 +109,12 @@ __global__ __launch_bounds__(pointwalk::kBlock) void sweep_walk_kernel(
         const T inv[3] = {T(1) / d[0], T(1) / d[1], T(1) / d[2]};
         const T r = radii[item];
         const T r2 = r * r, dd = dot3(d, d);
-        // L of include/ibvh.h: a hit is finite (a NaN limit stays NaN and admits nothing)
-        const T given = t_max ? t_max[item] : inf;
-        const T L = given > std::numeric_limits<T>::max() ? std::numeric_limits<T>::max() : given;
-        T best = L, best_q[3] = {T(0), T(0), T(0)};
-        I best_index = 0;
+        const T L = firsthit::limit(t_max, item);
+        firsthit::Answer<T, I> answer(L);
+        T best_q[3] = {T(0), T(0), T(0)};
         int best_feature = 0;
-        bool touched = false;
         // the entry of the centre's ray into a box grown by r (monotone roundings: a grown node holds its grown children)
-        auto grown = [&](const T *lo, const T *up) {
-            const T glo[3] = {lo[0] - r, lo[1] - r, lo[2] - r}, gup[3] = {up[0] + r, up[1] + r, up[2] + r};
-            return slab_entry(glo, gup, p, d, inv);
-        };
+        auto grown = [&](const T *lo, const T *up) { return slab::grown_entry(lo, up, r, p, d, inv); };
         // only a leaf that passes gathers its triangle (36 / 72 bytes)
         auto visit = [&](const char *rec) {
             I index;
@@ -147,37 +140,20 @@ __global__ __launch_bounds__(pointwalk::kBlock) void sweep_walk_kernel(
                     vertex(k, c, p, d, dd, r2, 3);
                 }
                 const T ts = entry > k.t ? entry : k.t; // t*: the clamp (+Inf: no candidate, or the grown box refused)
-                if constexpr (ANY) {
-                    touched |= ts <= L;
-                } else if (pointwalk::wins(ts, index, best, best_index)) { // (t*, index) lexicographically; best starts at L
-                    best = ts;
-                    best_index = index;
+                firsthit::offer<ANY>(answer, ts, index, [&]() {
                     best_feature = k.feature;
 #pragma unroll
                     for (int j = 0; j < 3; ++j) best_q[j] = k.q[j];
-                }
+                });
             } else {
                 bad = true;
             }
         };
         // a negative or NaN radius touches nothing; t* >= 0: a negative or NaN limit admits nothing, and a NaN could not prune
-        if ((r >= T(0)) & (L >= T(0))) {
-            if constexpr (ANY)
-                pointwalk::walk<BBox<T>, TN>(tree, built_level, leaves, lay, nodes, grown, [&]() { return touched ? -inf : L; }, visit);
-            else
-                pointwalk::walk<BBox<T>, TN>(tree, built_level, leaves, lay, nodes, grown, [&]() { return best; }, visit);
-        }
-        if constexpr (ANY) {
-            out_touched[item] = touched ? 1 : 0;
-        } else {
-            const bool hit = best_index != 0;
-            if (out_index) out_index[item] = best_index;
-            if (out_t) out_t[item] = hit ? best : inf;
-            if (out_q) {
-                out_q[3 * item] = best_q[0];
-                out_q[3 * item + 1] = best_q[1];
-                out_q[3 * item + 2] = best_q[2];
-            }
+        if ((r >= T(0)) & (L >= T(0))) firsthit::walk<ANY, BBox<T>, TN>(tree, built_level, leaves, lay, nodes, answer, grown, visit);
+        firsthit::store<ANY>(answer, item, out_index, out_t, out_touched);
+        if constexpr (!ANY) {
+            if (out_q) out_q[3 * item] = best_q[0], out_q[3 * item + 1] = best_q[1], out_q[3 * item + 2] = best_q[2];
             if (out_feature) out_feature[item] = (uint8_t)best_feature;
         }
     }
@@ -196,10 +172,8 @@ ibvh_status ibvh_sweep_spheres(const ibvh_bvh *bvh, const void *triangles, int64
                                int32_t mode, void *hit_index, void *hit_t, void *hit_point, void *hit_feature, void *touched,
                                void *flag, void *stream) {
     if (!bvh || num_triangles < 0 || num_spheres < 0) return IBVH_ERR_INVALID_ARG;
-    if (mode != IBVH_SWEEP_CLOSEST && mode != IBVH_SWEEP_ANY) return IBVH_ERR_INVALID_ARG;
+    if (!firsthit::outputs_ok(mode, touched, hit_index || hit_t || hit_point || hit_feature)) return IBVH_ERR_INVALID_ARG;
     const bool any = mode == IBVH_SWEEP_ANY;
-    const bool closest_outputs = hit_index || hit_t || hit_point || hit_feature;
-    if (any ? (!touched || closest_outputs) : (touched || !closest_outputs)) return IBVH_ERR_INVALID_ARG;
     // box leaves: the lossless bound needs boxes that contain their triangles' boxes exactly, all the way up
     pointwalk::Prepared pre;
     const bool pointers_ok = (num_triangles == 0 || triangles) && (num_spheres == 0 || (centers && displacements && radii));

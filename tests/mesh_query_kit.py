@@ -5,7 +5,11 @@ check of the GPU tests; the fake ibvh_bvh, the header / Julia matchers, the chai
 facts about the shared front end (csrc/ibvh_pointwalk.hpp) of the host tests.  For the four list queries also everything
 about their count / write protocol, which is one protocol: the description of a list query (ListQuery), the checkers'
 re-sorting into a leaf order, the two passes through the C entry point, the two comparators, the offsets-and-capacity
-scenario, the one-kernel-per-pass check and the entry points' common argument matrix.  Each query's checker, hand-made meshes
+scenario, the one-kernel-per-pass check and the entry points' common argument matrix.  For the three first-hit queries
+cast_rays, sweep_spheres and cast_spheres (a cloud's, the one query here that is not a mesh's) likewise their closest / any-hit
+protocol: the description of a first-hit query (FirstHit), the one call straight through the C entry point, the bit-for-bit
+comparator, the closest / any comparators for Python results, the source-text facts about csrc/ibvh_firsthit.hpp and the mode /
+outputs part of the entry points' argument matrix.  Each query's checker, hand-made meshes
 and reference builders stay with its own tests.  Importing this needs no GPU."""
 import collections
 import ctypes as C
@@ -262,6 +266,93 @@ def check_each_pass_is_one_kernel(query, bvh, tdev, python_call, head, tail, wri
     assert len(mine) >= 2 and all((mine[k] == getattr(got, query.columns[k].result)).all() for k in mine)
 
 
+# ---- the first-hit queries ------------------------------------------------------------------------------------------------------
+# A first-hit query: its C entry point (mesh: it takes the triangles and a flag word), its one kernel, the Python result's
+# class, its two modes, and letter -> Column in the entry point's order of outputs: the closest outputs, the index first, then
+# the any-hit byte (its `result` is None: the Python query returns the mask itself).
+FirstHit = collections.namedtuple("FirstHit", "entry mesh kernel result closest any columns")
+_hit = lambda checker, dtype="float", shape=(), sentinel=-7: Column(checker, checker, dtype, shape, sentinel)
+CAST_RAYS = FirstHit("ibvh_cast_rays", True, "cast_walk_kernel", "RayCast", abi.CAST_CLOSEST, abi.CAST_ANY,
+                     dict(i=_hit("index", "index"), t=_hit("t"), u=_hit("uv", shape=(2,)), o=Column("occluded", None, "uint8", (), 7)))
+SWEEP_SPHERES = FirstHit("ibvh_sweep_spheres", True, "sweep_walk_kernel", "SphereSweep", abi.SWEEP_CLOSEST, abi.SWEEP_ANY,
+                         dict(i=_hit("index", "index"), t=_hit("t"), q=_hit("point", shape=(3,)), g=_hit("feature", "uint8", sentinel=249),
+                              o=Column("touched", None, "uint8", (), 7)))
+CAST_SPHERES = FirstHit("ibvh_cast_spheres", False, "cast_walk_kernel", "SphereCast", abi.SPHERECAST_CLOSEST, abi.SPHERECAST_ANY,
+                        dict(i=_hit("index", "index"), t=_hit("t"), a=Column("touched", None, "uint8", (), 9)))
+
+
+def closest_letters(query):
+    return "".join(query.columns)[:-1]
+
+
+def first_hit_call(query, bvh, tris, head, tail=(), mode=None, outs=None, num=None, num_triangles=None, flag=0):
+    """one launch straight through the C entry point -> dict: the outputs as numpy arrays (prefilled with their sentinel so
+    that 'not written' is visible), the status and, a mesh query, the flag word.  head: the item arrays before the number of
+    items, tail: those between it and the mode (None = a NULL pointer); floats go in the leaves' type, integers in the index
+    type.  outs: the letters of the outputs handed over (default: the mode's own)."""
+    import torch
+    from implicitbvh_amd import api
+    from test_gpu_parity import cuda
+    mode = query.closest if mode is None else mode
+    outs = (closest_letters(query) if mode == query.closest else list(query.columns)[-1]) if outs is None else outs
+    n = len(head[0]) if num is None else num
+    rows = max(len(head[0]), 1)
+    np_t = {"f": NP_F[bvh.types.leaf_float], "i": NP_I[bvh.types.index_type], "u": NP_I[bvh.types.index_type]}
+    dev = lambda x: None if x is None else cuda(np.ascontiguousarray(np.array(x)).astype(np_t[np.asarray(x).dtype.kind]))
+    H, L = [dev(x) for x in head], [dev(x) for x in tail]
+    dtypes = {"index": api._torch_index(bvh.types.index_type), "float": tf(bvh.types.leaf_float), "uint8": torch.uint8}
+    o = {k: torch.full((rows,) + col.shape, col.sentinel, dtype=dtypes[col.dtype], device="cuda") for k, col in query.columns.items()}
+    fl = torch.full((1,), flag, dtype=torch.int32, device="cuda")
+    front, back = [C.byref(bvh.struct())], [api._stream()]
+    if query.mesh:
+        T = cuda(np.array(tris))   # (copies: the shared reference arrays are read-only)
+        front, back = front + [api._ptr(T), len(tris) if num_triangles is None else num_triangles], [api._ptr(fl)] + back
+    st = getattr(lib.load(), query.entry)(*front, *[api._ptr(x) for x in H], n, *[api._ptr(x) for x in L], mode,
+                                          *[api._ptr(o[k]) if k in outs else None for k in query.columns], *back)
+    torch.cuda.synchronize()
+    out = {k: v.cpu().numpy() for k, v in o.items()}
+    out["status"] = st
+    if query.mesh:
+        out["flag"] = int(fl.item())
+    return out
+
+
+def first_hit_same(query, got, exp, what=None, outs=None):
+    """what first_hit_call() returned is the checker's `exp`: the status, every output asked for of the checker's dtype —
+    index, feature and byte by value, the floats BIT FOR BIT — and every other output untouched"""
+    outs = closest_letters(query) if outs is None else outs
+    assert got["status"] == 0, what
+    for k, col in query.columns.items():
+        if k in outs:
+            e = getattr(exp, col.checker)
+            assert got[k].dtype == e.dtype, (what, k)
+            same = bits(got[k]) == bits(e) if col.dtype == "float" else (got[k] == e).all()
+            assert same, (what, k, got[k], e)
+        else:
+            assert (got[k] == col.sentinel).all(), (what, k, "not asked for, yet written")
+
+
+def assert_closest(query, got, exp, what=None):
+    """a Python result `got` is the checker's `exp`: the query's result class; the index by value; the floats by dtype, shape
+    and BIT FOR BIT; a uint8 column by dtype and value; and .hit"""
+    assert type(got).__name__ == query.result, what
+    for k in closest_letters(query):
+        col = query.columns[k]
+        g, e = _host(getattr(got, col.result)), getattr(exp, col.checker)
+        if col.dtype == "float":
+            assert g.dtype == e.dtype and g.shape == e.shape and bits(g) == bits(e), (what, k, int((g != e).sum()))
+        else:
+            assert (col.dtype == "index" or g.dtype == np.uint8) and (g == e).all(), (what, k, int((g != e).sum()))
+    assert (_host(got.hit) == (exp.index != 0)).all(), what
+
+
+def assert_any(query, got, exp, what=None):
+    """the Python query's any-hit result is a bool mask: the checker's byte"""
+    import torch
+    byte = getattr(exp, list(query.columns.values())[-1].checker)
+    assert got.dtype == torch.bool and ((byte == 0) | (byte == 1)).all() and (_host(got) == (byte == 1)).all(), what
+
+
 # ---- host tests -------------------------------------------------------------------------------------------------------------
 def fake_bvh(leaf_kind=abi.BSPHERE, leaf_float=abi.F32, node_kind=abi.BBOX, node_float=abi.F32, idx=abi.I32, morton=abi.U32, n=5,
              built_level=1, leaves=64, nodes=64):
@@ -334,6 +425,42 @@ PROTOCOL_USES = ("pointwalk::first_row<WRITE>(offsets, item)", "pointwalk::conta
                  "pointwalk::dispatch_box_types_and_bool(bvh->types, mode == ", "raise_flag(flag, 4u)")
 
 
+# the first-hit queries' protocol, which only csrc/ibvh_firsthit.hpp spells: the limit's two statements and why a NaN stays one,
+# how a candidate enters the answer, the two limits of the walk, the common stores, the mode / outputs rule, the one pair
+FIRST_HIT = ("const T given = t_max ? t_max[item] : std::numeric_limits<T>::infinity();",
+             "return given > std::numeric_limits<T>::max() ? std::numeric_limits<T>::max() : given;", "a NaN limit stays NaN and admits nothing",
+             "a.touched |= ts <= a.L;", "} else if (pointwalk::wins(ts, index, a.best, a.best_index)) {", "keep();",
+             "[&]() { return a.touched ? -inf : L; }", "[&]() { return a.best; }", "out_any[item] = a.touched ? 1 : 0;",
+             "const bool hit = a.best_index != 0;", "if (out_index) out_index[item] = a.best_index;",
+             "if (out_t) out_t[item] = hit ? a.best : std::numeric_limits<T>::infinity();",
+             "return mode == IBVH_CAST_ANY ? any_output && !closest_outputs : mode == IBVH_CAST_CLOSEST && !any_output && closest_outputs;",
+             "static_assert(IBVH_CAST_CLOSEST == 0 && IBVH_CAST_ANY == 1 && IBVH_SWEEP_CLOSEST == 0 && IBVH_SWEEP_ANY == 1,",
+             "static_assert(IBVH_SPHERECAST_CLOSEST == 0 && IBVH_SPHERECAST_ANY == 1,")
+# ... and the unit's use of it, once each
+FIRST_HIT_USES = ("const T L = firsthit::limit(t_max, item);", "firsthit::Answer<T, I> answer(L);", "firsthit::offer<ANY>(answer, ts, index, ",
+                  "firsthit::store<ANY>(answer, item, out_index, out_t, out_", "if (!firsthit::outputs_ok(mode, ")
+
+
+def first_hit_unit(src, leaf="BBox<T>"):
+    """The unit `src` answers with the closest or any hit through csrc/ibvh_firsthit.hpp: it includes it (and through it the
+    shared walk), uses each piece once — the limit, the answer, the offer, the ONE walk call for both modes over `leaf`
+    leaves, the common stores, the mode / outputs rule ahead of everything but the entry's own counts — and spells none of
+    the protocol, the tie rule's call included -> the header's text"""
+    fh = read("implicitbvh.jl_amd", "csrc", "ibvh_firsthit.hpp")
+    assert re.search(r'^#include "ibvh_firsthit.hpp"$', src, flags=re.M) and re.search(r'^#include "ibvh_pointwalk.hpp"$', fh, flags=re.M)
+    for use in FIRST_HIT_USES + ("firsthit::walk<ANY, " + leaf + ", TN>(tree, built_level, leaves, lay, nodes, answer, ",):
+        assert src.count(use) == 1, use
+    for text in FIRST_HIT:
+        assert text not in src and fh.count(text) == 1, text
+    for text in ("pointwalk::walk<", "wins(", "given", "-inf", "hit ?", "_CLOSEST"):
+        assert text not in src, text
+    assert fh.count("pointwalk::walk<VL, TN>(tree, built_level, leaves, lay, nodes, bound, ") == fh.count("pointwalk::walk<") == 2
+    assert src.index("return IBVH_ERR_INVALID_ARG;") < src.index("firsthit::outputs_ok(") < src.index("const bool any = mode == ") < src.index("pointwalk::prepare(")
+    for banned in BANNED + ("fma",):
+        assert banned not in fh, banned
+    return fh
+
+
 def pair_routine(src):
     """The unit `src` answers with the closest pair through csrc/ibvh_pairwalk.hpp, once: the routine walks twice — first from
     the seed point on the shared point-box bound, which seeds the limit of the second —, applies the shared tie rule once and
@@ -368,7 +495,8 @@ def query_unit(unit, kernel, walks=1, mesh=True, own_gather=False, lists=False, 
     text.  The Makefile builds it; its ONE launch — of `kernel`, on the shared grid and block size — goes through the profiling
     wrapper and is checked; it calls the shared walk (`walks` times), the shared prologue once and, a mesh query, the shared
     gather (own_gather: spells its statements out once, with the reason), dispatch and raise_flag; it spells none of BANNED and
-    none of FRONT_END itself.  A query with an any-hit mode (any_mode) dispatches on it through the shared four-tag dispatch.  A
+    none of FRONT_END itself.  A query with an any-hit mode (any_mode) dispatches on it through the shared four-tag dispatch and
+    takes the closest / any-hit protocol, its two walks included, from csrc/ibvh_firsthit.hpp (first_hit_unit).  A
     list query (lists) dispatches on the pass through the same and uses each piece of the shared count / write
     protocol once, which the header defines once and the unit does not spell.  The header defines each shared piece once, refuses in the documented order and dispatches three
     (T, TN) pairs per index type."""
@@ -382,7 +510,10 @@ def query_unit(unit, kernel, walks=1, mesh=True, own_gather=False, lists=False, 
     for text in (src, header):
         for banned in BANNED:
             assert banned not in text, banned
-    assert re.search(r'^#include "ibvh_pointwalk.hpp"$', src, flags=re.M) and src.count("pointwalk::walk<") == (0 if pair else walks)
+    if any_mode:  # a first-hit query: its walk under either mode's limit is the shared protocol's, and so is the include
+        assert walks == 2 and first_hit_unit(src)
+    else:
+        assert re.search(r'^#include "ibvh_pointwalk.hpp"$', src, flags=re.M) and src.count("pointwalk::walk<") == (0 if pair else walks)
     if pair:  # a closest-pair query: its two walks, its tie rule and its five stores are the shared lane routine's
         assert walks == 2 and pair_routine(src)
     assert "__builtin_clzll" not in src and "void raise_flag(" not in src
@@ -430,6 +561,28 @@ def query_unit(unit, kernel, walks=1, mesh=True, own_gather=False, lists=False, 
     assert dispatch.count("dispatch_index(t.index_type") == 1
     assert re.findall(r"f\(Tag<(\w+)>\{\}, Tag<(\w+)>\{\}, it\)", dispatch) == [("double", "double"), ("float", "double"), ("float", "float")]
     return src
+
+
+def check_mode_and_outputs(call, query, p, num, outputs, any_output):
+    """The part of a first-hit query's argument matrix that is the closest / any-hit protocol's.  call(**changes) -> status,
+    from a base that is the closest mode with the first of the closest outputs set and no items; p: a fake non-NULL pointer;
+    num: the name of the number of items; outputs: the names of the closest outputs, any_output: that of the any-hit byte.
+    Every refusal is asserted without items and with some: it comes before anything is read -> the any-hit base's changes."""
+    any_ = {"mode": query.any, outputs[0]: None, any_output: p}
+    assert call() == abi.OK and call(**any_) == abi.OK                     # no items: nothing to do
+    for mask in range(1, 1 << len(outputs)):
+        sub = {name: (p if mask >> j & 1 else None) for j, name in enumerate(outputs)}
+        assert call(**sub) == abi.OK, sub                                  # closest: any non-empty subset of its outputs ...
+        for n in (0, 5):
+            assert call(**{any_output: p, num: n}, **sub) == abi.ERR_INVALID_ARG, sub      # ... never the byte
+            assert call(**dict(any_, **{num: n}, **sub)) == abi.ERR_INVALID_ARG, sub       # any: the byte and nothing else
+    for n in (0, 5):
+        none = {outputs[0]: None, num: n}
+        assert call(**none) == abi.ERR_INVALID_ARG                         # no output at all
+        assert call(**{any_output: p}, **none) == abi.ERR_INVALID_ARG and call(mode=query.any, **none) == abi.ERR_INVALID_ARG
+        for mode in (-1, 2, 7):
+            assert call(mode=mode, **{num: n}) == abi.ERR_INVALID_ARG and call(mode=mode, **{any_output: p}, **none) == abi.ERR_INVALID_ARG
+    return any_
 
 
 def check_two_pass_arguments(call, count, write, p, num, outputs, needs, absent, fake):

@@ -18,6 +18,7 @@ from implicitbvh_amd import abi, api, lib  # noqa: E402
 from implicitbvh_amd.synthetic import torus_mesh  # noqa: E402
 
 import ray_cast_checker as rcc  # noqa: E402
+import mesh_query_kit as kit  # noqa: E402
 from mesh_query_kit import FLOATS, MESHES, NP_F, NP_I, assert_one_kernel, build as _build, tf as _tf  # noqa: E402
 from test_gpu_parity import cuda  # noqa: E402
 
@@ -42,18 +43,9 @@ def _bits(a):
     return a.view(BITS[a.dtype])
 
 
-def _assert_closest(got, exp, what):
-    """index, and t, u, v BIT FOR BIT"""
-    index, t, uv = got.index.cpu().numpy(), got.t.cpu().numpy(), got.uv.cpu().numpy()
-    assert t.dtype == exp.t.dtype and uv.dtype == exp.uv.dtype and uv.shape == exp.uv.shape, what
-    assert (index == exp.index).all(), (what, int((index != exp.index).sum()))
-    assert (_bits(t) == _bits(exp.t)).all(), (what, int((_bits(t) != _bits(exp.t)).sum()))
-    assert (_bits(uv) == _bits(exp.uv)).all(), what
-    assert (got.hit.cpu().numpy() == (exp.index != 0)).all(), what
-
-
-def _assert_any(got, exp, what):
-    assert got.dtype == torch.bool and (got.cpu().numpy() == (exp.occluded == 1)).all(), what
+_assert_closest = functools.partial(kit.assert_closest, kit.CAST_RAYS)   # index, and t, u, v BIT FOR BIT
+_assert_any = functools.partial(kit.assert_any, kit.CAST_RAYS)
+_same = functools.partial(kit.first_hit_same, kit.CAST_RAYS)
 
 
 # ---- 1. brute force, whole pipeline ------------------------------------------------------------------------------------
@@ -123,36 +115,8 @@ def test_t_max_per_ray(floats):
 
 
 # ---- 3. hand-made, straight through the C entry ------------------------------------------------------------------------
-def _call(bvh, tris, p, d, t_max=None, mode=abi.CAST_CLOSEST, num_triangles=None, flag=0, outs=None, num_rays=None):
-    """-> dict of numpy outputs (prefilled with a sentinel so that 'not written' is visible), the flag word, the status"""
-    outs = ("itu" if mode == abi.CAST_CLOSEST else "o") if outs is None else outs
-    n = len(p) if num_rays is None else num_rays
-    rows = max(len(p), 1)
-    T, Pp, Dd = cuda(tris), cuda(p), cuda(d)
-    ft, idt = _tf(bvh.types.leaf_float), api._torch_index(bvh.types.index_type)
-    o = {"i": torch.full((rows,), -7, dtype=idt, device="cuda"), "t": torch.full((rows,), -7, dtype=ft, device="cuda"),
-         "u": torch.full((rows, 2), -7, dtype=ft, device="cuda"), "o": torch.full((rows,), 7, dtype=torch.uint8, device="cuda")}
-    L = None if t_max is None else cuda(t_max)
-    fl = torch.full((1,), flag, dtype=torch.int32, device="cuda")
-    ptr = lambda k: api._ptr(o[k]) if k in outs else None
-    st = getattr(lib.load(), NAME)(C.byref(bvh.struct()), api._ptr(T), len(tris) if num_triangles is None else num_triangles,
-                                   api._ptr(Pp), api._ptr(Dd), n, api._ptr(L), mode, ptr("i"), ptr("t"), ptr("u"), ptr("o"),
-                                   api._ptr(fl), api._stream())
-    torch.cuda.synchronize()
-    out = {k: v.cpu().numpy() for k, v in o.items()}
-    out["flag"], out["status"] = int(fl.item()), st
-    return out
-
-
-def _same(got, exp, what=None, outs="itu"):
-    assert got["status"] == 0, what
-    for k, e in (("i", exp.index), ("t", exp.t), ("u", exp.uv), ("o", exp.occluded)):
-        if k in outs:
-            assert got[k].dtype == e.dtype, (what, k)
-            same = got[k] == e if k in "io" else _bits(got[k]) == _bits(e)
-            assert same.all(), (what, k, got[k], e)
-        else:
-            assert (got[k] == (7 if k == "o" else -7)).all(), (what, k, "not asked for, yet written")
+def _call(bvh, tris, p, d, t_max=None, num_rays=None, **kw):
+    return kit.first_hit_call(kit.CAST_RAYS, bvh, tris, (p, d), (t_max,), num=num_rays, **kw)
 
 
 Z = 0.3

@@ -6,7 +6,6 @@ boxes poke out of their parents' stored boxes (the hazard step 5 of the definiti
 tensor; per-query limits and skipped leaves; a cloud swept against itself; trees from one leaf to one level more than a power
 of two at every built level, every output subset, batches around a wave; agreement with the pair traversal about who
 overlaps; refit; the refusals; the empty batch; and the one launch."""
-import ctypes as C
 import functools
 
 import numpy as np
@@ -15,7 +14,7 @@ import pytest
 pytestmark = pytest.mark.gpu
 torch = pytest.importorskip("torch")
 import implicitbvh_amd as ibvh  # noqa: E402
-from implicitbvh_amd import abi, api, lib  # noqa: E402
+from implicitbvh_amd import abi, api  # noqa: E402
 
 import mesh_query_kit as kit  # noqa: E402
 import sphere_cast_checker as scc  # noqa: E402
@@ -68,15 +67,9 @@ def _run(bvh, p, d, r=None, t_max=None, skip=None, **kw):
                              t_max=t_max if t_max is None or np.isscalar(t_max) else _dev(t_max), skip=sk, **kw)
 
 
-def _same(got, exp, what=None):
-    assert (got.index.cpu().numpy() == exp.index).all(), what
-    t = got.t.cpu().numpy()
-    assert t.dtype == exp.t.dtype and _bits(t) == _bits(exp.t), what
-    assert (got.hit.cpu().numpy() == (exp.index != 0)).all(), what
-
-
-def _same_any(mask, exp, what=None):
-    assert mask.dtype == torch.bool and (mask.cpu().numpy() == (exp.touched != 0)).all(), what
+_same = functools.partial(kit.assert_closest, kit.CAST_SPHERES)       # the index by value, t BIT FOR BIT, .hit
+_same_any = functools.partial(kit.assert_any, kit.CAST_SPHERES)
+_same_c = functools.partial(kit.first_hit_same, kit.CAST_SPHERES)     # ... straight through the C entry
 
 
 def _check(bvh, spheres, p, d, r, t_max=None, skip=None, key=None, what=None, orders=(True, False)):
@@ -209,22 +202,8 @@ def test_a_cloud_swept_against_itself():
 
 
 # ---- 3. straight through the C entry ---------------------------------------------------------------------------------------------
-def _call(bvh, p, d, r=None, t_max=None, skip=None, mode=abi.SPHERECAST_CLOSEST, outs="it", num=None):
-    """-> dict of numpy outputs (prefilled with a sentinel: 'not written' is visible) and the status"""
-    ft, it = _tf(bvh.types.leaf_float), api._torch_index(bvh.types.index_type)
-    n = len(p) if num is None else num
-    dev = lambda x, dtype: None if x is None else torch.from_numpy(np.ascontiguousarray(x)).to(dtype).cuda()
-    P, D, R, L, S = dev(p, ft), dev(d, ft), dev(r, ft), dev(t_max, ft), dev(skip, it)
-    rows = max(len(p), 1)
-    o = {"i": torch.full((rows,), -7, dtype=it, device="cuda"), "t": torch.full((rows,), -7.0, dtype=ft, device="cuda"),
-         "a": torch.full((rows,), 9, dtype=torch.uint8, device="cuda")}
-    ptr = lambda key: api._ptr(o[key]) if key in outs else None
-    st = getattr(lib.load(), "ibvh_cast_spheres")(C.byref(bvh.struct()), api._ptr(P), api._ptr(D), api._ptr(R), n, api._ptr(L), api._ptr(S),
-                                                  mode, ptr("i"), ptr("t"), ptr("a"), api._stream())
-    torch.cuda.synchronize()
-    out = {key: v.cpu().numpy() for key, v in o.items()}
-    out["status"] = st
-    return out
+def _call(bvh, p, d, r=None, t_max=None, skip=None, **kw):
+    return kit.first_hit_call(kit.CAST_SPHERES, bvh, None, (p, d, r), (t_max, skip), **kw)
 
 
 @functools.lru_cache(maxsize=None)
@@ -253,15 +232,11 @@ def test_every_tree_shape_built_level_and_output_subset(n):
         assert bvh.tree.levels == levels and bvh.built_level == built_level
         order, boxes = _inputs(bvh)
         assert (boxes is None) == (levels < 2 or built_level == levels)
-        exp = scc.brute_force(spheres, order, boxes, p, d, r)
+        exp = scc.brute_force(spheres, order, boxes, p, d, r, idt=np.int32)
         hits += int((exp.index != 0).sum())
-        for outs in ("it", "i", "t"):
-            got = _call(bvh, p, d, r, outs=outs)
-            assert got["status"] == abi.OK and (got["a"] == 9).all(), (n, built_level, outs)
-            assert (got["i"] == (exp.index if "i" in outs else -7)).all(), (n, built_level, outs)
-            assert _bits(got["t"]) == _bits(exp.t if "t" in outs else np.full_like(exp.t, -7)), (n, built_level, outs)
-        got = _call(bvh, p, d, r, mode=abi.SPHERECAST_ANY, outs="a")
-        assert got["status"] == abi.OK and (got["a"] == exp.touched).all() and (got["i"] == -7).all() and (got["t"] == -7).all(), (n, built_level)
+        for outs in ("it", "i", "t"):   # what is asked for is the checker's, the rest keeps its sentinel
+            _same_c(_call(bvh, p, d, r, outs=outs), exp, (n, built_level, outs), outs=outs)
+        _same_c(_call(bvh, p, d, r, mode=abi.SPHERECAST_ANY), exp, (n, built_level), outs="a")
     assert hits >= 10 * levels
 
 
@@ -270,10 +245,9 @@ def test_query_batches_around_a_wave(m):
     spheres, p, d, r = _small(129, m)
     bvh = _build(spheres)
     order, boxes = _inputs(bvh)
-    exp = scc.brute_force(spheres, order, boxes, p, d, r)
-    got = _call(bvh, p, d, r)
-    assert got["status"] == abi.OK and (got["i"] == exp.index).all() and _bits(got["t"]) == _bits(exp.t)
-    assert (_call(bvh, p, d, r, mode=abi.SPHERECAST_ANY, outs="a")["a"] == exp.touched).all()
+    exp = scc.brute_force(spheres, order, boxes, p, d, r, idt=np.int32)
+    _same_c(_call(bvh, p, d, r), exp, m)
+    _same_c(_call(bvh, p, d, r, mode=abi.SPHERECAST_ANY), exp, m, outs="a")
     # fewer queries than rows: the rest is not written
     if m > 1:
         part = _call(bvh, p, d, r, num=m - 1)

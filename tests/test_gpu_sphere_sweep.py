@@ -18,6 +18,7 @@ from implicitbvh_amd import abi, api, lib  # noqa: E402
 
 import ray_cast_checker as rcc  # noqa: E402
 import sphere_sweep_checker as ssc  # noqa: E402
+import mesh_query_kit as kit  # noqa: E402
 from mesh_query_kit import FLOATS, MESHES, NP_F, NP_I, assert_one_kernel, build as _build, tf as _tf  # noqa: E402
 from test_gpu_parity import cuda  # noqa: E402
 
@@ -39,20 +40,9 @@ def _bits(a):
     return a.view(BITS[a.dtype])
 
 
-def _assert_closest(got, exp, what):
-    """index and feature, and t and the point BIT FOR BIT"""
-    assert isinstance(got, ibvh.SphereSweep), what
-    index, t, q, g = got.index.cpu().numpy(), got.t.cpu().numpy(), got.point.cpu().numpy(), got.feature.cpu().numpy()
-    assert t.dtype == exp.t.dtype and q.dtype == exp.point.dtype and q.shape == exp.point.shape and g.dtype == np.uint8, what
-    assert (index == exp.index).all(), (what, int((index != exp.index).sum()))
-    assert (_bits(t) == _bits(exp.t)).all(), (what, int((_bits(t) != _bits(exp.t)).sum()))
-    assert (_bits(q) == _bits(exp.point)).all(), what
-    assert (g == exp.feature).all(), what
-    assert (got.hit.cpu().numpy() == (exp.index != 0)).all(), what
-
-
-def _assert_any(got, exp, what):
-    assert got.dtype == torch.bool and (got.cpu().numpy() == (exp.touched == 1)).all(), what
+_assert_closest = functools.partial(kit.assert_closest, kit.SWEEP_SPHERES)   # index and feature, and t and the point BIT FOR BIT
+_assert_any = functools.partial(kit.assert_any, kit.SWEEP_SPHERES)
+_same = functools.partial(kit.first_hit_same, kit.SWEEP_SPHERES)
 
 
 # ---- 1. brute force, whole pipeline ------------------------------------------------------------------------------------
@@ -157,40 +147,8 @@ def test_t_max_per_sphere(floats):
 OUTS = "itqg"
 
 
-def _call(bvh, tris, p, d, r, t_max=None, mode=abi.SWEEP_CLOSEST, num_triangles=None, flag=0, outs=None, num_spheres=None):
-    """-> dict of numpy outputs (prefilled with a sentinel so that 'not written' is visible), the flag word, the status"""
-    outs = (OUTS if mode == abi.SWEEP_CLOSEST else "o") if outs is None else outs
-    n = len(p) if num_spheres is None else num_spheres
-    rows = max(len(p), 1)
-    T, Pp, Dd, Rr = _dev(tris, p, d, r)
-    ft, idt = _tf(bvh.types.leaf_float), api._torch_index(bvh.types.index_type)
-    o = {"i": torch.full((rows,), -7, dtype=idt, device="cuda"), "t": torch.full((rows,), -7, dtype=ft, device="cuda"),
-         "q": torch.full((rows, 3), -7, dtype=ft, device="cuda"), "g": torch.full((rows,), 249, dtype=torch.uint8, device="cuda"),
-         "o": torch.full((rows,), 7, dtype=torch.uint8, device="cuda")}
-    L = None if t_max is None else cuda(np.array(t_max))
-    fl = torch.full((1,), flag, dtype=torch.int32, device="cuda")
-    ptr = lambda k: api._ptr(o[k]) if k in outs else None
-    st = getattr(lib.load(), NAME)(C.byref(bvh.struct()), api._ptr(T), len(tris) if num_triangles is None else num_triangles,
-                                   api._ptr(Pp), api._ptr(Dd), api._ptr(Rr), n, api._ptr(L), mode, ptr("i"), ptr("t"), ptr("q"),
-                                   ptr("g"), ptr("o"), api._ptr(fl), api._stream())
-    torch.cuda.synchronize()
-    out = {k: v.cpu().numpy() for k, v in o.items()}
-    out["flag"], out["status"] = int(fl.item()), st
-    return out
-
-
-SENTINEL = dict(i=-7, t=-7, q=-7, g=249, o=7)
-
-
-def _same(got, exp, what=None, outs=OUTS):
-    assert got["status"] == 0, what
-    for k, e in (("i", exp.index), ("t", exp.t), ("q", exp.point), ("g", exp.feature), ("o", exp.touched)):
-        if k in outs:
-            assert got[k].dtype == e.dtype, (what, k)
-            same = got[k] == e if k in "igo" else _bits(got[k]) == _bits(e)
-            assert same.all(), (what, k, got[k], e)
-        else:
-            assert (got[k] == SENTINEL[k]).all(), (what, k, "not asked for, yet written")
+def _call(bvh, tris, p, d, r, t_max=None, num_spheres=None, **kw):
+    return kit.first_hit_call(kit.SWEEP_SPHERES, bvh, tris, (p, d, r), (t_max,), num=num_spheres, **kw)
 
 
 Z = 0.3

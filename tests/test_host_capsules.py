@@ -77,8 +77,9 @@ def test_binding_tables_makefile_launches_and_python_surface():
     src = kit.query_unit(UNITS[CONTACTS], "capsules::capsules_walk_kernel", lists=True)
     assert len(re.findall(r"__global__", src)) == 1 and "template <class T, class TN, class I, bool WRITE>\n__global__" in src
     assert "fma" not in src and "[]() { return T(0); }" in src and "mode == IBVH_CAPSULES_WRITE" in src
-    for line in ("const T glo[3] = {lo[0] - r, lo[1] - r, lo[2] - r}, gup[3] = {up[0] + r, up[1] + r, up[2] + r};",
-                 "trigeom::box_gap(lo, up, slo, sup)", "slab::slab_entry(glo, gup, a, d, inv)", "(gap > r2) | (entry > T(1))",
+    slab = kit.read("implicitbvh.jl_amd", "csrc", "ibvh_slab.hpp")   # (the box grown by r: the ONE grown entry, the sweep's too)
+    assert slab.count("const T glo[3] = {lo[0] - r, lo[1] - r, lo[2] - r}, gup[3] = {up[0] + r, up[1] + r, up[2] + r};\n    return slab_entry(glo, gup, p, d, inv);") == 1
+    for line in ("trigeom::box_gap(lo, up, slo, sup)", "slab::grown_entry(lo, up, r, a, d, inv)", "(gap > r2) | (entry > T(1))",
                  "if (p.d2 <= r2) {", "const T inv[3] = {T(1) / d[0], T(1) / d[1], T(1) / d[2]};",
                  "(r >= T(0)) && !pointwalk::hopeless(a, r2) && !pointwalk::hopeless(b, r2)"):
         assert line in src, line

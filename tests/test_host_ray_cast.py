@@ -73,8 +73,10 @@ def test_binding_table_makefile_launch_and_python_surface():
     assert "const bool any = mode == " in src and "modes" not in src and "type_traits" not in src
     header = kit.read("implicitbvh.jl_amd", "csrc", "ibvh_pointwalk.hpp")
     assert header.count("return flag ? f(ft, nt, it, std::true_type{}) : f(ft, nt, it, std::false_type{});") == 1
-    assert "the any-hit mode of ibvh_cast.hip and ibvh_sweep.hip" in " ".join(header[:header.index("#pragma once")].replace("//", " ").split())
-    assert src.count("} else if (pointwalk::wins(ts, index, best, best_index)) {") == 1 and "best_index == 0" not in src
+    assert "the any-hit mode of ibvh_cast.hip, ibvh_sweep.hip and ibvh_spherecast.hip" in " ".join(header[:header.index("#pragma once")].replace("//", " ").split())
+    # ... applied where a candidate is offered to the answer (csrc/ibvh_firsthit.hpp, pinned by query_unit); the payload is uv
+    assert src.count("firsthit::offer<ANY>(answer, ts, index, [&]() { best_u = u, best_v = v; });") == 1 and "best_index == 0" not in src
+    assert "if (L >= T(0)) firsthit::walk<ANY, " in src and "firsthit::outputs_ok(mode, occluded, hit_index || hit_t || hit_uv)" in src
 
 
 def test_julia_wrapper_binds_it_with_the_ctypes_signature_and_the_docs_name_it():
@@ -91,27 +93,15 @@ def test_entry_point_validates_its_arguments_before_any_launch():
     p = C.c_void_p(64)  # never dereferenced: every call below returns before a launch
     ok = dict(bvh=_fake_bvh(), tris=p, nt=5, pts=p, dirs=p, nr=0, tmax=None, mode=abi.CAST_CLOSEST, index=p, t=None, uv=None, occ=None,
               flag=None, stream=None)
-    any_ = dict(mode=abi.CAST_ANY, index=None, occ=p)
 
     def call(**kw):
         a = dict(ok, **kw)
         bvh = C.byref(a["bvh"]) if a["bvh"] is not None else None
         return f(bvh, a["tris"], a["nt"], a["pts"], a["dirs"], a["nr"], a["tmax"], a["mode"], a["index"], a["t"], a["uv"], a["occ"],
                  a["flag"], a["stream"])
-    assert call() == abi.OK and call(**any_) == abi.OK              # num_rays = 0: nothing to do
+    # the two modes and which outputs each takes: closest any non-empty subset of the three, never `occluded`; any that alone
+    any_ = kit.check_mode_and_outputs(call, kit.CAST_RAYS, p, "nr", ("index", "t", "uv"), "occ")
     assert call(tmax=p) == abi.OK and call(tmax=p, **any_) == abi.OK
-    # closest: any non-empty subset of the three outputs, never `occluded`
-    for sub in (dict(index=None, t=p), dict(index=None, uv=p), dict(t=p, uv=p), dict(t=p), dict(index=None, t=p, uv=p)):
-        assert call(**sub) == abi.OK, sub
-    for nr in (0, 5):
-        assert call(index=None, nr=nr) == abi.ERR_INVALID_ARG          # no output at all
-        assert call(occ=p, nr=nr) == abi.ERR_INVALID_ARG and call(index=None, occ=p, nr=nr) == abi.ERR_INVALID_ARG
-        # any: `occluded` and nothing else
-        assert call(mode=abi.CAST_ANY, index=None, nr=nr) == abi.ERR_INVALID_ARG
-        for extra in ("index", "t", "uv"):
-            assert call(**dict(any_, **{extra: p, "nr": nr})) == abi.ERR_INVALID_ARG, extra
-        for mode in (-1, 2, 7):
-            assert call(mode=mode, nr=nr) == abi.ERR_INVALID_ARG and call(mode=mode, index=None, occ=p, nr=nr) == abi.ERR_INVALID_ARG
     for bad in (dict(bvh=None), dict(nt=-1), dict(nr=-1), dict(tris=None), dict(nr=5, pts=None), dict(nr=5, dirs=None),
                 dict(bvh=_fake_bvh(leaves=None)), dict(bvh=_fake_bvh(nodes=None)), dict(bvh=_fake_bvh(built_level=0)),
                 dict(bvh=_fake_bvh(built_level=5))):

@@ -74,16 +74,21 @@ def test_binding_table_makefile_launch_and_python_surface():
     assert "dim3(pre.blocks), dim3(pointwalk::kBlock)" in src and not re.search(r"\bkBlock\s*=", src)
     assert "template <class T, class TN, class I, bool ANY>" in src and "constexpr bool ANY = decltype(mt)::value;" in src
     # the shared walk, once per mode; the shared prologue, for sphere leaves; the shared four-tag dispatch; the shared tie rule
-    assert re.search(r'^#include "ibvh_pointwalk.hpp"$', src, flags=re.M) and src.count("pointwalk::walk<BSphere<T>, TN>(") == src.count("pointwalk::walk<") == 2
+    # (csrc/ibvh_firsthit.hpp: the walk over sphere leaves under either mode's limit, the tie rule where a candidate is offered)
+    kit.first_hit_unit(src, leaf="BSphere<T>")
     assert src.count("pointwalk::prepare(bvh, false, ") == src.count("pointwalk::prepare(") == 1
     assert src.index("leaf_kind != IBVH_BSPHERE) return IBVH_ERR_UNSUPPORTED;") < src.index("pointwalk::prepare(")
     assert "using pointwalk::dispatch_box_types_and_bool;" in src and src.count("dispatch_box_types_and_bool(bvh->types, any, launch)") == 1
-    assert "using pointwalk::wins;" in src and src.count("} else if (wins(ts, index, best, best_index)) {") == src.count("wins(") == 1 and "best_index == 0" not in src
+    assert "using pointwalk::wins;" not in src and "best_index == 0" not in src
+    assert src.count("if (index != ignored) firsthit::offer<ANY>(answer, ts, index, []() {});") == 1   # no payload
     for banned in kit.BANNED + kit.FRONT_END + ("fma", "sqrtf", "__builtin_clzll", "raise_flag", "box_bound"):
         assert banned not in src, banned
-    # the bound is the slab entry of the box grown by r; the limits; the skipped leaf; the parent from the record pointer
-    assert "lo[0] - r, lo[1] - r, lo[2] - r" in src and "up[0] + r, up[1] + r, up[2] + r" in src and "slab_entry(glo, gup, p, d, inv)" in src
-    assert "touched ? -inf : L" in src and "return best;" in src and "(r >= T(0)) & (L >= T(0))" in src and "index != ignored" in src
+    # the bound is the slab entry of the box grown by r, the ONE grown entry; the limits; the skipped leaf; the parent from the
+    # record pointer
+    slab = kit.read("implicitbvh.jl_amd", "csrc", "ibvh_slab.hpp")
+    assert src.count("auto grown = [&](const T *lo, const T *up) { return slab::grown_entry(lo, up, r, p, d, inv); };") == 1 and "glo[" not in src
+    assert slab.count("const T glo[3] = {lo[0] - r, lo[1] - r, lo[2] - r}, gup[3] = {up[0] + r, up[1] + r, up[2] + r};\n    return slab_entry(glo, gup, p, d, inv);") == 1
+    assert "if (numbers & (r >= T(0)) & (L >= T(0))) firsthit::walk<ANY, " in src and "firsthit::outputs_ok(mode, touched, hit_index || hit_t)" in src
     assert "(rec - leaves)" in src and "(leaf_first + position) >> 1" in src and "level_skips(levels, tree.virtual_leaves, levels - 1) + 1" in src
     assert "levels >= 2 && built_level <= levels - 1" in src
     assert "const T tk = raysphere::first_touch(s.x, s.r, p, d, dd, r);" in src and "T ts = tk > entry ? tk : entry;" in src and "ts = ts > above ? ts : above;" in src
@@ -94,7 +99,7 @@ def test_binding_table_makefile_launch_and_python_surface():
         assert phrase in head, phrase
     header = kit.read("implicitbvh.jl_amd", "csrc", "ibvh_pointwalk.hpp")
     top = _flat(header[:header.index("#pragma once")])
-    assert "ibvh_spherecast.hip" in top and "the any-hit mode of ibvh_cast.hip and ibvh_sweep.hip" in top
+    assert "the any-hit mode of ibvh_cast.hip, ibvh_sweep.hip and ibvh_spherecast.hip" in top and "is ibvh_firsthit.hpp's" in top
 
 
 def test_the_slab_test_the_tie_rule_and_the_quadratic_exist_once_and_the_unit_shares_them():
@@ -108,7 +113,7 @@ def test_the_slab_test_the_tie_rule_and_the_quadratic_exist_once_and_the_unit_sh
     src, shared = text[UNIT], text[SHARED]
     # the tie rule is the point walk's (the list resolve of ibvh_raytri.hip has one of its own, for another key)
     assert len(re.findall(r"IBVH_D bool wins\(", text["ibvh_pointwalk.hpp"])) == 1 and not re.search(r"\bwins\s*\([^)]*\)\s*\{", src)
-    assert "using slab::slab_entry;" in src and "tmin" not in src and "ibvh_sqrt(" not in src and "disc" not in src
+    assert "slab::grown_entry(" in src and "slab_entry" not in src and "tmin" not in src and "ibvh_sqrt(" not in src and "disc" not in src
     # steps 1 to 3, operation for operation; nothing fused; the square root is the library's
     for line in ("const T S = R + r;", "const T m[3] = {p[0] - c[0], p[1] - c[1], p[2] - c[2]};", "const T mm = dot3(m, m);", "const T S2 = S * S;",
                  "const T B = dot3(m, d);", "const T Cq = mm - S2;", "const T disc = B * B - dd * Cq;", "const T t = (-B - ibvh_sqrt(disc)) / dd;",
@@ -141,26 +146,15 @@ def test_entry_point_validates_its_arguments_before_any_launch():
     p = C.c_void_p(64)  # never dereferenced: every call below returns before a launch
     fake = kit.fake_bvh
     ok = dict(bvh=fake(), p=p, d=p, r=None, n=0, tmax=None, skip=None, mode=abi.SPHERECAST_CLOSEST, index=p, t=None, touched=None, stream=None)
-    any_ = dict(mode=abi.SPHERECAST_ANY, index=None, touched=p)
 
     def call(**kw):
         a = dict(ok, **kw)
         bvh = C.byref(a["bvh"]) if a["bvh"] is not None else None
         return f(bvh, a["p"], a["d"], a["r"], a["n"], a["tmax"], a["skip"], a["mode"], a["index"], a["t"], a["touched"], a["stream"])
-    assert call() == abi.OK and call(**any_) == abi.OK                  # num = 0: nothing to do
+    # the two modes and which outputs each takes: closest any non-empty subset of the two, never `touched`; any that alone
+    any_ = kit.check_mode_and_outputs(call, kit.CAST_SPHERES, p, "n", ("index", "t"), "touched")
     for optional in (dict(r=p), dict(tmax=p), dict(skip=p), dict(r=p, tmax=p, skip=p)):
         assert call(**optional) == abi.OK and call(**dict(any_, **optional)) == abi.OK, optional
-    # closest: any non-empty subset of the two outputs, never `touched`; any: `touched` and nothing else
-    for mask in range(1, 4):
-        sub = dict(index=p if mask & 1 else None, t=p if mask & 2 else None)
-        assert call(**sub) == abi.OK and call(touched=p, **sub) == abi.ERR_INVALID_ARG, sub
-        assert call(**dict(any_, **sub)) == abi.ERR_INVALID_ARG, sub
-    for n in (0, 5):
-        assert call(index=None, n=n) == abi.ERR_INVALID_ARG               # no output at all
-        assert call(index=None, touched=p, n=n) == abi.ERR_INVALID_ARG
-        assert call(mode=abi.SPHERECAST_ANY, index=None, n=n) == abi.ERR_INVALID_ARG
-        for mode in (-1, 2, 7):
-            assert call(mode=mode, n=n) == abi.ERR_INVALID_ARG and call(mode=mode, index=None, touched=p, n=n) == abi.ERR_INVALID_ARG
     for bad in (dict(bvh=None), dict(n=-1), dict(n=5, p=None), dict(n=5, d=None), dict(bvh=fake(leaves=None)), dict(bvh=fake(nodes=None)),
                 dict(bvh=fake(built_level=0)), dict(bvh=fake(built_level=5))):
         assert call(**bad) == abi.ERR_INVALID_ARG and call(**dict(any_, **bad)) == abi.ERR_INVALID_ARG, bad

@@ -85,12 +85,17 @@ def test_binding_table_makefile_launch_and_python_surface():
     assert "const bool any = mode == " in src and "modes" not in src and "type_traits" not in src
     header = kit.read("implicitbvh.jl_amd", "csrc", "ibvh_pointwalk.hpp")
     assert header.count("return flag ? f(ft, nt, it, std::true_type{}) : f(ft, nt, it, std::false_type{});") == 1
-    assert "the any-hit mode of ibvh_cast.hip and ibvh_sweep.hip" in " ".join(header[:header.index("#pragma once")].replace("//", " ").split())
-    assert src.count("} else if (pointwalk::wins(ts, index, best, best_index)) {") == 1 and "best_index == 0" not in src
-    # the bound is the slab entry of the box grown by r; nothing fused, the square root is the library's
-    assert "lo[0] - r, lo[1] - r, lo[2] - r" in src and "up[0] + r, up[1] + r, up[2] + r" in src and "slab_entry(glo, gup, p, d, inv)" in src
+    assert "the any-hit mode of ibvh_cast.hip, ibvh_sweep.hip and ibvh_spherecast.hip" in " ".join(header[:header.index("#pragma once")].replace("//", " ").split())
+    # ... applied where a candidate is offered to the answer (csrc/ibvh_firsthit.hpp, pinned by query_unit); the payload is q
+    # and the feature
+    assert src.count("firsthit::offer<ANY>(answer, ts, index, [&]() {\n                    best_feature = k.feature;") == 1 and "best_index == 0" not in src
+    # the bound is the slab entry of the box grown by r, the ONE grown entry; nothing fused, the square root is the library's
+    slab = kit.read("implicitbvh.jl_amd", "csrc", "ibvh_slab.hpp")
+    assert src.count("slab::grown_entry(lo, up, r, p, d, inv)") == 1 and "glo[" not in src and "slab_entry" not in src
+    assert slab.count("const T glo[3] = {lo[0] - r, lo[1] - r, lo[2] - r}, gup[3] = {up[0] + r, up[1] + r, up[2] + r};\n    return slab_entry(glo, gup, p, d, inv);") == 1
     assert "ibvh_sqrt(" in src and "sqrtf" not in src and "fma" not in src
-    assert "touched ? -inf : L" in src and "return best;" in src and "(r >= T(0)) & (L >= T(0))" in src
+    assert "if ((r >= T(0)) & (L >= T(0))) firsthit::walk<ANY, " in src
+    assert "firsthit::outputs_ok(mode, touched, hit_index || hit_t || hit_point || hit_feature)" in src
 
 
 def test_the_start_the_face_and_the_slab_test_exist_once_and_the_unit_shares_them():
@@ -136,27 +141,15 @@ def test_entry_point_validates_its_arguments_before_any_launch():
     p = C.c_void_p(64)  # never dereferenced: every call below returns before a launch
     ok = dict(bvh=_fake_bvh(), tris=p, nt=5, c=p, d=p, r=p, ns=0, tmax=None, mode=abi.SWEEP_CLOSEST, index=p, t=None, q=None, g=None,
               touched=None, flag=None, stream=None)
-    any_ = dict(mode=abi.SWEEP_ANY, index=None, touched=p)
-    outputs = ("index", "t", "q", "g")
 
     def call(**kw):
         a = dict(ok, **kw)
         bvh = C.byref(a["bvh"]) if a["bvh"] is not None else None
         return f(bvh, a["tris"], a["nt"], a["c"], a["d"], a["r"], a["ns"], a["tmax"], a["mode"], a["index"], a["t"], a["q"], a["g"],
                  a["touched"], a["flag"], a["stream"])
-    assert call() == abi.OK and call(**any_) == abi.OK              # num_spheres = 0: nothing to do
+    # the two modes and which outputs each takes: closest any non-empty subset of the four, never `touched`; any that alone
+    any_ = kit.check_mode_and_outputs(call, kit.SWEEP_SPHERES, p, "ns", ("index", "t", "q", "g"), "touched")
     assert call(tmax=p) == abi.OK and call(tmax=p, **any_) == abi.OK and call(flag=p) == abi.OK
-    # closest: any non-empty subset of the four outputs, never `touched`
-    for mask in range(1, 16):
-        sub = {name: (p if mask >> j & 1 else None) for j, name in enumerate(outputs)}
-        assert call(**sub) == abi.OK and call(touched=p, **sub) == abi.ERR_INVALID_ARG, sub
-        assert call(**dict(any_, **sub)) == abi.ERR_INVALID_ARG, sub   # any: `touched` and nothing else
-    for ns in (0, 5):
-        assert call(index=None, ns=ns) == abi.ERR_INVALID_ARG          # no output at all
-        assert call(index=None, touched=p, ns=ns) == abi.ERR_INVALID_ARG
-        assert call(mode=abi.SWEEP_ANY, index=None, ns=ns) == abi.ERR_INVALID_ARG
-        for mode in (-1, 2, 7):
-            assert call(mode=mode, ns=ns) == abi.ERR_INVALID_ARG and call(mode=mode, index=None, touched=p, ns=ns) == abi.ERR_INVALID_ARG
     for bad in (dict(bvh=None), dict(nt=-1), dict(ns=-1), dict(tris=None), dict(ns=5, c=None), dict(ns=5, d=None), dict(ns=5, r=None),
                 dict(bvh=_fake_bvh(leaves=None)), dict(bvh=_fake_bvh(nodes=None)), dict(bvh=_fake_bvh(built_level=0)),
                 dict(bvh=_fake_bvh(built_level=5))):

@@ -90,6 +90,13 @@ SHARED_PIECES = (
     (r"IBVH_D bool segment_cuts\(", "ibvh_trigeom.hpp"), (r"IBVH_D I closest_pair\(", "ibvh_pairwalk.hpp"),
     (r"IBVH_D void store_pair\(", "ibvh_pairwalk.hpp"), (r"IBVH_D bool wins\(T x, I index, T best, I best_index\)", "ibvh_pointwalk.hpp"),
     (r"int dispatch_box_types_and_bool\(", "ibvh_pointwalk.hpp"))
+# ... and what the three first-hit queries and the grown-box queries share: (what defines it, its one home, the units that include it)
+FIRST_HIT_UNITS = ("ibvh_cast.hip", "ibvh_sweep.hip", "ibvh_spherecast.hip")
+FIRST_HIT_PIECES = (
+    (r"IBVH_D T limit\(", "ibvh_firsthit.hpp", FIRST_HIT_UNITS), (r"\bstruct Answer\b", "ibvh_firsthit.hpp", FIRST_HIT_UNITS),
+    (r"IBVH_D void offer\(Answer<T, I> &a, ", "ibvh_firsthit.hpp", FIRST_HIT_UNITS), (r"IBVH_D void store\(", "ibvh_firsthit.hpp", FIRST_HIT_UNITS),
+    (r"inline bool outputs_ok\(", "ibvh_firsthit.hpp", FIRST_HIT_UNITS),
+    (r"IBVH_D T grown_entry\(", "ibvh_slab.hpp", ("ibvh_sweep.hip", "ibvh_spherecast.hip", "ibvh_capsules.hip")))
 # ... the operations behind them, which no other source spells: (the text, its one home)
 SPELLED_ONCE = (
     ("l = v[3 + k] < l ? v[3 + k] : l;", "ibvh_trigeom.hpp"), ("u = v[6 + k] > u ? v[6 + k] : u;", "ibvh_trigeom.hpp"),
@@ -100,7 +107,12 @@ SPELLED_ONCE = (
     ("if (d < d2) put(d, q, k, c);", "ibvh_trigeom.hpp"), ("& (t <= T(1))", "ibvh_trigeom.hpp"), ("x[k] = p0[k] + t * d[k];", "ibvh_trigeom.hpp"),
     ("(x < best) | ((x == best) & ((best_index == 0) | (index < best_index)))", "ibvh_pointwalk.hpp"),
     ("std::true_type{}", "ibvh_pointwalk.hpp"), ("seed = d2 < seed ? d2 : seed;", "ibvh_pairwalk.hpp"),
-    ("hit ? best.d2 : std::numeric_limits<T>::infinity()", "ibvh_pairwalk.hpp"))
+    ("hit ? best.d2 : std::numeric_limits<T>::infinity()", "ibvh_pairwalk.hpp"),
+    # the first-hit protocol: the limit's two statements, the any-hit limit, the any-hit bit, the miss's t, the mode / outputs rule
+    ("given = t_max ? t_max[item] : ", "ibvh_firsthit.hpp"), ("given > std::numeric_limits<T>::max() ? std::numeric_limits<T>::max() : given", "ibvh_firsthit.hpp"),
+    ("? -inf : L", "ibvh_firsthit.hpp"), ("touched |= ts <= ", "ibvh_firsthit.hpp"), ("hit ? a.best : std::numeric_limits<T>::infinity()", "ibvh_firsthit.hpp"),
+    ("any_output && !closest_outputs", "ibvh_firsthit.hpp"), ("IBVH_SPHERECAST_CLOSEST == 0 && IBVH_SPHERECAST_ANY == 1", "ibvh_firsthit.hpp"),
+    ("lo[0] - r, lo[1] - r, lo[2] - r", "ibvh_slab.hpp"), ("up[0] + r, up[1] + r, up[2] + r", "ibvh_slab.hpp"))
 # ... and how often each unit that used to spell one calls it now: as often as it spelled it
 CALLS = {
     "trigeom::triangle_box(": {"ibvh_tritri.hip": 1, "ibvh_tridist.hip": 2, "ibvh_segtri.hpp": 1},
@@ -109,7 +121,11 @@ CALLS = {
     "trigeom::shares_vertex(Q.v, K.v)": {"ibvh_tritri.hip": 1, "ibvh_tridist.hip": 1},
     "trigeom::segment_cuts(": {"ibvh_tritri.hip": 1, "ibvh_tridist.hip": 1, "ibvh_segtri.hpp": 1},
     "trigeom::Pair<T>": {"ibvh_tridist.hip": 3, "ibvh_segtri.hpp": 1, "ibvh_segdist.hip": 2, "ibvh_capsules.hip": 1, "ibvh_pairwalk.hpp": 3},
-    "pointwalk::wins(": {"ibvh_closest.hip": 1, "ibvh_cast.hip": 1, "ibvh_sweep.hip": 1, "ibvh_pairwalk.hpp": 1},
+    "pointwalk::wins(": {"ibvh_closest.hip": 1, "ibvh_firsthit.hpp": 1, "ibvh_pairwalk.hpp": 1},   # (no longer the three first-hit units)
+    "firsthit::limit(": dict.fromkeys(FIRST_HIT_UNITS, 1), "firsthit::offer<ANY>(": dict.fromkeys(FIRST_HIT_UNITS, 1),
+    "firsthit::walk<ANY, ": dict.fromkeys(FIRST_HIT_UNITS, 1), "firsthit::store<ANY>(": dict.fromkeys(FIRST_HIT_UNITS, 1),
+    "firsthit::outputs_ok(": dict.fromkeys(FIRST_HIT_UNITS, 1), "pointwalk::walk<VL, TN>(tree, built_level, leaves, lay, nodes, bound, [&]() { return a.": {"ibvh_firsthit.hpp": 2},
+    "slab::grown_entry(": {"ibvh_sweep.hip": 1, "ibvh_spherecast.hip": 1, "ibvh_capsules.hip": 1},
     "pairwalk::closest_pair<I>(": {"ibvh_tridist.hip": 1, "ibvh_segdist.hip": 1},
     "pairwalk::store_pair(": {"ibvh_tridist.hip": 1, "ibvh_segdist.hip": 1},
     "pointwalk::dispatch_box_types_and_bool(": {"ibvh_cast.hip": 1, "ibvh_sweep.hip": 1, "ibvh_spheres.hip": 1, "ibvh_tritri.hip": 1,
@@ -124,6 +140,10 @@ def test_the_shared_routines_exist_once_and_the_unit_includes_them():
         assert [f for f in sources if re.search(define, text[f])] == [home], define
         assert len(re.findall(define, text[home])) == 1
         assert re.search(r'^#include "' + home + '"$', text[UNIT], flags=re.M), home
+    for define, home, units in FIRST_HIT_PIECES:
+        assert [f for f in sources if re.search(define, text[f])] == [home] and len(re.findall(define, text[home])) == 1, define
+        assert all(re.search(r'^#include "' + home + '"$', text[u], flags=re.M) for u in units), home
+    assert all("wins(" not in text[u] for u in FIRST_HIT_UNITS)
     for spelled, home in SPELLED_ONCE:
         assert [f for f in sources if spelled in text[f]] == [home] and text[home].count(spelled) == 1, spelled
     assert [f for f in sources if "best_index == 0" in text[f]] == ["ibvh_pointwalk.hpp"]
