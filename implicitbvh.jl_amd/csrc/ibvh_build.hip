@@ -319,6 +319,7 @@ struct BuildCall {
 // sort (ibvh_sort.hip) the smaller ones.  Both plans live in the sort region of the scratch (carve()).
 struct SortRoute {
     msd::Plan records;      // bits != 0: the record sort
+    msd::Tables tables;     // ... and its tables in the sort scratch
     rsort::PairsPlan pairs; // otherwise
     // The per-tile histogram the route's first pass expects from the key encoder: a workgroup of `tpb` threads per tile of
     // `tile_elems` keys counts the digit (key >> shift) & mask; tile-major rows for the record sort, digit-major for the pairs.
@@ -328,11 +329,12 @@ struct SortRoute {
 };
 inline SortRoute choose_route(int64_t n, int key_bits, int key_bytes, int leaf_bytes, void *sort_scratch) {
     SortRoute r{};
-    r.records = msd::make_plan(n, key_bits, key_bytes, leaf_bytes, sort_scratch);
+    r.records = msd::plan_records(n, key_bits, key_bytes, leaf_bytes);
     if (r.by_records()) {
         const msd::Plan &p = r.records;
-        r.tpb = p.ptpb, r.tile_elems = p.ptpb * p.pipt, r.num_tiles = p.num_tiles, r.shift = p.shift, r.tile_major = 1;
-        r.mask = (1u << p.bits) - 1u, r.tile_hist = p.tb.tile_hist;
+        r.tables = msd::bind_tables(p, sort_scratch);
+        r.tpb = p.part.tpb, r.tile_elems = p.tile(), r.num_tiles = p.num_tiles, r.shift = p.shift, r.tile_major = 1;
+        r.mask = (uint32_t)p.radix() - 1u, r.tile_hist = r.tables.tile_hist;
     } else {
         const rsort::PairsPlan &p = r.pairs = rsort::plan_pairs(n, key_bits, key_bytes, sort_scratch);
         r.tpb = p.tile.tpb, r.tile_elems = p.tile.tile(), r.num_tiles = p.num_tiles, r.shift = p.shift, r.tile_major = 0;
@@ -393,7 +395,7 @@ inline int sort_records(const BuildCall &b, const SortRoute &route) {
     const rsort::RecordArgs ra{b.src, dst, b.src_stride, b.wrapped ? 1 : 0, (int32_t)(b.lay.volume_bytes / 8),
                                index_bytes(d.types.index_type), b.dlay};
     if (route.by_records()) {
-        if (int e = msd::sort_records(route.records, b.key_bytes, b.key_bits, sc.keys, b.n, ra, sc.records2, (char *)b.leaves,
+        if (int e = msd::sort_records(route.records, route.tables, b.key_bytes, b.key_bits, sc.keys, ra, sc.records2, (char *)b.leaves,
                                       sc.keys_alt, (uint32_t *)sc.vals_alt, sc.keys, (uint32_t *)sc.vals, d.sort_levels,
                                       d.sort_equalize != 0, d.skew_flag, b.st))
             return e;

@@ -29,6 +29,9 @@
 //
 // Stability: partitions rank in memory order and the LDS passes are stable, so equal keys keep input order (the
 // oracle's definition of the unpinned AK.sort! tie order).
+//
+// Host side (the end of this file): everything one sort decides — digit, geometries, LDS budget, table layout — is the Plan of
+// ibvh_msd_plan.hpp (plain integers, checked on the CPU); the code here binds its tables to the scratch and launches.
 #include "ibvh_msd_impl.hpp"
 
 namespace ibvh {
@@ -930,11 +933,6 @@ __global__ __launch_bounds__(TPB, partition_min_waves(TPB, IPT)) void partition_
     }
     } // rp
 }
-template <class K, int TPB, int IPT> inline size_t partition_smem(int bits, int stride, bool eq = false) {
-    const size_t hist = (size_t)(TPB / 64) * ((size_t)2 << bits), st = (size_t)TPB * IPT * (size_t)stride + (eq ? (size_t)TPB * IPT * 2 : 0);
-    return ((size_t)8 << bits) + 128 + (hist > st ? hist : st);
-}
-
 // ------------------------------------------------------------------------------------------------------------
 // finish: sort a contiguous range of partitioned records — one cell of level 1, or a window of consecutive
 // sub-cells of an oversized cell — on the key bits that still vary inside it, and write the records to `out`
@@ -942,231 +940,133 @@ template <class K, int TPB, int IPT> inline size_t partition_smem(int bits, int 
 // ------------------------------------------------------------------------------------------------------------
 // host side
 // ------------------------------------------------------------------------------------------------------------
-static size_t carve_tables(Tables *tb, char *base, int radix, int num_tiles, int max_seg, int max_tiles2, int64_t n, int rescuers, int cap) {
-    size_t off = 0;
-    auto take = [&](size_t bytes) {
-        uint32_t *p = base ? (uint32_t *)(base + off) : nullptr;
-        off += (size_t)align_up((int64_t)bytes, 256);
-        return p;
-    };
-    Tables t;
-    t.tile_hist = take((size_t)radix * num_tiles * 4);
-    t.tile_scan = take((size_t)radix * num_tiles * 4);
-    t.cell_total = take((size_t)radix * 4);
-    t.cell_start = take((size_t)(radix + 1) * 4);
-    t.needed = take(64);
-    t.tile_hist2 = take((size_t)max_tiles2 * 4 << L2_BITS);
-    t.tile_scan2 = take((size_t)max_tiles2 * 4 << L2_BITS);
-    t.tile_and = (uint64_t *)take((size_t)max_tiles2 * 8);
-    t.tile_or = (uint64_t *)take((size_t)max_tiles2 * 8);
-    t.splitters = take(((size_t)(radix + 1) * 2 + 32768) * 8); // splitters, candidates, the sorted sample lists
-    t.dig = (uint16_t *)take((size_t)n * 2);
-    t.rescue = take((size_t)max_seg * 64);
-    t.rescue_priv = take((size_t)rescuers * 2 * (size_t)cap * 4);
-    for (int l = 0; l < MAX_LEVELS; ++l) {
-        Level &L = t.lvl[l];
-        L.hdr = take(64);
-        L.seg_start = take((size_t)max_seg * 4);
-        L.seg_count = take((size_t)max_seg * 4);
-        L.seg_tile = take((size_t)max_seg * 4);
-        L.seg_and = (uint64_t *)take((size_t)max_seg * 8);
-        L.seg_or = (uint64_t *)take((size_t)max_seg * 8);
-        L.sub_start = take((size_t)max_seg * 4 * ((1 << L2_BITS) + 1));
-        L.tile_seg = take((size_t)max_tiles2 * 4);
-    }
-    if (tb) *tb = t;
-    return off;
-}
-
-Plan make_plan(int64_t n, int key_bits, int key_bytes, int leaf_bytes, void *sort_scratch) {
-    // development knob (ibvh_set_tuning): msd_avg moves the digit width (the finish geometry is still a row of kFinish)
-    Plan p{};
-    if (n < 4096 || key_bits <= 8 || n >= ((int64_t)1 << 32) - 65536) return p;
-    int bits = 6; // (>= 6: the scan kernel works on blocks of 64 digits)
-    while (bits < 11 && bits < key_bits - 1 && (n >> bits) > g_tuning.msd_avg) ++bits;
-    // 1.3e7 .. 2.7e7 leaves: 4,096 cells keep the average cell within the 8,192-record finish workgroup (the 16,384-
-    // record one runs one workgroup per CU: 2e7 leaves 0.73 -> 0.40 ms for the finish, +0.05 for the wider partition)
-    constexpr int64_t kCellMax8k = 8192 * 8 / 10;
-    if (bits == 11 && key_bits > 13 && (n >> 11) > kCellMax8k && (n >> 12) <= kCellMax8k) bits = 12;
-    if (bits >= key_bits) bits = key_bits - 1;
-    if (bits < 6) return p;
-    const int64_t avg = n >> bits;
-    // capacity of the finish workgroup: the average cell fills at most 5/8 of it (uniform clouds vary by a few per
-    // cent; denser cells get the rest of the headroom before the second partition level takes them)
-    // (the last step is taken later — the average cell may fill 8/10 of the 8,192-record workgroup, a Poisson cell count
-    // then stays below it — because the 16,384-record workgroup is so much slower: 1.25e7 leaves 0.43 -> 0.26 ms)
-    const FinishGeometry *fin = nullptr;
-    for (const FinishGeometry &f : kFinish) {
-        if (f.key_bytes != key_bytes || f.resident) continue;
-        fin = &f;
-        if (f.cap < 8192 ? avg * 8 <= (int64_t)f.cap * 5 : avg * 10 <= (int64_t)f.cap * 8) break;
-    }
-    if (!fin) return p;
-    // Round 4: cells of the 8,192-record geometry (~2.5 .. 6.5 k records of 24 bytes: 1e7-leaf builds) are finished with
-    // their RECORDS resident in LDS — read from memory once instead of ~2.8 times (finish_range, resident path) — by one
-    // 1,024-thread workgroup per CU (the memory phases of a lone workgroup need that many loads in flight); cells beyond the
-    // ~5,000 records that fit beside the sort's arrays take the plain path inside the same kernel.  Measured at 1e7 leaves:
-    // finish 212 -> 196 us, Morton+sort 463 -> 448 us; smaller geometries lose (1e6: 24 -> 32 us: fewer workgroups per CU)
-    // and keep the plain kernel.  kFinish has that form for 32-bit keys only.
-    // (cells of ~3,000 records — 1.25e7 leaves at 12 bits — lose: 289 against 265 us; the rule asks for >= 4,096 on average)
-    if (fin->cap == 8192 && avg >= 4096 && leaf_bytes <= 24)
-        for (const FinishGeometry &f : kFinish)
-            if (f.key_bytes == key_bytes && f.cap == fin->cap && f.resident) fin = &f;
-    const int cap = fin->cap;
-    // partition tile: its records are staged in LDS (tile * leaf_bytes + 2 tables of 2^bits words <= 160 KiB)
-    int tile = (n >= (int64_t(1) << 22) && leaf_bytes <= 32) ? 4096 : 2048;
-    while (tile > 1024 && (size_t)tile * leaf_bytes + ((size_t)8 << bits) + 128 > 160 * 1024) tile >>= 1;
-    while (tile > 1024 && tile > cap / 2) tile >>= 1; // a window of sub-cells (< tile + one sub-cell) should fit the LDS sort
-    switch (tile) {
-    case 1024: p.ptpb = 256, p.pipt = 4; break;
-    case 2048: p.ptpb = 256, p.pipt = 8; break;
-    default: tile = 4096, p.ptpb = 512, p.pipt = 8; break;
-    }
-    if ((size_t)tile * leaf_bytes + ((size_t)8 << bits) + 128 > 160 * 1024) return p;
-    // finish workgroups are small (4 or 8 waves, many keys per thread): several ranges per CU at different phases
-    p.ftpb = fin->threads;
-    p.fipt = cap / fin->threads;
-    p.bits = bits;
-    p.shift = key_bits - bits;
-    p.num_tiles = (int)ceil_div(n, (int64_t)tile);
-    // segments of an extra level hold more than cap records each; a segment's last tile may be partial
-    p.max_seg = (int)(n / cap + 1);
-    p.max_tiles2 = p.num_tiles + p.max_seg;
-    // rescue workgroups of the finish kernel (ibvh_msd_finish.inc): no more than there can be windows to sort (the launch
-    // clamps them to half of what the device holds at once)
-    p.rescuers = g_tuning.msd_rescue ? (p.max_seg < kRescuers ? p.max_seg : kRescuers) : 0;
-    carve_tables(&p.tb, (char *)sort_scratch, 1 << bits, p.num_tiles, p.max_seg, p.max_tiles2, n, p.rescuers, cap);
-    return p;
-}
-
-// scratch for the tables of the plan make_plan() chooses for this input (0 when the path does not apply)
+Plan plan_records(int64_t n, int key_bits, int key_bytes, int leaf_bytes) { return make_plan(n, key_bits, key_bytes, leaf_bytes, g_tuning.msd_avg); }
 size_t scratch_bytes(int64_t n, int key_bits, int key_bytes, int leaf_bytes) {
-    const Plan p = make_plan(n, key_bits, key_bytes, leaf_bytes, nullptr);
-    if (!p.bits) return 0;
-    return carve_tables(nullptr, nullptr, 1 << p.bits, p.num_tiles, p.max_seg, p.max_tiles2, n, p.rescuers, p.ftpb * p.fipt) + 4096;
+    const Plan p = plan_records(n, key_bits, key_bytes, leaf_bytes);
+    return p.bits ? table_layout(p).total + 4096 : 0;
+}
+Tables bind_tables(const Plan &p, void *sort_scratch) {
+    const TableLayout l = table_layout(p);
+    char *base = (char *)sort_scratch;
+    auto u32 = [&](int i) { return (uint32_t *)(base + l.at[i]); };
+    auto u64 = [&](int i) { return (uint64_t *)(base + l.at[i]); };
+    Tables t;
+    t.tile_hist = u32(T_TILE_HIST), t.tile_scan = u32(T_TILE_SCAN), t.cell_total = u32(T_CELL_TOTAL), t.cell_start = u32(T_CELL_START);
+    t.needed = u32(T_NEEDED), t.tile_hist2 = u32(T_TILE_HIST2), t.tile_scan2 = u32(T_TILE_SCAN2);
+    t.tile_and = u64(T_TILE_AND), t.tile_or = u64(T_TILE_OR), t.splitters = u32(T_SPLITTERS), t.dig = (uint16_t *)u32(T_DIG);
+    t.rescue = u32(T_RESCUE), t.rescue_priv = u32(T_RESCUE_PRIV);
+    for (int l0 = 0, i = T_LEVELS; l0 < MAX_LEVELS; ++l0, i += L_TABLES) {
+        Level &L = t.lvl[l0];
+        L.hdr = u32(i + L_HDR), L.seg_start = u32(i + L_SEG_START), L.seg_count = u32(i + L_SEG_COUNT), L.seg_tile = u32(i + L_SEG_TILE);
+        L.seg_and = u64(i + L_SEG_AND), L.seg_or = u64(i + L_SEG_OR), L.sub_start = u32(i + L_SUB_START), L.tile_seg = u32(i + L_TILE_SEG);
+    }
+    return t;
 }
 
 template <class K, int PT, int PI>
-static int launch_partitions(const Plan &p, const K *keys, int64_t n, const RecordArgs &ra, char *part2, char *out, K *side0, K *side1, int levels,
-                             bool eq, hipStream_t st) {
-    const size_t smem = partition_smem<K, PT, PI>(p.bits, ra.lay.stride, eq);
-    if (smem > 160 * 1024) return IBVH_ERR_INVALID_ARG; // (make_plan sizes the tile for the record)
+static int launch_partitions(const Plan &p, const Tables &tb, const K *keys, const RecordArgs &ra, char *part2, char *out, K *side0, K *side1,
+                             int levels, bool eq, hipStream_t st) {
+    constexpr Geometry g{PT, PI};
+    if (!partition_fits(g, ra.lay.stride, p.bits, eq)) return IBVH_ERR_INVALID_ARG; // (make_plan sized the tile with the same function)
+    const uint32_t inv_words = record_words(ra.lay.stride).inv_words;
     // The attribute is per function and per device, and calls may come from several host threads with different geometries:
     // always the SAME value (the whole LDS), so that the order of concurrent calls cannot matter; a launch still only
     // allocates what it asks for.
-    IBVH_HIP_CHECK(hipFuncSetAttribute((const void *)partition_kernel<K, PT, PI, false>, hipFuncAttributeMaxDynamicSharedMemorySize, kMaxLds));
-    const uint32_t words = (uint32_t)ra.lay.stride / 8u;
-    const uint32_t inv_words = (uint32_t)((((uint64_t)1 << 32) + words - 1) / words);
-    if (eq) {
-        IBVH_HIP_CHECK(hipFuncSetAttribute((const void *)partition_kernel<K, PT, PI, false, true>, hipFuncAttributeMaxDynamicSharedMemorySize, kMaxLds));
-        IBVH_LAUNCH((partition_kernel<K, PT, PI, false, true>), dim3(p.num_tiles), dim3(PT), smem, st, keys, n, p.shift, p.bits, p.tb,
-                    p.num_tiles, ra, inv_words, p.bits, levels > 0 ? 0 : -(p.ftpb * p.fipt), out, levels > 0 ? side0 : (K *)nullptr);
-    } else
-    IBVH_LAUNCH((partition_kernel<K, PT, PI, false>), dim3(p.num_tiles), dim3(PT), smem, st, keys, n, p.shift, p.bits, p.tb,
-                p.num_tiles, ra, inv_words, p.bits, levels > 0 ? 0 : -(p.ftpb * p.fipt), out, levels > 0 ? side0 : (K *)nullptr);
+    auto level1 = [&](auto equalised) -> int {
+        constexpr bool EQ = decltype(equalised)::value;
+        IBVH_HIP_CHECK(hipFuncSetAttribute((const void *)partition_kernel<K, PT, PI, false, EQ>, hipFuncAttributeMaxDynamicSharedMemorySize, kMaxLds));
+        IBVH_LAUNCH((partition_kernel<K, PT, PI, false, EQ>), dim3(p.num_tiles), dim3(PT), partition_lds(g, ra.lay.stride, p.bits, EQ), st, keys, p.n,
+                    p.shift, p.bits, tb, p.num_tiles, ra, inv_words, p.bits, levels > 0 ? 0 : -p.cap(), out, levels > 0 ? side0 : (K *)nullptr);
+        return IBVH_OK;
+    };
+    if (int e = eq ? level1(std::bool_constant<true>{}) : level1(std::bool_constant<false>{})) return e;
     if (levels <= 0) return IBVH_OK;
     // extra levels: only the segments the level before found crowded (none for a uniform cloud: every workgroup
     // returns at once)
-    const uint32_t tile = (uint32_t)PT * PI, cap = (uint32_t)(p.ftpb * p.fipt);
-    const LeafLayout lay = ra.lay;
-    const size_t smem2 = partition_smem<K, PT, PI>(L2_BITS, ra.lay.stride);
+    const uint32_t tile = (uint32_t)p.tile(), cap = (uint32_t)p.cap();
     IBVH_HIP_CHECK(hipFuncSetAttribute((const void *)partition_kernel<K, PT, PI, true>, hipFuncAttributeMaxDynamicSharedMemorySize, kMaxLds));
     char *buf[2] = {(char *)ra.dst, part2};
     K *side[2] = {side0, side1}; // compact keys of the records in buf[0] / buf[1]
     const unsigned stride_grid = (unsigned)(p.max_tiles2 < 2048 ? p.max_tiles2 : 2048);
     const unsigned seg_grid = (unsigned)(p.max_seg < 1024 ? p.max_seg : 1024);
     for (int li = 0; li < levels; ++li) {
-        const char *src = buf[li & 1];
         const bool measured = li == 0;
-        if (measured) IBVH_LAUNCH((range_kernel<K>), dim3(stride_grid), dim3(256), 0, st, p.tb, li, (const K *)side[li & 1], tile);
-        IBVH_LAUNCH((hist_level_kernel<K>), dim3(stride_grid), dim3(256), 0, st, p.tb, li, (const K *)side[li & 1], tile, measured ? 1 : 0);
-        IBVH_LAUNCH((scan_level_kernel), dim3(seg_grid), dim3(1024), 0, st, p.tb, li, levels, cap, tile);
+        if (measured) IBVH_LAUNCH((range_kernel<K>), dim3(stride_grid), dim3(256), 0, st, tb, li, (const K *)side[li & 1], tile);
+        IBVH_LAUNCH((hist_level_kernel<K>), dim3(stride_grid), dim3(256), 0, st, tb, li, (const K *)side[li & 1], tile, measured ? 1 : 0);
+        IBVH_LAUNCH((scan_level_kernel), dim3(seg_grid), dim3(1024), 0, st, tb, li, levels, cap, tile);
         RecordArgs r2 = ra;
-        r2.src = src; // whole records, copied as they are
+        r2.src = buf[li & 1]; // whole records, copied as they are
         r2.dst = buf[(li + 1) & 1];
         r2.src_stride = ra.lay.stride;
         r2.src_wrapped = 1;
-        IBVH_LAUNCH((partition_kernel<K, PT, PI, true>), dim3(p.max_tiles2), dim3(PT), smem2, st, (const K *)side[li & 1], n, 0, L2_BITS, p.tb,
-                    p.max_tiles2, r2, inv_words, L2_BITS, li, out, li + 1 < levels ? side[(li + 1) & 1] : (K *)nullptr);
+        IBVH_LAUNCH((partition_kernel<K, PT, PI, true>), dim3(p.max_tiles2), dim3(PT), partition_lds(g, ra.lay.stride, L2_BITS, false), st,
+                    (const K *)side[li & 1], p.n, 0, L2_BITS, tb, p.max_tiles2, r2, inv_words, L2_BITS, li, out,
+                    li + 1 < levels ? side[(li + 1) & 1] : (K *)nullptr);
     }
     return IBVH_OK;
 }
-// keys: n Morton keys (uint32 / uint64) in source order, their top-digit tile histogram already in p.tb.tile_hist.
+// keys: p.n Morton keys (uint32 / uint64) in source order, their top-digit tile histogram already in tb.tile_hist.
 // ra: source -> level-1 partitioned records (ra.dst: n records of scratch); part2: n more records of scratch (the
 // extra levels ping-pong between the two); out: the sorted records.  (kalt, valt, kpri, vpri): n-entry scratch arrays:
 // kalt / kpri carry the compact key copies of the extra levels, then all four serve the slow path (kpri may alias
 // `keys`: the source keys are dead once the first partition has run).  levels: extra partition levels to launch.
-int sort_records(const Plan &p, int key_bytes, int key_bits, const void *keys, int64_t n, const RecordArgs &ra, char *part2, char *out, void *kalt,
-                 uint32_t *valt, void *kpri, uint32_t *vpri, int levels, bool equalize, void *skew_flag, hipStream_t st) {
+int sort_records(const Plan &p, const Tables &tb, int key_bytes, int key_bits, const void *keys, const RecordArgs &ra, char *part2, char *out,
+                 void *kalt, uint32_t *valt, void *kpri, uint32_t *vpri, int levels, bool equalize, void *skew_flag, hipStream_t st) {
     if (levels < 0 || levels > MAX_LEVELS) levels = MAX_LEVELS;
-    // equalised cells: only where the partition's LDS stage has room for the 2-byte digit of every staged record
-    const size_t tile_elems = (size_t)p.ptpb * p.pipt;
-    bool eq = equalize && g_tuning.msd_equalize >= 0 && tile_elems * ((size_t)ra.lay.stride + 2) + ((size_t)8 << p.bits) + 128 <= (size_t)160 * 1024;
-    if (g_tuning.msd_equalize > 0) eq = tile_elems * ((size_t)ra.lay.stride + 2) + ((size_t)8 << p.bits) + 128 <= (size_t)160 * 1024; // (test knob: always)
+    const int64_t n = p.n;
+    // equalised cells: when the build asks (test knob msd_equalize: 1 = always, -1 = never), and only where the partition's LDS
+    // stage has room for the 2-byte digit of every staged record
+    const bool eq = (g_tuning.msd_equalize > 0 || (equalize && g_tuning.msd_equalize == 0)) && partition_fits(p.part, ra.lay.stride, p.bits, true);
     if (eq) {
         // sorted sample -> splitter candidates -> every leaf's cell + the tile histogram (three launches in place of the histogram
         // the encode kernel fused; the lists and the candidates live behind the splitters in the sort scratch)
         const size_t hsm = ((size_t)(2 * key_bytes + 4)) << p.bits;
-        const uint32_t cap = (uint32_t)(p.ftpb * p.fipt);
         const int e = dispatch_key(key_bytes, [&](auto kt) -> int {
             using K = typename decltype(kt)::type;
             using SG = SampleGeom<K>;
-            K *cand = (K *)p.tb.splitters + ((size_t)1 << p.bits) + 1, *lists = cand + ((size_t)1 << p.bits) + 1;
+            K *cand = (K *)tb.splitters + (size_t)p.radix() + 1, *lists = cand + (size_t)p.radix() + 1;
             IBVH_HIP_CHECK(hipFuncSetAttribute((const void *)sample_rank_kernel<K>, hipFuncAttributeMaxDynamicSharedMemorySize, kMaxLds));
             // (4,096 cells of 64-bit codes: 80 KB of splitters, tree and counters; bucket_hist_kernel has a few static bytes of its own)
             IBVH_HIP_CHECK(hipFuncSetAttribute((const void *)bucket_hist_kernel<K>, hipFuncAttributeMaxDynamicSharedMemorySize, kMaxLds - 8192));
             IBVH_LAUNCH((sample_sort_kernel<K>), dim3(SG::G), dim3(SG::TPB), SG::sort_smem, st, (const K *)keys, n, lists, key_bits);
             IBVH_LAUNCH((sample_rank_kernel<K>), dim3(SG::G * 4), dim3(1024), (size_t)SG::S * sizeof(K), st, (const K *)lists, cand, p.bits);
-            IBVH_LAUNCH((bucket_hist_kernel<K>), dim3(p.num_tiles), dim3(512), hsm, st, (const K *)keys, n, p.tb, (const K *)cand, p.bits, (int)tile_elems,
-                        key_bits, cap);
+            IBVH_LAUNCH((bucket_hist_kernel<K>), dim3(p.num_tiles), dim3(512), hsm, st, (const K *)keys, n, tb, (const K *)cand, p.bits, p.tile(),
+                        key_bits, (uint32_t)p.cap());
             return IBVH_OK;
         });
         if (e) return e;
     }
     {
-        const int radix = 1 << p.bits, ndb = radix >> 6;
+        const int radix = p.radix(), ndb = radix >> 6;
         int chunks = 512 / ndb < 1 ? 1 : 512 / ndb; // ~512 workgroups
         if (chunks > (p.num_tiles + 15) / 16) chunks = (p.num_tiles + 15) / 16;
         const int rows = (p.num_tiles + chunks - 1) / chunks;
         chunks = (p.num_tiles + rows - 1) / rows;
-        IBVH_LAUNCH((scan_tiles_kernel), dim3(ndb * chunks), dim3(SCAN_TPB), 0, st, p.tb.tile_hist, p.tb.tile_scan, p.num_tiles, radix, rows,
-                    p.tb.cell_total);
+        IBVH_LAUNCH((scan_tiles_kernel), dim3(ndb * chunks), dim3(SCAN_TPB), 0, st, tb.tile_hist, tb.tile_scan, p.num_tiles, radix, rows,
+                    tb.cell_total);
         // (no extra levels: nothing but the cell starts and the hint would come out of the plan, and the partition kernel
         // derives those from the cell totals itself — one dependent launch less)
         if (levels > 0)
-            IBVH_LAUNCH((plan_kernel), dim3(1), dim3(PLAN_TPB), 0, st, p.tb, radix, (uint32_t)(p.ftpb * p.fipt), (uint32_t)(p.ptpb * p.pipt),
-                        levels, p.shift, eq ? key_bytes : 0, key_bits);
+            IBVH_LAUNCH((plan_kernel), dim3(1), dim3(PLAN_TPB), 0, st, tb, radix, (uint32_t)p.cap(), (uint32_t)p.tile(), levels, p.shift,
+                        eq ? key_bytes : 0, key_bits);
     }
-    int rc = IBVH_ERR_INVALID_ARG;
+    int rc = IBVH_ERR_INVALID_ARG; // (make_plan takes the tile from the same table, so one case matches)
 #define IBVH_PART(K, T, I) \
-    if (p.ptpb == T && p.pipt == I) rc = launch_partitions<K, T, I>(p, (const K *)keys, n, ra, part2, out, (K *)kalt, (K *)kpri, levels, eq, st);
-    if (key_bytes == 4) {
-        IBVH_PART(uint32_t, 256, 4) IBVH_PART(uint32_t, 256, 8) IBVH_PART(uint32_t, 512, 8)
-    } else {
-        IBVH_PART(uint64_t, 256, 4) IBVH_PART(uint64_t, 256, 8) IBVH_PART(uint64_t, 512, 8)
-    }
+    if (sizeof(K) == (size_t)key_bytes && p.part.tpb == T && p.part.ipt == I) \
+        rc = launch_partitions<K, T, I>(p, tb, (const K *)keys, ra, part2, out, (K *)kalt, (K *)kpri, levels, eq, st);
+    IBVH_PARTITION_GEOMETRIES(IBVH_PART, uint32_t) IBVH_PARTITION_GEOMETRIES(IBVH_PART, uint64_t)
 #undef IBVH_PART
     if (rc) return rc;
     FinishArgs fa{};
-    fa.buf[0] = ra.dst;
-    fa.buf[1] = part2;
-    fa.out = out;
-    fa.lay = ra.lay;
-    fa.words = (uint32_t)ra.lay.stride / 8u;
-    fa.inv_words = (uint32_t)((((uint64_t)1 << 32) + fa.words - 1) / fa.words);
-    fa.cap = (uint32_t)(p.ftpb * p.fipt);
-    fa.tile = (uint32_t)(p.ptpb * p.pipt);
-    fa.levels = levels;
-    fa.shift1 = p.shift;
+    fa.buf[0] = ra.dst, fa.buf[1] = part2, fa.out = out, fa.lay = ra.lay;
+    fa.words = record_words(ra.lay.stride).words, fa.inv_words = record_words(ra.lay.stride).inv_words;
+    fa.cap = (uint32_t)p.cap(), fa.tile = (uint32_t)p.tile(), fa.levels = levels, fa.shift1 = p.shift;
     fa.eq_key_bits = eq ? key_bits : 0;
     fa.skew_flag = (int32_t *)skew_flag;
-    fa.kalt = kalt;
-    fa.kpri = kpri;
-    fa.valt = valt;
-    fa.vpri = vpri;
-    fa.rescuers = (uint32_t)p.rescuers;
-    fa.rescue_priv = p.tb.rescue_priv;
-    rc = run_finish(p, key_bytes, fa, st);
+    fa.kalt = kalt, fa.kpri = kpri, fa.valt = valt, fa.vpri = vpri;
+    fa.rescuers = g_tuning.msd_rescue ? (uint32_t)p.rescue_slots : 0u; // (the knob: the slots are carved either way)
+    fa.rescue_priv = tb.rescue_priv;
+    rc = run_finish(p, tb, key_bytes, fa, st);
     if (rc) return rc;
     IBVH_LAUNCH_CHECK();
     return IBVH_OK;

@@ -1,13 +1,13 @@
 // ibvh_msd.hpp — interface of ibvh_msd.hip (the build's sort: MSD partition of whole records + in-LDS finish) for
-// ibvh_build.hip.
+// ibvh_build.hip.  What one sort decides on the host — the Plan, its geometries, the layout of the tables below in the
+// sort scratch — lives in ibvh_msd_plan.hpp (plain integers, checked on the CPU: tests/test_host_msd_plan.py).
 #pragma once
 #include "ibvh_common.hpp"
+#include "ibvh_msd_plan.hpp"
 #include "ibvh_radix.hpp"
 
 namespace ibvh {
 namespace msd {
-
-constexpr int MAX_LEVELS = 4; // partition levels beyond the first (levels 2 .. 5)
 
 // One extra partition level: the SEGMENTS (contiguous record ranges with a common key prefix) the level before found
 // crowded, each split into 256 sub-cells by the top 8 of the key bits that actually vary inside it.
@@ -42,21 +42,10 @@ struct Tables {
     Level lvl[MAX_LEVELS];
 };
 
-struct Plan {
-    int bits;            // MSD digit width; 0: this path does not apply (tiny input) -> ibvh_sort.hip
-    int shift;           // key_bits - bits: the cell is key >> shift
-    int ptpb, pipt;      // partition (and histogram) tile geometry
-    int num_tiles;
-    int ftpb, fipt;      // finish workgroup: threads, keys per thread (capacity = ftpb * fipt): a row of kFinish (ibvh_msd_impl.hpp)
-    int max_seg;         // S
-    int max_tiles2;      // T2
-    int rescuers;        // H: rescue workgroups at the end of the finish grid (scratch is carved for them)
-    Tables tb;
-};
-
-Plan make_plan(int64_t n, int key_bits, int key_bytes, int leaf_bytes, void *sort_scratch);
-size_t scratch_bytes(int64_t n, int key_bits, int key_bytes, int leaf_bytes);
-int sort_records(const Plan &p, int key_bytes, int key_bits, const void *keys, int64_t n, const rsort::RecordArgs &ra, char *part2, char *out,
+Plan plan_records(int64_t n, int key_bits, int key_bytes, int leaf_bytes); // make_plan() under the msd_avg knob
+size_t scratch_bytes(int64_t n, int key_bits, int key_bytes, int leaf_bytes); // of that plan's tables (0: the path does not apply)
+Tables bind_tables(const Plan &p, void *sort_scratch);                         // table_layout(p) in the caller's scratch
+int sort_records(const Plan &p, const Tables &tb, int key_bytes, int key_bits, const void *keys, const rsort::RecordArgs &ra, char *part2, char *out,
                  void *kalt, uint32_t *valt, void *kpri, uint32_t *vpri, int levels, bool equalize, void *skew_flag, hipStream_t st);
 
 } // namespace msd

@@ -663,7 +663,7 @@ template <class K, int TPB, int IPT> constexpr size_t finish_smem() {
 }
 
 template <class K, int FT, int FI, bool RES>
-int launch_finish(const Plan &p, const FinishArgs &fa_in, hipStream_t st) {
+int launch_finish(const Plan &p, const Tables &tb, const FinishArgs &fa_in, hipStream_t st) {
     FinishArgs fa = fa_in;
     size_t smem = finish_smem<K, FT, FI>();
     // resident geometry (kFinish): room for a full range of records behind the sort's arrays, as long as the workgroup
@@ -681,40 +681,37 @@ int launch_finish(const Plan &p, const FinishArgs &fa_in, hipStream_t st) {
         }
     }
     const int f2 = fa.levels <= 0 ? 0 : (p.max_tiles2 < 1024 ? p.max_tiles2 : 1024); // workgroups that stride over the extra levels' windows
-    fa.normal_wgs = (1u << p.bits) + (uint32_t)f2;
-    // the rescue workgroups WAIT for the ordinary ones: never more of them than HALF the workgroups of this kernel the device
-    // holds at once (whatever order the hardware starts workgroups in, the ordinary ones then always find room to run)
-    auto clamp_rescuers = [&](const void *kernel) -> int {
-        struct Memo { // (per host thread: the queries cost microseconds, a build is on the host's critical path)
-            const void *kernel;
-            size_t smem;
-            int dev;
-            uint32_t room;
-        };
-        static thread_local Memo memo{nullptr, 0, -1, 0};
-        int dev = 0;
-        IBVH_HIP_CHECK(hipGetDevice(&dev));
-        if (memo.kernel != kernel || memo.smem != smem || memo.dev != dev) {
-            int ncu = 0, per_cu = 0;
-            IBVH_HIP_CHECK(hipDeviceGetAttribute(&ncu, hipDeviceAttributeMultiprocessorCount, dev));
-            IBVH_HIP_CHECK(hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, kernel, FT, smem));
-            memo = Memo{kernel, smem, dev, (uint32_t)((int64_t)ncu * (per_cu > 0 ? per_cu : 1) / 2)};
+    fa.normal_wgs = (uint32_t)p.radix() + (uint32_t)f2;
+    // the kernel (resident: a kernel of its own, the resident branch must not cost the plain one registers), then its launch
+    auto launch = [&](auto resident) -> int {
+        const void *kernel = (const void *)finish_kernel<K, FT, FI, decltype(resident)::value>;
+        IBVH_HIP_CHECK(hipFuncSetAttribute(kernel, hipFuncAttributeMaxDynamicSharedMemorySize, kMaxLds));
+        // the rescue workgroups WAIT for the ordinary ones: never more of them than HALF the workgroups of this kernel the device
+        // holds at once (whatever order the hardware starts workgroups in, the ordinary ones then always find room to run)
+        if (fa.rescuers) {
+            struct Memo { // (per host thread: the queries cost microseconds, a build is on the host's critical path)
+                const void *kernel;
+                size_t smem;
+                int dev;
+                uint32_t room;
+            };
+            static thread_local Memo memo{nullptr, 0, -1, 0};
+            int dev = 0;
+            IBVH_HIP_CHECK(hipGetDevice(&dev));
+            if (memo.kernel != kernel || memo.smem != smem || memo.dev != dev) {
+                int ncu = 0, per_cu = 0;
+                IBVH_HIP_CHECK(hipDeviceGetAttribute(&ncu, hipDeviceAttributeMultiprocessorCount, dev));
+                IBVH_HIP_CHECK(hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, kernel, FT, smem));
+                memo = Memo{kernel, smem, dev, (uint32_t)((int64_t)ncu * (per_cu > 0 ? per_cu : 1) / 2)};
+            }
+            if (fa.rescuers > memo.room) fa.rescuers = memo.room;
         }
-        if (fa.rescuers > memo.room) fa.rescuers = memo.room;
+        IBVH_LAUNCH((finish_kernel<K, FT, FI, decltype(resident)::value>), dim3(fa.normal_wgs + fa.rescuers), dim3(FT), smem, st, tb, p.radix(), fa);
         return IBVH_OK;
     };
-    if constexpr (RES) {
-        if (fa.resident_words) { // (a kernel of its own: the resident branch must not cost the plain one registers)
-            IBVH_HIP_CHECK(hipFuncSetAttribute((const void *)finish_kernel<K, FT, FI, true>, hipFuncAttributeMaxDynamicSharedMemorySize, kMaxLds));
-            if (fa.rescuers) { if (int e = clamp_rescuers((const void *)finish_kernel<K, FT, FI, true>)) return e; }
-            IBVH_LAUNCH((finish_kernel<K, FT, FI, true>), dim3(fa.normal_wgs + fa.rescuers), dim3(FT), smem, st, p.tb, 1 << p.bits, fa);
-            return IBVH_OK;
-        }
-    }
-    IBVH_HIP_CHECK(hipFuncSetAttribute((const void *)finish_kernel<K, FT, FI>, hipFuncAttributeMaxDynamicSharedMemorySize, kMaxLds));
-    if (fa.rescuers) { if (int e = clamp_rescuers((const void *)finish_kernel<K, FT, FI>)) return e; }
-    IBVH_LAUNCH((finish_kernel<K, FT, FI>), dim3(fa.normal_wgs + fa.rescuers), dim3(FT), smem, st, p.tb, 1 << p.bits, fa);
-    return IBVH_OK;
+    if constexpr (RES)
+        if (fa.resident_words) return launch(std::bool_constant<true>{});
+    return launch(std::bool_constant<false>{});
 }
 
 

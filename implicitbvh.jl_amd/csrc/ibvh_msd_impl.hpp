@@ -26,7 +26,6 @@ using rsort::RecordArgs;
 using rsort::wave_rank;
 
 constexpr int MSD_MAX_BITS = 12;
-constexpr int L2_BITS = 8; // sub-cells per oversized cell: 2^8
 
 // Diagnostic build only (-DIBVH_PHASE_STAMPS, tools/phase_stamps.sh): thread 0 of every workgroup stamps s_memtime
 // at the phase boundaries into a buffer no product code reads.  In the product build the macro is empty.
@@ -81,26 +80,6 @@ template <class K> IBVH_D void cell_range(const Tables &tb, uint32_t d, int radi
     *nbits_out = span == 0 ? 0 : 64 - __builtin_clzll(span);
 }
 
-// Every finish workgroup make_plan() can choose: X(key type, capacity, threads, resident); keys per thread = capacity / threads.
-// run_finish() (ibvh_msd_finish.hip) dispatches over this table and so instantiates exactly its kernels; `resident` marks the
-// geometry whose launch may keep a range's RECORDS in LDS (its kernel exists in that form as well as the plain one).  For each
-// key type the plain rows are in ascending capacity: make_plan takes the first one the average cell fits, else the last
-// (64-bit keys stop at 8,192: 16,384 x 10 B does not fit the LDS).
-#define IBVH_FINISH_GEOMETRIES(X)                                                                                             \
-    X(uint32_t, 2048, 256, false) X(uint32_t, 4096, 256, false) X(uint32_t, 8192, 512, false) X(uint32_t, 8192, 1024, true)    \
-    X(uint32_t, 16384, 512, false) X(uint64_t, 2048, 256, false) X(uint64_t, 4096, 256, false) X(uint64_t, 8192, 512, false)
-struct FinishGeometry {
-    int key_bytes, cap, threads;
-    bool resident;
-};
-#define IBVH_FINISH_ROW(K, C, T, R) FinishGeometry{(int)sizeof(K), C, T, R},
-constexpr FinishGeometry kFinish[] = {IBVH_FINISH_GEOMETRIES(IBVH_FINISH_ROW)};
-#undef IBVH_FINISH_ROW
-
-constexpr int kMaxLds = 160 * 1024; // LDS of a gfx950 CU
-constexpr int kRescuers = 512;       // rescue workgroups of the finish kernel that scratch is carved for; a launch uses at most half of what the device holds at once (they WAIT for the ordinary workgroups)
-
-
 struct FinishArgs {
     const char *buf[2]; // the two record buffers: level 1 writes buf[0]; extra level li reads buf[li & 1], writes buf[(li + 1) & 1]
     char *out;          // sorted records
@@ -127,7 +106,7 @@ struct FinishArgs {
 
 
 // the finish launch for the plan's geometry (ibvh_msd_finish.hip)
-int run_finish(const Plan &p, int key_bytes, const FinishArgs &fa, hipStream_t st);
+int run_finish(const Plan &p, const Tables &tb, int key_bytes, const FinishArgs &fa, hipStream_t st);
 
 } // namespace msd
 } // namespace ibvh

@@ -1,6 +1,6 @@
 """ibvh_build against the oracle, bit for bit (leaves: volume, index, Morton; nodes; skips; extrema), at the sizes where the
-build's sort changes its route or its kernel geometry (csrc/ibvh_build.hip choose_route, ibvh_sort.hip plan_pairs, ibvh_msd.hip
-make_plan):
+build's sort changes its route or its kernel geometry (csrc/ibvh_build.hip choose_route, ibvh_sort.hip plan_pairs,
+ibvh_msd_plan.hpp make_plan):
     n < 2,048            the pair sort's LSD passes, the last scatter writing the records
     2,048 <= n < 4,096   the pair sort's hybrid: one MSD partition of the pairs, the bucket sort writing the records
     n >= 4,096           the record sort: partition of whole records + in-LDS finish
